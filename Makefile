@@ -8,8 +8,10 @@
 # The Agility blocks (pd_input / cassie_core_sim / state_output + pack/unpack) exist
 # only as the closed static library shipped with the reference
 # (src/libagilitycassie.a); it is whole-archived into the product .so exactly like
-# the reference's own Makefile does (reference Makefile:18).  On a box without
-# /root/reference the prebuilt .so is used as is.
+# the reference's own Makefile does (reference Makefile:18).  Where the reference tree
+# is absent, the copy oracle/build_ref.sh staged in the git-ignored oracle/_ref/ is
+# linked.  With neither, the product is linked with stand-ins for the archive's entry
+# points that stop the process with a message when called (see AGILITY_ABSENT).
 
 ROCM      ?= /opt/rocm
 HIPCC     ?= $(ROCM)/bin/hipcc
@@ -41,13 +43,31 @@ OBJS     := $(patsubst $(CSRC)/%.cpp,$(OBJD)/%.o,$(HOST_CPP)) $(patsubst $(CSRC)
 
 PRODUCT := $(LIBD)/libcassiemujoco.so
 
+AGILITY_STAGED := oracle/_ref/libagilitycassie.a
+ifeq ($(wildcard $(AGILITY)),)
+AGILITY := $(AGILITY_STAGED)
+endif
+# Neither copy of the archive here: its 25 entry points are linked as stand-ins that print which block is missing and abort.
+# Only the reference's host-side API needs the blocks (cassie_sim_*, cassie_batch_* / step_pd, the state estimator); the
+# physics API (phys_*: Model / Batch) and everything on the device do not, and run as usual.  The library exports
+# cassie_agility_blocks_absent so that a caller can tell such a build.  AGILITY_STAMP records which of the two the product
+# was linked with, so that it is relinked whenever that changes (whatever the files' times).
+AGILITY_ABSENT := $(OBJD)/agility_absent.o
+AGILITY_SYMS := cassie_core_sim_alloc cassie_core_sim_copy cassie_core_sim_free cassie_core_sim_setup cassie_core_sim_step \
+                pd_input_alloc pd_input_copy pd_input_free pd_input_setup pd_input_step \
+                state_output_alloc state_output_copy state_output_free state_output_setup state_output_step \
+                pack_cassie_in_t pack_cassie_out_t pack_cassie_user_in_t pack_pd_in_t pack_state_out_t \
+                unpack_cassie_in_t unpack_cassie_out_t unpack_cassie_user_in_t unpack_pd_in_t unpack_state_out_t
+AGILITY_STAMP := $(OBJD)/agility_link
 ifneq ($(wildcard $(AGILITY)),)
 AGILITY_LINK := -Wl,--whole-archive $(AGILITY) -Wl,--no-whole-archive
+AGILITY_DEPS := $(AGILITY)
 else
-AGILITY_LINK :=
+AGILITY_LINK := $(AGILITY_ABSENT)
+AGILITY_DEPS := $(AGILITY_ABSENT)
 endif
 
-.PHONY: all product oracle emu models clean apps
+.PHONY: all product oracle emu models clean apps FORCE
 all: product oracle emu apps
 apps: $(PKG)/bin/cassiesim
 product: $(PRODUCT)
@@ -64,9 +84,23 @@ $(OBJD)/%.hip.o: $(CSRC)/%.hip $(wildcard $(CSRC)/*.h) $(wildcard $(CSRC)/*.inc)
 	@mkdir -p $(OBJD)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
-$(PRODUCT): $(OBJS)
+$(AGILITY_STAMP): FORCE
+	@mkdir -p $(OBJD)
+	@echo '$(AGILITY_LINK)' | cmp -s - $@ || echo '$(AGILITY_LINK)' > $@
+
+$(PRODUCT): $(OBJS) $(AGILITY_DEPS) $(AGILITY_STAMP)
+	@test -f $(AGILITY) || echo "WARNING: no Agility archive (neither $(AGILITY) nor the reference's): linking stand-ins that abort when" \
+	    "called; the reference's host-side API (cassie_sim_*, cassie_batch_*) is unusable in this build" >&2
 	@mkdir -p $(LIBD)
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $(OBJS) $(AGILITY_LINK) -lm -lpthread
+
+$(AGILITY_ABSENT):
+	@mkdir -p $(OBJD)
+	@{ echo '#include <stdio.h>'; echo '#include <stdlib.h>'; \
+	   echo 'const int cassie_agility_blocks_absent = 1;'; \
+	   printf '%s\n' 'static void absent(const char *f) { fprintf(stderr, "libcassiemujoco: %s belongs to the closed Agility library, which this build was linked without\n", f); abort(); }'; \
+	   for f in $(AGILITY_SYMS); do echo "void $$f(void) { absent(\"$$f\"); }"; done; } > $(OBJD)/agility_absent.c
+	gcc $(CFLAGS) -c $(OBJD)/agility_absent.c -o $@
 
 # the UDP lock-step server (reference example/cassiesim.c role) against the product library
 $(PKG)/bin/cassiesim: $(PKG)/apps/cassiesim.c $(PRODUCT)

@@ -21,26 +21,32 @@ With N>1 envs shard across GPUs with no data-path exchange; the only collective 
 observation block (qpos|qvel|sensordata, 96 doubles/env, ONE tensor the kernel writes in place) per 50 steps.
 Env counts: one GPU runs BASELINE configs[1] (4096 envs); N > 1 GPUs run configs[2]'s shard, 8192 envs per GPU = 65536
 at 8 GPUs (weak scaling); `--total-envs T` shards a fixed total instead (strong scaling).
-Timing: `--repeats` (10) fenced regions of exactly `--steps` steps each, one after the other on the stationary mix; every
+Timing: `--repeats` fenced regions of exactly `--steps` steps each, one after the other on the stationary mix; every
 region is bracketed by barrier + torch.cuda.synchronize on both sides and counted at its slowest rank; `value` is the
-MEDIAN region, `value_min` / `value_max` the slowest / fastest.
+MEDIAN region, `value_min` / `value_max` the slowest / fastest.  A plain run times ONE region, so `--steps` is the number
+of timed steps; `--full` times 10 by default.  `ms_per_step` is the median region's time per step.
 
-The JSON line carries, beside the contract's fields:
-  max_qpos_err    BASELINE.json's second half of the metric: sampled envs of EVERY rank's shard of the timed batch are
+A plain run does only what `value` needs: set-up, pre-roll and warm-up, the timed steps, the outputs (`--dump-outputs DIR`:
+what the timed path computed in its last step -- qpos, qvel, sensordata, ... of every env, one DIR/<name>.npy each, float64;
+a fixed seeded sample of the envs above 64 MB in all)
+and the line.  `--full` adds everything else below: the CPU replay behind `max_qpos_err`, the other legs and the CPU figures.
+
+The JSON line carries, beside the contract's fields (* = with --full only):
+* max_qpos_err    BASELINE.json's second half of the metric: sampled envs of EVERY rank's shard of the timed batch are
                   replayed on the CPU reference (oracle/, the fp64 restatement of mj_step1 + mj_step2) through the same
                   schedule (pre-roll, warm-up, timed steps, restarts) and the qpos at a timed region's end compared
-  value_exact_pd  (or value_drive_pd) a short run of the other device mode, with its own parity figure
-  value_all_outputs_every_substep
+* value_exact_pd  (or value_drive_pd) a short run of the other device mode, with its own parity figure
+* value_all_outputs_every_substep
                   `value` when every substep of a launch also forms the outputs nobody can read: a launch of 50 fused substeps
                   returns its LAST substep's sensordata / measurement block / xquat, so by default the IMU sensor words and
                   body quaternions of the 48 substeps whose values are neither returned nor fed back are not evaluated
                   (state trajectory and returned outputs are bit for bit the same either way)
-  value_step_pd   the same workload through the drop-in API itself (cassie_batch_step_pd = cassie_sim_step_pd for every
+* value_step_pd   the same workload through the drop-in API itself (cassie_batch_step_pd = cassie_sim_step_pd for every
                   env: Agility blocks + encoder / motor models, see include/cassie_batch.h) -- PCIe- and host-inclusive
   roofline        algorithmic HBM bytes of one launch (1976 B per env-step) divided by the mean kernel
                   duration measured with HIP events on the launch stream
-  cpu_baseline    the fp64 CPU oracle ("port") on the host cores, OpenMP over envs, same workload, bounded sample
-  true_reference  genuine MuJoCo (libmujoco210 / `mujoco` wheel) timed and compared on the same inputs when one is
+* cpu_baseline    the fp64 CPU oracle ("port") on the host cores, OpenMP over envs, same workload, bounded sample
+* true_reference  genuine MuJoCo (libmujoco210 / `mujoco` wheel) timed and compared on the same inputs when one is
                   discoverable at run time, otherwise the string "unavailable"
 """
 import argparse
@@ -101,6 +107,7 @@ ENVS_PER_GPU_SHARDED = 8192         # BASELINE configs[2]: 65536 envs sharded ov
 STREAMS = 2                         # env ranges per rank, each stepped on its own stream (see device_rollout)
 REPEATS = 10                        # fenced timed regions of exactly --steps steps each; `value` is their median
 REPLAY_BUDGET_STEPS = 2200          # the CPU replay follows the schedule up to the last region boundary within this many steps
+DUMP_BYTES_MAX = 64 << 20           # --dump-outputs: above this, a fixed seeded sample of the envs is written
 
 
 def resolve_envs(world, envs_per_gpu=None, total_envs=None):
@@ -491,7 +498,14 @@ class GpuRuntime:
         return Batch(model, n, device=self.local_rank)
 
     def init_sensordata(self, model, hfield):
-        return HostChainEnvs(model, [0], hfield).init_sensordata()
+        """The init pose's sensordata (what cassie_sim_init leaves, as HostChainEnvs.reset computes it): the CPU oracle's
+        forward pass alone, so that stepping on the device never needs the host chain or the closed Agility blocks."""
+        import oracle_py
+        if hfield is not None:
+            oracle_py.set_hfield(hfield)
+        o = oracle_py.Oracle(model.pod, model.qpos_init())
+        o.forward()
+        return o.sensordata.copy()
 
     def replay_envs(self, drive):
         return HostChainEnvs if drive else OracleEnvs
@@ -502,7 +516,7 @@ class GpuRuntime:
 
 
 def device_rollout(model, mode, n, steps, warmup, rank, world, local_rank, substeps_per_launch=HOLD, parity_envs=64, hfield=None, collect=None,
-                   all_outputs=False, repeats=1, nstreams=1, rt=None, randomise=None):
+                   all_outputs=False, repeats=1, nstreams=1, rt=None, randomise=None, parity=True, outputs=False):
     """One device-resident rollout of the workload in `mode`, timed as `repeats` fenced regions of exactly `steps` steps:
 
       "drive-pd"  CM_DRIVE_PD: every substep runs pd_input's motor PD on the ENCODER measurements of the
@@ -522,8 +536,9 @@ def device_rollout(model, mode, n, steps, warmup, rank, world, local_rank, subst
     start of its launches.  Restarts, PD targets and (N > 1) the observation all-gather are per range.
 
     State and inputs are resident in HBM before the timed regions.  Every region is bracketed by barrier +
-    torch.cuda.synchronize on both sides; a region's time is the maximum over the ranks.  Sampled envs of EVERY rank are
-    snapshotted at a region boundary and compared on rank 0 with their replay on the CPU reference."""
+    torch.cuda.synchronize on both sides; a region's time is the maximum over the ranks.  parity: sampled envs of EVERY rank
+    are snapshotted at a region boundary and compared on rank 0 with their replay on the CPU reference (res["parity"]).
+    outputs: res["outputs"] on rank 0 = what a caller of the timed path holds after its last step, every env (last_step_outputs)."""
     import torch
     import torch.distributed as dist
     from cassie_amd import phys as P
@@ -662,7 +677,7 @@ def device_rollout(model, mode, n, steps, warmup, rank, world, local_rank, subst
         region_launches.append(sch.launches)
         kn, kms = b.kernel_timing()       # (after the fence: the region's launches are complete)
         kern_n, kern_ms_total = kern_n + kn, kern_ms_total + kms
-        if r == snap_r:     # between two fenced regions: the sampled rows of this rank for the CPU replay
+        if parity and r == snap_r:     # between two fenced regions: the sampled rows of this rank for the CPU replay
             q_sample = obs[sample_dev, :nq].clone()
             info_sample = torch.from_numpy(b.warnings()[1][sample][:, :3].astype(np.int64)).to(dev)
     if collect:   # a region's time is the slowest rank's
@@ -670,6 +685,7 @@ def device_rollout(model, mode, n, steps, warmup, rank, world, local_rank, subst
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         region_s = [float(x) for x in t.cpu()]
     launches = int(sum(region_launches))
+    outs = last_step_outputs(b, obs, nq, nv, warm, actvel if drive else None, meas if drive else None, collect, world) if outputs else None
     res = {"mode": mode, "n": n, "steps": steps, "warmup": warmup, "repeats": repeats, "launches": launches, "streams": len(ranges),
            # mean stream time of ONE range's launch (includes the rare restart / gather); with several streams the ranges' launches
            # overlap, each sharing the GPU with the others'
@@ -678,6 +694,8 @@ def device_rollout(model, mode, n, steps, warmup, rank, world, local_rank, subst
            # on its launch stream (phys_batch_kernel_timing) -- the quantity rocprofv3 --kernel-trace --stats averages
            "kernel_ms": kern_ms_total / max(1, kern_n), "kernel_launches": kern_n,
            "region_s": region_s, "elapsed": float(np.median(region_s))}
+    if outs is not None and rank == 0:
+        res["outputs"] = outs
     if collect and rank == 0:
         # the gathered block of the last policy boundary must hold this rank's rows (global env order, rank-major)
         res["gather_ok"] = bool(sch.gathers > 0 and og.holds_own_rows(rank))
@@ -703,12 +721,13 @@ def device_rollout(model, mode, n, steps, warmup, rank, world, local_rank, subst
         res["env_clocks_per_substep"] = None
         res["shader_clock_hz"] = None
         res.setdefault("wide_pass_envs_last_launch", None)
-    b_params = b.params() if rand_info is not None and rank == 0 else None
+    b_params = b.params() if parity and rand_info is not None and rank == 0 else None
     # ---- the metric's second half: sampled envs of EVERY rank against the CPU reference, same schedule ----
-    ids_sample = torch.from_numpy(env_ids[sample].astype(np.int64)).to(dev)
-    if collect and world > 1:
+    if parity:
+        ids_sample = torch.from_numpy(env_ids[sample].astype(np.int64)).to(dev)
+    if parity and collect and world > 1:
         q_sample, info_sample, ids_sample = (gather_rows(x, world) for x in (q_sample, info_sample, ids_sample))
-    if rank == 0:
+    if parity and rank == 0:
         q_gpu, counts_gpu, ids = q_sample.cpu().numpy(), info_sample.cpu().numpy(), ids_sample.cpu().numpy()
         threads = rt.host_threads()
         tg_replay = pd_targets(ids, (replay_steps + HOLD - 1) // HOLD + 1)      # seeds depend on the global env id only
@@ -760,6 +779,36 @@ def device_rollout(model, mode, n, steps, warmup, rank, world, local_rank, subst
     return res
 
 
+def last_step_outputs(b, obs, nq, nv, warm, actvel, meas, collect, world):
+    """What a caller of the timed path holds after its last step (the batch is fenced): the observation block's qpos / qvel /
+    sensordata, the warm start the next step reads, in the drive modes the actuator velocities and the measurement block,
+    and the body poses of the last substep -- every env, in global env order (gathered over the ranks), as float64 numpy."""
+    import torch
+    from cassie_amd import phys as P
+    arrs = {"qpos": obs[:, :nq], "qvel": obs[:, nq:nq + nv], "sensordata": obs[:, nq + nv:], "qacc_warmstart": warm}
+    if actvel is not None:
+        arrs.update(actuator_velocity=actvel, meas=meas)
+    if hasattr(b, "get"):       # (the CPU dry run's stand-in keeps no body poses)
+        arrs.update(xpos=torch.from_numpy(b.get(P.F_XPOS)).to(obs.device), xquat=torch.from_numpy(b.get(P.F_XQUAT)).to(obs.device))
+    if collect and world > 1:
+        arrs = {k: gather_rows(v, world) for k, v in arrs.items()}
+    return {k: v.detach().cpu().numpy().astype(np.float64) for k, v in arrs.items()}
+
+
+def dump_outputs(outdir, arrays):
+    """--dump-outputs: every array as <outdir>/<name>.npy in float64, one row per env.  Above DUMP_BYTES_MAX in all, the same
+    fixed seeded sample of rows from every array; env_ids.npy names the rows written."""
+    os.makedirs(outdir, exist_ok=True)
+    n = len(next(iter(arrays.values())))
+    row_bytes = 8 + sum(a.nbytes for a in arrays.values()) / n
+    rows = np.arange(n)
+    if row_bytes * n > DUMP_BYTES_MAX:
+        rows = np.sort(np.random.default_rng(0).choice(n, int(DUMP_BYTES_MAX // row_bytes), replace=False))
+    np.save(os.path.join(outdir, "env_ids.npy"), rows.astype(np.float64))
+    for name, a in arrays.items():
+        np.save(os.path.join(outdir, name + ".npy"), np.ascontiguousarray(a[rows], dtype=np.float64))
+
+
 SLOTS_PER_GPU = 256 * 4        # one env per workgroup, 40 KB of LDS each: four workgroups per CU
 SHADER_CLOCK_HZ = 2.4e9        # MI355X peak engine clock: the fallback when the launch did not measure its own (slot_occupancy)
 
@@ -809,8 +858,15 @@ def main(argv=None):
                          % (ENVS_PER_GPU_SINGLE, ENVS_PER_GPU_SHARDED))
     ap.add_argument("--total-envs", type=int, default=None,
                     help="shard a FIXED total over the GPUs instead (strong scaling), e.g. 65536 at 1 / 2 / 4 / 8 GPUs")
-    ap.add_argument("--repeats", type=int, default=REPEATS,
-                    help="fenced timed regions of exactly --steps steps each; `value` is the median region, value_min / value_max the extremes")
+    ap.add_argument("--repeats", type=int, default=None,
+                    help="fenced timed regions of exactly --steps steps each; `value` is the median region, value_min / value_max the extremes "
+                         "(default: 1, so that --steps is the number of timed steps; %d with --full)" % REPEATS)
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside `value`: the CPU replay of sampled envs (max_qpos_err, parity), the legs of the other modes / "
+                         "configurations, the drop-in API, the CPU baseline and the true reference")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path computed in its last step as DIR/<name>.npy (float64, "
+                         "one row per env; a fixed seeded sample of the envs above 64 MB in all)")
     ap.add_argument("--streams", type=int, default=STREAMS,
                     help="a rank's batch is stepped as this many contiguous env ranges, each on its own stream at its own pace "
                          "(1 = the whole batch in one launch per policy step)")
@@ -877,6 +933,11 @@ def main(argv=None):
     from cassie_amd import Model
 
     model = Model(args.model)
+    if args.full and not args.dry_run_cpu:
+        from cassie_amd._lib import lib
+        if hasattr(lib(), "cassie_agility_blocks_absent"):
+            raise SystemExit("--full needs the closed Agility blocks (the drop-in API's leg, the safety layer's CPU replay), and this "
+                             "build of the library was linked without them (Makefile: AGILITY_ABSENT)")
     if args.hfield_contacts == "prism":
         if args.model != "cassie_hfield":
             raise SystemExit("--hfield-contacts prism applies to --model cassie_hfield")
@@ -887,14 +948,17 @@ def main(argv=None):
         model.set_flag(_P.FLAG_BOX8, True)      # box-box keeps up to eight points like MuJoCo's mjc_BoxBox
     pod = model.pod
     n, scaling, shape = resolve_envs(world, args.envs_per_gpu, args.total_envs)
-    repeats = max(1, args.repeats)
+    repeats = max(1, args.repeats if args.repeats is not None else (REPEATS if args.full else 1))
     hfield = None
     if args.model == "cassie_hfield":   # terrain of reference example/test_hfield.py:39-41, shared by all envs
         hfield = np.random.default_rng(99).random((200, 200)).astype(np.float32)
         hfield[95:105, 95:105] = 0
     nstreams = max(1, args.streams)
     r = device_rollout(model, args.mode, n, args.steps, args.warmup, rank, world, local_rank, args.substeps_per_launch, args.parity_envs, hfield,
-                       collect=collect, repeats=repeats, nstreams=nstreams, rt=rt, randomise=args.randomise if world == 1 else None)
+                       collect=collect, repeats=repeats, nstreams=nstreams, rt=rt, randomise=args.randomise if world == 1 else None,
+                       parity=args.full, outputs=args.dump_outputs is not None)
+    if rank == 0 and args.dump_outputs is not None:
+        dump_outputs(args.dump_outputs, r["outputs"])
 
     if rank == 0:
         elapsed, kern_ms, timed_launches = r["elapsed"], r["kernel_ms"], r["launches"]
@@ -924,12 +988,12 @@ def main(argv=None):
         out = {
             "metric": "env-steps/sec (whole node) at N envs; max |qpos_err| vs CPU ref", "value": value, "unit": "env-steps/s",
             "value_min": rate(max(r["region_s"])), "value_max": rate(min(r["region_s"])),
-            "max_qpos_err": r["parity"]["max_qpos_err"], "max_qpos_rel_err": r["parity"]["max_qpos_rel_err"],
+            **({"max_qpos_err": r["parity"]["max_qpos_err"], "max_qpos_rel_err": r["parity"]["max_qpos_rel_err"]} if args.full else {}),
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": 1e3 * elapsed / args.steps,
             "higher_is_better": True, "scaling": scaling, "vs_baseline": None, "dtype": "f64",
             "data": "synthetic" if not args.dry_run_cpu else rt.name,
             "config": {"workload": "READ FIRST -- `value` is the device-resident API (phys_batch_step_range, mode `%s`: see api_of_value), the batch stepped as %d "
-                                   "env ranges on %d streams that nothing joins between policy steps; beside it in this line: `value_step_pd` = "
+                                   "env ranges on %d streams that nothing joins between policy steps; beside it in this line (with --full): `value_step_pd` = "
                                    "cassie_sim_step_pd itself, batched (the API BASELINE configs[1] names; Agility blocks on host threads, PCIe every "
                                    "step), `value_one_stream` = the whole batch as ONE launch per policy step, `value_all_outputs_every_substep` = "
                                    "every output of every P-row formed by every substep.  Workload: %d envs/GPU x %d GPU = %d envs (%s), %s.xml, "
@@ -959,7 +1023,7 @@ def main(argv=None):
                                               "body quaternions of the substeps in between, which nobody can read, are not formed -- "
                                               "`value_all_outputs_every_substep` is the rate with every output of every P-row formed by every substep",
                        "preroll_steps": PREROLL, "episode_steps": EPISODE},
-            "parity": r["parity"],
+            **({"parity": r["parity"]} if args.full else {}),
             **({"safety_messages": r["safety_messages"]} if r.get("safety_messages") else {}),
             "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
                          "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_src,
@@ -997,7 +1061,7 @@ def main(argv=None):
             "frac_envs_in_the_127_row_pass_in_the_last_launch": (r.get("wide_pass_envs_last_launch") / float(n)) if r.get("wide_pass_envs_last_launch") is not None else None,
             "mean_constraint_rows": r["mean_constraint_rows"], "mean_pgs_iterations": r["mean_pgs_iterations"], "mean_pgs_guarded_sweeps": r["mean_pgs_guarded_sweeps"],
         }
-        if world == 1 and args.model == "cassie" and args.total_envs is None and not args.dry_run_cpu:
+        if args.full and world == 1 and args.model == "cassie" and args.total_envs is None and not args.dry_run_cpu:
             # the GPU legs first, back to back with the timed region; the CPU legs (tens of seconds with an idle GPU) last
             if not args.no_other_mode:
                 other = "exact-pd" if args.mode != "exact-pd" else "drive-pd-safe"
@@ -1048,7 +1112,7 @@ def main(argv=None):
                 out["cpu_baseline"] = cpu_baseline(model)
             tsample = np.arange(8)
             out["true_reference"] = true_reference(args.model, model.qpos_init(), pd_targets(tsample, EPISODE // HOLD + 1), EPISODE)
-        elif world == 1 and args.total_envs is None and not args.dry_run_cpu and not args.no_cpu_baseline:
+        elif args.full and world == 1 and args.total_envs is None and not args.dry_run_cpu and not args.no_cpu_baseline:
             if args.model == "cassie_hfield" and args.hfield_contacts == "default" and not args.no_other_mode:
                 # config 4 carries BOTH height-field contact definitions: `value` is the default one (one contact per geom pair, the
                 # deepest sample), this leg the MuJoCo-shaped set (CM_FLAG_HFPRISM: one contact per penetrated grid triangle, up to 32
@@ -1067,7 +1131,7 @@ def main(argv=None):
                                                 "what": "CM_FLAG_HFPRISM: MuJoCo's per-prism height-field contact set; off by default (DESIGN.md 4.2, 7.3)"}
                 out["value_hfield_contacts_prism"] = out["hfield_contacts_prism"]["value"]
             out["cpu_baseline"] = cpu_baseline(model, hfield=hfield)      # configs 4 / 5: the oracle on this box's cores, same workload
-        elif world > 1 and not args.no_cpu_baseline:
+        elif args.full and world > 1 and not args.no_cpu_baseline:
             # N > 1 (a SCALE line): rank 0 alone times the CPU oracle on the node's host cores, after the timed regions, while the
             # other ranks wait at the barrier below -- the line must not read as unmeasured for want of the key
             out["cpu_baseline"] = cpu_baseline(model, budget_s=1.0 if args.dry_run_cpu else 12.0, hfield=hfield)

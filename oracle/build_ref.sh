@@ -6,7 +6,8 @@
 #     constants and types, the NUM_* defines, and the functions drive_encoder / joint_encoder / motor),
 #     written to oracle/_ref/ref_extract.inc at build time and compiled inside oracle/ref_hostpath_harness.c,
 #     which supplies the few mjModel / mjData fields those functions touch;
-#   * the Agility blocks come from src/libagilitycassie.a (closed binary, whole-archived).
+#   * the Agility blocks come from src/libagilitycassie.a (closed binary, whole-archived); a copy of the archive is
+#     staged as oracle/_ref/libagilitycassie.a, from which the Makefile links the product where the reference is absent.
 # The full reference library cannot be built: it needs MuJoCo 2.1.0 headers and binaries.
 set -e
 REF=${REF:-/root/reference}
@@ -14,6 +15,8 @@ HERE=$(cd "$(dirname "$0")" && pwd)
 SRC=$REF/src/cassiemujoco.c
 [ -f "$SRC" ] || { echo "reference not present at $REF: nothing to build"; exit 0; }
 mkdir -p "$HERE/_ref"
+# The closed Agility archive itself, staged for the product's link where the reference tree is absent (Makefile: AGILITY_STAGED).
+cp "$REF/src/libagilitycassie.a" "$HERE/_ref/libagilitycassie.a"
 {
   sed -n '/^#define DRIVE_FILTER_NB/,/^} joint_filter_t;/p' "$SRC"
   grep -E '^#define (NUM_DRIVES|NUM_JOINTS|TORQUE_DELAY_CYCLES) ' "$SRC"

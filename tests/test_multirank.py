@@ -220,7 +220,7 @@ def test_bench_main_starts_its_own_ranks_and_prints_one_line_for_all_of_them():
     import subprocess
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "2", "--steps", "60", "--warmup", "20", "--repeats", "2",
-           "--envs-per-gpu", "48", "--parity-envs", "12", "--dry-run-cpu"]
+           "--envs-per-gpu", "48", "--parity-envs", "12", "--dry-run-cpu", "--full"]
     out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith('{"metric"')]

@@ -1,5 +1,5 @@
 # A/B inside one lease, library variants (VARIANTS="tree prev"): config 4 with the default and with the prism contact definition
-B="--no-cpu-baseline --no-step-pd --no-other-mode --no-randomised --steps 500 --repeats 4 --model cassie_hfield"
+B="--full --no-cpu-baseline --no-step-pd --no-other-mode --no-randomised --steps 500 --repeats 4 --model cassie_hfield"
 for rep in 1 2; do for def in default prism; do for v in ${VARIANTS:-tree prev}; do
 if [ $v = tree ]; then unset CASSIE_LIB; else export CASSIE_LIB=$PWD/cassie-mujoco-sim_amd/lib/variants/libcassiemujoco_$v.so; fi
 python bench.py $B --hfield-contacts $def 2>/dev/null | grep '^{' > gpurun_out/t.json; python -c "

@@ -1,5 +1,5 @@
 # A/B of the fast kernel's form inside one lease, alternating: plain (kernel + list-walking pass), in place, auto (per range; the default)
-B="--no-cpu-baseline --no-step-pd --no-other-mode --no-randomised --steps 500 --repeats 6"
+B="--full --no-cpu-baseline --no-step-pd --no-other-mode --no-randomised --steps 500 --repeats 6"
 run() { python bench.py $@ $B 2>/dev/null | grep '^{' > gpurun_out/t.json; python -c "
 import json,sys; d=json.load(open('gpurun_out/t.json')); print('%-50s %7.3f M (min %.3f max %.3f) err %.1e kernel_ms %.3f stream_ms %.3f launches plain/in place %s' % (' '.join(sys.argv[1:]), d['value']/1e6, d['value_min']/1e6, d['value_max']/1e6, d['max_qpos_rel_err'], d['roofline']['kernel_ms'], d['roofline']['stream_ms_per_policy_step'], d.get('fast_kernel_launches_plain_in_place')))" "$@"; }
 for rep in 1 2; do

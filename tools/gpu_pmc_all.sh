@@ -1,6 +1,7 @@
 # PMC passes of the bench's dominant kernel (separate --pmc runs with --kernel-trace only, as gpurun requires), then
-# tools/pmc_summary.py reduces the CSVs to gpurun_out/pmc_summary.json.  MODE=exact-pd|drive-pd (default drive-pd).
-mkdir -p gpurun_out/pmc; cd /tmp; export TMPDIR=/tmp
+# tools/pmc_summary.py reduces the CSVs to $OUT/pmc_summary.json (OUT: the folder the run's files go to).  MODE=exact-pd|drive-pd (default drive-pd).
+OUT=${OUT:-build/runs}
+mkdir -p $OUT/pmc; cd /tmp; export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT
 CMD="python $R/bench.py ${MODEL:+--model $MODEL} --mode ${MODE:-drive-pd} --streams 1 --steps 100 --warmup 50 --no-cpu-baseline --no-step-pd --no-other-mode --parity-envs 4"
 i=0
@@ -13,8 +14,8 @@ for set in "SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE
            "SQ_INSTS_VALU_ADD_F32 SQ_INSTS_VALU_MUL_F32 SQ_INSTS_VALU_FMA_F32 SQ_INSTS_VALU_TRANS_F32 SQ_INSTS_BRANCH SQ_INSTS_VSKIPPED SQ_INSTS_LDS_LOAD SQ_INSTS_LDS_STORE"; do
   i=$((i+1))
   [ -n "$ONLY" ] && ! echo " $ONLY " | grep -q " $i " && continue   # (ONLY="1 8 9": the totals and the instruction-class passes)
-  timeout 600 rocprofv3 --kernel-trace --pmc $set --output-format csv -d $R/gpurun_out/pmc/p$i -- $CMD > $R/gpurun_out/pmc/p$i.log 2>&1
+  timeout 600 rocprofv3 --kernel-trace --pmc $set --output-format csv -d $R/$OUT/pmc/p$i -- $CMD > $R/$OUT/pmc/p$i.log 2>&1
 done
 cd $R
-python tools/pmc_summary.py gpurun_out/pmc > gpurun_out/pmc_summary.json
-cat gpurun_out/pmc_summary.json | head -70
+python tools/pmc_summary.py $OUT/pmc > $OUT/pmc_summary.json
+cat $OUT/pmc_summary.json | head -70

@@ -1,4 +1,4 @@
-B="--no-cpu-baseline --no-step-pd --no-other-mode --no-randomised --steps 500 --repeats 4 --model cassie_hfield --hfield-contacts prism"
+B="--full --no-cpu-baseline --no-step-pd --no-other-mode --no-randomised --steps 500 --repeats 4 --model cassie_hfield --hfield-contacts prism"
 for rep in 1 2; do for v in ${VARIANTS:-tree widev1}; do
 if [ $v = tree ]; then unset CASSIE_LIB; else export CASSIE_LIB=$PWD/cassie-mujoco-sim_amd/lib/variants/libcassiemujoco_$v.so; fi
 python bench.py $B 2>/dev/null | grep '^{' > gpurun_out/t.json; python -c "
