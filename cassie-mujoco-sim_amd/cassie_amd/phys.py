@@ -33,7 +33,8 @@ WARN_CONTACT_FULL, WARN_CONSTRAINT_FULL, WARN_UNSUPPORTED_PAIR, WARN_DIVERGED = 
 WARN_CHUNK_PLACEMENT = 16   # a chunk of a stepping launch found its predecessor on another XCD: the env's state may be stale, discard its results
 
 # per-env physical parameters (CM_P_* in cm_model.h): what Batch.randomize takes
-P_BODY_MASS, P_BODY_IPOS, P_BODY_INERTIA, P_DOF_DAMPING, P_GEOM_FRICTION = range(5)
+(P_BODY_MASS, P_BODY_IPOS, P_BODY_INERTIA, P_DOF_DAMPING, P_GEOM_FRICTION,
+ P_GEOM_POS, P_GEOM_QUAT, P_JNT_STIFFNESS, P_QPOS_SPRING) = range(9)
 # views of the host model's arrays (PHYS_M_* in cassie_phys.h) that Model.array hands out
 (M_BODY_MASS, M_BODY_IPOS, M_BODY_POS, M_BODY_QUAT, M_DOF_DAMPING, M_JNT_STIFFNESS, M_QPOS_SPRING, M_GEOM_POS, M_GEOM_QUAT,
  M_GEOM_SIZE, M_GEOM_FRICTION, M_ACTUATOR_GEAR, M_ACTUATOR_CTRLRANGE, M_ACTUATOR_USER, M_SENSOR_USER, M_HFIELD_SIZE, M_TIMESTEP,
@@ -172,10 +173,16 @@ class Batch:
 
     def randomize(self, param, values, env0=0, device_ptr=None, n=None, stream=None):
         """Per-env physical parameters (P_BODY_MASS [nbody], P_BODY_IPOS [nbody*3], P_BODY_INERTIA [nbody*3], P_DOF_DAMPING [nv],
-        P_GEOM_FRICTION [pod.ngeom*3], collision geoms in compiled order) for envs env0 ...: `values` is a host array
-        [n][dim], or pass `device_ptr` (+ n) to read rows that are already in HBM (a torch tensor's data_ptr()).  Masses /
-        inertial offsets / inertias: follow with set_const()."""
+        P_GEOM_FRICTION [pod.ngeom*3], P_GEOM_POS [pod.ngeom*3], P_GEOM_QUAT [pod.ngeom*4], P_JNT_STIFFNESS [njnt],
+        P_QPOS_SPRING [nq]; geoms are the collision geoms in compiled order, pod.geom_fullid maps them to the full list) for envs
+        env0 ...: `values` is a host array [n][dim], or pass `device_ptr` and n to read rows that are already in HBM (a torch
+        tensor's data_ptr()).  Masses / inertial offsets / inertias: follow with set_const().  Geometry (unit quaternions
+        expected: they are not normalised) and springs act from the next step on with no set_const().
+        The rows are written in order on `stream` (default: the batch's own): ranges stepped on other streams must be joined
+        with it first."""
         if device_ptr is not None:
+            if n is None:
+                raise ValueError("randomize: device_ptr needs n, the number of rows to read")
             rc = lib().phys_batch_randomize(self._h, int(param), device_ptr, 1, int(env0), int(n), stream)
         else:
             a = np.ascontiguousarray(values, dtype=np.float64).reshape(-1, self.param_dim(param))

@@ -115,9 +115,10 @@ typedef struct cm_kinrec {
  * (reference :949-977: the inverse weights at qpos0 behind the constraint regularisers, the mean inertia behind the solver's
  * tolerance), already denormalised into the per-joint / per-equality / per-pair values the constraint stages read.  The
  * step kernel reads THESE fields through one pointer per env: cm_model_t::params of the shared model, or the env's own
- * block (PhysIO::envparams, [nenv], 10 KB each) once phys_batch_randomize has been used -- the other 95 KB of the model
- * stay shared.  The first five arrays are the inputs (phys_batch_randomize), the rest is written by the device's set_const
- * kernel (phys_batch_set_const) or, for the model's own block, by the host compile. */
+ * block (PhysIO::envparams, [nenv], 15.5 KB each) once phys_batch_randomize has been used -- the rest of the model stays
+ * shared.  The first five arrays and the four of the geometry / spring group are the inputs (phys_batch_randomize), the rest is
+ * written by the device's set_const kernel (phys_batch_set_const, or phys_batch_randomize itself for friction, geometry and
+ * springs) or, for the model's own block, by the host compile. */
 typedef struct cm_envparams {
     double body_mass[CM_MAXBODY];
     double body_ipos[CM_MAXBODY][3];
@@ -132,9 +133,21 @@ typedef struct cm_envparams {
     double eq_invweight[CM_MAXEQ];
     double pair_invweight[CM_MAXPAIR];
     double pair_friction[CM_MAXPAIR][3];
+    /* geometry and springs (appended: the offsets above stay put).  Inputs: where the collision geoms sit in their bodies (compiled
+     * order, like geom_friction), the joints' spring stiffness and the qpos the springs pull towards (reference
+     * cassie_sim_set_geom_name_pos / _quat, src/cassiemujoco.c:1478-1537; jnt_stiffness / qpos_spring through the raw model) */
+    double geom_pos[CM_MAXGEOM][3], geom_quat[CM_MAXGEOM][4];
+    double jnt_stiffness[CM_MAXJNT], qpos_spring[CM_MAXQ];
+    /* derived from them (the set_const kernel, at once on phys_batch_randomize): geom_quat as a matrix, the kinematic trees' reach
+     * behind the block cull of far static geoms, the per-dof spring records of the passive stage.  The step kernel reads these five
+     * arrays from the env's block only once the batch has randomised geometry / springs (cm_model_t::env_geom / env_springs) */
+    double geom_mat[CM_MAXGEOM][9];
+    double body_reach[CM_MAXBODY];
+    double dof_stiffness[CM_MAXV], dof_springref[CM_MAXV];
 } cm_envparams_t;
 /* the inputs of a cm_envparams_t, as phys_batch_randomize names them */
-enum { CM_P_BODY_MASS = 0, CM_P_BODY_IPOS = 1, CM_P_BODY_INERTIA = 2, CM_P_DOF_DAMPING = 3, CM_P_GEOM_FRICTION = 4, CM_P_COUNT = 5 };
+enum { CM_P_BODY_MASS = 0, CM_P_BODY_IPOS = 1, CM_P_BODY_INERTIA = 2, CM_P_DOF_DAMPING = 3, CM_P_GEOM_FRICTION = 4,
+       CM_P_GEOM_POS = 5, CM_P_GEOM_QUAT = 6, CM_P_JNT_STIFFNESS = 7, CM_P_QPOS_SPRING = 8, CM_P_COUNT = 9 };
 
 typedef struct cm_model {
     /* sizes */
@@ -283,6 +296,11 @@ typedef struct cm_model {
     int dof_trans0[CM_MAXV];
     /* the model's own parameter block: what every env uses until it is given one of its own */
     cm_envparams_t params;
+    /* Where the step kernel reads geometry (geom_pos / geom_mat / body_reach) and springs (dof_stiffness / dof_springref): 0 = this
+     * block, `params`, whose lines every env of a shared model reads; 1 = the env's own cm_envparams_t (PhysIO::envparams; no effect
+     * while a launch has none).  The compile leaves both 0; phys_batch_randomize sets them on the batch's shared model once it has
+     * randomised geometry / springs -- until then an env does not read ~12 doubles per collision geom and substep from its own block. */
+    int env_geom, env_springs;
 } cm_model_t;
 
 /* A cm_model_t handed over by a caller may have been edited field by field (tests and tools do: a heavier pelvis, another
@@ -305,6 +323,15 @@ static inline void cm_model_sync_params(cm_model_t *m) {
         p->pair_invweight[i] = m->pair_invweight[i];
         for (k = 0; k < 3; ++k) p->pair_friction[i][k] = m->pair_friction[i][k];
     }
+    for (i = 0; i < CM_MAXGEOM; ++i) {
+        for (k = 0; k < 3; ++k) p->geom_pos[i][k] = m->geom_pos[i][k];
+        for (k = 0; k < 4; ++k) p->geom_quat[i][k] = m->geom_quat[i][k];
+        for (k = 0; k < 9; ++k) p->geom_mat[i][k] = m->geom_mat[i][k];
+    }
+    for (i = 0; i < CM_MAXJNT; ++i) p->jnt_stiffness[i] = m->jnt_stiffness[i];
+    for (i = 0; i < CM_MAXQ; ++i) p->qpos_spring[i] = m->qpos_spring[i];
+    for (i = 0; i < CM_MAXBODY; ++i) p->body_reach[i] = m->body_reach[i];
+    for (i = 0; i < CM_MAXV; ++i) { p->dof_stiffness[i] = m->dof_stiffness[i]; p->dof_springref[i] = m->dof_springref[i]; }
 }
 
 /* Drive-level I/O state of one env: what `struct cassie_sim` keeps beside mjData for cassie_sim_step_ethercat

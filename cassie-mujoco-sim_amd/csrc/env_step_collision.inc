@@ -55,7 +55,7 @@
                     const int r = m->root_body[ri];
                     double dv[3] = {S.x.s.geom_xpos[lane][0] - S.x.s.xpos[r][0], S.x.s.geom_xpos[lane][1] - S.x.s.xpos[r][1],
                                     S.x.s.geom_xpos[lane][2] - S.x.s.xpos[r][2]};
-                    const double bound = m->body_reach[r] + rb + 0.01;
+                    const double bound = PG->body_reach[r] + rb + 0.01;
                     if (dot3(dv, dv) < bound * bound) nearby = true;
                 }
             }

@@ -55,7 +55,7 @@
                 CK_STAMP(4);
                 {
                     const int kd = isdof ? k_ : 0;
-                    const double kdamp = P->dof_damping[kd], kstiff = m->dof_stiffness[kd], kref = m->dof_springref[kd];
+                    const double kdamp = P->dof_damping[kd], kstiff = PS->dof_stiffness[kd], kref = PS->dof_springref[kd];
                     const double kgear = m->dof_gear[kd], klo = m->dof_ctrl_lo[kd], khi = m->dof_ctrl_hi[kd];
                     const int kq = m->dof_qadr[kd], ka = m->dof_act[kd];
                     wv::wait_for(&S.cmd[1], sub1 + 1); /* wave 0's velocity stage has the body forces (cfrc) in LDS */

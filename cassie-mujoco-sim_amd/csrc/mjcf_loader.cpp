@@ -1427,6 +1427,15 @@ bool HostModel::compile(cm_model_t *o, std::string *err) const {
             p->pair_invweight[i] = o->pair_invweight[i];
             for (int k = 0; k < 3; ++k) p->pair_friction[i][k] = o->pair_friction[i][k];
         }
+        for (int g = 0; g < o->ngeom; ++g) {
+            for (int i = 0; i < 3; ++i) p->geom_pos[g][i] = o->geom_pos[g][i];
+            for (int i = 0; i < 4; ++i) p->geom_quat[g][i] = o->geom_quat[g][i];
+            for (int i = 0; i < 9; ++i) p->geom_mat[g][i] = o->geom_mat[g][i];
+        }
+        for (int j = 0; j < njnt; ++j) p->jnt_stiffness[j] = o->jnt_stiffness[j];
+        for (int i = 0; i < nq; ++i) p->qpos_spring[i] = o->qpos_spring[i];
+        for (int b = 0; b < nbody; ++b) p->body_reach[b] = o->body_reach[b];
+        for (int d = 0; d < nv; ++d) { p->dof_stiffness[d] = o->dof_stiffness[d]; p->dof_springref[d] = o->dof_springref[d]; }
     }
     return true;
 }

@@ -420,6 +420,7 @@ phys_batch_t *phys_batch_create(const cm_model_t *model, int nenv, int device) {
     if (const char *tw = getenv("CASSIE_TRAY_TWO_WAVES")) b->waves_per_env_tray = atoi(tw) ? 2 : 1;
     b->host_model = *model;
     cm_model_sync_params(&b->host_model);
+    b->host_model.env_geom = 0; b->host_model.env_springs = 0; /* (no blocks yet: the model's own geometry and springs) */
     model = &b->host_model;
     const int d[PHYS_F_COUNT] = {model->nq, model->nv, model->nv, 1, model->nu, model->nv, model->nbody * 6,
                                  model->nv, model->nsensordata, model->nu, model->nbody * 3, model->nbody * 4,
@@ -532,6 +533,7 @@ int phys_batch_set_model(phys_batch_t *b, const cm_model_t *model, int env) {
     if (!quiesce(b)) return -1;
     cm_model_t synced = *model;     /* (the caller's top-level arrays are the authority: cm_model_sync_params) */
     cm_model_sync_params(&synced);
+    synced.env_geom = 0; synced.env_springs = 0; /* (a new model drops the blocks; per-env models have none) */
     model = &synced;
     if (env < 0) {
         if (b->d_envparams) { (void)hipFree(b->d_envparams); b->d_envparams = nullptr; } /* (the new model's own block again, for every env) */
@@ -883,10 +885,18 @@ int phys_batch_derive(phys_batch_t *b, const int ids[6], void *stream) {
 /* ------------------------------------------------ per-env physical parameters ---- */
 static const struct { size_t off; int per; } PARAM_TABLE[CM_P_COUNT] = {
     {offsetof(cm_envparams_t, body_mass), 1}, {offsetof(cm_envparams_t, body_ipos), 3}, {offsetof(cm_envparams_t, body_inertia), 3},
-    {offsetof(cm_envparams_t, dof_damping), 1}, {offsetof(cm_envparams_t, geom_friction), 3}};
+    {offsetof(cm_envparams_t, dof_damping), 1}, {offsetof(cm_envparams_t, geom_friction), 3},
+    {offsetof(cm_envparams_t, geom_pos), 3}, {offsetof(cm_envparams_t, geom_quat), 4}, {offsetof(cm_envparams_t, jnt_stiffness), 1},
+    {offsetof(cm_envparams_t, qpos_spring), 1}};
 static int param_count(const phys_batch *b, int param) {
     const cm_model_t &m = b->host_model;
-    return param == CM_P_DOF_DAMPING ? m.nv : param == CM_P_GEOM_FRICTION ? m.ngeom : m.nbody;
+    switch (param) {
+        case CM_P_DOF_DAMPING: return m.nv;
+        case CM_P_GEOM_FRICTION: case CM_P_GEOM_POS: case CM_P_GEOM_QUAT: return m.ngeom;
+        case CM_P_JNT_STIFFNESS: return m.njnt;
+        case CM_P_QPOS_SPRING: return m.nq;
+        default: return m.nbody;
+    }
 }
 int phys_batch_param_dim(const phys_batch_t *b, int param) {
     return (b && param >= 0 && param < CM_P_COUNT) ? param_count(b, param) * PARAM_TABLE[param].per : 0;
@@ -911,6 +921,14 @@ static int launch_setconst(phys_batch *b, int env0, int n, int derive_inertial, 
     hipLaunchKernelGGL(ck::cassie_setconst_kernel, dim3((unsigned)(n < 2048 ? n : 2048)), dim3(WV_WAVE), 0, s, io);
     return hip_ok(hipGetLastError(), "cassie_setconst_kernel launch") ? 0 : -1;
 }
+/* the shared model's cm_model_t::env_geom / env_springs word (at `off`): from now on the step kernel reads that group from the blocks
+ * (in order on `s`, behind the rows and their re-derive) */
+static int read_from_blocks(phys_batch *b, int *host_word, size_t off, hipStream_t s) {
+    static const int one = 1;
+    if (*host_word) return 0;
+    *host_word = 1;
+    return hip_ok(hipMemcpyAsync((char *)b->d_models + off, &one, sizeof one, hipMemcpyHostToDevice, s), "hipMemcpy(model word)") ? 0 : -1;
+}
 int phys_batch_randomize(phys_batch_t *b, int param, const double *values, int on_device, int env0, int n, void *stream) {
     if (!b || !values || param < 0 || param >= CM_P_COUNT || env0 < 0 || n < 0 || env0 + n > b->nenv) { phys_set_last_error("phys_batch_randomize: bad arguments"); return -1; }
     (void)hipSetDevice(b->device);
@@ -931,9 +949,19 @@ int phys_batch_randomize(phys_batch_t *b, int param, const double *values, int o
                        (int)(PARAM_TABLE[param].off / sizeof(double)), dim, src, env0, n);
     int rc = hip_ok(hipGetLastError(), "cassie_param_scatter_kernel launch") ? 0 : -1;
     /* friction needs no set_const in the reference (mj_contactParam mixes the geoms' values at every step): the pairs' mixed
-     * values are refreshed right away; so is nothing else -- masses, inertial offsets and inertias wait for phys_batch_set_const
-     * like mjModel edits wait for mj_setConst, damping takes effect as it is */
-    if (rc == 0 && param == CM_P_GEOM_FRICTION) rc = launch_setconst(b, env0, n, 0, s);
+     * values are refreshed right away; so are geometry (MuJoCo's kinematics reads geom_pos / geom_quat at every step) and springs
+     * (mj_passive reads jnt_stiffness / qpos_spring): their derived records follow at once, and the step kernel reads those of
+     * the blocks from now on; nothing else is -- masses, inertial offsets and inertias wait for phys_batch_set_const like
+     * mjModel edits wait for mj_setConst, damping takes effect as it is */
+    if (rc == 0 && param == CM_P_GEOM_FRICTION) rc = launch_setconst(b, env0, n, ck::SETCONST_FRICTION, s);
+    if (rc == 0 && (param == CM_P_GEOM_POS || param == CM_P_GEOM_QUAT)) {
+        rc = launch_setconst(b, env0, n, ck::SETCONST_GEOMETRY, s);
+        if (rc == 0) rc = read_from_blocks(b, &b->host_model.env_geom, offsetof(cm_model_t, env_geom), s);
+    }
+    if (rc == 0 && (param == CM_P_JNT_STIFFNESS || param == CM_P_QPOS_SPRING)) {
+        rc = launch_setconst(b, env0, n, ck::SETCONST_SPRINGS, s);
+        if (rc == 0) rc = read_from_blocks(b, &b->host_model.env_springs, offsetof(cm_model_t, env_springs), s);
+    }
     if (staged) { if (!hip_ok(hipStreamSynchronize(s), "randomize sync")) rc = -1; (void)hipFree(staged); }
     return rc;
 }
@@ -942,7 +970,7 @@ int phys_batch_set_const(phys_batch_t *b, int env0, int n, void *stream) {
     (void)hipSetDevice(b->device);
     if (!ensure_envparams(b)) return -1;
     if (n == 0) return 0;
-    return launch_setconst(b, env0, n, 1, stream ? (hipStream_t)stream : b->stream);
+    return launch_setconst(b, env0, n, ck::SETCONST_ALL, stream ? (hipStream_t)stream : b->stream);
 }
 int phys_batch_download_params(phys_batch_t *b, cm_envparams_t *host, int env0, int n) {
     if (!b || !host || env0 < 0 || n < 0 || env0 + n > b->nenv) return -1;

@@ -110,6 +110,9 @@ WV_DEVICE int env_step(const PhysIO &io, EnvShared<NVP, LPack<TOPO, NVP>::count,
     ModelPtr m = m_launch;
     /* the env's physical parameters: its own block, or the model's (wave-uniform either way: scalar loads) */
     const ParamPtr P = io.envparams ? (ParamPtr)(io.envparams + (size_t)env) : (ParamPtr)&m_launch->params;
+    /* ... of which geometry and springs come from the env's block only once the batch has randomised them (cm_model_t::env_geom /
+     * env_springs of the shared model: uniform per launch) */
+    const ParamPtr PG = m_launch->env_geom ? P : (ParamPtr)&m_launch->params, PS = m_launch->env_springs ? P : (ParamPtr)&m_launch->params;
     int lane = wv::lane();
     const int nq = m->nq, nv = m->nv, nu = m->nu, nbody = m->nbody, njnt = m->njnt;
     /* rows / contacts a substep may use: what this instantiation holds, within the model's caps (cm_model_t::maxefc / maxcon) */
@@ -365,8 +368,8 @@ WV_DEVICE int env_step(const PhysIO &io, EnvShared<NVP, LPack<TOPO, NVP>::count,
         const int pf_jpb = lane < njnt ? m->jnt_parentbody[lane] : -1, pf_gb = m->geom_bodyid[pf_gs];
         const double pf_mass = P->body_mass[pf_b];
         double pf_ipos[3], pf_imat[9], pf_iner[3], pf_gpos[3], pf_gmat[9];
-        for (int i = 0; i < 3; ++i) { pf_ipos[i] = P->body_ipos[pf_b][i]; pf_iner[i] = P->body_inertia[pf_b][i]; pf_gpos[i] = m->geom_pos[pf_gs][i]; }
-        for (int i = 0; i < 9; ++i) { pf_imat[i] = m->body_imat[pf_b][i]; pf_gmat[i] = m->geom_mat[pf_gs][i]; }
+        for (int i = 0; i < 3; ++i) { pf_ipos[i] = P->body_ipos[pf_b][i]; pf_iner[i] = P->body_inertia[pf_b][i]; pf_gpos[i] = PG->geom_pos[pf_gs][i]; }
+        for (int i = 0; i < 9; ++i) { pf_imat[i] = m->body_imat[pf_b][i]; pf_gmat[i] = PG->geom_mat[pf_gs][i]; }
         /* recursion over the tree by radix-3 pointer jumping: in round r every body composes its partial transform with
          * those of its 3^r-th and 2 * 3^r-th ancestors, after which it holds the product of the local transforms of its
          * 3^(r+1) nearest ancestors-or-self -- two LDS round trips for Cassie's nine levels where doubling needed four, for
@@ -506,7 +509,7 @@ WV_DEVICE int env_step(const PhysIO &io, EnvShared<NVP, LPack<TOPO, NVP>::count,
         if (!isbody) blast = -1;
         if (!isdof) kvin = -1;
         const int kd = isdof ? k_ : 0;
-        const double kdamp = P->dof_damping[kd], kstiff = m->dof_stiffness[kd], kref = m->dof_springref[kd];
+        const double kdamp = P->dof_damping[kd], kstiff = PS->dof_stiffness[kd], kref = PS->dof_springref[kd];
         const double kgear = m->dof_gear[kd], klo = m->dof_ctrl_lo[kd], khi = m->dof_ctrl_hi[kd];
         const int kq = m->dof_qadr[kd], ka = m->dof_act[kd];
         auto chain_sums = [&](double (&acc)[6]) { /* acc: this dof's term in, its chain sum out; tile: buf */

@@ -238,12 +238,18 @@ struct SetConstShared {
     double bw[CM_MAXBODY][2], dinv[CM_MAXV], dw[CM_MAXV];
     double piv;
     int ok;
+    double glen[CM_MAXGEOM];      /* geometry: each collision geom's distance bound from its tree's root body */
 };
+/* what a launch of the set_const kernel re-derives (SetConstIO::derive_inertial) */
+enum { SETCONST_FRICTION = 0,     /* the pairs' mixed friction (phys_batch_randomize of CM_P_GEOM_FRICTION) */
+       SETCONST_ALL = 1,          /* everything: inverse weights, mean inertia, the pair tables, geometry and springs (phys_batch_set_const) */
+       SETCONST_GEOMETRY = 2,     /* geom_mat and body_reach only (CM_P_GEOM_POS / CM_P_GEOM_QUAT) */
+       SETCONST_SPRINGS = 3 };    /* dof_stiffness and dof_springref only (CM_P_JNT_STIFFNESS / CM_P_QPOS_SPRING) */
 struct SetConstIO {
     const cm_model_t *model;      /* the shared model (topology, kinematics at qpos0, armature, pair / equality tables) */
     cm_envparams_t *params;       /* [nenv] blocks, indexed by the absolute env */
     int env0, nenv;               /* the range to (re)derive */
-    int derive_inertial;          /* 0: only the friction / pair tables (phys_batch_randomize of CM_P_GEOM_FRICTION); 1: all */
+    int derive_inertial;          /* a SETCONST_* value (0 and 1 as before the geometry / spring modes existed) */
 };
 
 /* Jacobian column of dof d for a world point p attached to body b (HostKin::jac): translational part jp, rotational jr */
@@ -272,6 +278,75 @@ WV_DEVICE void setconst_chol_solve(const SetConstShared &S, int n, double *x) {
     }
 }
 
+/* |v| of a 3-vector, as the host compile's sqrt(x x + y y + z z) */
+WV_DEVICE double setconst_norm3(double x, double y, double z) {
+    return wv::sqrt_rn(wv::add_rn(wv::add_rn(wv::mul_rn(x, x), wv::mul_rn(y, y)), wv::mul_rn(z, z)));
+}
+/* Geometry of an env (lane = collision geom, then lane = body): geom_mat = the host compile's quat2mat of geom_quat (no
+ * normalisation, like phys_model_compile), and body_reach = for every tree root the largest distance bound of the tree's collision
+ * geoms -- |geom_pos| + rbound, plus |body_pos| and 2 |jnt_pos| of every body / joint on the way to the root, unbounded past a slide
+ * or free joint below the root, plus 2 |jnt_pos| of the root's own joints (HostModel::compile, the same additions in the same order).
+ * (f64 sqrt on the device is the correctly rounded one, __dsqrt_rn, so the bound is the host's bit for bit -- as the Cholesky
+ * pivots of the inertial part are.) */
+WV_DEVICE void setconst_geometry(SetConstShared &S, ModelPtr m, cm_envparams_t *P, int lane) {
+    const int ngeom = m->ngeom, nbody = m->nbody;
+    if (lane < ngeom) {
+        const double *q = P->geom_quat[lane];
+        double *R = P->geom_mat[lane];
+        const double q00 = wv::mul_rn(q[0], q[0]), q11 = wv::mul_rn(q[1], q[1]), q22 = wv::mul_rn(q[2], q[2]), q33 = wv::mul_rn(q[3], q[3]);
+        const double q01 = wv::mul_rn(q[0], q[1]), q02 = wv::mul_rn(q[0], q[2]), q03 = wv::mul_rn(q[0], q[3]);
+        const double q12 = wv::mul_rn(q[1], q[2]), q13 = wv::mul_rn(q[1], q[3]), q23 = wv::mul_rn(q[2], q[3]);
+        R[0] = wv::sub_rn(wv::sub_rn(wv::add_rn(q00, q11), q22), q33);
+        R[1] = wv::mul_rn(2.0, wv::sub_rn(q12, q03));
+        R[2] = wv::mul_rn(2.0, wv::add_rn(q13, q02));
+        R[3] = wv::mul_rn(2.0, wv::add_rn(q12, q03));
+        R[4] = wv::sub_rn(wv::add_rn(wv::sub_rn(q00, q11), q22), q33);
+        R[5] = wv::mul_rn(2.0, wv::sub_rn(q23, q01));
+        R[6] = wv::mul_rn(2.0, wv::sub_rn(q13, q02));
+        R[7] = wv::mul_rn(2.0, wv::add_rn(q23, q01));
+        R[8] = wv::add_rn(wv::sub_rn(wv::sub_rn(q00, q11), q22), q33);
+        const int b = m->geom_bodyid[lane];
+        double len = 0.0;
+        if (m->body_weldid[b] != 0) {
+            len = wv::add_rn(setconst_norm3(P->geom_pos[lane][0], P->geom_pos[lane][1], P->geom_pos[lane][2]), m->geom_rbound[lane]);
+            const int r = m->body_rootid[b];
+            for (int a = b; a != r && a > 0; a = m->body_parentid[a]) {
+                len = wv::add_rn(len, setconst_norm3(m->body_pos[a][0], m->body_pos[a][1], m->body_pos[a][2]));
+                for (int jj = 0; jj < m->body_jntnum[a]; ++jj) {
+                    const int j = m->body_jntadr[a] + jj;
+                    len = wv::add_rn(len, wv::mul_rn(2.0, setconst_norm3(m->jnt_pos[j][0], m->jnt_pos[j][1], m->jnt_pos[j][2])));
+                    if (m->jnt_type[j] == CM_JNT_SLIDE || m->jnt_type[j] == CM_JNT_FREE) len = 1e30;
+                }
+            }
+            for (int jj = 0; jj < m->body_jntnum[r]; ++jj) {
+                const int j = m->body_jntadr[r] + jj;
+                len = wv::add_rn(len, wv::mul_rn(2.0, setconst_norm3(m->jnt_pos[j][0], m->jnt_pos[j][1], m->jnt_pos[j][2])));
+            }
+        }
+        S.glen[lane] = len;
+    }
+    wv::sync();
+    if (lane < nbody) {
+        double reach = 0.0;
+        for (int g = 0; g < ngeom; ++g) {
+            const int b = m->geom_bodyid[g];
+            if (m->body_weldid[b] != 0 && m->body_rootid[b] == lane && S.glen[g] > reach) reach = S.glen[g];
+        }
+        P->body_reach[lane] = reach;
+    }
+    wv::sync();
+}
+/* Springs of an env (lane = dof): the passive stage's per-dof records of the dof's hinge / slide joint (zero stiffness otherwise) */
+WV_DEVICE void setconst_springs(ModelPtr m, cm_envparams_t *P, int lane) {
+    if (lane < m->nv) {
+        const int j = m->dof_jntid[lane], jt = m->jnt_type[j];
+        const bool scalar = jt == CM_JNT_HINGE || jt == CM_JNT_SLIDE;
+        P->dof_stiffness[lane] = scalar ? P->jnt_stiffness[j] : 0.0;
+        P->dof_springref[lane] = scalar ? P->qpos_spring[m->jnt_qposadr[j]] : 0.0;
+    }
+    wv::sync();
+}
+
 WV_GLOBAL void __launch_bounds__(WV_WAVE) cassie_setconst_kernel(SetConstIO io) {
     WV_SHARED SetConstShared S;
     const int lane = wv::lane();
@@ -280,7 +355,10 @@ WV_GLOBAL void __launch_bounds__(WV_WAVE) cassie_setconst_kernel(SetConstIO io) 
     const ModelPtr m = (ModelPtr)io.model;
     cm_envparams_t *P = io.params + env;
     const int nv = m->nv, nbody = m->nbody, njnt = m->njnt;
-    if (io.derive_inertial) {
+    if (io.derive_inertial == SETCONST_GEOMETRY || io.derive_inertial == SETCONST_ALL) setconst_geometry(S, m, P, lane);
+    if (io.derive_inertial == SETCONST_SPRINGS || io.derive_inertial == SETCONST_ALL) setconst_springs(m, P, lane);
+    if (io.derive_inertial == SETCONST_GEOMETRY || io.derive_inertial == SETCONST_SPRINGS) continue;
+    if (io.derive_inertial == SETCONST_ALL) {
     /* inertial origins at qpos0: xipos = xmat0 ipos + xpos0 */
     if (lane < nbody) {
         const int b = lane;

@@ -102,19 +102,29 @@ int phys_batch_set_model(phys_batch_t *b, const cm_model_t *model, int env);
 /* Per-env domain randomisation ON THE DEVICE (the batched form of the reference's per-simulator setters
  * cassie_sim_set_body_mass / set_body_ipos / set_dof_damping / set_geom_friction, reference src/cassiemujoco.c:1323-1436, and of
  * cassie_sim_just_set_const = mj_setConst, :974-977).  Every env gets a compact parameter block (cm_envparams_t in csrc/cm_model.h,
- * 10 KB) that the step kernel reads INSTEAD OF the shared model's fields; the rest of the model (95 KB) stays shared.
+ * 15.5 KB) that the step kernel reads INSTEAD OF the shared model's fields; the rest of the model stays shared.
  *   phys_batch_randomize   writes rows [n][phys_batch_param_dim] of one parameter (CM_P_BODY_MASS [nbody], CM_P_BODY_IPOS
  *                          [nbody][3], CM_P_BODY_INERTIA [nbody][3] principal moments, CM_P_DOF_DAMPING [nv], CM_P_GEOM_FRICTION
  *                          [model->ngeom][3]: the COLLISION geoms in compiled order, cm_model_t::geom_fullid maps them to the
  *                          reference's full geom list) for envs [env0, env0 + n); values may be a DEVICE pointer (on_device != 0:
  *                          e.g. a torch tensor, nothing crosses PCIe) or host memory.  Damping and friction act from the next
  *                          step on, like in the reference; masses / inertial offsets / inertias act on the dynamics at once and
- *                          on the constraint regularisers after
- *   phys_batch_set_const   which recomputes, per env and on the device, what mj_setConst derives: body_invweight0,
+ *                          on the constraint regularisers after phys_batch_set_const.  Geometry and springs (the reference's
+ *                          cassie_sim_set_geom_name_pos / _quat, src/cassiemujoco.c:1478-1537, and jnt_stiffness / qpos_spring):
+ *                          CM_P_GEOM_POS [model->ngeom][3] and CM_P_GEOM_QUAT [model->ngeom][4] (unit quaternions; collision geoms
+ *                          as for friction: the floor's tilt, the stair boxes, the terrain geom's offset), CM_P_JNT_STIFFNESS
+ *                          [njnt] and CM_P_QPOS_SPRING [nq] act from the next step on with no phys_batch_set_const: the rows'
+ *                          derived records (rotation matrices, the trees' reach behind the cull of far static geoms, the per-dof
+ *                          springs) are re-derived right behind the rows.  Until a batch has randomised geometry (springs) its
+ *                          steps read those of the shared model.  Not randomisable: body_pos (it moves the kinematics at qpos0
+ *                          set_const starts from), geom_size (MuJoCo does not recompute rbound after a raw edit either), the
+ *                          timestep and the height-field size; the batched cassie_batch.h API takes none of these.
+ *   phys_batch_set_const   recomputes, per env and on the device, what mj_setConst derives: body_invweight0,
  *                          dof_invweight0, meaninertia (M(qpos0) and its Cholesky factor per env) and the per-joint /
  *                          per-equality / per-pair values the constraint stages read -- bit for bit what compiling a host model
  *                          with the same parameters gives (phys_model_set_const + phys_model_compile).
- * Both are asynchronous on `stream` (NULL = the batch's own) and ordered with the stepping launches there.  Replacing the shared
+ * Both are asynchronous on `stream` (NULL = the batch's own) and ordered with the stepping launches there: ranges stepped on
+ * other streams must be joined with it first.  Replacing the shared
  * model (phys_batch_set_model, env = -1) drops the blocks; per-env MODELS (env >= 0) and per-env parameter blocks do not mix. */
 int phys_batch_param_dim(const phys_batch_t *b, int param);
 int phys_batch_randomize(phys_batch_t *b, int param, const double *values, int on_device, int env0, int n, void *stream);
