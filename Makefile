@@ -88,11 +88,12 @@ $(AGILITY_STAMP): FORCE
 	@mkdir -p $(OBJD)
 	@echo '$(AGILITY_LINK)' | cmp -s - $@ || echo '$(AGILITY_LINK)' > $@
 
+# (-z defs: an instantiation of the step kernel that phys_batch.hip names and no kernels_*.hip provides fails here, not at load time)
 $(PRODUCT): $(OBJS) $(AGILITY_DEPS) $(AGILITY_STAMP)
 	@test -f $(AGILITY) || echo "WARNING: no Agility archive (neither $(AGILITY) nor the reference's): linking stand-ins that abort when" \
 	    "called; the reference's host-side API (cassie_sim_*, cassie_batch_*) is unusable in this build" >&2
 	@mkdir -p $(LIBD)
-	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $(OBJS) $(AGILITY_LINK) -lm -lpthread
+	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -Wl,-z,defs -o $@ $(OBJS) $(AGILITY_LINK) -lm -lpthread
 
 $(AGILITY_ABSENT):
 	@mkdir -p $(OBJD)

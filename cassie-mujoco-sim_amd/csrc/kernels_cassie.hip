@@ -1,7 +1,8 @@
-/* the step kernel for plain cassie.xml (BASELINE configs 1-3): 32 dofs, compile-time topology, no height-field / box code */
-#include "step_launch.h"
+/* the step kernel for plain cassie.xml (BASELINE configs 1-3): 32 dofs, compile-time topology, no height-field / box code --
+ * the one-wave forms: alone (a large grid: forward / read-out passes of a whole batch, the fast kernel switched off) or as the
+ * pass behind the one-wave fast kernel that looks every env's record up, and the one-wave fast kernel */
+#include "step_kernels.h"
 namespace ck {
-bool launch_step_cassie(dim3 grid, const TierGrids &tg, hipStream_t s, PhysIO io, const HandoverLists &hl, bool fast, bool wide_caps, hipEvent_t after_first, int waves, bool inplace) {
-    return launch_three_tiers<32, TopoCassie32, 0>(grid, tg, s, io, hl, fast, wide_caps, after_first, waves == 2 ? launch_fast_cassie_2w : nullptr, waves == 2 ? launch_mid_cassie_2w : nullptr, launch_wide_cassie, launch_alone63_cassie, inplace ? launch_fast_cassie_2w_inplace : nullptr);
-}
+template void launch_step<32, TopoCassie32, 0>(unsigned, hipStream_t, const PhysIO &);
+template void launch_step<32, TopoCassie32, 0, FAST_ROWS>(unsigned, hipStream_t, const PhysIO &);
 }  // namespace ck

@@ -197,6 +197,109 @@ static phys_batch::OrderSeg *order_segment_for(phys_batch *b, int env0, int n, h
     return &b->order_segs.back();
 }
 
+/* The step kernel's instantiations per model family, by form (step_plan.h; null: the family has no such form).  Each is instantiated
+ * explicitly in one of the kernels_*.hip translation units. */
+using ck::launch_step;
+using ck::FAST_ROWS; using ck::FAST_ROWS_TRAY; using ck::MID_ROWS; using ck::WIDE_ROWS;
+using ck::TopoCassie32; using ck::TopoCassieTray38; using ck::TopoRuntime;
+/* plain cassie.xml (FEAT 0) and cassie_hfield.xml (FEAT_HFIELD): all three tiers */
+template <int FEAT>
+static const ck::StepLauncher CASSIE_FORMS[ck::FORM_COUNT] = {
+    launch_step<32, TopoCassie32, FEAT>,                                   /* FORM_ALONE (+ the one-wave lookup pass) */
+    launch_step<32, TopoCassie32, FEAT, MID_ROWS, 2, false, 1>,           /* FORM_ALONE_2W: 512 registers a lane */
+    launch_step<32, TopoCassie32, FEAT, WIDE_ROWS, 2, false, 1>,          /* FORM_WIDE */
+    launch_step<32, TopoCassie32, FEAT, FAST_ROWS>,                        /* FORM_FAST */
+    launch_step<32, TopoCassie32, FEAT, FAST_ROWS, 2>,                     /* FORM_FAST_2W */
+    launch_step<32, TopoCassie32, FEAT, FAST_ROWS, 2, false, 2, MID_ROWS>, /* FORM_FAST_INPLACE */
+    nullptr,                                                               /* FORM_MID_WALK */
+    launch_step<32, TopoCassie32, FEAT, MID_ROWS, 2, true>,               /* FORM_MID_WALK_2W */
+    launch_step<32, TopoCassie32, FEAT, WIDE_ROWS, 2, true, 1>,           /* FORM_WIDE_WALK */
+};
+/* cassie_tray_box.xml without height-field pairs: fast (47 rows) and 63 rows */
+static const ck::StepLauncher TRAY_FORMS[ck::FORM_COUNT] = {
+    launch_step<40, TopoCassieTray38, ck::FEAT_WAVEPAIRS>,                         /* FORM_ALONE */
+    launch_step<40, TopoCassieTray38, ck::FEAT_WAVEPAIRS, MID_ROWS, 2>,            /* FORM_ALONE_2W */
+    nullptr,                                                                       /* FORM_WIDE */
+    launch_step<40, TopoCassieTray38, ck::FEAT_WAVEPAIRS, FAST_ROWS_TRAY>,         /* FORM_FAST */
+    launch_step<40, TopoCassieTray38, ck::FEAT_WAVEPAIRS, FAST_ROWS_TRAY, 2>,      /* FORM_FAST_2W */
+    nullptr,                                                                       /* FORM_FAST_INPLACE */
+    launch_step<40, TopoCassieTray38, ck::FEAT_WAVEPAIRS, MID_ROWS, 1, true>,      /* FORM_MID_WALK */
+    launch_step<40, TopoCassieTray38, ck::FEAT_WAVEPAIRS, MID_ROWS, 2, true>,      /* FORM_MID_WALK_2W */
+    nullptr,                                                                       /* FORM_WIDE_WALK */
+};
+/* FORM_ALONE only: the Cassie topology with both height-field and box pairs, the tray model with height-field pairs, any other model */
+static const ck::StepLauncher CASSIE_ALL_FORMS[ck::FORM_COUNT] = {launch_step<32, TopoCassie32, ck::FEAT_ALL>};
+static const ck::StepLauncher TRAY_HFIELD_FORMS[ck::FORM_COUNT] = {launch_step<40, TopoCassieTray38, ck::FEAT_ALL>};
+static const ck::StepLauncher GENERIC32_FORMS[ck::FORM_COUNT] = {launch_step<32, TopoRuntime, ck::FEAT_ALL>};
+static const ck::StepLauncher GENERIC40_FORMS[ck::FORM_COUNT] = {launch_step<40, TopoRuntime, ck::FEAT_ALL>};
+
+constexpr int SMALL_BATCH_NSUB = 4;  /* substeps per launch up to which a small batch skips the fast kernel + passes (three launches) for one instantiation alone */
+constexpr int SMALL_BATCH = 512;     /* envs up to which that holds (half the chip's workgroup slots) */
+
+/* The launch of the fast kernel over the range [env0, env0 + n) in chunks of at least CHUNK_MIN_SUBSTEPS substeps (PhysIO::nchunk,
+ * chunk_seq, chunk_flag, chunk_fault), where the launch is long enough and the stream places workgroups round the XCDs */
+static void set_chunks(phys_batch *b, ck::PhysIO &io, int n, int nsub, hipStream_t s) {
+    io.nchunk = 1;
+    /* (n % 8: workgroup w runs on XCD w % 8, so the chunks of an env -- workgroups n apart -- share an XCD and its L2) */
+    if (!b->chunks_allowed || (n == b->nenv ? b->chunks : b->chunks_range) <= 1 || n < CHUNK_MIN_ENVS || n % 8 != 0 || nsub < 2 * CHUNK_MIN_SUBSTEPS ||
+        !stream_may_chunk(b, s))
+        return;
+    /* (round 6: a range's launch of 15 .. 25 substeps -- a consumer that fences every few substeps, the driver's 20-step regions --
+     * as three chunks instead of two: nothing fills the end of such a launch's queue, finer jobs shorten it, + 1.5 %; at 50
+     * substeps between fences three cost 0.6 %, profiles/round6/chunks3_ab.txt) */
+    const int range_chunks = b->chunks_default && nsub <= 25 ? 3 : b->chunks_range;
+    const int most = nsub / CHUNK_MIN_SUBSTEPS, asked = n == b->nenv ? b->chunks : range_chunks;
+    io.nchunk = asked < most ? asked : most;
+    if (b->chunk_seq >= (1 << 24)) { /* (the tag has 25 bits: start over once NOTHING is in flight on the device -- the words of
+                                       * envs in flight on a stream this batch does not remember must not be cleared under them --
+                                       * and the clearing itself is complete before the next chunk can publish) */
+        (void)hipDeviceSynchronize();
+        (void)hipMemsetAsync(b->d_chunk_flag, 0, sizeof(int) * (size_t)b->nenv, s);
+        (void)hipStreamSynchronize(s);
+        b->chunk_seq = 0;
+    }
+    io.chunk_seq = ++b->chunk_seq;
+    io.chunk_flag = b->d_chunk_flag;
+    io.chunk_fault = b->d_chunk_fault;
+}
+
+/* The hand-over lists of the range [env0, env0 + n) and the grids of the passes that walk them: twice what the range's last launch
+ * handed over (the launcher learns that a launch late, through host memory) plus 16, at most one workgroup per env; the 127-row pass
+ * behind that one likewise, plus 8.  (A floor of 256 workgroups under both grids was measured: no gain on the prism workload, -0.6 %
+ * on config 2, profiles/round5.) */
+static void range_lists(phys_batch *b, int env0, int n, bool wide, ck::HandoverLists &hl, ck::StepGrids &g) {
+    hl.list1 = b->d_handover_list; hl.count1 = b->d_handover_count + 2 * (size_t)env0; hl.seen1 = b->d_handover_seen + env0;
+    if (wide) { hl.list2 = b->d_handover_list2; hl.count2 = b->d_handover_count2 + 2 * (size_t)env0; hl.seen2 = b->d_handover_seen2 + env0; }
+    const int seen = b->h_handover_seen[env0], seen2 = wide ? b->h_handover_seen2[env0] : 0;
+    const int seen12 = seen > seen2 ? seen : seen2; /* (the first pass is never smaller than the second: it feeds it) */
+    const long want = 2L * (seen12 > 0 ? seen12 : 0) + 16, want2 = 2L * (seen2 > 0 ? seen2 : 0) + 8;
+    g.mid = (unsigned)(want < n ? want : n);
+    g.wide = (unsigned)(want2 < n ? want2 : n);
+}
+
+/* Whether the two-wave fast kernel of the range starting at env0 takes its in-place form (see phys_batch::inplace_mode); auto_ok: the
+ * order kernel runs behind the range's launches (auto mode needs it: it reports the in-place count) */
+static bool range_inplace(phys_batch *b, int env0, bool auto_ok, int *count1, hipStream_t s) {
+    constexpr int INPLACE_QUIET = 8;
+    phys_batch::RangeForm *rf = nullptr;
+    for (auto &r : b->range_forms) if (r.env0 == env0) rf = &r;
+    if (!rf) { b->range_forms.push_back({env0, false}); rf = &b->range_forms.back(); }
+    const bool was = rf->inplace;
+    /* the range's word in host memory: > 0 = env-launches the last reporting launch handed over (plain form: the pass behind the
+     * kernel writes it) or finished in place (the order kernel does); -k = the last k reports of the in-place form had none */
+    const int seen = *(volatile int *)(b->h_handover_seen + env0);
+    if (b->inplace_mode != 2 || !auto_ok) rf->inplace = b->inplace_mode == 1;
+    else if (!rf->inplace) { if (seen > 0) rf->inplace = true; }
+    else if (seen <= -INPLACE_QUIET) rf->inplace = false;
+    if (was != rf->inplace) {
+        /* the first list's count word changes its meaning with the form: start the new form from zero (stream-ordered) */
+        (void)hipMemsetAsync(count1, 0, 2 * sizeof(int), s);
+        b->h_handover_seen[env0] = 0;
+    }
+    ++b->form_launches[rf->inplace ? 1 : 0];
+    return rf->inplace;
+}
+
 static int launch(phys_batch *b, int nsub, int integrate, hipStream_t s, bool scratch_outputs = false, int env0 = 0, int n = -1) {
     ck::PhysIO io = make_io(b, nsub, integrate);
     if (n < 0) n = b->nenv;
@@ -216,20 +319,6 @@ static int launch(phys_batch *b, int nsub, int integrate, hipStream_t s, bool sc
         io.actuator_velocity = io.sensordata + (size_t)b->nenv * m.nsensordata;
     }
     note_stream(b, s);
-    const dim3 grid(n);
-    /* the compile-time-topology instantiations are used only when the model's dof tree is exactly theirs */
-    const cm_model_t &hm = b->host_model;
-    auto matches = [&](const unsigned long long *table, int nv, int body_levels) {
-        /* (kin_simple, and a body tree no deeper than theirs: the record-based local transforms and the round count of the
-         * recursion in their kinematics stage) */
-        if (b->generic_kernel || hm.nv != nv || !hm.kin_simple || hm.maxdepth > body_levels) return false;
-        for (int k = 0; k < nv; ++k) if (hm.dof_ancmask[k] != table[k]) return false;
-        return true;
-    };
-    /* ... and the collision code of an instantiation is what the model's pair list needs (FEAT_*): plain cassie.xml has
-     * neither height-field nor whole-wave (plane-box / box-box) pairs */
-    const bool hf = hm.nhfpair > 0 || hm.hfield_geom >= 0, wp = hm.npair > hm.npair_simple;
-    bool launched;
     hipEvent_t ev_after = nullptr;
     if (b->timing && integrate) {
         if (b->ev_used == b->ev_pool.size() && b->ev_pool.size() < 65536) { /* (launches beyond that between two queries go untimed) */
@@ -242,103 +331,75 @@ static int launch(phys_batch *b, int nsub, int integrate, hipStream_t s, bool sc
             ++b->ev_used;
         }
     }
-    /* a row-capped fast instantiation with the passes behind it: the fast kernel's record of completed substeps, the launch in
-     * chunks, and the hand-over lists the passes walk -> their grids */
-    ck::HandoverLists hl = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    ck::TierGrids tg = {grid, grid};
-    auto tiers = [&](bool fast) {
-        io.progress = fast ? b->d_progress : nullptr;
-        io.nchunk = 1;
-        if (fast && b->d_chunk_flag && b->chunks_allowed && (n == b->nenv ? b->chunks : b->chunks_range) > 1 && n >= CHUNK_MIN_ENVS && n % 8 == 0 && nsub >= 2 * CHUNK_MIN_SUBSTEPS &&
-            stream_may_chunk(b, s)) {
-            /* (n % 8: workgroup w runs on XCD w % 8, so the chunks of an env -- workgroups n apart -- share an XCD and its L2) */
-            /* the fast kernel's launch as chunks of at least CHUNK_MIN_SUBSTEPS substeps (the launchers size its grid) */
-            /* (round 6: a range's launch of 15 .. 25 substeps -- a consumer that fences every few substeps, the driver's 20-step regions --
-             * as three chunks instead of two: nothing fills the end of such a launch's queue, finer jobs shorten it, + 1.5 %; at 50
-             * substeps between fences three cost 0.6 %, profiles/round6/chunks3_ab.txt) */
-            const int range_chunks = b->chunks_default && nsub <= 25 ? 3 : b->chunks_range;
-            const int most = nsub / CHUNK_MIN_SUBSTEPS, asked = n == b->nenv ? b->chunks : range_chunks;
-            io.nchunk = asked < most ? asked : most;
-            if (b->chunk_seq >= (1 << 24)) { /* (the tag has 25 bits: start over once NOTHING is in flight on the device -- the words of
-                                               * envs in flight on a stream this batch does not remember must not be cleared under them --
-                                               * and the clearing itself is complete before the next chunk can publish) */
-                (void)hipDeviceSynchronize();
-                (void)hipMemsetAsync(b->d_chunk_flag, 0, sizeof(int) * (size_t)b->nenv, s);
-                (void)hipStreamSynchronize(s);
-                b->chunk_seq = 0;
-            }
-            io.chunk_seq = ++b->chunk_seq;
-            io.chunk_flag = b->d_chunk_flag;
-            io.chunk_fault = b->d_chunk_fault;
-        }
-        if (fast && b->d_handover_list && b->d_handover_list2) {
-            const bool wide_caps = hm.maxefc > CM_MAXEFC_NARROW;
-            /* the pass behind the fast kernel walks the hand-over list with a small grid: twice what the range's last launch
-             * handed over (the launcher learns that a launch late, through host memory) plus 16, at most one workgroup per env;
-             * the 127-row pass behind that one likewise, plus 8 */
-            hl.list1 = b->d_handover_list; hl.count1 = b->d_handover_count + 2 * (size_t)env0; hl.seen1 = b->d_handover_seen + env0;
-            if (wide_caps) { hl.list2 = b->d_handover_list2; hl.count2 = b->d_handover_count2 + 2 * (size_t)env0; hl.seen2 = b->d_handover_seen2 + env0; }
-            const int seen = b->h_handover_seen[env0], seen2 = wide_caps ? b->h_handover_seen2[env0] : 0;
-            const int seen12 = seen > seen2 ? seen : seen2; /* (the first pass is never smaller than the second: it feeds it) */
-            const long want = 2L * (seen12 > 0 ? seen12 : 0) + 16, want2 = 2L * (seen2 > 0 ? seen2 : 0) + 8;
-            /* (a floor of 256 workgroups under both grids was measured: no gain on the prism workload, -0.6 % on config 2, profiles/round5) */
-            tg.mid = dim3((unsigned)(want < n ? want : n));
-            tg.wide = dim3((unsigned)(want2 < n ? want2 : n));
-        }
+    /* the compile-time-topology instantiations are used only when the model's dof tree is exactly theirs */
+    const cm_model_t &hm = b->host_model;
+    auto matches = [&](const unsigned long long *table, int nv, int body_levels) {
+        /* (kin_simple, and a body tree no deeper than theirs: the record-based local transforms and the round count of the
+         * recursion in their kinematics stage) */
+        if (b->generic_kernel || hm.nv != nv || !hm.kin_simple || hm.maxdepth > body_levels) return false;
+        for (int k = 0; k < nv; ++k) if (hm.dof_ancmask[k] != table[k]) return false;
+        return true;
     };
-    bool inplace_launch = false;
-    if (matches(ck::TopoCassie32::table, ck::TopoCassie32::nv, ck::TopoCassie32::body_levels)) {
-        /* stepping launches of the two Cassie instantiations go through the row-capped fast instantiation first; the 63-row pass
-         * behind it finishes the envs that met a substep with more rows, and -- for a model with the wide caps (CM_FLAG_HFPRISM) -- the
-         * 127-row pass behind that one what is left; forward / read-out passes and small batches take one instantiation alone */
-        const bool fast = b->fast_rows && integrate && !wp && !io.ext && b->d_progress;
-        tiers(fast);
-        if (fast && hl.list1 && b->waves_per_env == 2 && !wp) {
-            /* the form of this range's fast kernel (see phys_batch::inplace_mode) */
-            constexpr int INPLACE_QUIET = 8;
-            phys_batch::RangeForm *rf = nullptr;
-            for (auto &r : b->range_forms) if (r.env0 == env0) rf = &r;
-            if (!rf) { b->range_forms.push_back({env0, false}); rf = &b->range_forms.back(); }
-            const bool was = rf->inplace;
-            /* the range's word in host memory: > 0 = env-launches the last reporting launch handed over (plain form: the pass behind the
-             * kernel writes it) or finished in place (the order kernel does); -k = the last k reports of the in-place form had none */
-            const int seen = *(volatile int *)(b->h_handover_seen + env0);
-            if (b->inplace_mode != 2 || !(io.order && seg)) rf->inplace = b->inplace_mode == 1;   /* (auto needs the order kernel: it reports the in-place count) */
-            else if (!rf->inplace) { if (seen > 0) rf->inplace = true; }
-            else if (seen <= -INPLACE_QUIET) rf->inplace = false;
-            if (was != rf->inplace) {
-                /* the first list's count word changes its meaning with the form: start the new form from zero (stream-ordered) */
-                (void)hipMemsetAsync(hl.count1, 0, 2 * sizeof(int), s);
-                b->h_handover_seen[env0] = 0;
-            }
-            inplace_launch = rf->inplace;
-            ++b->form_launches[inplace_launch ? 1 : 0];
-        }
-        if (!hf && !wp) { launched = ck::launch_step_cassie(grid, tg, s, io, hl, fast, hm.maxefc > CM_MAXEFC_NARROW, ev_after, b->waves_per_env, inplace_launch); ev_after = nullptr; }
-        else if (hf && !wp) { launched = ck::launch_step_cassie_hfield(grid, tg, s, io, hl, fast, hm.maxefc > CM_MAXEFC_NARROW, ev_after, b->waves_per_env, inplace_launch); ev_after = nullptr; }
-        else launched = ck::launch_step_cassie_all(grid, s, io);
-    } else if (matches(ck::TopoCassieTray38::table, ck::TopoCassieTray38::nv, ck::TopoCassieTray38::body_levels)) {
-        /* the 40-dof model: a fast instantiation of 47 rows (the boxes resting on the tray take it to 32 .. 40 routinely) -- one wave
-         * per env and the Gram matrix on the matrix core by default, or the two-wave form -- with the 63-row one behind it */
-        const bool plain = integrate && !io.ext && !hf;
-        const bool two = plain && b->waves_per_env_tray == 2;
-        const bool fast = plain && b->fast_rows && b->d_progress;
-        tiers(fast);
-        launched = ck::launch_step_tray(grid, tg.mid, s, io, hl, hf, fast, ev_after, two ? 2 : 1); ev_after = nullptr;
+    /* ... and the collision code of an instantiation is what the model's pair list needs (FEAT_*): plain cassie.xml has
+     * neither height-field nor whole-wave (plane-box / box-box) pairs */
+    const bool hf = hm.nhfpair > 0 || hm.hfield_geom >= 0, wp = hm.npair > hm.npair_simple;
+    /* the family, and the forms of this launch (step_plan.h) */
+    const ck::StepLauncher *family;
+    ck::StepForms forms = {ck::FORM_ALONE, ck::FORM_ALONE, false, FAST_ROWS - 4};
+    /* (inplace_stay_rows: once in the 63-row code an env stays there until a substep needs at most FAST_ROWS - 4 rows again -- the
+     * margin keeps an env that hovers about the fast code's capacity from changing codes every substep) */
+    if (matches(TopoCassie32::table, TopoCassie32::nv, TopoCassie32::body_levels) && !wp) {
+        /* stepping launches go through the row-capped fast instantiation first; the 63-row pass behind it finishes the envs that met
+         * a substep with more rows, and -- for a model with the wide caps (CM_FLAG_HFPRISM) -- the 127-row pass behind that one what
+         * is left.  Forward / read-out passes take one instantiation alone, and so does a small batch stepping a few substeps per
+         * launch (somebody's control loop around a handful of envs): one launch instead of two or three -- a launch costs what four
+         * substeps' difference between the kernels saves */
+        family = hf ? CASSIE_FORMS<ck::FEAT_HFIELD> : CASSIE_FORMS<0>;
+        forms.wide = hm.maxefc > CM_MAXEFC_NARROW;
+        if (!b->fast_rows || !integrate || io.ext || (n <= SMALL_BATCH && nsub <= SMALL_BATCH_NSUB))
+            /* (alone and a LARGE grid -- phys_batch_derive / forward passes of a whole batch, the fast kernel switched off -- with 63-row
+             * caps: the one-wave form, whose 421 registers leave room for four envs per CU; the two-wave 512-register form halves that
+             * and only pays where the chip is not full anyway, profiles/round6/alone_pass_ab.txt) */
+            forms.first = forms.wide ? ck::FORM_WIDE : n > SMALL_BATCH ? ck::FORM_ALONE : ck::FORM_ALONE_2W;
+        else if (b->waves_per_env == 2) { forms.first = ck::FORM_FAST_2W; forms.mid = ck::FORM_MID_WALK_2W; }
+        else forms.first = ck::FORM_FAST;     /* (behind it the one-wave 63-row pass looks every env's record up: FORM_ALONE) */
+    } else if (matches(TopoCassie32::table, TopoCassie32::nv, TopoCassie32::body_levels)) family = CASSIE_ALL_FORMS;
+    else if (matches(TopoCassieTray38::table, TopoCassieTray38::nv, TopoCassieTray38::body_levels) && !hf) {
+        /* the 40-dof model: a fast instantiation of 47 rows (the boxes resting on the tray take it to 32 .. 40 routinely) with the 63-row
+         * one behind it walking the list, both in the two-wave form by default (waves_per_env_tray) -- or the 63-row one alone */
+        family = TRAY_FORMS;
+        const bool plain = integrate && !io.ext, two = plain && b->waves_per_env_tray == 2;
+        if (plain && b->fast_rows) { forms.first = two ? ck::FORM_FAST_2W : ck::FORM_FAST; forms.mid = two ? ck::FORM_MID_WALK_2W : ck::FORM_MID_WALK; }
+        else forms.first = two ? ck::FORM_ALONE_2W : ck::FORM_ALONE;
+    } else if (matches(TopoCassieTray38::table, TopoCassieTray38::nv, TopoCassieTray38::body_levels)) family = TRAY_HFIELD_FORMS;
+    else family = hm.nv > 32 ? GENERIC40_FORMS : GENERIC32_FORMS;
+    /* a fast kernel first: its record of completed substeps, its launch in chunks, the hand-over lists of the passes behind it, its form */
+    ck::HandoverLists hl = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    ck::StepGrids grids = {(unsigned)n, (unsigned)n, (unsigned)n};
+    if (ck::is_fast_form(forms.first)) {
+        io.progress = b->d_progress;
+        set_chunks(b, io, n, nsub, s);
+        range_lists(b, env0, n, forms.wide, hl, grids);
+        if (forms.first == ck::FORM_FAST_2W && family[ck::FORM_FAST_INPLACE] && range_inplace(b, env0, io.order && seg, hl.count1, s))
+            forms.first = ck::FORM_FAST_INPLACE;
     }
-    else launched = ck::launch_step_generic(grid, s, io, hm.nv > 32);
-    if (ev_after) (void)hipEventRecord(ev_after, s);
-    if (!launched) { (void)hip_ok(hipErrorLaunchFailure, "cassie_step_kernel launch"); return -1; }
-    if (!hip_ok(hipGetLastError(), "cassie_step_kernel launch")) return -1;
+    const ck::StepPlan plan = ck::plan_step(io, forms, hl, grids);
+    for (int i = 0; i < plan.n; ++i) {
+        const ck::StepPass &p = plan.pass[i];
+        if (!family[p.form]) { (void)hip_ok(hipErrorInvalidDeviceFunction, "cassie_step_kernel launch (no instantiation of this form)"); return -1; }
+        family[p.form](p.grid, s, p.io);
+        if (!hip_ok(hipGetLastError(), "cassie_step_kernel launch")) return -1;
+        if (i == 0 && ev_after) (void)hipEventRecord(ev_after, s);   /* (the first kernel of the launch does the work: per-kernel timing) */
+    }
     /* the next launch's order from this one's per-env cost: after every long launch, now and then after short ones.  (Round 6: "long" is
      * more than 25 substeps, not 8 -- the sort is 20 - 25 us at the end of the launch's stream, 0.7 % of a fenced 20-substep launch, and the
-     * order itself is worth nothing either way since launches go in chunks: profiles/round6/launch_order_ab.txt.  The CASSIE_ORDER_EVERY
-     * switch: the A/B.) */
-    static const int sort_every_above = getenv("CASSIE_ORDER_EVERY") ? atoi(getenv("CASSIE_ORDER_EVERY")) : 25;
-    if (io.order && integrate && (nsub > sort_every_above || ++seg->launches_since_sort >= 16)) {
+     * order itself is worth nothing either way since launches go in chunks: profiles/round6/launch_order_ab.txt.)  It reports the in-place
+     * count of the range when the in-place form ran. */
+    if (io.order && integrate && (nsub > 25 || ++seg->launches_since_sort >= 16)) {
         seg->launches_since_sort = 0;
+        const bool inplace = forms.first == ck::FORM_FAST_INPLACE;
         hipLaunchKernelGGL(ck::cassie_order_kernel, dim3(1), dim3(ck::ORDER_THREADS), 0, s, b->d_cost, b->d_order, n, env0,
-                           inplace_launch ? hl.count1 : (int *)nullptr, inplace_launch ? hl.seen1 : (volatile int *)nullptr);
+                           inplace ? hl.count1 : (int *)nullptr, inplace ? hl.seen1 : (volatile int *)nullptr);
         if (!hip_ok(hipGetLastError(), "cassie_order_kernel launch")) return -1;
     }
     return 0;

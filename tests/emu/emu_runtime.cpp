@@ -17,6 +17,7 @@
 #include <cstring>
 
 #include "small_kernels.h"
+#include "step_plan.h"
 
 namespace {
 constexpr int NL = 64, NWMAX = 2, NLMAX = NL * NWMAX;
@@ -203,7 +204,6 @@ static void body32s_fast() { ck::cassie_step_kernel<32, ck::TopoCassie32, ck::FE
 /* the two-wave forms (wave 1 runs the mass-matrix stage group beside wave 0's collision / velocity / row stages) */
 static void body32s_2w() { ck::cassie_step_kernel<32, ck::TopoCassie32, ck::FEAT_ALL, ck::MID_ROWS, 2>(g_io); }
 /* the full instantiation as the list-walking pass behind the fast kernel */
-static void body32s_walk() { ck::cassie_step_kernel<32, ck::TopoCassie32, ck::FEAT_ALL, ck::MID_ROWS, 1, true>(g_io); }
 static void body32s_2w_walk() { ck::cassie_step_kernel<32, ck::TopoCassie32, ck::FEAT_ALL, ck::MID_ROWS, 2, true>(g_io); }
 /* the 127-row instantiation (two wavefronts; the solve of a substep with more than 64 rows is spread over both): alone, and as the
  * pass that walks the list of envs the 63-row pass handed on */
@@ -246,6 +246,20 @@ static void body40s_walk() { ck::cassie_step_kernel<40, ck::TopoCassieTray38, ck
 static void body40s_2w_walk() { ck::cassie_step_kernel<40, ck::TopoCassieTray38, ck::FEAT_WAVEPAIRS, ck::MID_ROWS, 2, true>(g_io); }
 static void body32() { ck::cassie_step_kernel<32, ck::TopoRuntime>(g_io); }
 static void body40() { ck::cassie_step_kernel<40, ck::TopoRuntime>(g_io); }
+/* the bodies by form (step_plan.h) of the compile-time topologies and the run-time one: FEAT_ALL, except the 40-dof model's tiers
+ * and its two-wave form alone (FEAT_WAVEPAIRS: no height-field pairs) */
+struct EmuForm { void (*body)(); int nw; };
+static const EmuForm CASSIE32_BODIES[ck::FORM_COUNT] = {
+    {body32s, 1}, {body32s_2w, 2}, {body32s_wide, 2},                                  /* FORM_ALONE, FORM_ALONE_2W, FORM_WIDE */
+    {body32s_fast, 1}, {body32s_fast_2w, 2}, {body32s_fast_2w_inplace, 2},             /* FORM_FAST, FORM_FAST_2W, FORM_FAST_INPLACE */
+    {nullptr, 0}, {body32s_2w_walk, 2}, {body32s_wide_walk, 2},                        /* FORM_MID_WALK, FORM_MID_WALK_2W, FORM_WIDE_WALK */
+};
+static const EmuForm TRAY38_BODIES[ck::FORM_COUNT] = {
+    {body40s, 1}, {body40s_2w, 2}, {nullptr, 0},
+    {body40s_fast, 1}, {nullptr, 0}, {nullptr, 0},
+    {body40s_walk, 1}, {body40s_2w_walk, 2}, {nullptr, 0},
+};
+static const EmuForm GENERIC32_BODIES[ck::FORM_COUNT] = {{body32, 1}}, GENERIC40_BODIES[ck::FORM_COUNT] = {{body40, 1}};
 extern "C" void emu_force_runtime_topology(int on) { g_force_runtime_topology = on; }
 static bool topo_matches(const cm_model_t *m, const unsigned long long *t, int nv, int body_levels) {
     if (m->nv != nv || !m->kin_simple || m->maxdepth > body_levels) return false;
@@ -297,78 +311,44 @@ extern "C" int emu_phys_run(const cm_model_t *model, int nenv, int nsub, int int
     g_io.drive_mode = g_drive_mode; g_io.drive_state = g_drive_state; g_io.drive_cmd = g_drive_cmd; g_io.meas = g_meas;
     g_io.pd_dtarget = g_pd_dtarget; g_io.pd_torque = g_pd_torque;
     const bool cassie32 = !g_force_runtime_topology && topo_matches(model, ck::TopoCassie32::table, ck::TopoCassie32::nv, ck::TopoCassie32::body_levels);
-    const bool tray38 = !cassie32 && !g_force_runtime_topology && model->nhfpair == 0 && model->hfield_geom < 0 &&
-                        topo_matches(model, ck::TopoCassieTray38::table, ck::TopoCassieTray38::nv, ck::TopoCassieTray38::body_levels);
+    const bool tray = !cassie32 && !g_force_runtime_topology && topo_matches(model, ck::TopoCassieTray38::table, ck::TopoCassieTray38::nv, ck::TopoCassieTray38::body_levels);
+    const bool tray38 = tray && model->nhfpair == 0 && model->hfield_geom < 0;
+    const EmuForm *bodies = cassie32 ? CASSIE32_BODIES : tray ? TRAY38_BODIES : model->nv <= 32 ? GENERIC32_BODIES : GENERIC40_BODIES;
+    /* the forms, as phys_batch.hip picks them (with this emulator's settings): the row-capped fast instantiation for every env, then
+     * the passes behind it -- a list-walking one as ONE small grid (here: g_resume_grid workgroups) -- or one instantiation alone */
+    ck::StepForms forms = {ck::FORM_ALONE, ck::FORM_ALONE, false, g_inplace_stay};
+    static int progress[1 << 16], list[1 << 16], count[2], list2[1 << 16], count2[2], chunk_flag[1 << 16];
+    static volatile int seen, seen2;
+    ck::HandoverLists hl = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     if ((cassie32 || tray38) && g_fast_rows && integrate && nenv <= (1 << 16)) {
-        /* as phys_batch.hip launches them: the row-capped fast instantiation for every env (it appends the envs it hands over to
-         * the hand-over list), then the full instantiation as ONE small grid walking that list (here: g_resume_grid workgroups) */
-        static int progress[1 << 16], list[1 << 16], count[2], list2[1 << 16], count2[2];
-        static volatile int seen, seen2;
         count[0] = count[1] = 0; seen = -1; count2[0] = count2[1] = 0; seen2 = -1;
-        /* the fast kernel appends to `list`; the 63-row pass walks it and -- for models that may use 127 rows -- appends what it cannot
-         * hold to `list2`, which the 127-row pass walks */
-        const bool third = cassie32 && model->maxefc > ck::MID_ROWS;
-        g_io.progress = progress; g_io.resume = 0; g_io.has_next = 1;
-        g_io.handover_list = nullptr; g_io.handover_count = nullptr; g_io.handover_seen = nullptr;
-        g_io.handover_out_list = list; g_io.handover_out_count = count;
-        /* the in-place form (cassie_step_kernel's INROWS): no first list, no 63-row pass; the inner 63-row call appends to the second list */
-        const bool inplace = g_inplace && cassie32 && g_two_waves;
-        if (inplace) {
-            g_io.handover_out_list = nullptr; g_io.handover_out_count = nullptr;
-            g_io.inplace_has_next = third ? 1 : 0; g_io.inplace_out_list = third ? list2 : nullptr; g_io.inplace_out_count = third ? count2 : nullptr;
-            g_io.inplace_stay_rows = g_inplace_stay;
+        hl = {list, count, &seen, list2, count2, &seen2};
+        if (tray38) forms = {ck::FORM_FAST, g_two_waves ? ck::FORM_MID_WALK_2W : ck::FORM_MID_WALK, false, g_inplace_stay};
+        else forms = {!g_two_waves ? ck::FORM_FAST : g_inplace ? ck::FORM_FAST_INPLACE : ck::FORM_FAST_2W, g_two_waves ? ck::FORM_MID_WALK_2W : ck::FORM_ALONE,
+                      model->maxefc > ck::MID_ROWS, g_inplace_stay};
+        g_io.progress = progress;
+        g_io.nchunk = (g_chunks > 1 && nsub >= 2) ? g_chunks : 1;
+        g_io.chunk_seq = ++g_chunk_seq; g_io.chunk_flag = chunk_flag; g_io.chunk_fault = &g_chunk_fault;
+    } else if (cassie32) forms.first = model->maxefc > ck::MID_ROWS ? ck::FORM_WIDE : g_two_waves ? ck::FORM_ALONE_2W : ck::FORM_ALONE;
+    else if (tray38 && g_two_waves) forms.first = ck::FORM_ALONE_2W;
+    const ck::StepPlan plan = ck::plan_step(g_io, forms, hl, {(unsigned)nenv, (unsigned)g_resume_grid, (unsigned)(g_resume_grid > 1 ? g_resume_grid - 1 : 1)});
+    for (int i = 0; i < plan.n; ++i) {
+        const ck::StepPass &p = plan.pass[i];
+        const EmuForm &f = bodies[p.form];
+        if (!f.body) wv::emu_fail("no instantiation of this form");
+        g_io = p.io;
+        const int handed = p.io.handover_list ? p.io.handover_count[0] : 0;
+        if (p.form == ck::FORM_WIDE_WALK) g_wide_envs += handed;
+        g_grid = (int)p.grid;
+        for (int wg = 0; wg < g_grid; ++wg) { g_env = wg; run_block(f.body, f.nw); }
+        if (ck::is_fast_form(p.form)) for (int e = 0; e < nenv; ++e) if (progress[e] < nsub) ++g_fast_bails;
+        /* a pass that walks a list leaves it empty for the next launch and reports its length */
+        if (p.io.handover_list && (p.io.handover_count[0] != 0 || p.io.handover_count[1] != 0 || *p.io.handover_seen != handed)) {
+            fprintf(stderr, "emu: the pass of form %d left count %d ticket %d seen %d (handed %d)\n", p.form, p.io.handover_count[0], p.io.handover_count[1], (int)*p.io.handover_seen, handed);
+            abort();
         }
-        static int chunk_flag[1 << 16];
-        const int nchunk = (g_chunks > 1 && nsub >= 2) ? g_chunks : 1;
-        g_io.nchunk = nchunk; g_io.chunk_seq = ++g_chunk_seq; g_io.chunk_flag = chunk_flag; g_io.chunk_fault = &g_chunk_fault;
-        g_grid = nenv * nchunk;
-        for (int wg = 0; wg < nenv * nchunk; ++wg) {
-            g_env = wg;
-            if (tray38) run_block(body40s_fast);
-            else if (inplace) run_block(body32s_fast_2w_inplace, 2);
-            else if (g_two_waves) run_block(body32s_fast_2w, 2); else run_block(body32s_fast);
-        }
-        for (int e = 0; e < nenv; ++e) if (progress[e] < nsub) ++g_fast_bails;
-        g_io.nchunk = 1;
-        const int handed = count[0];
-        g_io.resume = 1; g_io.has_next = third ? 1 : 0;
-        g_io.handover_list = list; g_io.handover_count = count; g_io.handover_seen = &seen;
-        g_io.handover_out_list = third ? list2 : nullptr; g_io.handover_out_count = third ? count2 : nullptr;
-        g_grid = g_resume_grid;
-        for (int wg = 0; wg < g_resume_grid && !inplace; ++wg) {
-            g_env = wg;
-            if (tray38) { if (g_two_waves) run_block(body40s_2w_walk, 2); else run_block(body40s_walk); }
-            else if (g_two_waves) run_block(body32s_2w_walk, 2); else run_block(body32s_walk);
-        }
-        if (!inplace && (count[0] != 0 || count[1] != 0 || seen != handed)) { fprintf(stderr, "emu: the pass behind the fast kernel left count %d ticket %d seen %d (handed %d)\n", count[0], count[1], (int)seen, handed); abort(); }
-        if (third) {
-            const int handed2 = count2[0];
-            g_wide_envs += handed2;
-            g_io.has_next = 0;
-            g_io.handover_list = list2; g_io.handover_count = count2; g_io.handover_seen = &seen2;
-            g_io.handover_out_list = nullptr; g_io.handover_out_count = nullptr;
-            const int grid2 = g_resume_grid > 1 ? g_resume_grid - 1 : 1;
-            g_grid = grid2;
-            for (int wg = 0; wg < grid2; ++wg) { g_env = wg; run_block(body32s_wide_walk, 2); }
-            if (count2[0] != 0 || count2[1] != 0 || seen2 != handed2) { fprintf(stderr, "emu: the 127-row pass left count %d ticket %d seen %d (handed %d)\n", count2[0], count2[1], (int)seen2, handed2); abort(); }
-        }
-        g_grid = 1;
-        g_io.progress = nullptr; g_io.resume = 0; g_io.has_next = 0; g_io.handover_list = nullptr; g_io.handover_count = nullptr; g_io.handover_seen = nullptr;
-        return 0;
     }
-    for (int e = 0; e < nenv; ++e) {
-        g_env = e;
-        if (cassie32) {
-            /* (alone -- forward / read-out passes, the fast kernel switched off: the 127-row instantiation for models that may use
-             * its rows, the 63-row one for per-env models capped there) */
-            if (model->maxefc > ck::MID_ROWS) run_block(body32s_wide, 2);
-            else if (g_two_waves) run_block(body32s_2w, 2); else run_block(body32s);
-        }
-        else if (!g_force_runtime_topology && topo_matches(model, ck::TopoCassieTray38::table, ck::TopoCassieTray38::nv, ck::TopoCassieTray38::body_levels)) {
-            if (g_two_waves && model->nhfpair == 0 && model->hfield_geom < 0) run_block(body40s_2w, 2); else run_block(body40s);
-        }
-        else run_block(model->nv <= 32 ? body32 : body40);
-    }
+    g_grid = 1;
     return 0;
 }
 /* phys_batch_derive on the emulator: a forward pass with the read-out enabled, then the derive kernel, env by env */
