@@ -3,6 +3,7 @@
 #   make            product library  cassie-mujoco-sim_amd/lib/libcassiemujoco.so   (hipcc, gfx950)
 #   make oracle     CPU oracle       oracle/libcassie_oracle.so                     (gcc, test-only)
 #   make emu        wave emulator    tests/emu/libcassie_emu.so                     (g++, test-only)
+#                   + wave checks    tests/device/libwave_check.so                  (hipcc, gfx950, test-only)
 #   make models     models/*.cmodel from the reference MJCF (needs /root/reference)
 #
 # The Agility blocks (pd_input / cassie_core_sim / state_output + pack/unpack) exist
@@ -67,12 +68,15 @@ AGILITY_LINK := $(AGILITY_ABSENT)
 AGILITY_DEPS := $(AGILITY_ABSENT)
 endif
 
-.PHONY: all product oracle emu models clean apps FORCE
+.PHONY: all product oracle emu wave_check models clean apps FORCE
 all: product oracle emu apps
 apps: $(PKG)/bin/cassiesim
 product: $(PRODUCT)
 oracle: oracle/libcassie_oracle.so
-emu: tests/emu/libcassie_emu.so
+# (the wave checks' sources live in the test tree: a tree without them -- an older tests/ -- builds the rest as before)
+WAVE_CHECK := $(if $(wildcard tests/device/wave_check.hip),tests/device/libwave_check.so)
+emu: tests/emu/libcassie_emu.so $(WAVE_CHECK)
+wave_check: tests/device/libwave_check.so
 
 $(OBJD)/%.o: $(CSRC)/%.cpp $(wildcard $(CSRC)/*.h) $(wildcard include/*.h)
 	@mkdir -p $(OBJD)
@@ -111,11 +115,16 @@ $(PKG)/bin/cassiesim: $(PKG)/apps/cassiesim.c $(PRODUCT)
 oracle/libcassie_oracle.so: oracle/cassie_oracle.c oracle/cassie_oracle.h $(CSRC)/cm_model.h
 	gcc -O2 -std=gnu11 -fPIC -shared -fopenmp -I$(CSRC) -Ioracle oracle/cassie_oracle.c -o $@ -lm
 
-tests/emu/libcassie_emu.so: tests/emu/emu_runtime.cpp tests/emu/wave.h $(wildcard $(CSRC)/*.h) $(wildcard $(CSRC)/*.inc)
-	g++ -O2 -std=c++17 -fPIC -shared -Wl,-Bsymbolic -Itests/emu -I$(CSRC) tests/emu/emu_runtime.cpp -o $@
+tests/emu/libcassie_emu.so: tests/emu/emu_runtime.cpp tests/emu/wave.h $(wildcard tests/device/wave_bodies.h) $(wildcard $(CSRC)/*.h) $(wildcard $(CSRC)/*.inc)
+	g++ -O2 -std=c++17 -fPIC -shared -Wl,-Bsymbolic -Itests/emu -I$(CSRC) -Itests/device tests/emu/emu_runtime.cpp -o $@
+
+# the wave primitives and the kernel's numerical helpers one at a time (tests/test_wave_primitives.py): the bodies of
+# wave_bodies.h for gfx950, with the product's flags -- the emulator library above runs the same bodies
+tests/device/libwave_check.so: tests/device/wave_check.hip tests/device/wave_bodies.h $(wildcard $(CSRC)/*.h) $(wildcard $(CSRC)/*.inc) $(wildcard include/*.h)
+	$(HIPCC) $(HIPFLAGS) -Itests/device -shared -o $@ $<
 
 models: product
 	python3 tools/make_models.py $(REF)/model models tests/golden
 
 clean:
-	rm -rf $(OBJD) $(PRODUCT) oracle/libcassie_oracle.so tests/emu/libcassie_emu.so
+	rm -rf $(OBJD) $(PRODUCT) oracle/libcassie_oracle.so tests/emu/libcassie_emu.so tests/device/libwave_check.so

@@ -87,13 +87,14 @@ WV_DEVICE unsigned long long anc_mask(ModelPtr m, int k) {
  * ops, no compare -> scalar mask -> select round trip, which costs ~30 clocks per use on this hardware) */
 WV_DEVICE double bitf(unsigned long long mask, int c) { return (double)(unsigned)((mask >> c) & 1ull); }
 
-/* reciprocal to full fp64 accuracy without the IEEE division sequence: hardware estimate + two Newton steps
- * (the pivots are positive and far from the denormal / overflow ranges) */
+/* reciprocal to full fp64 accuracy (within half an ulp and a hair, tests/test_wave_primitives.py) without the IEEE division
+ * sequence: hardware estimate + two Newton steps, the second as r + r (1 - x r) with the residual exact and one rounding
+ * (written r (2 - x r) it rounds 2 - x r first: 1.24 ulp off at worst on the device, 1.86 in the emulator build).  The
+ * pivots are positive and far from the denormal / overflow ranges. */
 WV_DEVICE double fast_rcp(double x) {
     double r = wv::rcp_estimate(x);
     r = r * (2.0 - x * r);
-    r = r * (2.0 - x * r);
-    return r;
+    return fma(r, fma(-x, r, 1.0), r);
 }
 
 /* L^T D L factorisation of two tree-sparse matrices (M and M + hB) held one column per lane in registers

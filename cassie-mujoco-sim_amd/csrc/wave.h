@@ -158,7 +158,7 @@ WV_DEVICE int shfl_i(int v, int src_lane) { return __shfl(v, src_lane, WV_WAVE);
 
 /* v_mfma_f64_16x16x4_f64: D = A B + C on the matrix core, A 16 x 4, B 4 x 16, C / D 16 x 16 spread over the wave -- lane l
  * supplies A[l & 15][l >> 4] and B[l >> 4][l & 15] and holds C / D[(l >> 4) + 4 v][l & 15] in c[v], v = 0 .. 3.  Every
- * element is the plain FMA chain over k = 0 .. 3 on top of C, bit for bit (tools/mfma_f64_probe.hip), at 64 clocks
+ * element is the plain FMA chain over k = 0 .. 3 on top of C, bit for bit (tests/test_wave_primitives.py), at 64 clocks
  * per instruction whether or not the next one depends on it.  All 64 lanes must be active.  Callers keep three or four
  * independent accumulations in flight (the _x3 / _x4 forms) so that a dependent instruction never follows directly;
  * mfma_f64_drain is a no-op on the device (the compiler inserts the wait states in front of the first read of a result). */
@@ -297,7 +297,8 @@ WV_DEVICE long long hw_id() {
 }
 
 WV_DEVICE int popc64(unsigned long long x) { return __popcll(x); }
-/* max of two doubles that are known not to be signalling NaNs, as the single instruction */
+/* max of two doubles that are known not to be signalling NaNs, as the single instruction: in IEEE mode a quiet NaN operand
+ * yields the other operand, and +0 is larger than -0 (tests/test_wave_primitives.py) */
 WV_DEVICE double max_raw(double a, double b) { double r; asm("v_max_f64 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }
 
 }  // namespace wv

@@ -1,0 +1,41 @@
+/*
+ * wave_check.hip -- TEST-ONLY: the bodies of wave_bodies.h as gfx950 kernels, built with the product's HIPFLAGS (the
+ * contraction and the code generation must be the step kernel's).  One workgroup of one wave per trial.
+ *
+ * extern "C" int wc_<name>(const double *in, double *out, int ntrial): host buffers of ntrial * nin * 64 and
+ * ntrial * nout * 64 doubles (tests/wave_check.py checks the sizes against wc_shape); returns the first HIP error, 0 if none.
+ * The emulator library exports the same functions (tests/emu/emu_runtime.cpp).
+ */
+#include "physics_kernel.h"
+#include "wave_bodies.h"
+
+#define WC_KERNEL(name, nin, nout)                                                                  \
+    __global__ __launch_bounds__(64) void wc_kernel_##name(const double *in, double *out) {       \
+        const size_t t = blockIdx.x;                                                              \
+        wc::name(in + t * (nin) * 64, out + t * (nout) * 64);                                      \
+    }
+WAVE_CHECK_BODIES(WC_KERNEL)
+
+static int wc_launch(void (*kernel)(const double *, double *), const double *in, double *out, int ntrial, int nin, int nout) {
+    if (ntrial <= 0) return 0;
+    const size_t bin = (size_t)ntrial * nin * 64 * sizeof(double), bout = (size_t)ntrial * nout * 64 * sizeof(double);
+    double *din = nullptr, *dout = nullptr;
+    hipError_t e = hipMalloc((void **)&din, bin);
+    if (e == hipSuccess) e = hipMalloc((void **)&dout, bout);
+    if (e == hipSuccess) e = hipMemcpy(din, in, bin, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemset(dout, 0xff, bout); /* (NaN: an output a body does not write shows) */
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(kernel, dim3((unsigned)ntrial), dim3(64), 0, 0, (const double *)din, dout);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e == hipSuccess) e = hipMemcpy(out, dout, bout, hipMemcpyDeviceToHost);
+    if (din) (void)hipFree(din);
+    if (dout) (void)hipFree(dout);
+    return (int)e;
+}
+
+#define WC_LAUNCHER(name, nin, nout) \
+    extern "C" int wc_##name(const double *in, double *out, int ntrial) { return wc_launch(wc_kernel_##name, in, out, ntrial, nin, nout); }
+WAVE_CHECK_BODIES(WC_LAUNCHER)
+

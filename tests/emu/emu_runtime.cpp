@@ -162,26 +162,6 @@ int g_force_guarded = 0;
 int g_poison_lds = 0;
 int g_skip_com_init = 0;
 unsigned long g_poison_lo = 0, g_poison_hi = ~0ul;
-double wave_sum(double v) { /* same association order as the device's DPP reduction (csrc/wave.h) */
-    const int l = lane(), row = l >> 4;
-    v += shfl(v, l ^ 1);
-    v += shfl(v, l ^ 2);
-    v += shfl(v, (l & ~7) | (7 - (l & 7)));
-    v += shfl(v, (l & ~15) | (15 - (l & 15)));
-    { const double t = shfl(v, ((row > 0 ? row - 1 : 0) << 4) | 15); if (row & 1) v += t; }
-    { const double t = shfl(v, 31); if (row >= 2) v += t; }
-    return shfl(v, 63);
-}
-float wave_sum_f32(float v) { /* same tree in single precision */
-    const int l = lane(), row = l >> 4;
-    v += (float)shfl((double)v, l ^ 1);
-    v += (float)shfl((double)v, l ^ 2);
-    v += (float)shfl((double)v, (l & ~7) | (7 - (l & 7)));
-    v += (float)shfl((double)v, (l & ~15) | (15 - (l & 15)));
-    { const float t = (float)shfl((double)v, ((row > 0 ? row - 1 : 0) << 4) | 15); if (row & 1) v += t; }
-    { const float t = (float)shfl((double)v, 31); if (row >= 2) v += t; }
-    return (float)shfl((double)v, 63);
-}
 }  // namespace wv
 
 static ck::PhysIO g_io;
@@ -424,3 +404,22 @@ extern "C" int emu_lpack_check(void) {
     return lpack_mismatches<ck::TopoCassieTray38, 40>() + lpack_mismatches<ck::TopoCassie32, 32>() + lpack_mismatches<ck::TopoRuntime, 40>();
 }
 extern "C" int emu_lpack_count(int which) { return which ? ck::LPack<ck::TopoCassieTray38, 40>::count : ck::LPack<ck::TopoCassie32, 32>::count; }
+
+/* the primitive checks of tests/device/wave_bodies.h, one emulated wave per trial: the same entry points as the device's
+ * wave_check.hip (tests/wave_check.py) */
+#include "wave_bodies.h"
+static const double *g_wc_in;
+static double *g_wc_out;
+static void (*g_wc_body)(const double *, double *);
+static int g_wc_nin, g_wc_nout;
+static void wc_trial() { g_wc_body(g_wc_in + (size_t)g_env * g_wc_nin * 64, g_wc_out + (size_t)g_env * g_wc_nout * 64); }
+static int wc_run(void (*body)(const double *, double *), const double *in, double *out, int ntrial, int nin, int nout) {
+    g_wc_body = body; g_wc_in = in; g_wc_out = out; g_wc_nin = nin; g_wc_nout = nout;
+    g_grid = ntrial;
+    for (int t = 0; t < ntrial; ++t) { g_env = t; run_block(wc_trial); }
+    g_grid = 1;
+    return 0;
+}
+#define WC_ENTRY(name, nin, nout) \
+    extern "C" int wc_##name(const double *in, double *out, int ntrial) { return wc_run(wc::name, in, out, ntrial, nin, nout); }
+WAVE_CHECK_BODIES(WC_ENTRY)

@@ -45,6 +45,7 @@ double shfl_xor(double v, int mask);
 int shfl_i(int v, int src_lane);
 struct mfma_acc { double c[4]; };
 void mfma_f64_16x16x4(double a, double b, double (&c)[4]);
+inline void mfma_f64_16x16x4(double a, double b, mfma_acc &c) { mfma_f64_16x16x4(a, b, c.c); } /* (the device's signature) */
 inline void mfma_f64_16x16x4_x3(double a0, double b0, mfma_acc &c0, double a1, double b1, mfma_acc &c1, double a2, double b2, mfma_acc &c2) {
     mfma_f64_16x16x4(a0, b0, c0.c); mfma_f64_16x16x4(a1, b1, c1.c); mfma_f64_16x16x4(a2, b2, c2.c);
 }
@@ -59,8 +60,41 @@ double readlane(double v, int src);
 int lane();
 template <int DST> inline double writelane(double v, double s) { return lane() == DST ? s : v; } /* s is the same in every lane */
 unsigned long long ballot(bool p);
-double wave_sum(double v);
-float wave_sum_f32(float v);
+/* v from another lane through a DPP control, as v_mov_dpp with old = 0 and bound_ctrl off: 0.0 in the rows ROW_MASK leaves
+ * out and in the rows the control broadcasts nothing into (row_bcast15: row 0; row_bcast31: rows 0 and 1 -- rows the sums mask off) */
+template <int CTRL, int ROW_MASK> inline double dpp_take(double v) {
+    static_assert(CTRL <= 0xFF || (CTRL >= 0x140 && CTRL <= 0x143), "quad_perm, row_mirror, row_half_mirror, row_bcast15/31");
+    const int l = lane(), row = l >> 4;
+    int src = l;
+    bool valid = true;
+    if (CTRL <= 0xFF) src = (l & ~3) | ((CTRL >> (2 * (l & 3))) & 3);       /* quad_perm */
+    else if (CTRL == 0x140) src = (l & ~15) | (15 - (l & 15));             /* row_mirror */
+    else if (CTRL == 0x141) src = (l & ~7) | (7 - (l & 7));                /* row_half_mirror */
+    else if (CTRL == 0x142) { src = 16 * row - 1; valid = row > 0; }       /* row_bcast15: lane 15 of the row before */
+    else { src = 31; valid = row >= 2; }                                   /* row_bcast31 */
+    const double t = shfl(v, valid ? src : l);
+    return valid && ((ROW_MASK >> row) & 1) ? t : 0.0;
+}
+template <int CTRL, int ROW_MASK> inline float dpp_take_f32(float v) { return (float)dpp_take<CTRL, ROW_MASK>((double)v); }
+/* the device's reductions (csrc/wave.h), step for step */
+inline double wave_sum(double v) {
+    v += dpp_take<0xB1, 0xf>(v);
+    v += dpp_take<0x4E, 0xf>(v);
+    v += dpp_take<0x141, 0xf>(v);
+    v += dpp_take<0x140, 0xf>(v);
+    v += dpp_take<0x142, 0xa>(v);
+    v += dpp_take<0x143, 0xc>(v);
+    return readlane(v, 63);
+}
+inline float wave_sum_f32(float v) {
+    v += dpp_take_f32<0xB1, 0xf>(v);
+    v += dpp_take_f32<0x4E, 0xf>(v);
+    v += dpp_take_f32<0x141, 0xf>(v);
+    v += dpp_take_f32<0x140, 0xf>(v);
+    v += dpp_take_f32<0x142, 0xa>(v);
+    v += dpp_take_f32<0x143, 0xc>(v);
+    return (float)readlane((double)v, 63);
+}
 /* workgroups run one after the other here, in launch order: the word a chunk waits for must be there already */
 /* (the word is 64 tag + 8 XCC + done, wave.h of the product; the emulator has one "XCD", number emu_xcc(): a test hook that lets
  * a test place a producer elsewhere and see the consumer's check fire) */
@@ -76,7 +110,13 @@ template <int NW> inline bool wait_global(const int *flag, int tag, int done) {
 inline long long clock() { return 0; }
 inline long long wall_clock() { return 0; }
 inline long long hw_id() { return 0; }
-inline double max_raw(double a, double b) { return a > b ? a : b; }
+/* v_max_f64 in IEEE mode: a quiet NaN operand yields the other operand (NaN only when both are), and -0 < +0 */
+inline double max_raw(double a, double b) {
+    if (a != a) return b;
+    if (b != b) return a;
+    if (a == 0.0 && b == 0.0) return std::signbit(a) ? b : a;
+    return a > b ? a : b;
+}
 inline int opaque(int x) { return x; }
 template <int P> inline void set_priority() {}
 #define CK_PRIO_W0 0
@@ -108,7 +148,7 @@ inline void test_launch_hook(void *shared, unsigned long size) {
 }
 inline int fresh_lane() { return lane(); }
 template <class P> inline P opaque_ptr(P p) { return p; }
-inline double rcp_estimate(double x) { return (double)(1.0f / (float)x); } /* deliberately low precision, like the hardware estimate */
+inline double rcp_estimate(double x) { return (double)(1.0f / (float)x); } /* deliberately low precision, like the hardware estimate (both within 2^-16, test_wave_primitives.py) */
 inline double rsq_estimate(double x) { return (double)(1.0f / sqrtf((float)x)); }
 /* individually rounded double operations (the emulator is built without FMA contraction: baseline x86-64) */
 inline double mul_rn(double a, double b) { volatile double r = a * b; return r; }
