@@ -19,6 +19,7 @@ _structs = cstruct.parse_structs(_hdr, MACROS)
 CmModel = _structs["cm_model_t"]
 CmDriveState = _structs["cm_drive_state_t"]
 CmEnvParams = _structs["cm_envparams_t"]
+CmEpisodeRules = _structs.get("cm_episode_rules_t")   # (None with the header of an older variant build)
 
 _lib = None
 
@@ -37,6 +38,8 @@ def lib():
             raise RuntimeError("cm_model_t layout mismatch between cm_model.h and the built library")
         if hasattr(_lib, "phys_sizeof_envparams") and _lib.phys_sizeof_envparams() != ctypes.sizeof(CmEnvParams):
             raise RuntimeError("cm_envparams_t layout mismatch between cm_model.h and the built library")
+        if hasattr(_lib, "phys_sizeof_episode_rules") and _lib.phys_sizeof_episode_rules() != ctypes.sizeof(CmEpisodeRules):
+            raise RuntimeError("cm_episode_rules_t layout mismatch between cm_model.h and the built library")
     return _lib
 
 
@@ -122,6 +125,16 @@ def _declare(L):
         L.phys_batch_step_range.argtypes = [vp, c.c_int, c.c_int, c.c_int, vp]
     if hasattr(L, "phys_batch_reset_envs"):
         L.phys_batch_reset_envs.argtypes = [vp, c.c_int, c.c_int, c.c_int, vp, vp, vp]
+    if hasattr(L, "phys_batch_end_episodes"):   # (absent from older variant builds selected with CASSIE_LIB)
+        L.phys_batch_episodes_enable.argtypes = [vp, c.POINTER(CmEpisodeRules)]
+        L.phys_batch_episodes_set_bank.argtypes = [vp, vp, c.c_int, c.c_int]
+        L.phys_batch_episode_row_dim.argtypes = [vp]
+        L.phys_batch_episode_ptr.restype = vp
+        L.phys_batch_episode_ptr.argtypes = [vp, c.c_int]
+        L.phys_batch_episode_bind.argtypes = [vp, c.c_int, vp]
+        L.phys_batch_end_episodes.argtypes = [vp, c.c_int, c.c_int, c.c_int, vp, vp, vp]
+        L.phys_batch_download_episodes.argtypes = [vp, c.c_int, vp]
+        L.phys_sizeof_episode_rules.restype = c.c_size_t
     if hasattr(L, "phys_batch_download_progress"):   # (absent from older variant builds selected with CASSIE_LIB)
         L.phys_batch_download_progress.argtypes = [vp, vp]
     L.phys_batch_set_all_outputs_every_substep.argtypes = [vp, c.c_int]

@@ -10,7 +10,7 @@ import os
 
 import numpy as np
 
-from ._lib import CmDriveState, CmEnvParams, CmModel, MODEL_DIR, lib
+from ._lib import CmDriveState, CmEnvParams, CmEpisodeRules, CmModel, MODEL_DIR, lib
 
 # field ids (enum in cassie_phys.h)
 (F_QPOS, F_QVEL, F_QACC_WARMSTART, F_TIME, F_CTRL, F_QFRC_APPLIED, F_XFRC_APPLIED, F_QACC, F_SENSORDATA,
@@ -40,6 +40,9 @@ WARN_CHUNK_PLACEMENT = 16   # a chunk of a stepping launch found its predecessor
  M_GEOM_SIZE, M_GEOM_FRICTION, M_ACTUATOR_GEAR, M_ACTUATOR_CTRLRANGE, M_ACTUATOR_USER, M_SENSOR_USER, M_HFIELD_SIZE, M_TIMESTEP,
  M_QPOS0, M_JNT_RANGE, M_STAT_CENTER, M_STAT_EXTENT, M_GEOM_USER, M_BODY_INERTIA) = range(23)
 SIZE_NGEOM = 5               # PHYS_NGEOM: geoms in the host model's full list
+# episodes on the device: bits of an env's reason word (CM_DONE_* in cm_model.h) and the per-env arrays (PHYS_EP_* in cassie_phys.h)
+DONE_HEIGHT, DONE_UPRIGHT, DONE_TIME, DONE_WARN, DONE_NONFINITE, DONE_FORCED = 1, 2, 4, 8, 16, 32
+EP_DONE, EP_REASON, EP_STEPS, EP_COUNT, EP_TERMINAL = range(5)
 
 # joint configuration the reference writes at init (reference src/cassiemujoco.c:1023-1028)
 QPOS_INIT_JOINTS = np.array(
@@ -127,6 +130,7 @@ class Batch:
         self.nenv = int(nenv)
         pod = model.pod if isinstance(model, Model) else model
         self.pod = pod
+        self.device = int(device)
         self._h = lib().phys_batch_create(ctypes.byref(pod), self.nenv, device)
         if not self._h:
             raise RuntimeError("phys_batch_create failed: " + (lib().phys_last_error() or b"").decode())
@@ -261,6 +265,83 @@ class Batch:
         zero, sensordata from `sens_row_ptr` if given."""
         if lib().phys_batch_reset_envs(self._h, int(first), int(stride), int(count), qpos_row_ptr, sens_row_ptr, stream) != 0:
             raise RuntimeError("reset_envs failed: " + (lib().phys_last_error() or b"").decode())
+
+    # ---- episodes that end and restart on the device (phys_batch_end_episodes) ----
+    def enable_episodes(self, min_height=-np.inf, min_upright=-np.inf, max_steps=0, warn_mask=0, nonfinite=False):
+        """Allocates the per-env episode arrays (first call) and sets the termination rules; every rule is off by default:
+        pelvis height qpos[2] < min_height, pelvis z axis' world-z component 1 - 2 (qx^2 + qy^2) < min_upright, episode step counter
+        >= max_steps, (warning word & warn_mask) != 0 (WARN_DIVERGED: MuJoCo's auto-reset), any non-finite qpos / qvel entry."""
+        r = CmEpisodeRules(min_height=float(min_height), min_upright=float(min_upright), max_steps=int(max_steps),
+                           warn_mask=int(warn_mask), nonfinite=1 if nonfinite else 0)
+        if lib().phys_batch_episodes_enable(self._h, ctypes.byref(r)) != 0:
+            raise RuntimeError("enable_episodes failed: " + (lib().phys_last_error() or b"").decode())
+
+    def episode_row_dim(self):
+        """Doubles per row of the bank of start states: qpos | qvel | sensordata | actuator_velocity | qacc."""
+        return lib().phys_batch_episode_row_dim(self._h)
+
+    def make_reset_bank(self, qpos, qvel=None):
+        """The bank rows [K][episode_row_dim()] of K start states: a K-env batch of the same (shared) model is set to qpos[K] /
+        qvel[K] (default zero) and run through forward() on the GPU, which gives the sensordata / actuator_velocity / qacc a
+        restarted env needs to continue exactly like a fresh one.  Hand the result to set_reset_bank."""
+        pod = self.pod
+        q = np.ascontiguousarray(qpos, dtype=np.float64).reshape(-1, pod.nq)
+        v = np.zeros((q.shape[0], pod.nv)) if qvel is None else np.ascontiguousarray(qvel, dtype=np.float64).reshape(-1, pod.nv)
+        if v.shape[0] != q.shape[0]:
+            raise ValueError("make_reset_bank: qpos and qvel need the same number of rows")
+        t = Batch(self.model, q.shape[0], self.device)
+        try:
+            t.set(F_QPOS, q)
+            t.set(F_QVEL, v)
+            t.forward()
+            return np.concatenate([t.get(f) for f in (F_QPOS, F_QVEL, F_SENSORDATA, F_ACTUATOR_VELOCITY, F_QACC)], axis=1)
+        finally:
+            t.close()
+
+    def set_reset_bank(self, rows=None, device_ptr=None, n=None):
+        """The start states restarted envs take: host `rows` [K][episode_row_dim()] (copied; waits for the batch's streams), or
+        `device_ptr` and n for rows already in HBM (used in place: keep them alive; they may be rewritten in stream order)."""
+        if device_ptr is not None:
+            if n is None:
+                raise ValueError("set_reset_bank: device_ptr needs n, the number of rows")
+            rc = lib().phys_batch_episodes_set_bank(self._h, device_ptr, 1, int(n))
+        else:
+            a = np.ascontiguousarray(rows, dtype=np.float64).reshape(-1, self.episode_row_dim())
+            rc = lib().phys_batch_episodes_set_bank(self._h, a.ctypes.data, 0, a.shape[0])
+        if rc != 0:
+            raise RuntimeError("set_reset_bank failed: " + (lib().phys_last_error() or b"").decode())
+
+    def end_episodes(self, env0=0, n=None, restart=True, pick_ptr=None, force_ptr=None, stream=None):
+        """One small launch on `stream` (default: the batch's own), in order with the step launches there and with no host read:
+        for every env of [env0, env0 + n) counts the policy step, evaluates the rules on the env's own state (| DONE_FORCED where
+        the int32 device array force_ptr[n] is non-zero), writes EP_DONE / EP_REASON, and for the envs that ended keeps the
+        terminal state, counts the episode and -- with `restart` -- restarts them from bank row pick_ptr[i] (int32 device array
+        [n]; default (env + episodes ended) % rows): state from the row, time / ctrl / warm start / drive-level state /
+        measurement block zero, warning word clear."""
+        n = self.nenv - env0 if n is None else n
+        if lib().phys_batch_end_episodes(self._h, int(env0), int(n), 1 if restart else 0, pick_ptr, force_ptr, stream) != 0:
+            raise RuntimeError("end_episodes failed: " + (lib().phys_last_error() or b"").decode())
+
+    def episode_ptr(self, which):
+        """Device pointer of an episode array (EP_DONE / EP_REASON / EP_STEPS / EP_COUNT: int32 [nenv]; EP_TERMINAL: float64
+        [nenv][nq + nv])."""
+        return lib().phys_batch_episode_ptr(self._h, int(which))
+
+    def bind_episode(self, which, device_ptr):
+        """Caller-owned HBM (e.g. a torch tensor the policy reads) in the place of an episode array."""
+        if lib().phys_batch_episode_bind(self._h, int(which), device_ptr) != 0:
+            raise RuntimeError("bind_episode failed: " + (lib().phys_last_error() or b"").decode())
+
+    def episodes(self):
+        """(done, reason, steps, count, terminal) downloaded; waits for the batch's streams."""
+        out = []
+        for which in (EP_DONE, EP_REASON, EP_STEPS, EP_COUNT, EP_TERMINAL):
+            a = (np.empty((self.nenv, self.pod.nq + self.pod.nv), dtype=np.float64) if which == EP_TERMINAL
+                 else np.empty(self.nenv, dtype=np.int32))
+            if lib().phys_batch_download_episodes(self._h, which, a.ctypes.data) != 0:
+                raise RuntimeError("episode download failed: " + (lib().phys_last_error() or b"").decode())
+            out.append(a)
+        return tuple(out)
 
     def get_drive_state(self, env0=0, n=None):
         n = self.nenv - env0 if n is None else n

@@ -378,6 +378,20 @@ enum { CM_DRIVE_OFF = 0,     /* ctrl (or the exact-state PD of phys_batch_set_pd
                                 reference src/cassiemujoco.c:1147-1157, on the device; cm_drive_state_t::safety_msg collects the block's
                                 diagnostic messages */
 
+/* When an episode ends (phys_batch_end_episodes): the rules one launch evaluates on every env's own state.  A rule is off at its
+ * neutral value. */
+typedef struct cm_episode_rules {
+    double min_height;     /* done if qpos[2] < min_height                                              (off: -inf) */
+    double min_upright;    /* done if 1 - 2 (qx qx + qy qy) < min_upright, q = qpos[3..6] = (w, x, y, z): the world-z component of
+                              the pelvis' z axis                                                        (off: -inf) */
+    int max_steps;         /* done if the env's episode step counter >= max_steps                       (off: 0) */
+    unsigned warn_mask;    /* done if (warn word & warn_mask) != 0, e.g. WARN_DIVERGED = 8              (off: 0) */
+    int nonfinite;         /* != 0: done if any qpos / qvel entry is NaN or |v| > 1e10 (the step kernel's own divergence test) */
+    int pad;
+} cm_episode_rules_t;
+/* bits of an env's `reason` word */
+enum { CM_DONE_HEIGHT = 1, CM_DONE_UPRIGHT = 2, CM_DONE_TIME = 4, CM_DONE_WARN = 8, CM_DONE_NONFINITE = 16, CM_DONE_FORCED = 32 };
+
 /* Optional per-env "extended" outputs of a step (what the reference reads out of mjData for its
  * derived getters: contact list + forces, body velocities, site frames, com; SURVEY.md 8b field census). */
 typedef struct cm_ext {

@@ -112,6 +112,14 @@ struct phys_batch {
     int waves_per_env = 2;          /* two-wave form of the fast instantiations (phys_batch_set_waves_per_env) */
     int waves_per_env_tray = DEFAULT_TRAY_WAVES; /* ... of the 40-dof instantiations (CASSIE_TRAY_TWO_WAVES=0/1 overrides the default: A/B aid) */
     double *d_scratch_out = nullptr; /* [nenv][nv + nsensordata + nu]: where phys_batch_forward_kinematics sends qacc / sensordata / actuator_velocity */
+    /* episodes on the device (phys_batch_end_episodes): the rules, the per-env arrays PHYS_EP_* and the bank of start states */
+    bool episodes = false;
+    cm_episode_rules_t ep_rules;
+    void *d_ep[PHYS_EP_ARRAYS] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+    bool ep_owned[PHYS_EP_ARRAYS] = {false, false, false, false, false};
+    const double *d_ep_bank = nullptr;
+    bool ep_bank_owned = false;
+    int ep_bank_rows = 0;
 };
 
 static bool hip_ok(hipError_t e, const char *what) {
@@ -557,6 +565,8 @@ void phys_batch_free(phys_batch_t *b) {
     if (b->d_hfield) (void)hipFree(b->d_hfield);
     if (b->d_ext) (void)hipFree(b->d_ext);
     if (b->d_scratch_out) (void)hipFree(b->d_scratch_out);
+    for (int a = 0; a < PHYS_EP_ARRAYS; ++a) if (b->ep_owned[a] && b->d_ep[a]) (void)hipFree(b->d_ep[a]);
+    if (b->ep_bank_owned && b->d_ep_bank) (void)hipFree((void *)b->d_ep_bank);
     if (b->d_progress) (void)hipFree(b->d_progress);
     if (b->d_chunk_flag) (void)hipFree(b->d_chunk_flag);
     if (b->d_handover_list) (void)hipFree(b->d_handover_list);
@@ -877,6 +887,96 @@ int phys_batch_reset_envs(phys_batch_t *b, int first, int stride, int count, con
     hipLaunchKernelGGL(ck::cassie_reset_kernel, dim3(count < 4 ? count : 4), dim3(WV_WAVE), 0, s, io);
     return hip_ok(hipGetLastError(), "cassie_reset_kernel launch") ? 0 : -1;
 }
+
+/* ------------------------------------------------ episodes on the device ---- */
+static size_t episode_array_bytes(const phys_batch *b, int which) {
+    return which == PHYS_EP_TERMINAL ? sizeof(double) * (size_t)b->nenv * (size_t)(b->host_model.nq + b->host_model.nv) : sizeof(int) * (size_t)b->nenv;
+}
+int phys_batch_episodes_enable(phys_batch_t *b, const cm_episode_rules_t *rules) {
+    if (!b || !rules) { phys_set_last_error("phys_batch_episodes_enable: bad arguments"); return -1; }
+    (void)hipSetDevice(b->device);
+    if (!b->episodes) {
+        for (int a = 0; a < PHYS_EP_ARRAYS; ++a) {
+            if (b->d_ep[a]) continue;
+            const size_t bytes = episode_array_bytes(b, a);
+            if (!hip_ok(hipMalloc(&b->d_ep[a], bytes), "hipMalloc(episode array)") || !hip_ok(hipMemset(b->d_ep[a], 0, bytes), "hipMemset(episode array)")) return -1;
+            b->ep_owned[a] = true;
+        }
+        if (!hip_ok(hipDeviceSynchronize(), "episode arrays sync")) return -1;
+        b->episodes = true;
+    }
+    b->ep_rules = *rules; /* (passed to every launch by value: launches already queued keep the rules they were given) */
+    return 0;
+}
+int phys_batch_episode_row_dim(const phys_batch_t *b) {
+    if (!b) return 0;
+    const cm_model_t &m = b->host_model;
+    return m.nq + m.nv + m.nsensordata + m.nu + m.nv;
+}
+int phys_batch_episodes_set_bank(phys_batch_t *b, const double *rows, int on_device, int nrows) {
+    if (!b || !rows || nrows <= 0) { phys_set_last_error("phys_batch_episodes_set_bank: bad arguments"); return -1; }
+    (void)hipSetDevice(b->device);
+    if (!quiesce(b)) return -1; /* (launches in flight may be reading the bank that goes away) */
+    if (b->ep_bank_owned && b->d_ep_bank) (void)hipFree((void *)b->d_ep_bank);
+    b->d_ep_bank = nullptr; b->ep_bank_owned = false; b->ep_bank_rows = 0;
+    if (on_device) b->d_ep_bank = rows;
+    else {
+        const size_t bytes = sizeof(double) * (size_t)nrows * (size_t)phys_batch_episode_row_dim(b);
+        double *d = nullptr;
+        if (!hip_ok(hipMalloc((void **)&d, bytes), "hipMalloc(reset bank)")) return -1;
+        if (!hip_ok(hipMemcpy(d, rows, bytes, hipMemcpyHostToDevice), "hipMemcpy(reset bank)")) { (void)hipFree(d); return -1; }
+        b->d_ep_bank = d; b->ep_bank_owned = true;
+    }
+    b->ep_bank_rows = nrows;
+    return 0;
+}
+void *phys_batch_episode_ptr(phys_batch_t *b, int which) {
+    return (b && which >= 0 && which < PHYS_EP_ARRAYS) ? b->d_ep[which] : nullptr;
+}
+int phys_batch_episode_bind(phys_batch_t *b, int which, void *device_ptr) {
+    if (!b || !device_ptr || which < 0 || which >= PHYS_EP_ARRAYS) { phys_set_last_error("phys_batch_episode_bind: bad arguments"); return -1; }
+    (void)hipSetDevice(b->device);
+    /* (as phys_batch_bind: launches already queued keep the pointer they were given; hipFree waits for the device by itself) */
+    if (b->ep_owned[which] && b->d_ep[which]) (void)hipFree(b->d_ep[which]);
+    b->d_ep[which] = device_ptr;
+    b->ep_owned[which] = false;
+    return 0;
+}
+int phys_batch_end_episodes(phys_batch_t *b, int env0, int n, int restart, const int *pick, const int *force, void *stream) {
+    if (!b) return -1;
+    if (!b->episodes) { phys_set_last_error("phys_batch_end_episodes: call phys_batch_episodes_enable first"); return -1; }
+    if (env0 < 0 || n < 0 || (size_t)env0 + (size_t)n > (size_t)b->nenv) { phys_set_last_error("phys_batch_end_episodes: env range out of bounds"); return -1; }
+    if (restart && (!b->d_ep_bank || b->ep_bank_rows <= 0)) { phys_set_last_error("phys_batch_end_episodes: restart needs a bank of start states (phys_batch_episodes_set_bank)"); return -1; }
+    for (int a = 0; a < PHYS_EP_ARRAYS; ++a) if (!b->d_ep[a]) { phys_set_last_error("phys_batch_end_episodes: an episode array is missing"); return -1; }
+    (void)hipSetDevice(b->device);
+    if (n == 0) return 0;
+    const cm_model_t &m = b->host_model;
+    ck::EpisodeIO io;
+    memset(&io, 0, sizeof io);
+    io.env0 = env0; io.n = n; io.restart = restart ? 1 : 0; io.nrows = b->ep_bank_rows;
+    io.nq = m.nq; io.nv = m.nv; io.nu = m.nu; io.nsd = m.nsensordata; io.row_dim = phys_batch_episode_row_dim(b);
+    io.sq = b->stride[PHYS_F_QPOS]; io.sqv = b->stride[PHYS_F_QVEL]; io.ssd = b->stride[PHYS_F_SENSORDATA];
+    io.rules = b->ep_rules;
+    io.qpos = b->d_field[PHYS_F_QPOS]; io.qvel = b->d_field[PHYS_F_QVEL]; io.warm = b->d_field[PHYS_F_QACC_WARMSTART];
+    io.ctrl = b->d_field[PHYS_F_CTRL]; io.qacc = b->d_field[PHYS_F_QACC]; io.time = b->d_field[PHYS_F_TIME];
+    io.sens = b->d_field[PHYS_F_SENSORDATA]; io.actvel = b->d_field[PHYS_F_ACTUATOR_VELOCITY];
+    io.meas = b->d_drive ? b->d_field[PHYS_F_MEAS] : nullptr;
+    io.drive = b->d_drive;
+    io.warn = b->d_warn;
+    io.done = (int *)b->d_ep[PHYS_EP_DONE]; io.reason = (int *)b->d_ep[PHYS_EP_REASON]; io.steps = (int *)b->d_ep[PHYS_EP_STEPS];
+    io.count = (int *)b->d_ep[PHYS_EP_COUNT]; io.terminal = (double *)b->d_ep[PHYS_EP_TERMINAL];
+    io.bank = b->d_ep_bank; io.pick = pick; io.force = force;
+    hipStream_t s = stream ? (hipStream_t)stream : b->stream;
+    note_stream(b, s);
+    hipLaunchKernelGGL(ck::cassie_episode_kernel, dim3((unsigned)(n < ck::EPISODE_GRID ? n : ck::EPISODE_GRID)), dim3(WV_WAVE), 0, s, io);
+    return hip_ok(hipGetLastError(), "cassie_episode_kernel launch") ? 0 : -1;
+}
+int phys_batch_download_episodes(phys_batch_t *b, int which, void *host) {
+    if (!b || !host || which < 0 || which >= PHYS_EP_ARRAYS || !b->d_ep[which]) { phys_set_last_error("phys_batch_download_episodes: bad arguments, or episodes not enabled"); return -1; }
+    (void)hipSetDevice(b->device);
+    return quiesce(b) && hip_ok(hipMemcpy(host, b->d_ep[which], episode_array_bytes(b, which), hipMemcpyDeviceToHost), "episode array download") ? 0 : -1;
+}
+size_t phys_sizeof_episode_rules(void) { return sizeof(cm_episode_rules_t); }
 
 int phys_batch_sync(phys_batch_t *b) {
     if (!b) return -1;

@@ -515,5 +515,81 @@ WV_GLOBAL void __launch_bounds__(WV_WAVE) cassie_reset_kernel(ResetIO io) {
 #endif
 }
 
+/* Episodes that end and restart on the device from each env's own state (phys_batch_end_episodes, include/cassie_phys.h), one wave
+ * per env: the lanes load the env's qpos / qvel entries; the non-finite test (the step kernel's own: NaN or |v| > 1e10) and the
+ * height / tilt thresholds are combined with wv::ballot; lane 0 writes done / reason / steps / count; the envs that ended keep their
+ * terminal state and -- with `restart` -- take a row of the bank of start states [qpos | qvel | sensordata | actuator_velocity | qacc]
+ * (what upload + forward leave on a fresh batch), zero time / ctrl / warm start / measurement block / drive-level state and a clear
+ * warning word.  The tilt expression is 1 - 2 (qx qx + qy qy) as written (it may contract to an fma on the device: thresholds are
+ * not meant to be met to the last bit).
+ * Like cassie_reset_kernel a few workgroups walk the range, for the reason given there: the launch runs behind a range's step launch
+ * while the other range's step kernel fills the chip. */
+constexpr int EPISODE_GRID = 32;
+struct EpisodeIO {
+    int env0, n, restart, nrows;
+    int nq, nv, nu, nsd, sq, sqv, ssd, row_dim;
+    cm_episode_rules_t rules;
+    double *qpos, *qvel, *warm, *ctrl, *qacc, *time, *sens, *actvel, *meas;   /* meas: null until a drive mode is in use */
+    cm_drive_state_t *drive;    /* likewise */
+    int *warn;
+    int *done, *reason, *steps, *count;
+    double *terminal;           /* [nenv][nq + nv] */
+    const double *bank;         /* [nrows][row_dim], may be null when restart == 0 */
+    const int *pick, *force;    /* [n] or null */
+};
+WV_GLOBAL void __launch_bounds__(WV_WAVE) cassie_episode_kernel(EpisodeIO io) {
+    const int lane = wv::lane();
+    const cm_episode_rules_t &R = io.rules;
+    for (int i = wv::env_id(); i < io.n; i += wv::grid_size()) {
+        const size_t env = (size_t)io.env0 + (size_t)i;
+        const double qp = lane < io.nq ? io.qpos[env * io.sq + lane] : 0.0;
+        const double qv = lane < io.nv ? io.qvel[env * io.sqv + lane] : 0.0;
+        const int warn = io.warn[env], steps = io.steps[env] + 1;
+        const int forced = io.force ? io.force[i] : 0, picked = io.pick ? io.pick[i] : 0;
+        int count = io.count[env];
+        const bool bad = (lane < io.nq && (!(qp == qp) || fabs(qp) > 1e10)) || (lane < io.nv && (!(qv == qv) || fabs(qv) > 1e10));
+        const double qx = wv::shfl(qp, 4), qy = wv::shfl(qp, 5);
+        const double upright = 1.0 - 2.0 * (qx * qx + qy * qy);
+        int reason = 0;
+        if (wv::ballot(lane == 2 && qp < R.min_height) != 0ull) reason |= CM_DONE_HEIGHT;
+        if (wv::ballot(upright < R.min_upright) != 0ull) reason |= CM_DONE_UPRIGHT;
+        if (R.max_steps > 0 && steps >= R.max_steps) reason |= CM_DONE_TIME;
+        if (((unsigned)warn & R.warn_mask) != 0u) reason |= CM_DONE_WARN;
+        if (wv::ballot(bad) != 0ull && R.nonfinite) reason |= CM_DONE_NONFINITE;
+        if (forced) reason |= CM_DONE_FORCED;
+        const bool done = reason != 0, restart = done && io.restart;
+        if (done) {
+            ++count;
+            double *t = io.terminal + env * (size_t)(io.nq + io.nv);
+            if (lane < io.nq) t[lane] = qp;
+            if (lane < io.nv) t[io.nq + lane] = qv;
+        }
+        if (lane == 0) {
+            io.done[env] = done ? 1 : 0; io.reason[env] = reason; io.steps[env] = restart ? 0 : steps;
+            if (done) io.count[env] = count;
+        }
+        if (restart) {
+            int r = io.pick ? picked % io.nrows : (int)((env + (size_t)count) % (size_t)io.nrows);
+            if (r < 0) r += io.nrows;
+            const double *row = io.bank + (size_t)r * io.row_dim;
+            for (int k = lane; k < io.nq; k += WV_WAVE) io.qpos[env * io.sq + k] = row[k];
+            row += io.nq;
+            for (int k = lane; k < io.nv; k += WV_WAVE) { io.qvel[env * io.sqv + k] = row[k]; io.warm[env * io.nv + k] = 0.0; }
+            row += io.nv;
+            for (int k = lane; k < io.nsd; k += WV_WAVE) io.sens[env * io.ssd + k] = row[k];
+            row += io.nsd;
+            for (int k = lane; k < io.nu; k += WV_WAVE) { io.actvel[env * io.nu + k] = row[k]; io.ctrl[env * io.nu + k] = 0.0; }
+            row += io.nu;
+            for (int k = lane; k < io.nv; k += WV_WAVE) io.qacc[env * io.nv + k] = row[k];
+            if (io.meas) for (int k = lane; k < CM_MEAS_DIM; k += WV_WAVE) io.meas[env * CM_MEAS_DIM + k] = 0.0;
+            if (io.drive) {
+                int *w = (int *)(io.drive + env);
+                for (int k = lane; k < (int)(sizeof(cm_drive_state_t) / sizeof(int)); k += WV_WAVE) w[k] = 0;
+            }
+            if (lane == 0) { io.time[env] = 0.0; io.warn[env] = 0; }
+        }
+    }
+}
+
 }  // namespace ck
 #endif

@@ -177,6 +177,44 @@ int phys_batch_forward(phys_batch_t *b, void *stream);
  * new episode's first drive-level pass reads.  The sticky warning word stays (phys_batch_clear_warn).  One small launch on
  * `stream`, ordered with the step launches there. */
 int phys_batch_reset_envs(phys_batch_t *b, int first, int stride, int count, const double *qpos_row, const double *sens_row, void *stream);
+/* Episodes that end and restart on the device, from each env's own state: one small launch per env range per policy step, no host
+ * read anywhere (MuJoCo's auto-reset and a training loop's "done" logic at policy rate).
+ *
+ * phys_batch_episodes_enable allocates the per-env arrays (all zero) and sets the rules (cm_episode_rules_t, cm_model.h); calling it
+ * again only replaces the rules.  The arrays, in HBM (phys_batch_episode_ptr; phys_batch_episode_bind puts caller-owned memory in
+ * their place, e.g. a torch tensor the policy reads):
+ *   PHYS_EP_DONE     int32 [nenv]           1 if the env's episode ended in the last phys_batch_end_episodes over it, else 0
+ *   PHYS_EP_REASON   int32 [nenv]           OR of the CM_DONE_* bits that ended it (0 if it goes on)
+ *   PHYS_EP_STEPS    int32 [nenv]           policy steps (end_episodes calls) of the running episode
+ *   PHYS_EP_COUNT    int32 [nenv]           episodes ended so far
+ *   PHYS_EP_TERMINAL double [nenv][nq + nv] qpos | qvel that ended the env's last episode (rows of envs that go on are left alone)
+ *
+ * phys_batch_end_episodes over envs [env0, env0 + n), per env and in this order:
+ *   1. steps += 1;
+ *   2. reason = OR of the rules that hold on the env's qpos, qvel, warning word and steps, | CM_DONE_FORCED if force && force[i] != 0
+ *      (i = env - env0); done = reason != 0.  Both words are written for every env of the range;
+ *   3. if done: terminal[env] = qpos | qvel, count += 1;
+ *   4. if done && restart: the env becomes what a fresh batch holds after upload(qpos), upload(qvel), forward for bank row
+ *      r = pick ? pick[i] mod nrows : (env + count) % nrows (count as step 3 left it): qpos | qvel | sensordata | actuator_velocity |
+ *      qacc from the row; time, ctrl and warm start zero; the measurement block and the drive-level state zero once a drive mode
+ *      is in use; the warning word cleared; steps = 0.
+ * pick / force are DEVICE arrays [n] of int32 or NULL.  A bank row holds phys_batch_episode_row_dim doubles,
+ * [nq | nv | nsensordata | nu | nv] in the order above: everything a forward pass leaves that a later step reads, and qacc.
+ * phys_batch_episodes_set_bank copies host rows (on_device == 0; waits for the batch's streams) or uses device rows in place
+ * (on_device != 0: caller-owned, must outlive their use, and may be rewritten in stream order).
+ * The launch honours strided qpos / qvel / sensordata bindings, goes to `stream` (NULL: the batch's own) in order with the step
+ * launches there, and never synchronises the host.  -1 + phys_last_error(): episodes not enabled, restart without a bank, range out
+ * of bounds. */
+enum { PHYS_EP_DONE, PHYS_EP_REASON, PHYS_EP_STEPS, PHYS_EP_COUNT, PHYS_EP_TERMINAL, PHYS_EP_ARRAYS };
+int phys_batch_episodes_enable(phys_batch_t *b, const cm_episode_rules_t *rules);
+int phys_batch_episodes_set_bank(phys_batch_t *b, const double *rows, int on_device, int nrows);
+int phys_batch_episode_row_dim(const phys_batch_t *b);
+void *phys_batch_episode_ptr(phys_batch_t *b, int which);
+int phys_batch_episode_bind(phys_batch_t *b, int which, void *device_ptr);
+int phys_batch_end_episodes(phys_batch_t *b, int env0, int n, int restart, const int *pick, const int *force, void *stream);
+/* one whole episode array to the host (int32 [nenv], or double [nenv][nq + nv] for PHYS_EP_TERMINAL); waits for the batch's streams */
+int phys_batch_download_episodes(phys_batch_t *b, int which, void *host);
+size_t phys_sizeof_episode_rules(void);
 /* the read-out half of mj_forward -- what the reference's getters obtain from mj_kinematics / mj_comPos / mj_comVel /
  * mj_fwdPosition (reference src/cassiemujoco.c:1223-1301, :1604-1770): xpos / xquat / the ext read-out / body_cfrc of the
  * current state, while the fields qacc, sensordata and actuator_velocity keep what the last STEP left (the encoder and
