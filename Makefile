@@ -115,9 +115,10 @@ $(PKG)/bin/cassiesim: $(PKG)/apps/cassiesim.c $(PRODUCT)
 oracle/libcassie_oracle.so: oracle/cassie_oracle.c oracle/cassie_oracle.h $(CSRC)/cm_model.h
 	gcc -O2 -std=gnu11 -fPIC -shared -fopenmp -I$(CSRC) -Ioracle oracle/cassie_oracle.c -o $@ -lm
 
-# (emu_episodes.cpp includes emu_runtime.cpp: one translation unit, the episode kernel's entry points use the runtime's workgroup loop)
-tests/emu/libcassie_emu.so: tests/emu/emu_episodes.cpp tests/emu/emu_runtime.cpp tests/emu/wave.h $(wildcard tests/device/wave_bodies.h) $(wildcard $(CSRC)/*.h) $(wildcard $(CSRC)/*.inc)
-	g++ -O2 -std=c++17 -fPIC -shared -Wl,-Bsymbolic -Itests/emu -I$(CSRC) -Itests/device tests/emu/emu_episodes.cpp -o $@
+# (emu_terrain.cpp includes emu_episodes.cpp, which includes emu_runtime.cpp: one translation unit, the entry points of the episode and
+# scan kernels use the runtime's workgroup loop)
+tests/emu/libcassie_emu.so: tests/emu/emu_terrain.cpp tests/emu/emu_episodes.cpp tests/emu/emu_runtime.cpp tests/emu/wave.h $(wildcard tests/device/wave_bodies.h) $(wildcard $(CSRC)/*.h) $(wildcard $(CSRC)/*.inc)
+	g++ -O2 -std=c++17 -fPIC -shared -Wl,-Bsymbolic -Itests/emu -I$(CSRC) -Itests/device tests/emu/emu_terrain.cpp -o $@
 
 # the wave primitives and the kernel's numerical helpers one at a time (tests/test_wave_primitives.py): the bodies of
 # wave_bodies.h for gfx950, with the product's flags -- the emulator library above runs the same bodies

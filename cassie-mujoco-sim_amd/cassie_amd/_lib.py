@@ -135,6 +135,15 @@ def _declare(L):
         L.phys_batch_end_episodes.argtypes = [vp, c.c_int, c.c_int, c.c_int, vp, vp, vp]
         L.phys_batch_download_episodes.argtypes = [vp, c.c_int, vp]
         L.phys_sizeof_episode_rules.restype = c.c_size_t
+    if hasattr(L, "phys_batch_set_hfield_bank"):   # (absent from older variant builds selected with CASSIE_LIB)
+        L.phys_batch_set_hfield_bank.argtypes = [vp, vp, c.c_int, c.c_int, c.c_int]
+        L.phys_batch_nterrain.argtypes = [vp]
+        L.phys_batch_terrain_index_ptr.restype = vp
+        L.phys_batch_terrain_index_ptr.argtypes = [vp]
+        L.phys_batch_bind_terrain_index.argtypes = [vp, vp]
+        L.phys_batch_set_terrain.argtypes = [vp, vp, c.c_int, c.c_int, c.c_int, vp]
+        L.phys_batch_scan_configure.argtypes = [vp, vp, c.c_int, c.c_int, c.c_double]
+        L.phys_batch_height_scan.argtypes = [vp, c.c_int, c.c_int, vp]
     if hasattr(L, "phys_batch_download_progress"):   # (absent from older variant builds selected with CASSIE_LIB)
         L.phys_batch_download_progress.argtypes = [vp, vp]
     L.phys_batch_set_all_outputs_every_substep.argtypes = [vp, c.c_int]

@@ -15,7 +15,7 @@ from ._lib import CmDriveState, CmEnvParams, CmEpisodeRules, CmModel, MODEL_DIR,
 # field ids (enum in cassie_phys.h)
 (F_QPOS, F_QVEL, F_QACC_WARMSTART, F_TIME, F_CTRL, F_QFRC_APPLIED, F_XFRC_APPLIED, F_QACC, F_SENSORDATA,
  F_ACTUATOR_VELOCITY, F_XPOS, F_XQUAT, F_PD_PTARGET, F_PD_KP, F_PD_KD, F_BODY_CFRC, F_DRIVE_CMD, F_MEAS, F_PD_DTARGET,
- F_PD_TORQUE, F_DERIVED, F_QM) = range(22)
+ F_PD_TORQUE, F_DERIVED, F_QM, F_HEIGHT_SCAN) = range(23)
 
 # layout of the derived block F_DERIVED (CM_DRV_* in cm_model.h); MAXV = CM_MAXV
 MAXV = 40
@@ -31,6 +31,9 @@ MEAS_ORIENTATION, MEAS_ANGVEL, MEAS_LINACC, MEAS_MAG, MEAS_DIM = 42, 46, 49, 52,
 FLAG_EULERDAMP, FLAG_WARMSTART, FLAG_REFSAFE, FLAG_HFDENSE, FLAG_HFMULTI, FLAG_HFPRISM, FLAG_BOX8 = 1, 2, 4, 8, 16, 32, 64      # CM_FLAG_* (cm_model.h)
 WARN_CONTACT_FULL, WARN_CONSTRAINT_FULL, WARN_UNSUPPORTED_PAIR, WARN_DIVERGED = 1, 2, 4, 8
 WARN_CHUNK_PLACEMENT = 16   # a chunk of a stepping launch found its predecessor on another XCD: the env's state may be stale, discard its results
+WARN_TERRAIN_INDEX = 32     # the env's terrain index lay outside the bank and was clamped to it
+WARN_SCAN_TILTED = 64       # height scan: the env's height-field geom is tilted out of the world's z axis and was left out
+SCAN_MAXPOINTS = 1024
 
 # per-env physical parameters (CM_P_* in cm_model.h): what Batch.randomize takes
 (P_BODY_MASS, P_BODY_IPOS, P_BODY_INERTIA, P_DOF_DAMPING, P_GEOM_FRICTION,
@@ -161,7 +164,7 @@ class Batch:
         return lib().phys_batch_device_ptr(self._h, field)
 
     def bind(self, field, device_ptr, row_stride=None):
-        """Aliases a field to caller-owned HBM; `row_stride` (doubles, qpos / qvel / sensordata only) lets the field be a
+        """Aliases a field to caller-owned HBM; `row_stride` (doubles, qpos / qvel / sensordata / the height scan only) lets the field be a
         column block of a wider tensor, e.g. one [nenv][nq + nv + nsensordata] observation block."""
         rc = (lib().phys_batch_bind(self._h, field, device_ptr) if row_stride is None
               else lib().phys_batch_bind_strided(self._h, field, device_ptr, int(row_stride)))
@@ -231,6 +234,90 @@ class Batch:
         rc = lib().phys_batch_set_hfield(self._h, ptr, a.size) if env is None else lib().phys_batch_set_hfield_env(self._h, int(env), ptr, a.size)
         if rc != 0:
             raise RuntimeError("set_hfield failed")
+
+    # ---- a bank of terrains shared by the envs, a per-env index, and the height scan ----
+    def set_hfield_bank(self, grids=None, device_ptr=None, nterrain=None):
+        """A bank of terrains: host `grids` [T][nrow * ncol] (or [T][nrow][ncol]) float32, or `device_ptr` and nterrain for grids that
+        are already in HBM (a torch tensor's data_ptr(): float32, contiguous).  The batch keeps a copy.  Every env starts on terrain 0;
+        set_terrain / the terrain index choose per env.  set_hfield afterwards returns to one shared grid or per-env grids."""
+        n = self.pod.hfield_nrow * self.pod.hfield_ncol
+        if self.pod.hfield_geom < 0 or n <= 0:
+            raise ValueError("set_hfield_bank: the model has no height field")
+        if device_ptr is not None:
+            if nterrain is None or int(nterrain) < 1:
+                raise ValueError("set_hfield_bank: device_ptr needs nterrain >= 1, the number of grids")
+            rc = lib().phys_batch_set_hfield_bank(self._h, device_ptr, 1, int(nterrain), n)
+        else:
+            a = np.ascontiguousarray(grids, dtype=np.float32)
+            if a.size == 0 or a.size % n != 0:
+                raise ValueError("set_hfield_bank: every grid needs nrow * ncol = %d samples (got %d values)" % (n, a.size))
+            rc = lib().phys_batch_set_hfield_bank(self._h, a.ctypes.data, 0, a.size // n, n)
+        if rc != 0:
+            raise RuntimeError("set_hfield_bank failed: " + (lib().phys_last_error() or b"").decode())
+
+    @property
+    def nterrain(self):
+        """Terrains of the bank in use (0: none)."""
+        return lib().phys_batch_nterrain(self._h)
+
+    @property
+    def terrain_index(self):
+        """Device pointer of the terrain index, int32 [nenv]: plain device memory a loop may rewrite in stream order (wrap it in a
+        torch tensor, or bind one with bind_terrain_index).  Values outside the bank are clamped by the kernels and raise
+        WARN_TERRAIN_INDEX."""
+        p = lib().phys_batch_terrain_index_ptr(self._h)
+        if not p:
+            raise RuntimeError("terrain index: " + (lib().phys_last_error() or b"").decode())
+        return p
+
+    def bind_terrain_index(self, device_ptr):
+        """Caller-owned HBM (an int32 torch tensor [nenv]) in the place of the terrain index."""
+        if lib().phys_batch_bind_terrain_index(self._h, device_ptr) != 0:
+            raise RuntimeError("bind_terrain_index failed: " + (lib().phys_last_error() or b"").decode())
+
+    def set_terrain(self, ids=None, env0=0, device_ptr=None, n=None, stream=None):
+        """Terrain ids of envs env0 ...: a host array [n] (checked against the bank) or `device_ptr` and n for int32 ids in HBM; in
+        order on `stream` (default: the batch's own)."""
+        if self.nterrain <= 0:
+            raise ValueError("set_terrain: no bank of terrains (set_hfield_bank)")
+        if device_ptr is not None:
+            if n is None:
+                raise ValueError("set_terrain: device_ptr needs n, the number of ids to read")
+            if env0 < 0 or n < 0 or env0 + n > self.nenv:
+                raise ValueError("set_terrain: envs [%d, %d) are not in the batch" % (env0, env0 + n))
+            rc = lib().phys_batch_set_terrain(self._h, device_ptr, 1, int(env0), int(n), stream)
+        else:
+            a = np.asarray(ids)
+            if a.ndim != 1 or not np.issubdtype(a.dtype, np.integer):
+                raise ValueError("set_terrain: ids must be a one-dimensional integer array")
+            if env0 < 0 or env0 + a.size > self.nenv:
+                raise ValueError("set_terrain: envs [%d, %d) are not in the batch" % (env0, env0 + a.size))
+            if a.size and (a.min() < 0 or a.max() >= self.nterrain):
+                raise ValueError("set_terrain: ids must lie in [0, %d)" % self.nterrain)
+            a = np.ascontiguousarray(a, dtype=np.int32)
+            rc = lib().phys_batch_set_terrain(self._h, a.ctypes.data, 0, int(env0), a.size, stream)
+        if rc != 0:
+            raise RuntimeError("set_terrain failed: " + (lib().phys_last_error() or b"").decode())
+
+    def configure_scan(self, offsets_xy, body, scan_range):
+        """The height scan's pattern: offsets_xy [P][2] (P <= SCAN_MAXPOINTS) in the heading frame of `body` (a child of the world: Cassie's
+        pelvis), values clamped to +-scan_range.  Sizes F_HEIGHT_SCAN to P doubles per env (bind a tensor after this call)."""
+        a = np.ascontiguousarray(offsets_xy, dtype=np.float64)
+        if a.ndim != 2 or a.shape[1] != 2 or not 1 <= a.shape[0] <= SCAN_MAXPOINTS:
+            raise ValueError("configure_scan: offsets_xy must be [P][2] with 1 <= P <= %d" % SCAN_MAXPOINTS)
+        if not float(scan_range) > 0:
+            raise ValueError("configure_scan: the range must be positive")
+        if not 0 < int(body) < self.pod.nbody:
+            raise ValueError("configure_scan: no such body")
+        if lib().phys_batch_scan_configure(self._h, a.ctypes.data, a.shape[0], int(body), float(scan_range)) != 0:
+            raise ValueError("configure_scan failed: " + (lib().phys_last_error() or b"").decode())
+
+    def height_scan(self, env0=0, n=None, stream=None):
+        """One small launch on `stream` (default: the batch's own), in order with the step launches there: F_HEIGHT_SCAN of envs
+        [env0, env0 + n) = clamp(z_body - highest static surface under the scan point, +-range), +range where there is none."""
+        n = self.nenv - env0 if n is None else n
+        if lib().phys_batch_height_scan(self._h, int(env0), int(n), stream) != 0:
+            raise RuntimeError("height_scan failed: " + (lib().phys_last_error() or b"").decode())
 
     def set_pd_mode(self, on=True):
         lib().phys_batch_set_pd_mode(self._h, 1 if on else 0)

@@ -43,7 +43,8 @@
         if constexpr (request_early) request_pair(lane, pc);
         /* pass 1, lane = candidate pair (pair types that give at most two contacts) */
         int ncon = 0;
-        const float *const env_hfield = io.hfield ? io.hfield + (size_t)env * io.hfield_stride : nullptr;
+        /* (env_hfield, the env's grid: shared, its own, or the bank's terrain the env's index names -- resolved once per call ahead of the
+         * substep loop, physics_kernel.h) */
         /* block cull: pairs against static non-plane geoms (stairs ...) are visited only if one of those geoms is
          * within reach of a kinematic tree (lane = collision geom) */
         int npass = m->npair_always;

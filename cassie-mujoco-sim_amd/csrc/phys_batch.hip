@@ -47,6 +47,15 @@ struct phys_batch {
     int *d_warn = nullptr, *d_info = nullptr;
     float *d_hfield = nullptr;
     size_t hfield_stride = 0, hfield_floats = 0; /* stride 0: one grid shared by all envs; else one grid of hfield_floats per env */
+    /* a bank of terrains (phys_batch_set_hfield_bank): d_hfield then holds nterrain grids and env e stands on grid d_terrain_index[e]
+     * (PhysIO::hfield_index; the array is created on first use and may be the caller's) */
+    int nterrain = 0;
+    int *d_terrain_index = nullptr;
+    bool terrain_index_owned = false;
+    /* the height scan (phys_batch_scan_configure): the pattern in HBM, its body and range */
+    double *d_scan_offsets = nullptr;
+    int scan_points = 0, scan_body = 0;
+    double scan_range = 0;
     hipStream_t stream = nullptr;
     hipStream_t recent_streams[4] = {nullptr, nullptr, nullptr, nullptr}; /* streams of the most recent launches (callers may pass
                                        their own, and ranges of one batch may be in flight on several at once) */
@@ -153,6 +162,7 @@ static ck::PhysIO make_io(phys_batch *b, int nsub, int integrate) {
     io.body_cfrc = b->d_field[PHYS_F_BODY_CFRC];
     io.hfield = b->d_hfield;
     io.hfield_stride = b->hfield_stride;
+    if (b->nterrain > 0) { io.hfield_index = b->d_terrain_index; io.hfield_nterrain = b->nterrain; }
     if (b->pd_mode) {
         io.pd_ptarget = b->d_field[PHYS_F_PD_PTARGET]; io.pd_kp = b->d_field[PHYS_F_PD_KP]; io.pd_kd = b->d_field[PHYS_F_PD_KD];
     }
@@ -423,7 +433,7 @@ static void note_field_in_use(phys_batch *b, int field) {
 /* rows [env0, env0 + n) of a field between a dense host array and HBM (dense, or strided when the field is a column
  * block of a caller-owned tensor), asynchronously on the batch's stream */
 static bool copy_rows(phys_batch *b, int field, void *host, int env0, int n, bool to_device, const char *what) {
-    if (!b->d_field[field]) { phys_set_last_error("this field is allocated by phys_batch_derive; call it first"); return false; }
+    if (!b->d_field[field]) { phys_set_last_error("this field is allocated by phys_batch_derive (PHYS_F_HEIGHT_SCAN: phys_batch_scan_configure); call it first"); return false; }
     const size_t row = (size_t)b->dim[field], st = (size_t)b->stride[field];
     double *dev = b->d_field[field] + st * env0;
     if (n == 0) return true;
@@ -494,11 +504,12 @@ phys_batch_t *phys_batch_create(const cm_model_t *model, int nenv, int device) {
     const int d[PHYS_F_COUNT] = {model->nq, model->nv, model->nv, 1, model->nu, model->nv, model->nbody * 6,
                                  model->nv, model->nsensordata, model->nu, model->nbody * 3, model->nbody * 4,
                                  model->nu, model->nu, model->nu, model->nbody * 3,
-                                 model->nu + 1, CM_MEAS_DIM, model->nu, model->nu, CM_DRV_DIM, model->nv * model->nv};
+                                 model->nu + 1, CM_MEAS_DIM, model->nu, model->nu, CM_DRV_DIM, model->nv * model->nv, 0};
     bool ok = true;
     for (int f = 0; f < PHYS_F_COUNT; ++f) {
         b->dim[f] = d[f]; b->stride[f] = d[f]; b->d_field[f] = nullptr; b->owned[f] = true;
         if (f == PHYS_F_DERIVED || f == PHYS_F_QM) continue; /* large and optional: allocated by the first phys_batch_derive */
+        if (f == PHYS_F_HEIGHT_SCAN) continue;              /* sized and allocated by phys_batch_scan_configure */
         size_t bytes = sizeof(double) * (size_t)nenv * (d[f] > 0 ? d[f] : 1);
         ok = ok && hip_ok(hipMalloc((void **)&b->d_field[f], bytes), "hipMalloc(field)");
         if (ok) ok = hip_ok(hipMemset(b->d_field[f], 0, bytes), "hipMemset(field)");
@@ -563,6 +574,8 @@ void phys_batch_free(phys_batch_t *b) {
     if (b->d_warn) (void)hipFree(b->d_warn);
     if (b->d_info) (void)hipFree(b->d_info);
     if (b->d_hfield) (void)hipFree(b->d_hfield);
+    if (b->terrain_index_owned && b->d_terrain_index) (void)hipFree(b->d_terrain_index);
+    if (b->d_scan_offsets) (void)hipFree(b->d_scan_offsets);
     if (b->d_ext) (void)hipFree(b->d_ext);
     if (b->d_scratch_out) (void)hipFree(b->d_scratch_out);
     for (int a = 0; a < PHYS_EP_ARRAYS; ++a) if (b->ep_owned[a] && b->d_ep[a]) (void)hipFree(b->d_ep[a]);
@@ -647,6 +660,7 @@ int phys_batch_set_hfield(phys_batch_t *b, const float *data, int n) {
     if (!b || !data || n <= 0) return -1;
     (void)hipSetDevice(b->device);
     if (!quiesce(b)) return -1;
+    b->nterrain = 0;
     if (b->d_hfield && (b->hfield_stride != 0 || b->hfield_floats != (size_t)n)) { /* back to one shared grid */
         (void)hipFree(b->d_hfield);
         b->d_hfield = nullptr;
@@ -661,8 +675,9 @@ int phys_batch_set_hfield_env(phys_batch_t *b, int env, const float *data, int n
     if (!b || !data || n <= 0 || env < 0 || env >= b->nenv) return -1;
     (void)hipSetDevice(b->device);
     if (!quiesce(b)) return -1;
-    if (b->hfield_stride == 0 || b->hfield_floats != (size_t)n) {
-        /* first per-env grid: expand to one grid per env, every env starting from the shared grid (or from zeros) */
+    if (b->hfield_stride == 0 || b->hfield_floats != (size_t)n || b->nterrain > 0) {
+        /* first per-env grid: expand to one grid per env, every env starting from the shared grid (or from zeros: no shared grid, or a
+         * bank of terrains was in use) */
         float *all = nullptr;
         const size_t bytes = sizeof(float) * (size_t)n;
         if (!hip_ok(hipMalloc((void **)&all, bytes * (size_t)b->nenv), "hipMalloc(hfield per env)")) return -1;
@@ -672,6 +687,7 @@ int phys_batch_set_hfield_env(phys_batch_t *b, int env, const float *data, int n
             if (!hip_ok(hipMemcpy(all + (size_t)e * n, b->d_hfield, bytes, hipMemcpyDeviceToDevice), "hipMemcpy(hfield)")) { (void)hipFree(all); return -1; }
         if (b->d_hfield) (void)hipFree(b->d_hfield);
         b->d_hfield = all;
+        b->nterrain = 0;
         b->hfield_stride = (size_t)n;
         b->hfield_floats = (size_t)n;
     }
@@ -743,12 +759,13 @@ int phys_batch_bind(phys_batch_t *b, int field, void *device_ptr) {
 int phys_batch_bind_strided(phys_batch_t *b, int field, void *device_ptr, int row_stride) {
     if (!b || !device_ptr || field < 0 || field >= PHYS_F_COUNT) return -1;
     if (row_stride != b->dim[field]) {
-        const bool may = field == PHYS_F_QPOS || field == PHYS_F_QVEL || field == PHYS_F_SENSORDATA;
+        const bool may = field == PHYS_F_QPOS || field == PHYS_F_QVEL || field == PHYS_F_SENSORDATA || field == PHYS_F_HEIGHT_SCAN;
         if (!may || row_stride < b->dim[field]) {
-            phys_set_last_error("phys_batch_bind_strided: only qpos / qvel / sensordata take a row stride, and it must be >= the field's dim");
+            phys_set_last_error("phys_batch_bind_strided: only qpos / qvel / sensordata / the height scan take a row stride, and it must be >= the field's dim");
             return -1;
         }
     }
+    if (field == PHYS_F_HEIGHT_SCAN && b->scan_points <= 0) { phys_set_last_error("phys_batch_bind: configure the scan first (phys_batch_scan_configure sizes PHYS_F_HEIGHT_SCAN)"); return -1; }
     (void)hipSetDevice(b->device);
     /* no stream synchronisation: launches already queued keep the pointers they were given, and hipFree of the
      * replaced buffer waits for the device by itself */
@@ -977,6 +994,119 @@ int phys_batch_download_episodes(phys_batch_t *b, int which, void *host) {
     return quiesce(b) && hip_ok(hipMemcpy(host, b->d_ep[which], episode_array_bytes(b, which), hipMemcpyDeviceToHost), "episode array download") ? 0 : -1;
 }
 size_t phys_sizeof_episode_rules(void) { return sizeof(cm_episode_rules_t); }
+
+/* ------------------------------------------------ terrains: a bank shared by the envs, a per-env index ---- */
+static bool ensure_terrain_index(phys_batch *b) {
+    if (b->d_terrain_index) return true;
+    if (!hip_ok(hipMalloc((void **)&b->d_terrain_index, sizeof(int) * (size_t)b->nenv), "hipMalloc(terrain index)")) return false;
+    b->terrain_index_owned = true;
+    return hip_ok(hipMemset(b->d_terrain_index, 0, sizeof(int) * (size_t)b->nenv), "hipMemset(terrain index)");
+}
+int phys_batch_set_hfield_bank(phys_batch_t *b, const float *grids, int on_device, int nterrain, int n) {
+    if (!b || !grids || nterrain <= 0 || n <= 0) { phys_set_last_error("phys_batch_set_hfield_bank: bad arguments"); return -1; }
+    if (b->host_model.hfield_geom < 0 || n != b->host_model.hfield_nrow * b->host_model.hfield_ncol) {
+        phys_set_last_error("phys_batch_set_hfield_bank: a grid must hold the model's hfield_nrow * hfield_ncol samples");
+        return -1;
+    }
+    (void)hipSetDevice(b->device);
+    if (!quiesce(b)) return -1;
+    const size_t bytes = sizeof(float) * (size_t)n * (size_t)nterrain;
+    float *all = nullptr;
+    if (!hip_ok(hipMalloc((void **)&all, bytes), "hipMalloc(terrain bank)")) return -1;
+    if (!hip_ok(hipMemcpy(all, grids, bytes, on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice), "hipMemcpy(terrain bank)")) { (void)hipFree(all); return -1; }
+    if (!ensure_terrain_index(b)) { (void)hipFree(all); return -1; }
+    /* every env starts on terrain 0 (an index array of the caller's keeps what the caller put there) */
+    if (b->terrain_index_owned && !hip_ok(hipMemset(b->d_terrain_index, 0, sizeof(int) * (size_t)b->nenv), "hipMemset(terrain index)")) { (void)hipFree(all); return -1; }
+    if (b->d_hfield) (void)hipFree(b->d_hfield);
+    b->d_hfield = all;
+    b->hfield_stride = (size_t)n; b->hfield_floats = (size_t)n;
+    b->nterrain = nterrain;
+    return 0;
+}
+int phys_batch_nterrain(const phys_batch_t *b) { return b ? b->nterrain : 0; }
+void *phys_batch_terrain_index_ptr(phys_batch_t *b) {
+    if (!b) return nullptr;
+    (void)hipSetDevice(b->device);
+    return ensure_terrain_index(b) ? (void *)b->d_terrain_index : nullptr;
+}
+int phys_batch_bind_terrain_index(phys_batch_t *b, void *device_ptr) {
+    if (!b || !device_ptr) { phys_set_last_error("phys_batch_bind_terrain_index: bad arguments"); return -1; }
+    (void)hipSetDevice(b->device);
+    /* (as phys_batch_bind: launches already queued keep the pointer they were given; hipFree waits for the device by itself) */
+    if (b->terrain_index_owned && b->d_terrain_index) (void)hipFree(b->d_terrain_index);
+    b->d_terrain_index = (int *)device_ptr;
+    b->terrain_index_owned = false;
+    return 0;
+}
+int phys_batch_set_terrain(phys_batch_t *b, const int *ids, int on_device, int env0, int n, void *stream) {
+    if (!b || !ids || env0 < 0 || n < 0 || (size_t)env0 + (size_t)n > (size_t)b->nenv) { phys_set_last_error("phys_batch_set_terrain: bad arguments"); return -1; }
+    if (b->nterrain <= 0) { phys_set_last_error("phys_batch_set_terrain: no bank of terrains (phys_batch_set_hfield_bank)"); return -1; }
+    if (!on_device)
+        for (int i = 0; i < n; ++i)
+            if (ids[i] < 0 || ids[i] >= b->nterrain) { phys_set_last_error("phys_batch_set_terrain: a terrain id outside the bank"); return -1; }
+    (void)hipSetDevice(b->device);
+    if (!ensure_terrain_index(b)) return -1;
+    if (n == 0) return 0;
+    hipStream_t s = stream ? (hipStream_t)stream : b->stream;
+    note_stream(b, s);
+    if (!hip_ok(hipMemcpyAsync(b->d_terrain_index + env0, ids, sizeof(int) * (size_t)n, on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s), "hipMemcpy(terrain ids)")) return -1;
+    /* (host ids: the caller's array may go away once the call returns) */
+    return on_device || hip_ok(hipStreamSynchronize(s), "terrain ids sync") ? 0 : -1;
+}
+
+/* ------------------------------------------------ the height scan ---- */
+int phys_batch_scan_configure(phys_batch_t *b, const double *offsets_xy, int npoints, int body, double range) {
+    if (!b || !offsets_xy || npoints <= 0 || npoints > ck::SCAN_MAXPOINTS || !(range > 0)) {
+        phys_set_last_error("phys_batch_scan_configure: 1 .. 1024 points and a positive range");
+        return -1;
+    }
+    const cm_model_t &m = b->host_model;
+    const int rt = body > 0 && body < m.nbody ? m.body_kin[body].rot_type : CM_JNT_HINGE;
+    if (body <= 0 || body >= m.nbody || !m.kin_simple || m.body_parentid[body] != 0 || b->model_stride != 0 ||
+        (rt != CM_JNT_BALL && rt != CM_JNT_FREE && rt != -1)) {
+        phys_set_last_error("phys_batch_scan_configure: the body must be a child of the world whose joints are slides and at most a ball or free joint (a shared kin_simple model)");
+        return -1;
+    }
+    (void)hipSetDevice(b->device);
+    if (!quiesce(b)) return -1;
+    double *off = nullptr, *out = nullptr;
+    const size_t obytes = sizeof(double) * 2 * (size_t)npoints, fbytes = sizeof(double) * (size_t)npoints * (size_t)b->nenv;
+    if (!hip_ok(hipMalloc((void **)&off, obytes), "hipMalloc(scan pattern)")) return -1;
+    if (!hip_ok(hipMemcpy(off, offsets_xy, obytes, hipMemcpyHostToDevice), "hipMemcpy(scan pattern)")) { (void)hipFree(off); return -1; }
+    /* the field takes the pattern's size: a buffer of the batch's own of the new size (a caller's binding is dropped: bind again) */
+    if (!hip_ok(hipMalloc((void **)&out, fbytes), "hipMalloc(height scan)") || !hip_ok(hipMemset(out, 0, fbytes), "hipMemset(height scan)")) {
+        (void)hipFree(off); if (out) (void)hipFree(out);
+        return -1;
+    }
+    if (b->d_scan_offsets) (void)hipFree(b->d_scan_offsets);
+    if (b->owned[PHYS_F_HEIGHT_SCAN] && b->d_field[PHYS_F_HEIGHT_SCAN]) (void)hipFree(b->d_field[PHYS_F_HEIGHT_SCAN]);
+    b->d_scan_offsets = off;
+    b->d_field[PHYS_F_HEIGHT_SCAN] = out; b->owned[PHYS_F_HEIGHT_SCAN] = true;
+    b->dim[PHYS_F_HEIGHT_SCAN] = npoints; b->stride[PHYS_F_HEIGHT_SCAN] = npoints;
+    b->scan_points = npoints; b->scan_body = body; b->scan_range = range;
+    return 0;
+}
+int phys_batch_height_scan(phys_batch_t *b, int env0, int n, void *stream) {
+    if (!b) return -1;
+    if (b->scan_points <= 0 || !b->d_field[PHYS_F_HEIGHT_SCAN]) { phys_set_last_error("phys_batch_height_scan: call phys_batch_scan_configure first"); return -1; }
+    if (env0 < 0 || n < 0 || (size_t)env0 + (size_t)n > (size_t)b->nenv) { phys_set_last_error("phys_batch_height_scan: env range out of bounds"); return -1; }
+    (void)hipSetDevice(b->device);
+    if (n == 0) return 0;
+    ck::ScanIO io;
+    memset(&io, 0, sizeof io);
+    io.models = b->d_models; io.model_stride = b->model_stride; io.envparams = b->d_envparams;
+    io.env0 = env0; io.n = n; io.npoints = b->scan_points; io.body = b->scan_body; io.range = b->scan_range;
+    io.offsets = b->d_scan_offsets;
+    io.qpos = b->d_field[PHYS_F_QPOS]; io.sq = b->stride[PHYS_F_QPOS];
+    io.out = b->d_field[PHYS_F_HEIGHT_SCAN]; io.sout = b->stride[PHYS_F_HEIGHT_SCAN];
+    io.hfield = b->d_hfield; io.hfield_stride = b->hfield_stride;
+    if (b->nterrain > 0) { io.hfield_index = b->d_terrain_index; io.hfield_nterrain = b->nterrain; }
+    io.warn = b->d_warn;
+    hipStream_t s = stream ? (hipStream_t)stream : b->stream;
+    note_stream(b, s);
+    hipLaunchKernelGGL(ck::cassie_scan_kernel, dim3((unsigned)(n < ck::SCAN_GRID ? n : ck::SCAN_GRID)), dim3(WV_WAVE), 0, s, io);
+    return hip_ok(hipGetLastError(), "cassie_scan_kernel launch") ? 0 : -1;
+}
 
 int phys_batch_sync(phys_batch_t *b) {
     if (!b) return -1;

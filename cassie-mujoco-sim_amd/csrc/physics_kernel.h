@@ -184,6 +184,16 @@ WV_DEVICE int env_step(const PhysIO &io, EnvShared<NVP, LPack<TOPO, NVP>::count,
 
 #include "env_step_wave1.inc"
 
+    /* The env's height-field grid: io.hfield + env * io.hfield_stride (one grid shared by all, or one per env), or -- with a terrain
+     * index (PhysIO::hfield_index) -- the grid of the bank the env's index names, clamped to the bank.  One wave-uniform read per call,
+     * not per substep; instantiations without height-field code do not look. */
+    const float *env_hfield = nullptr;
+    if constexpr ((FEAT & FEAT_HFIELD) != 0) {
+        bool clamped;
+        env_hfield = terrain_grid(io.hfield, io.hfield_stride, io.hfield_index, io.hfield_nterrain, env, &clamped);
+        if (clamped && lane == 0 && wid == 0) wv::atomic_or(io.warn + env, WARN_TERRAIN_INDEX);
+    }
+
     bool bailed = false, bailed_down = false;
     int sub = sub_start;
     for (; sub < nsub; ++sub) {

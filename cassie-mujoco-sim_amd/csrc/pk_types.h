@@ -24,7 +24,9 @@ constexpr int NSTAMP = 48;   /* 0..15 stage boundaries, 16..32 sub-stage stamps,
 
 /* warning bits reported per env */
 enum { WARN_CONTACT_FULL = 1, WARN_CONSTRAINT_FULL = 2, WARN_UNSUPPORTED_PAIR = 4, WARN_DIVERGED = 8,
-       WARN_CHUNK_PLACEMENT = 16 /* a chunk of a launch found the chunk before it on another XCD (cassie_step_kernel): state possibly stale */ };
+       WARN_CHUNK_PLACEMENT = 16 /* a chunk of a launch found the chunk before it on another XCD (cassie_step_kernel): state possibly stale */,
+       WARN_TERRAIN_INDEX = 32   /* the env's terrain index (PhysIO::hfield_index) lay outside the bank: clamped to its first / last terrain */,
+       WARN_SCAN_TILTED = 64     /* phys_batch_height_scan: the env's height-field geom is tilted out of the world's z axis and was left out of the scan */ };
 
 #ifndef WV_OCC
 #define WV_OCC
@@ -128,7 +130,25 @@ struct PhysIO {
     int down_rows;
     int *inplace_count;         /* (may be null) device word: += 1 per env-launch (chunk) that finished a substep in place -- the launcher's
                                    signal for which form of the fast kernel the range's next launches take (phys_batch.hip) */
+    /* A bank of terrains shared by the envs (phys_batch_set_hfield_bank; last in the struct: the offsets of everything above stay put).
+     * hfield_index null: env e reads the grid at hfield + e * hfield_stride, as ever.  Else hfield holds hfield_nterrain grids
+     * hfield_stride floats apart and env e reads grid hfield_index[e] -- [nenv] int32 in HBM, indexed by the absolute env, plain device
+     * memory a training loop rewrites in stream order -- clamped to the bank (WARN_TERRAIN_INDEX where that was needed).  One
+     * wave-uniform read per env and launch (chunk), ahead of the substep loop. */
+    const int *hfield_index;
+    int hfield_nterrain;
 };
+
+/* The grid env `env` stands on (see PhysIO::hfield_index); *clamped: the env's index lay outside the bank */
+WV_DEVICE const float *terrain_grid(const float *hfield, size_t stride, const int *index, int nterrain, int env, bool *clamped) {
+    *clamped = false;
+    if (!hfield) return nullptr;
+    if (!index) return hfield + (size_t)env * stride;
+    const int want = index[env], last = nterrain - 1;
+    const int t = want > last ? last : (want < 0 ? 0 : want);
+    *clamped = t != want;
+    return hfield + (size_t)(t < 0 ? 0 : t) * stride;
+}
 
 /* MAXR: constraint rows this instantiation can hold (WIDE_ROWS, MID_ROWS, or fewer in the row-capped fast instantiations, see
  * cassie_step_kernel); the Y tile has one more row, the qfrc_smooth column */

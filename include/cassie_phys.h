@@ -86,6 +86,7 @@ enum { PHYS_F_QPOS, PHYS_F_QVEL, PHYS_F_QACC_WARMSTART, PHYS_F_TIME, PHYS_F_CTRL
        PHYS_F_PD_DTARGET, PHYS_F_PD_TORQUE, /* [nu] each: optional velocity targets / feed-forward torques of CM_DRIVE_PD */
        PHYS_F_DERIVED,    /* [CM_DRV_DIM]: the derived block of phys_batch_derive (layout: CM_DRV_* in cm_model.h) */
        PHYS_F_QM,         /* [nv * nv]: dense joint-space inertia matrix (mj_fullM role), written by phys_batch_derive */
+       PHYS_F_HEIGHT_SCAN, /* [npoints]: the height scan of phys_batch_height_scan (sized by phys_batch_scan_configure) */
        PHYS_F_COUNT };
 
 /* mj_makeData (reference :441-447) for nenv environments on HIP device `device`;
@@ -136,6 +137,54 @@ size_t phys_sizeof_envparams(void);
  * per-env terrain randomisation -- a grid of its own for one env (the others keep what they had) */
 int phys_batch_set_hfield(phys_batch_t *b, const float *data, int n);
 int phys_batch_set_hfield_env(phys_batch_t *b, int env, const float *data, int n);
+/* A BANK of terrains shared by the envs, and which of them each env stands on -- a few dozen grids for thousands of envs (a
+ * curriculum) instead of one grid per env, and a terrain change at an episode restart that never leaves the device.
+ *   phys_batch_set_hfield_bank   nterrain grids of n floats each (n = the model's hfield_nrow * hfield_ncol, checked), from host memory
+ *                                or (on_device != 0) from device memory, e.g. a torch tensor generated on the GPU.  The batch keeps its
+ *                                own copy (the call waits for the batch's streams).  Every env starts on terrain 0 (an index array the
+ *                                caller bound keeps its contents).  phys_batch_set_hfield / _set_hfield_env afterwards return to those
+ *                                modes (per-env grids then start from zeros).
+ *   the terrain index            int32 [nenv] in HBM, indexed by the absolute env: phys_batch_terrain_index_ptr hands out the batch's
+ *                                own array, phys_batch_bind_terrain_index puts caller-owned memory (a torch tensor) in its place.
+ *                                Plain device memory: a loop switches terrains with one statement on the stream of the env range,
+ *                                e.g. index[done] = next[done] behind phys_batch_end_episodes; the step launches queued behind it on
+ *                                that stream read the new value (one read per env and launch, ahead of the substeps).
+ *   phys_batch_set_terrain       ids [n] for envs [env0, env0 + n), from host memory (range-checked against the bank: -1 +
+ *                                phys_last_error() for an id outside it; returns once the copy is done) or device memory (asynchronous),
+ *                                in order on `stream` (NULL: the batch's own) like phys_batch_randomize.
+ * An index outside the bank that reaches the device is CLAMPED to [0, nterrain - 1], never followed, and raises bit 32 of the env's
+ * warning word (WARN_TERRAIN_INDEX).  The bank's terrains must agree where restarted envs are put down: start states do not follow
+ * the terrain's height.  A batch that never sets a bank runs exactly as before. */
+int phys_batch_set_hfield_bank(phys_batch_t *b, const float *grids, int on_device, int nterrain, int n);
+int phys_batch_nterrain(const phys_batch_t *b);   /* terrains of the bank in use, 0 = none */
+void *phys_batch_terrain_index_ptr(phys_batch_t *b);
+int phys_batch_bind_terrain_index(phys_batch_t *b, void *device_ptr);
+int phys_batch_set_terrain(phys_batch_t *b, const int *ids, int on_device, int env0, int n, void *stream);
+/* The HEIGHT SCAN: what a policy on rough terrain or stairs sees of the ground, read off the surfaces the contact code collides with.
+ *   phys_batch_scan_configure   a pattern of npoints <= 1024 points offsets_xy [npoints][2] (host memory) in the HEADING FRAME of `body`:
+ *                               origin at the body's world x, y, turned about world z by the yaw of the body's world quaternion
+ *                               (w, x, y, z): atan2(2 (w z + x y), 1 - 2 (y y + z z)).  The body must be a child of the world whose
+ *                               joints are slides and at most one ball or free joint (Cassie's pelvis: its pose is qpos[0:7], so the
+ *                               scan needs no forward pass).  Sizes PHYS_F_HEIGHT_SCAN to npoints doubles per env in a buffer of the
+ *                               batch's own (bind a tensor AFTER configuring; phys_batch_bind_strided takes a row stride for this
+ *                               field, so it can be a column block of an observation tensor).  Waits for the batch's streams.
+ *   phys_batch_height_scan      one small launch on `stream` (NULL: the batch's own), in order with the step launches there, for envs
+ *                               [env0, env0 + n): value of point j = clamp(z_body - S(X_j, Y_j), -range, +range), S = the highest point
+ *                               at which the vertical line through the point meets a STATIC collision geom of the env (a geom of a body
+ *                               welded to the world), +range where it meets none:
+ *                                 plane         the intersection, for planes whose normal has a positive world z;
+ *                                 box           where the line leaves the box upwards (slab test in the box's frame, any pose);
+ *                                 height field  the env's own grid (shared, per env, or the bank's terrain of the env's index) on the
+ *                                               triangulated surface of the narrow phase (vertices on the grid scaled by hfield_size,
+ *                                               cells split into v00 v10 v01 and v11 v01 v10), linear within the triangle; outside
+ *                                               the grid's footprint a miss.  ONLY for a height-field geom whose z axis is the world's
+ *                                               (translation and yaw): a tilted one is left out of that env's scan and raises bit 64
+ *                                               of its warning word (WARN_SCAN_TILTED).
+ *                               Geom poses are the env's own once geometry is randomised (CM_P_GEOM_POS / CM_P_GEOM_QUAT), the model's
+ *                               otherwise.  Spheres, capsules and everything on moving bodies are not scanned; noise, history and fp32
+ *                               conversion are the caller's. */
+int phys_batch_scan_configure(phys_batch_t *b, const double *offsets_xy, int npoints, int body, double range);
+int phys_batch_height_scan(phys_batch_t *b, int env0, int n, void *stream);
 /* host <-> HBM copies of whole fields or of a row range [env0, env0 + n) */
 int phys_batch_upload(phys_batch_t *b, int field, const double *host, int env0, int n);
 int phys_batch_download(phys_batch_t *b, int field, double *host, int env0, int n);
@@ -149,7 +198,7 @@ int phys_batch_download_warn(phys_batch_t *b, int *host_warn, int *host_info /* 
 /* raw device pointer of a field (for torch / RCCL interop); bind replaces it with caller-owned HBM */
 void *phys_batch_device_ptr(phys_batch_t *b, int field);
 int phys_batch_bind(phys_batch_t *b, int field, void *device_ptr);
-/* same with a row stride in doubles (>= the field's dim) for PHYS_F_QPOS / QVEL / SENSORDATA, so that the three can be
+/* same with a row stride in doubles (>= the field's dim) for PHYS_F_QPOS / QVEL / SENSORDATA / HEIGHT_SCAN, so that they can be
  * column blocks of ONE caller-owned [nenv][nq + nv + nsensordata] observation tensor -- the buffer an RCCL all-gather
  * sends as is; uploads / downloads of a strided field are 2-D copies */
 int phys_batch_bind_strided(phys_batch_t *b, int field, void *device_ptr, int row_stride);
