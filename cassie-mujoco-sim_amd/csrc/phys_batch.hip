@@ -19,6 +19,7 @@
 #include <vector>
 
 #include "cassie_phys.h"
+#include "device_mem.h"
 #include "small_kernels.h"
 #include "step_launch.h"
 
@@ -36,24 +37,22 @@ constexpr int DEFAULT_TRAY_WAVES = 2; /* the 40-dof model's default form (by mea
 struct phys_batch {
     int nenv = 0, device = 0;
     cm_model_t host_model;          /* copy of the shared model (sizes) */
-    cm_model_t *d_models = nullptr; /* 1 or nenv models in HBM */
-    cm_envparams_t *d_envparams = nullptr; /* null, or one parameter block per env (phys_batch_randomize: PhysIO::envparams) */
+    DevBuf<cm_model_t> d_models;    /* 1 or nenv models in HBM */
+    DevBuf<cm_envparams_t> d_envparams; /* null, or one parameter block per env (phys_batch_randomize: PhysIO::envparams) */
     int model_stride = 0;
     bool generic_kernel = false;   /* validation aid: never pick a compile-time-topology instantiation */
     int dim[PHYS_F_COUNT];
     int stride[PHYS_F_COUNT];       /* doubles between consecutive envs' rows (= dim unless bound with a stride) */
-    double *d_field[PHYS_F_COUNT];
-    bool owned[PHYS_F_COUNT];
-    int *d_warn = nullptr, *d_info = nullptr;
-    float *d_hfield = nullptr;
+    DevBuf<double> d_field[PHYS_F_COUNT]; /* the batch's own, or a caller's (phys_batch_bind) */
+    DevBuf<int> d_warn, d_info;
+    DevBuf<float> d_hfield;
     size_t hfield_stride = 0, hfield_floats = 0; /* stride 0: one grid shared by all envs; else one grid of hfield_floats per env */
     /* a bank of terrains (phys_batch_set_hfield_bank): d_hfield then holds nterrain grids and env e stands on grid d_terrain_index[e]
      * (PhysIO::hfield_index; the array is created on first use and may be the caller's) */
     int nterrain = 0;
-    int *d_terrain_index = nullptr;
-    bool terrain_index_owned = false;
+    DevBuf<int> d_terrain_index;
     /* the height scan (phys_batch_scan_configure): the pattern in HBM, its body and range */
-    double *d_scan_offsets = nullptr;
+    DevBuf<double> d_scan_offsets;
     int scan_points = 0, scan_body = 0;
     double scan_range = 0;
     hipStream_t stream = nullptr;
@@ -64,14 +63,14 @@ struct phys_batch {
     bool use_applied = false;       /* qfrc_applied / xfrc_applied are passed only once uploaded */
     bool pd_mode = false;
     int drive_mode = CM_DRIVE_OFF;
-    cm_drive_state_t *d_drive = nullptr; /* [nenv], allocated when a drive mode is first selected */
+    DevBuf<cm_drive_state_t> d_drive; /* [nenv], allocated when a drive mode is first selected */
     bool use_pd_dtarget = false, use_pd_torque = false;
-    long long *d_prof = nullptr;
+    DevBuf<long long> d_prof;
     /* launch-order balancing (see ck::cassie_order_kernel) */
     bool all_outputs = false;       /* measurement aid: see PhysIO::all_outputs_every_substep */
     bool balance = true;
-    unsigned *d_cost = nullptr, *d_cost_wall = nullptr; /* per-env span of the last launch in 64 shader clocks / in 100 MHz ticks */
-    int *d_order = nullptr;
+    DevBuf<unsigned> d_cost, d_cost_wall; /* per-env span of the last launch in 64 shader clocks / in 100 MHz ticks */
+    DevBuf<int> d_order;
     /* d_order holds a permutation of the env ids of every range it was last sorted for (the order kernel sorts one launch's
      * range [env0, env0 + n) at a time) and the identity everywhere else.  A launch may use the array only for a range that is
      * exactly one of these segments, or that lies wholly in identity territory: any other range would step envs outside itself
@@ -79,17 +78,17 @@ struct phys_batch {
     struct OrderSeg { int env0, n, launches_since_sort; };
     std::vector<OrderSeg> order_segs;
     std::vector<int> order_ident;   /* 0 .. nenv - 1, the source of those resets */
-    cm_ext_t *d_ext = nullptr;
+    DevBuf<cm_ext_t> d_ext;
     /* per-kernel timing (phys_batch_kernel_timing): event pairs around the kernel of every stepping launch that does the work */
     bool timing = false;
     std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_pool;
     size_t ev_used = 0;
-    int *d_progress = nullptr;      /* [nenv] substeps completed by the row-capped fast instantiation (PhysIO::progress) */
+    DevBuf<int> d_progress;         /* [nenv] substeps completed by the row-capped fast instantiation (PhysIO::progress) */
     /* stepping launches of the fast instantiations in chunks (PhysIO::nchunk): chunks per env-launch asked for (1 = off), the
      * words the chunks of an env hand over through, and the tag of the last chunked launch */
     int chunks = DEFAULT_CHUNKS_WHOLE, chunks_range = DEFAULT_CHUNKS_RANGE; /* (launches over the whole batch / over an env range) */
     bool chunks_default = true;    /* nobody has asked for a chunk count: a range's SHORT launches go as three (see launch) */
-    int *d_chunk_flag = nullptr;
+    DevBuf<int> d_chunk_flag;
     int chunk_seq = 0;
     bool chunks_allowed = true;     /* (false: this device does not place workgroup w on XCD w % 8 -- launches stay in one piece) */
     /* the placement rule is a property of the QUEUE a launch goes to (a CU-masked stream, another partition mode ...): every stream
@@ -97,15 +96,15 @@ struct phys_batch {
      * kernel checks every hand-over besides (PhysIO::chunk_fault: a word in pinned host memory a consumer sets when it finds its
      * producer on another XCD; launches stay in one piece from then on) */
     std::vector<std::pair<hipStream_t, bool>> probed_streams;
-    int *h_chunk_fault = nullptr, *d_chunk_fault = nullptr;
+    HostWords chunk_fault;
     bool chunk_fault_reported = false;
     /* the hand-over list (PhysIO::handover_list): env ids per range, [count, ticket] pairs indexed by a range's first env, and
      * -- in pinned host memory the device writes -- the number of envs the last launch of a range handed over */
-    int *d_handover_list = nullptr, *d_handover_count = nullptr;
-    int *h_handover_seen = nullptr, *d_handover_seen = nullptr;
+    DevBuf<int> d_handover_list, d_handover_count;
+    HostWords handover_seen;
     /* ... and the same for the second list: what the 63-row pass hands on to the 127-row pass (models on the Cassie dof tree) */
-    int *d_handover_list2 = nullptr, *d_handover_count2 = nullptr;
-    int *h_handover_seen2 = nullptr, *d_handover_seen2 = nullptr;
+    DevBuf<int> d_handover_list2, d_handover_count2;
+    HostWords handover_seen2;
     bool fast_rows = true;          /* use the row-capped fast instantiation where one exists (phys_batch_set_fast_rows) */
     /* Which form of the two-wave fast kernel a range's launches take (phys_batch_set_inplace): 0 = the kernel + the list-walking pass
      * behind it, 1 = the kernel that finishes the substeps it cannot hold in place, 2 (default) = per range by what its recent launches
@@ -120,14 +119,12 @@ struct phys_batch {
     long long form_launches[2] = {0, 0};   /* stepping launches of the two-wave fast kernel in the plain / the in-place form (diagnostics) */
     int waves_per_env = 2;          /* two-wave form of the fast instantiations (phys_batch_set_waves_per_env) */
     int waves_per_env_tray = DEFAULT_TRAY_WAVES; /* ... of the 40-dof instantiations (CASSIE_TRAY_TWO_WAVES=0/1 overrides the default: A/B aid) */
-    double *d_scratch_out = nullptr; /* [nenv][nv + nsensordata + nu]: where phys_batch_forward_kinematics sends qacc / sensordata / actuator_velocity */
+    DevBuf<double> d_scratch_out;    /* [nenv][nv + nsensordata + nu]: where phys_batch_forward_kinematics sends qacc / sensordata / actuator_velocity */
     /* episodes on the device (phys_batch_end_episodes): the rules, the per-env arrays PHYS_EP_* and the bank of start states */
     bool episodes = false;
     cm_episode_rules_t ep_rules;
-    void *d_ep[PHYS_EP_ARRAYS] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-    bool ep_owned[PHYS_EP_ARRAYS] = {false, false, false, false, false};
-    const double *d_ep_bank = nullptr;
-    bool ep_bank_owned = false;
+    DevBuf<char> d_ep[PHYS_EP_ARRAYS]; /* (ints, or doubles: PHYS_EP_TERMINAL; the batch's own or a caller's) */
+    DevBuf<const double> d_ep_bank;    /* (a copy of the host's rows, or the caller's device rows) */
     int ep_bank_rows = 0;
 };
 
@@ -197,6 +194,34 @@ static void note_stream(phys_batch *b, hipStream_t s) {
     for (hipStream_t r : b->recent_streams) if (r == s) return;
     b->recent_streams[b->recent_next] = s;
     b->recent_next = (b->recent_next + 1) % 4;
+}
+
+/* the stream an entry point enqueues on: the caller's, or the batch's own -- noted, so that quiesce waits for it */
+static hipStream_t launch_stream(phys_batch *b, void *stream) {
+    const hipStream_t s = stream ? (hipStream_t)stream : b->stream;
+    note_stream(b, s);
+    return s;
+}
+
+/* envs [env0, env0 + n), or envs first, first + stride, ... (count of them), inside the batch? */
+static bool range_ok(const phys_batch *b, int env0, int n) {
+    return env0 >= 0 && n >= 0 && (size_t)env0 + (size_t)n <= (size_t)b->nenv;
+}
+static bool strided_ok(const phys_batch *b, int first, int stride, int count) {
+    return first >= 0 && stride >= 1 && count >= 0 && (count == 0 || (size_t)first + (size_t)(count - 1) * (size_t)stride < (size_t)b->nenv);
+}
+
+/* what ResetIO and EpisodeIO share: sizes, row strides and the state arrays a restart writes */
+template <class IO>
+static void fill_state_block(const phys_batch *b, IO &io) {
+    const cm_model_t &m = b->host_model;
+    io.nq = m.nq; io.nv = m.nv; io.nu = m.nu; io.nsd = m.nsensordata;
+    io.sq = b->stride[PHYS_F_QPOS]; io.sqv = b->stride[PHYS_F_QVEL]; io.ssd = b->stride[PHYS_F_SENSORDATA];
+    io.qpos = b->d_field[PHYS_F_QPOS]; io.qvel = b->d_field[PHYS_F_QVEL]; io.warm = b->d_field[PHYS_F_QACC_WARMSTART];
+    io.ctrl = b->d_field[PHYS_F_CTRL]; io.qacc = b->d_field[PHYS_F_QACC]; io.time = b->d_field[PHYS_F_TIME];
+    io.sens = b->d_field[PHYS_F_SENSORDATA]; io.actvel = b->d_field[PHYS_F_ACTUATOR_VELOCITY];
+    io.meas = b->d_drive ? b->d_field[PHYS_F_MEAS].get() : nullptr;
+    io.drive = b->d_drive;
 }
 
 /* The launch-order array for the range [env0, env0 + n): returns the range's segment record (created if the range lies in
@@ -278,7 +303,7 @@ static void set_chunks(phys_batch *b, ck::PhysIO &io, int n, int nsub, hipStream
     }
     io.chunk_seq = ++b->chunk_seq;
     io.chunk_flag = b->d_chunk_flag;
-    io.chunk_fault = b->d_chunk_fault;
+    io.chunk_fault = b->chunk_fault.dev();
 }
 
 /* The hand-over lists of the range [env0, env0 + n) and the grids of the passes that walk them: twice what the range's last launch
@@ -286,9 +311,9 @@ static void set_chunks(phys_batch *b, ck::PhysIO &io, int n, int nsub, hipStream
  * behind that one likewise, plus 8.  (A floor of 256 workgroups under both grids was measured: no gain on the prism workload, -0.6 %
  * on config 2, profiles/round5.) */
 static void range_lists(phys_batch *b, int env0, int n, bool wide, ck::HandoverLists &hl, ck::StepGrids &g) {
-    hl.list1 = b->d_handover_list; hl.count1 = b->d_handover_count + 2 * (size_t)env0; hl.seen1 = b->d_handover_seen + env0;
-    if (wide) { hl.list2 = b->d_handover_list2; hl.count2 = b->d_handover_count2 + 2 * (size_t)env0; hl.seen2 = b->d_handover_seen2 + env0; }
-    const int seen = b->h_handover_seen[env0], seen2 = wide ? b->h_handover_seen2[env0] : 0;
+    hl.list1 = b->d_handover_list; hl.count1 = b->d_handover_count + 2 * (size_t)env0; hl.seen1 = b->handover_seen.dev() + env0;
+    if (wide) { hl.list2 = b->d_handover_list2; hl.count2 = b->d_handover_count2 + 2 * (size_t)env0; hl.seen2 = b->handover_seen2.dev() + env0; }
+    const int seen = b->handover_seen.host()[env0], seen2 = wide ? b->handover_seen2.host()[env0] : 0;
     const int seen12 = seen > seen2 ? seen : seen2; /* (the first pass is never smaller than the second: it feeds it) */
     const long want = 2L * (seen12 > 0 ? seen12 : 0) + 16, want2 = 2L * (seen2 > 0 ? seen2 : 0) + 8;
     g.mid = (unsigned)(want < n ? want : n);
@@ -305,14 +330,14 @@ static bool range_inplace(phys_batch *b, int env0, bool auto_ok, int *count1, hi
     const bool was = rf->inplace;
     /* the range's word in host memory: > 0 = env-launches the last reporting launch handed over (plain form: the pass behind the
      * kernel writes it) or finished in place (the order kernel does); -k = the last k reports of the in-place form had none */
-    const int seen = *(volatile int *)(b->h_handover_seen + env0);
+    const int seen = *(volatile int *)(b->handover_seen.host() + env0);
     if (b->inplace_mode != 2 || !auto_ok) rf->inplace = b->inplace_mode == 1;
     else if (!rf->inplace) { if (seen > 0) rf->inplace = true; }
     else if (seen <= -INPLACE_QUIET) rf->inplace = false;
     if (was != rf->inplace) {
         /* the first list's count word changes its meaning with the form: start the new form from zero (stream-ordered) */
         (void)hipMemsetAsync(count1, 0, 2 * sizeof(int), s);
-        b->h_handover_seen[env0] = 0;
+        b->handover_seen.host()[env0] = 0;
     }
     ++b->form_launches[rf->inplace ? 1 : 0];
     return rf->inplace;
@@ -456,19 +481,19 @@ __global__ void __launch_bounds__(128) cassie_xcd_probe_kernel(int *xcc) {
  * workgroups of the step kernel's shape (128 threads) reports where it ran. */
 static bool workgroups_go_round_the_xcds(hipStream_t s) {
     constexpr int NWG = 1024;
-    int *d = nullptr, h[NWG];
-    bool ok = hipMalloc((void **)&d, sizeof h) == hipSuccess;
+    DevBuf<int> d;
+    int h[NWG];
+    bool ok = d.alloc(NWG, false, "XCD probe");
     if (ok) {
-        hipLaunchKernelGGL(cassie_xcd_probe_kernel, dim3(NWG), dim3(128), 0, s, d);
+        hipLaunchKernelGGL(cassie_xcd_probe_kernel, dim3(NWG), dim3(128), 0, s, d.get());
         ok = hipGetLastError() == hipSuccess && hipMemcpyAsync(h, d, sizeof h, hipMemcpyDeviceToHost, s) == hipSuccess && hipStreamSynchronize(s) == hipSuccess;
         for (int w = 8; ok && w < NWG; ++w) ok = h[w] == h[w % 8];
     }
-    if (d) (void)hipFree(d);
     return ok;
 }
 static bool stream_may_chunk(phys_batch *b, hipStream_t s) {
     if (!b->chunks_allowed) return false;
-    if (b->h_chunk_fault && *(volatile int *)b->h_chunk_fault) {
+    if (b->chunk_fault.host() && *(volatile int *)b->chunk_fault.host()) {
         b->chunks_allowed = false;
         if (!b->chunk_fault_reported) {
             b->chunk_fault_reported = true;
@@ -505,51 +530,31 @@ phys_batch_t *phys_batch_create(const cm_model_t *model, int nenv, int device) {
                                  model->nv, model->nsensordata, model->nu, model->nbody * 3, model->nbody * 4,
                                  model->nu, model->nu, model->nu, model->nbody * 3,
                                  model->nu + 1, CM_MEAS_DIM, model->nu, model->nu, CM_DRV_DIM, model->nv * model->nv, 0};
+    const size_t n = (size_t)nenv;
     bool ok = true;
     for (int f = 0; f < PHYS_F_COUNT; ++f) {
-        b->dim[f] = d[f]; b->stride[f] = d[f]; b->d_field[f] = nullptr; b->owned[f] = true;
+        b->dim[f] = d[f]; b->stride[f] = d[f];
         if (f == PHYS_F_DERIVED || f == PHYS_F_QM) continue; /* large and optional: allocated by the first phys_batch_derive */
         if (f == PHYS_F_HEIGHT_SCAN) continue;              /* sized and allocated by phys_batch_scan_configure */
-        size_t bytes = sizeof(double) * (size_t)nenv * (d[f] > 0 ? d[f] : 1);
-        ok = ok && hip_ok(hipMalloc((void **)&b->d_field[f], bytes), "hipMalloc(field)");
-        if (ok) ok = hip_ok(hipMemset(b->d_field[f], 0, bytes), "hipMemset(field)");
+        ok = ok && b->d_field[f].alloc(n * (d[f] > 0 ? d[f] : 1), true, "field");
     }
-    ok = ok && hip_ok(hipMalloc((void **)&b->d_models, sizeof(cm_model_t)), "hipMalloc(model)");
+    ok = ok && b->d_models.alloc(1, false, "model");
     ok = ok && hip_ok(hipMemcpy(b->d_models, model, sizeof(cm_model_t), hipMemcpyHostToDevice), "hipMemcpy(model)");
-    ok = ok && hip_ok(hipMalloc((void **)&b->d_warn, sizeof(int) * nenv), "hipMalloc(warn)");
-    ok = ok && hip_ok(hipMemset(b->d_warn, 0, sizeof(int) * nenv), "hipMemset(warn)");
-    ok = ok && hip_ok(hipMalloc((void **)&b->d_info, sizeof(int) * 4 * nenv), "hipMalloc(info)");
-    ok = ok && hip_ok(hipMemset(b->d_info, 0, sizeof(int) * 4 * nenv), "hipMemset(info)");
+    ok = ok && b->d_warn.alloc(n, true, "warn") && b->d_info.alloc(4 * n, true, "info");
     if (nenv >= 2048) { /* fewer envs than a couple per wave slot leave nothing to balance */
-        b->order_ident.resize((size_t)nenv);
+        b->order_ident.resize(n);
         for (int e = 0; e < nenv; ++e) b->order_ident[(size_t)e] = e;
-        ok = ok && hip_ok(hipMalloc((void **)&b->d_order, sizeof(int) * (size_t)nenv), "hipMalloc(order)");
-        ok = ok && hip_ok(hipMemcpy(b->d_order, b->order_ident.data(), sizeof(int) * (size_t)nenv, hipMemcpyHostToDevice), "hipMemcpy(order)");
-        ok = ok && hip_ok(hipMalloc((void **)&b->d_cost, sizeof(unsigned) * (size_t)nenv), "hipMalloc(cost)");
-        ok = ok && hip_ok(hipMemset(b->d_cost, 0, sizeof(unsigned) * (size_t)nenv), "hipMemset(cost)");
-        ok = ok && hip_ok(hipMalloc((void **)&b->d_cost_wall, sizeof(unsigned) * (size_t)nenv), "hipMalloc(cost, wall clock)");
-        ok = ok && hip_ok(hipMemset(b->d_cost_wall, 0, sizeof(unsigned) * (size_t)nenv), "hipMemset(cost, wall clock)");
+        ok = ok && b->d_order.alloc(n, false, "order");
+        ok = ok && hip_ok(hipMemcpy(b->d_order, b->order_ident.data(), sizeof(int) * n, hipMemcpyHostToDevice), "hipMemcpy(order)");
+        ok = ok && b->d_cost.alloc(n, true, "cost") && b->d_cost_wall.alloc(n, true, "cost, wall clock");
     }
-    ok = ok && hip_ok(hipMalloc((void **)&b->d_progress, sizeof(int) * (size_t)nenv), "hipMalloc(progress)");
-    ok = ok && hip_ok(hipMemset(b->d_progress, 0, sizeof(int) * (size_t)nenv), "hipMemset(progress)");
-    ok = ok && hip_ok(hipMalloc((void **)&b->d_chunk_flag, sizeof(int) * (size_t)nenv), "hipMalloc(chunk words)");
-    ok = ok && hip_ok(hipMemset(b->d_chunk_flag, 0, sizeof(int) * (size_t)nenv), "hipMemset(chunk words)");
+    ok = ok && b->d_progress.alloc(n, true, "progress") && b->d_chunk_flag.alloc(n, true, "chunk words");
     if (const char *ck = getenv("CASSIE_CHUNKS")) { b->chunks = b->chunks_range = atoi(ck) > 1 ? (atoi(ck) < 7 ? atoi(ck) : 7) : 1; b->chunks_default = false; } /* (A/B switch) */
-    ok = ok && hip_ok(hipHostMalloc((void **)&b->h_chunk_fault, sizeof(int), hipHostMallocMapped), "hipHostMalloc(chunk fault word)");
-    if (ok) *b->h_chunk_fault = 0;
-    ok = ok && hip_ok(hipHostGetDevicePointer((void **)&b->d_chunk_fault, b->h_chunk_fault, 0), "hipHostGetDevicePointer");
-    ok = ok && hip_ok(hipMalloc((void **)&b->d_handover_list, sizeof(int) * (size_t)nenv), "hipMalloc(hand-over list)");
-    ok = ok && hip_ok(hipMalloc((void **)&b->d_handover_count, sizeof(int) * 2 * (size_t)nenv), "hipMalloc(hand-over counts)");
-    ok = ok && hip_ok(hipMemset(b->d_handover_count, 0, sizeof(int) * 2 * (size_t)nenv), "hipMemset(hand-over counts)");
-    ok = ok && hip_ok(hipHostMalloc((void **)&b->h_handover_seen, sizeof(int) * (size_t)nenv, hipHostMallocMapped), "hipHostMalloc(hand-over seen)");
-    if (ok) memset(b->h_handover_seen, 0, sizeof(int) * (size_t)nenv);
-    ok = ok && hip_ok(hipHostGetDevicePointer((void **)&b->d_handover_seen, b->h_handover_seen, 0), "hipHostGetDevicePointer");
-    ok = ok && hip_ok(hipMalloc((void **)&b->d_handover_list2, sizeof(int) * (size_t)nenv), "hipMalloc(second hand-over list)");
-    ok = ok && hip_ok(hipMalloc((void **)&b->d_handover_count2, sizeof(int) * 2 * (size_t)nenv), "hipMalloc(second hand-over counts)");
-    ok = ok && hip_ok(hipMemset(b->d_handover_count2, 0, sizeof(int) * 2 * (size_t)nenv), "hipMemset(second hand-over counts)");
-    ok = ok && hip_ok(hipHostMalloc((void **)&b->h_handover_seen2, sizeof(int) * (size_t)nenv, hipHostMallocMapped), "hipHostMalloc(second hand-over seen)");
-    if (ok) memset(b->h_handover_seen2, 0, sizeof(int) * (size_t)nenv);
-    ok = ok && hip_ok(hipHostGetDevicePointer((void **)&b->d_handover_seen2, b->h_handover_seen2, 0), "hipHostGetDevicePointer");
+    ok = ok && b->chunk_fault.alloc(1, "chunk fault word");
+    ok = ok && b->d_handover_list.alloc(n, false, "hand-over list") && b->d_handover_count.alloc(2 * n, true, "hand-over counts");
+    ok = ok && b->handover_seen.alloc(n, "hand-over seen");
+    ok = ok && b->d_handover_list2.alloc(n, false, "second hand-over list") && b->d_handover_count2.alloc(2 * n, true, "second hand-over counts");
+    ok = ok && b->handover_seen2.alloc(n, "second hand-over seen");
     ok = ok && hip_ok(hipStreamCreateWithFlags(&b->stream, hipStreamNonBlocking), "hipStreamCreate");
     ok = ok && hip_ok(hipEventCreate(&b->ev0), "hipEventCreate") && hip_ok(hipEventCreate(&b->ev1), "hipEventCreate");
     ok = ok && hip_ok(hipEventCreateWithFlags(&b->ev_mark, hipEventDisableTiming), "hipEventCreate");
@@ -567,38 +572,12 @@ phys_batch_t *phys_batch_create(const cm_model_t *model, int nenv, int device) {
 void phys_batch_free(phys_batch_t *b) {
     if (!b) return;
     (void)hipSetDevice(b->device);
-    for (int f = 0; f < PHYS_F_COUNT; ++f)
-        if (b->owned[f] && b->d_field[f]) (void)hipFree(b->d_field[f]);
-    if (b->d_models) (void)hipFree(b->d_models);
-    if (b->d_envparams) (void)hipFree(b->d_envparams);
-    if (b->d_warn) (void)hipFree(b->d_warn);
-    if (b->d_info) (void)hipFree(b->d_info);
-    if (b->d_hfield) (void)hipFree(b->d_hfield);
-    if (b->terrain_index_owned && b->d_terrain_index) (void)hipFree(b->d_terrain_index);
-    if (b->d_scan_offsets) (void)hipFree(b->d_scan_offsets);
-    if (b->d_ext) (void)hipFree(b->d_ext);
-    if (b->d_scratch_out) (void)hipFree(b->d_scratch_out);
-    for (int a = 0; a < PHYS_EP_ARRAYS; ++a) if (b->ep_owned[a] && b->d_ep[a]) (void)hipFree(b->d_ep[a]);
-    if (b->ep_bank_owned && b->d_ep_bank) (void)hipFree((void *)b->d_ep_bank);
-    if (b->d_progress) (void)hipFree(b->d_progress);
-    if (b->d_chunk_flag) (void)hipFree(b->d_chunk_flag);
-    if (b->d_handover_list) (void)hipFree(b->d_handover_list);
-    if (b->d_handover_count) (void)hipFree(b->d_handover_count);
-    if (b->h_handover_seen) (void)hipHostFree(b->h_handover_seen);
-    if (b->d_handover_list2) (void)hipFree(b->d_handover_list2);
-    if (b->d_handover_count2) (void)hipFree(b->d_handover_count2);
-    if (b->h_handover_seen2) (void)hipHostFree(b->h_handover_seen2);
-    if (b->h_chunk_fault) (void)hipHostFree(b->h_chunk_fault);
     for (auto &e : b->ev_pool) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }
-    if (b->d_drive) (void)hipFree(b->d_drive);
-    if (b->d_order) (void)hipFree(b->d_order);
-    if (b->d_cost) (void)hipFree(b->d_cost);
-    if (b->d_cost_wall) (void)hipFree(b->d_cost_wall);
     if (b->ev0) (void)hipEventDestroy(b->ev0);
     if (b->ev1) (void)hipEventDestroy(b->ev1);
     if (b->ev_mark) (void)hipEventDestroy(b->ev_mark);
     if (b->stream) (void)hipStreamDestroy(b->stream);
-    delete b;
+    delete b; /* (the buffers release what the batch owns, never a caller's) */
 }
 
 int phys_batch_nenv(const phys_batch_t *b) { return b ? b->nenv : 0; }
@@ -620,11 +599,9 @@ int phys_batch_set_model(phys_batch_t *b, const cm_model_t *model, int env) {
     synced.env_geom = 0; synced.env_springs = 0; /* (a new model drops the blocks; per-env models have none) */
     model = &synced;
     if (env < 0) {
-        if (b->d_envparams) { (void)hipFree(b->d_envparams); b->d_envparams = nullptr; } /* (the new model's own block again, for every env) */
+        b->d_envparams.reset(); /* (the new model's own block again, for every env) */
         if (b->model_stride == 1) { /* back to one shared model */
-            (void)hipFree(b->d_models);
-            b->d_models = nullptr;
-            if (!hip_ok(hipMalloc((void **)&b->d_models, sizeof(cm_model_t)), "hipMalloc(model)")) return -1;
+            if (!b->d_models.alloc(1, false, "model")) return -1;
             b->model_stride = 0;
         }
         b->host_model = *model;
@@ -645,12 +622,11 @@ int phys_batch_set_model(phys_batch_t *b, const cm_model_t *model, int env) {
         return -1;
     }
     if (b->model_stride == 0) { /* expand to one model per env */
-        cm_model_t *all = nullptr;
-        if (!hip_ok(hipMalloc((void **)&all, sizeof(cm_model_t) * (size_t)b->nenv), "hipMalloc(models)")) return -1;
+        DevBuf<cm_model_t> all;
+        if (!all.alloc((size_t)b->nenv, false, "models")) return -1;
         std::vector<cm_model_t> tmp((size_t)b->nenv, b->host_model);
         if (!hip_ok(hipMemcpy(all, tmp.data(), sizeof(cm_model_t) * tmp.size(), hipMemcpyHostToDevice), "hipMemcpy(models)")) return -1;
-        (void)hipFree(b->d_models);
-        b->d_models = all;
+        b->d_models = std::move(all);
         b->model_stride = 1;
     }
     return hip_ok(hipMemcpy(b->d_models + env, model, sizeof(cm_model_t), hipMemcpyHostToDevice), "hipMemcpy(model)") ? 0 : -1;
@@ -661,11 +637,8 @@ int phys_batch_set_hfield(phys_batch_t *b, const float *data, int n) {
     (void)hipSetDevice(b->device);
     if (!quiesce(b)) return -1;
     b->nterrain = 0;
-    if (b->d_hfield && (b->hfield_stride != 0 || b->hfield_floats != (size_t)n)) { /* back to one shared grid */
-        (void)hipFree(b->d_hfield);
-        b->d_hfield = nullptr;
-    }
-    if (!b->d_hfield && !hip_ok(hipMalloc((void **)&b->d_hfield, sizeof(float) * (size_t)n), "hipMalloc(hfield)")) return -1;
+    if (b->d_hfield && (b->hfield_stride != 0 || b->hfield_floats != (size_t)n)) b->d_hfield.reset(); /* back to one shared grid */
+    if (!b->d_hfield && !b->d_hfield.alloc((size_t)n, false, "hfield")) return -1;
     b->hfield_stride = 0;
     b->hfield_floats = (size_t)n;
     return hip_ok(hipMemcpy(b->d_hfield, data, sizeof(float) * (size_t)n, hipMemcpyHostToDevice), "hipMemcpy(hfield)") ? 0 : -1;
@@ -678,15 +651,14 @@ int phys_batch_set_hfield_env(phys_batch_t *b, int env, const float *data, int n
     if (b->hfield_stride == 0 || b->hfield_floats != (size_t)n || b->nterrain > 0) {
         /* first per-env grid: expand to one grid per env, every env starting from the shared grid (or from zeros: no shared grid, or a
          * bank of terrains was in use) */
-        float *all = nullptr;
+        DevBuf<float> all;
         const size_t bytes = sizeof(float) * (size_t)n;
-        if (!hip_ok(hipMalloc((void **)&all, bytes * (size_t)b->nenv), "hipMalloc(hfield per env)")) return -1;
+        if (!all.alloc((size_t)n * (size_t)b->nenv, false, "hfield per env")) return -1;
         const bool seed = b->d_hfield && b->hfield_stride == 0 && b->hfield_floats == (size_t)n;
-        if (!seed && !hip_ok(hipMemset(all, 0, bytes * (size_t)b->nenv), "hipMemset(hfield)")) { (void)hipFree(all); return -1; }
+        if (!seed && !hip_ok(hipMemset(all, 0, bytes * (size_t)b->nenv), "hipMemset(hfield)")) return -1;
         for (int e = 0; seed && e < b->nenv; ++e)
-            if (!hip_ok(hipMemcpy(all + (size_t)e * n, b->d_hfield, bytes, hipMemcpyDeviceToDevice), "hipMemcpy(hfield)")) { (void)hipFree(all); return -1; }
-        if (b->d_hfield) (void)hipFree(b->d_hfield);
-        b->d_hfield = all;
+            if (!hip_ok(hipMemcpy(all + (size_t)e * n, b->d_hfield, bytes, hipMemcpyDeviceToDevice), "hipMemcpy(hfield)")) return -1;
+        b->d_hfield = std::move(all);
         b->nterrain = 0;
         b->hfield_stride = (size_t)n;
         b->hfield_floats = (size_t)n;
@@ -695,28 +667,28 @@ int phys_batch_set_hfield_env(phys_batch_t *b, int env, const float *data, int n
 }
 
 int phys_batch_upload(phys_batch_t *b, int field, const double *host, int env0, int n) {
-    if (!b || !host || field < 0 || field >= PHYS_F_COUNT || env0 < 0 || n < 0 || env0 + n > b->nenv) return -1;
+    if (!b || !host || field < 0 || field >= PHYS_F_COUNT || !range_ok(b, env0, n)) return -1;
     (void)hipSetDevice(b->device);
     note_field_in_use(b, field);
     return copy_rows(b, field, (void *)host, env0, n, true, "upload") && hip_ok(hipStreamSynchronize(b->stream), "upload sync") ? 0 : -1;
 }
 
 int phys_batch_download(phys_batch_t *b, int field, double *host, int env0, int n) {
-    if (!b || !host || field < 0 || field >= PHYS_F_COUNT || env0 < 0 || n < 0 || env0 + n > b->nenv) return -1;
+    if (!b || !host || field < 0 || field >= PHYS_F_COUNT || !range_ok(b, env0, n)) return -1;
     (void)hipSetDevice(b->device);
     /* (launches on callers' streams -- step_range, reset_envs -- may still be writing the field) */
     return quiesce(b) && copy_rows(b, field, host, env0, n, false, "download") && hip_ok(hipStreamSynchronize(b->stream), "download sync") ? 0 : -1;
 }
 
 int phys_batch_upload_async(phys_batch_t *b, int field, const double *host, int env0, int n) {
-    if (!b || !host || field < 0 || field >= PHYS_F_COUNT || env0 < 0 || n < 0 || env0 + n > b->nenv) return -1;
+    if (!b || !host || field < 0 || field >= PHYS_F_COUNT || !range_ok(b, env0, n)) return -1;
     (void)hipSetDevice(b->device);
     note_field_in_use(b, field);
     return copy_rows(b, field, (void *)host, env0, n, true, "upload_async") ? 0 : -1;
 }
 
 int phys_batch_download_async(phys_batch_t *b, int field, double *host, int env0, int n) {
-    if (!b || !host || field < 0 || field >= PHYS_F_COUNT || env0 < 0 || n < 0 || env0 + n > b->nenv) return -1;
+    if (!b || !host || field < 0 || field >= PHYS_F_COUNT || !range_ok(b, env0, n)) return -1;
     (void)hipSetDevice(b->device);
     return copy_rows(b, field, host, env0, n, false, "download_async") ? 0 : -1;
 }
@@ -741,7 +713,7 @@ int phys_batch_download_warn(phys_batch_t *b, int *host_warn, int *host_info) {
 int phys_batch_uses_applied(const phys_batch_t *b) { return (b && b->use_applied) ? 1 : 0; }
 
 int phys_batch_clear_warn(phys_batch_t *b, int env0, int n) {
-    if (!b || env0 < 0 || n < 0 || env0 + n > b->nenv) return -1;
+    if (!b || !range_ok(b, env0, n)) return -1;
     (void)hipSetDevice(b->device);
     if (!quiesce(b)) return -1;
     return hip_ok(hipMemsetAsync(b->d_warn + env0, 0, sizeof(int) * (size_t)n, b->stream), "hipMemset(warn)") &&
@@ -769,10 +741,8 @@ int phys_batch_bind_strided(phys_batch_t *b, int field, void *device_ptr, int ro
     (void)hipSetDevice(b->device);
     /* no stream synchronisation: launches already queued keep the pointers they were given, and hipFree of the
      * replaced buffer waits for the device by itself */
-    if (b->owned[field] && b->d_field[field]) (void)hipFree(b->d_field[field]);
-    b->d_field[field] = (double *)device_ptr;
+    b->d_field[field].borrow((double *)device_ptr);
     b->stride[field] = row_stride;
-    b->owned[field] = false;
     note_field_in_use(b, field);
     return 0;
 }
@@ -780,19 +750,19 @@ int phys_batch_bind_strided(phys_batch_t *b, int field, void *device_ptr, int ro
 int phys_batch_step(phys_batch_t *b, int nsub, void *stream) {
     if (!b || nsub <= 0) return -1;
     (void)hipSetDevice(b->device);
-    return launch(b, nsub, 1, stream ? (hipStream_t)stream : b->stream);
+    return launch(b, nsub, 1, launch_stream(b, stream));
 }
 
 int phys_batch_step_range(phys_batch_t *b, int env0, int n, int nsub, void *stream) {
-    if (!b || nsub <= 0 || env0 < 0 || n <= 0 || env0 + n > b->nenv) return -1;
+    if (!b || nsub <= 0 || n <= 0 || !range_ok(b, env0, n)) return -1;
     (void)hipSetDevice(b->device);
-    return launch(b, nsub, 1, stream ? (hipStream_t)stream : b->stream, false, env0, n);
+    return launch(b, nsub, 1, launch_stream(b, stream), false, env0, n);
 }
 
 int phys_batch_forward(phys_batch_t *b, void *stream) {
     if (!b) return -1;
     (void)hipSetDevice(b->device);
-    return launch(b, 1, 0, stream ? (hipStream_t)stream : b->stream);
+    return launch(b, 1, 0, launch_stream(b, stream));
 }
 
 int phys_batch_forward_kinematics(phys_batch_t *b, void *stream) {
@@ -801,10 +771,9 @@ int phys_batch_forward_kinematics(phys_batch_t *b, void *stream) {
     if (b->drive_mode != CM_DRIVE_OFF) { phys_set_last_error("phys_batch_forward_kinematics: not in a drive mode (the pass reads the sensordata field)"); return -1; }
     if (!b->d_scratch_out) {
         const cm_model_t &m = b->host_model;
-        const size_t bytes = sizeof(double) * (size_t)b->nenv * (size_t)(m.nv + m.nsensordata + m.nu);
-        if (!hip_ok(hipMalloc((void **)&b->d_scratch_out, bytes), "hipMalloc(scratch outputs)")) return -1;
+        if (!b->d_scratch_out.alloc((size_t)b->nenv * (size_t)(m.nv + m.nsensordata + m.nu), false, "scratch outputs")) return -1;
     }
-    return launch(b, 1, 0, stream ? (hipStream_t)stream : b->stream, true);
+    return launch(b, 1, 0, launch_stream(b, stream), true);
 }
 
 int phys_batch_set_pd_mode(phys_batch_t *b, int on) {
@@ -821,7 +790,7 @@ static bool ensure_drive_state(phys_batch *b) {
     }
     if (!quiesce(b)) return false;
     const size_t bytes = sizeof(cm_drive_state_t) * (size_t)b->nenv;
-    if (!hip_ok(hipMalloc((void **)&b->d_drive, bytes), "hipMalloc(drive state)")) return false;
+    if (!b->d_drive.alloc((size_t)b->nenv, false, "drive state")) return false;
     return hip_ok(hipMemsetAsync(b->d_drive, 0, bytes, b->stream), "hipMemset(drive state)") && hip_ok(hipStreamSynchronize(b->stream), "sync");
 }
 
@@ -841,9 +810,8 @@ int phys_batch_drive_pass(phys_batch_t *b, int mode, void *stream) {
     b->drive_mode = mode;
     ck::PhysIO io = make_io(b, 1, 1);
     b->drive_mode = keep;
-    hipStream_t s = stream ? (hipStream_t)stream : b->stream;
-    note_stream(b, s);
-    hipLaunchKernelGGL(ck::cassie_drive_kernel, dim3(b->nenv), dim3(WV_WAVE), 0, s, io, b->d_field[PHYS_F_CTRL]);
+    hipStream_t s = launch_stream(b, stream);
+    hipLaunchKernelGGL(ck::cassie_drive_kernel, dim3(b->nenv), dim3(WV_WAVE), 0, s, io, b->d_field[PHYS_F_CTRL].get());
     return hip_ok(hipGetLastError(), "cassie_drive_kernel launch") ? 0 : -1;
 }
 
@@ -859,16 +827,16 @@ int phys_batch_wait_mark(phys_batch_t *b) {
 }
 
 int phys_batch_clear_drive_state(phys_batch_t *b, int first, int stride, int count, void *stream) {
-    if (!b || first < 0 || stride < 1 || count < 0 || (count > 0 && first + (size_t)(count - 1) * stride >= (size_t)b->nenv)) return -1;
+    if (!b || !strided_ok(b, first, stride, count)) return -1;
     (void)hipSetDevice(b->device);
     if (!ensure_drive_state(b)) return -1;
     if (count == 0) return 0;
     return hip_ok(hipMemset2DAsync(b->d_drive + first, sizeof(cm_drive_state_t) * (size_t)stride, 0, sizeof(cm_drive_state_t), (size_t)count,
-                                   stream ? (hipStream_t)stream : b->stream), "hipMemset2D(drive state)") ? 0 : -1;
+                                   launch_stream(b, stream)), "hipMemset2D(drive state)") ? 0 : -1;
 }
 
 int phys_batch_upload_drive_state(phys_batch_t *b, const cm_drive_state_t *host, int env0, int n) {
-    if (!b || !host || env0 < 0 || n < 0 || env0 + n > b->nenv) return -1;
+    if (!b || !host || !range_ok(b, env0, n)) return -1;
     (void)hipSetDevice(b->device);
     if (!ensure_drive_state(b)) return -1;
     return hip_ok(hipMemcpyAsync(b->d_drive + env0, host, sizeof(cm_drive_state_t) * (size_t)n, hipMemcpyHostToDevice, b->stream), "drive state upload") &&
@@ -876,7 +844,7 @@ int phys_batch_upload_drive_state(phys_batch_t *b, const cm_drive_state_t *host,
 }
 
 int phys_batch_download_drive_state(phys_batch_t *b, cm_drive_state_t *host, int env0, int n) {
-    if (!b || !host || env0 < 0 || n < 0 || env0 + n > b->nenv) return -1;
+    if (!b || !host || !range_ok(b, env0, n)) return -1;
     (void)hipSetDevice(b->device);
     if (!ensure_drive_state(b)) return -1;
     return hip_ok(hipMemcpyAsync(host, b->d_drive + env0, sizeof(cm_drive_state_t) * (size_t)n, hipMemcpyDeviceToHost, b->stream), "drive state download") &&
@@ -884,23 +852,15 @@ int phys_batch_download_drive_state(phys_batch_t *b, cm_drive_state_t *host, int
 }
 
 int phys_batch_reset_envs(phys_batch_t *b, int first, int stride, int count, const double *qpos_row, const double *sens_row, void *stream) {
-    if (!b || !qpos_row || first < 0 || stride < 1 || count < 0 || (count > 0 && first + (size_t)(count - 1) * stride >= (size_t)b->nenv)) return -1;
+    if (!b || !qpos_row || !strided_ok(b, first, stride, count)) return -1;
     (void)hipSetDevice(b->device);
     if (count == 0) return 0;
-    const cm_model_t &m = b->host_model;
     ck::ResetIO io;
     memset(&io, 0, sizeof io);
+    fill_state_block(b, io);
     io.first = first; io.stride = stride; io.count = count;
-    io.nq = m.nq; io.nv = m.nv; io.nu = m.nu; io.nsd = m.nsensordata;
-    io.sq = b->stride[PHYS_F_QPOS]; io.sqv = b->stride[PHYS_F_QVEL]; io.ssd = b->stride[PHYS_F_SENSORDATA];
-    io.qpos = b->d_field[PHYS_F_QPOS]; io.qvel = b->d_field[PHYS_F_QVEL]; io.warm = b->d_field[PHYS_F_QACC_WARMSTART];
-    io.ctrl = b->d_field[PHYS_F_CTRL]; io.qacc = b->d_field[PHYS_F_QACC]; io.time = b->d_field[PHYS_F_TIME];
-    io.sens = b->d_field[PHYS_F_SENSORDATA]; io.actvel = b->d_field[PHYS_F_ACTUATOR_VELOCITY];
-    io.meas = b->d_drive ? b->d_field[PHYS_F_MEAS] : nullptr;
-    io.drive = b->d_drive;
     io.qpos_row = qpos_row; io.sens_row = sens_row;
-    hipStream_t s = stream ? (hipStream_t)stream : b->stream;
-    note_stream(b, s);
+    hipStream_t s = launch_stream(b, stream);
     hipLaunchKernelGGL(ck::cassie_reset_kernel, dim3(count < 4 ? count : 4), dim3(WV_WAVE), 0, s, io);
     return hip_ok(hipGetLastError(), "cassie_reset_kernel launch") ? 0 : -1;
 }
@@ -915,9 +875,7 @@ int phys_batch_episodes_enable(phys_batch_t *b, const cm_episode_rules_t *rules)
     if (!b->episodes) {
         for (int a = 0; a < PHYS_EP_ARRAYS; ++a) {
             if (b->d_ep[a]) continue;
-            const size_t bytes = episode_array_bytes(b, a);
-            if (!hip_ok(hipMalloc(&b->d_ep[a], bytes), "hipMalloc(episode array)") || !hip_ok(hipMemset(b->d_ep[a], 0, bytes), "hipMemset(episode array)")) return -1;
-            b->ep_owned[a] = true;
+            if (!b->d_ep[a].alloc(episode_array_bytes(b, a), true, "episode array")) return -1;
         }
         if (!hip_ok(hipDeviceSynchronize(), "episode arrays sync")) return -1;
         b->episodes = true;
@@ -934,57 +892,47 @@ int phys_batch_episodes_set_bank(phys_batch_t *b, const double *rows, int on_dev
     if (!b || !rows || nrows <= 0) { phys_set_last_error("phys_batch_episodes_set_bank: bad arguments"); return -1; }
     (void)hipSetDevice(b->device);
     if (!quiesce(b)) return -1; /* (launches in flight may be reading the bank that goes away) */
-    if (b->ep_bank_owned && b->d_ep_bank) (void)hipFree((void *)b->d_ep_bank);
-    b->d_ep_bank = nullptr; b->ep_bank_owned = false; b->ep_bank_rows = 0;
-    if (on_device) b->d_ep_bank = rows;
+    b->d_ep_bank.reset(); b->ep_bank_rows = 0;
+    if (on_device) b->d_ep_bank.borrow(rows);
     else {
-        const size_t bytes = sizeof(double) * (size_t)nrows * (size_t)phys_batch_episode_row_dim(b);
-        double *d = nullptr;
-        if (!hip_ok(hipMalloc((void **)&d, bytes), "hipMalloc(reset bank)")) return -1;
-        if (!hip_ok(hipMemcpy(d, rows, bytes, hipMemcpyHostToDevice), "hipMemcpy(reset bank)")) { (void)hipFree(d); return -1; }
-        b->d_ep_bank = d; b->ep_bank_owned = true;
+        const size_t count = (size_t)nrows * (size_t)phys_batch_episode_row_dim(b);
+        DevBuf<const double> d;
+        if (!d.alloc(count, false, "reset bank")) return -1;
+        if (!hip_ok(hipMemcpy((void *)d.get(), rows, sizeof(double) * count, hipMemcpyHostToDevice), "hipMemcpy(reset bank)")) return -1;
+        b->d_ep_bank = std::move(d);
     }
     b->ep_bank_rows = nrows;
     return 0;
 }
 void *phys_batch_episode_ptr(phys_batch_t *b, int which) {
-    return (b && which >= 0 && which < PHYS_EP_ARRAYS) ? b->d_ep[which] : nullptr;
+    return (b && which >= 0 && which < PHYS_EP_ARRAYS) ? (void *)b->d_ep[which].get() : nullptr;
 }
 int phys_batch_episode_bind(phys_batch_t *b, int which, void *device_ptr) {
     if (!b || !device_ptr || which < 0 || which >= PHYS_EP_ARRAYS) { phys_set_last_error("phys_batch_episode_bind: bad arguments"); return -1; }
     (void)hipSetDevice(b->device);
     /* (as phys_batch_bind: launches already queued keep the pointer they were given; hipFree waits for the device by itself) */
-    if (b->ep_owned[which] && b->d_ep[which]) (void)hipFree(b->d_ep[which]);
-    b->d_ep[which] = device_ptr;
-    b->ep_owned[which] = false;
+    b->d_ep[which].borrow((char *)device_ptr);
     return 0;
 }
 int phys_batch_end_episodes(phys_batch_t *b, int env0, int n, int restart, const int *pick, const int *force, void *stream) {
     if (!b) return -1;
     if (!b->episodes) { phys_set_last_error("phys_batch_end_episodes: call phys_batch_episodes_enable first"); return -1; }
-    if (env0 < 0 || n < 0 || (size_t)env0 + (size_t)n > (size_t)b->nenv) { phys_set_last_error("phys_batch_end_episodes: env range out of bounds"); return -1; }
+    if (!range_ok(b, env0, n)) { phys_set_last_error("phys_batch_end_episodes: env range out of bounds"); return -1; }
     if (restart && (!b->d_ep_bank || b->ep_bank_rows <= 0)) { phys_set_last_error("phys_batch_end_episodes: restart needs a bank of start states (phys_batch_episodes_set_bank)"); return -1; }
     for (int a = 0; a < PHYS_EP_ARRAYS; ++a) if (!b->d_ep[a]) { phys_set_last_error("phys_batch_end_episodes: an episode array is missing"); return -1; }
     (void)hipSetDevice(b->device);
     if (n == 0) return 0;
-    const cm_model_t &m = b->host_model;
     ck::EpisodeIO io;
     memset(&io, 0, sizeof io);
+    fill_state_block(b, io);
     io.env0 = env0; io.n = n; io.restart = restart ? 1 : 0; io.nrows = b->ep_bank_rows;
-    io.nq = m.nq; io.nv = m.nv; io.nu = m.nu; io.nsd = m.nsensordata; io.row_dim = phys_batch_episode_row_dim(b);
-    io.sq = b->stride[PHYS_F_QPOS]; io.sqv = b->stride[PHYS_F_QVEL]; io.ssd = b->stride[PHYS_F_SENSORDATA];
+    io.row_dim = phys_batch_episode_row_dim(b);
     io.rules = b->ep_rules;
-    io.qpos = b->d_field[PHYS_F_QPOS]; io.qvel = b->d_field[PHYS_F_QVEL]; io.warm = b->d_field[PHYS_F_QACC_WARMSTART];
-    io.ctrl = b->d_field[PHYS_F_CTRL]; io.qacc = b->d_field[PHYS_F_QACC]; io.time = b->d_field[PHYS_F_TIME];
-    io.sens = b->d_field[PHYS_F_SENSORDATA]; io.actvel = b->d_field[PHYS_F_ACTUATOR_VELOCITY];
-    io.meas = b->d_drive ? b->d_field[PHYS_F_MEAS] : nullptr;
-    io.drive = b->d_drive;
     io.warn = b->d_warn;
-    io.done = (int *)b->d_ep[PHYS_EP_DONE]; io.reason = (int *)b->d_ep[PHYS_EP_REASON]; io.steps = (int *)b->d_ep[PHYS_EP_STEPS];
-    io.count = (int *)b->d_ep[PHYS_EP_COUNT]; io.terminal = (double *)b->d_ep[PHYS_EP_TERMINAL];
+    io.done = (int *)b->d_ep[PHYS_EP_DONE].get(); io.reason = (int *)b->d_ep[PHYS_EP_REASON].get(); io.steps = (int *)b->d_ep[PHYS_EP_STEPS].get();
+    io.count = (int *)b->d_ep[PHYS_EP_COUNT].get(); io.terminal = (double *)b->d_ep[PHYS_EP_TERMINAL].get();
     io.bank = b->d_ep_bank; io.pick = pick; io.force = force;
-    hipStream_t s = stream ? (hipStream_t)stream : b->stream;
-    note_stream(b, s);
+    hipStream_t s = launch_stream(b, stream);
     hipLaunchKernelGGL(ck::cassie_episode_kernel, dim3((unsigned)(n < ck::EPISODE_GRID ? n : ck::EPISODE_GRID)), dim3(WV_WAVE), 0, s, io);
     return hip_ok(hipGetLastError(), "cassie_episode_kernel launch") ? 0 : -1;
 }
@@ -998,9 +946,7 @@ size_t phys_sizeof_episode_rules(void) { return sizeof(cm_episode_rules_t); }
 /* ------------------------------------------------ terrains: a bank shared by the envs, a per-env index ---- */
 static bool ensure_terrain_index(phys_batch *b) {
     if (b->d_terrain_index) return true;
-    if (!hip_ok(hipMalloc((void **)&b->d_terrain_index, sizeof(int) * (size_t)b->nenv), "hipMalloc(terrain index)")) return false;
-    b->terrain_index_owned = true;
-    return hip_ok(hipMemset(b->d_terrain_index, 0, sizeof(int) * (size_t)b->nenv), "hipMemset(terrain index)");
+    return b->d_terrain_index.alloc((size_t)b->nenv, true, "terrain index");
 }
 int phys_batch_set_hfield_bank(phys_batch_t *b, const float *grids, int on_device, int nterrain, int n) {
     if (!b || !grids || nterrain <= 0 || n <= 0) { phys_set_last_error("phys_batch_set_hfield_bank: bad arguments"); return -1; }
@@ -1010,15 +956,14 @@ int phys_batch_set_hfield_bank(phys_batch_t *b, const float *grids, int on_devic
     }
     (void)hipSetDevice(b->device);
     if (!quiesce(b)) return -1;
-    const size_t bytes = sizeof(float) * (size_t)n * (size_t)nterrain;
-    float *all = nullptr;
-    if (!hip_ok(hipMalloc((void **)&all, bytes), "hipMalloc(terrain bank)")) return -1;
-    if (!hip_ok(hipMemcpy(all, grids, bytes, on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice), "hipMemcpy(terrain bank)")) { (void)hipFree(all); return -1; }
-    if (!ensure_terrain_index(b)) { (void)hipFree(all); return -1; }
+    const size_t count = (size_t)n * (size_t)nterrain;
+    DevBuf<float> all;
+    if (!all.alloc(count, false, "terrain bank")) return -1;
+    if (!hip_ok(hipMemcpy(all, grids, sizeof(float) * count, on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice), "hipMemcpy(terrain bank)")) return -1;
+    if (!ensure_terrain_index(b)) return -1;
     /* every env starts on terrain 0 (an index array of the caller's keeps what the caller put there) */
-    if (b->terrain_index_owned && !hip_ok(hipMemset(b->d_terrain_index, 0, sizeof(int) * (size_t)b->nenv), "hipMemset(terrain index)")) { (void)hipFree(all); return -1; }
-    if (b->d_hfield) (void)hipFree(b->d_hfield);
-    b->d_hfield = all;
+    if (b->d_terrain_index.owned() && !hip_ok(hipMemset(b->d_terrain_index, 0, sizeof(int) * (size_t)b->nenv), "hipMemset(terrain index)")) return -1;
+    b->d_hfield = std::move(all);
     b->hfield_stride = (size_t)n; b->hfield_floats = (size_t)n;
     b->nterrain = nterrain;
     return 0;
@@ -1027,19 +972,17 @@ int phys_batch_nterrain(const phys_batch_t *b) { return b ? b->nterrain : 0; }
 void *phys_batch_terrain_index_ptr(phys_batch_t *b) {
     if (!b) return nullptr;
     (void)hipSetDevice(b->device);
-    return ensure_terrain_index(b) ? (void *)b->d_terrain_index : nullptr;
+    return ensure_terrain_index(b) ? (void *)b->d_terrain_index.get() : nullptr;
 }
 int phys_batch_bind_terrain_index(phys_batch_t *b, void *device_ptr) {
     if (!b || !device_ptr) { phys_set_last_error("phys_batch_bind_terrain_index: bad arguments"); return -1; }
     (void)hipSetDevice(b->device);
     /* (as phys_batch_bind: launches already queued keep the pointer they were given; hipFree waits for the device by itself) */
-    if (b->terrain_index_owned && b->d_terrain_index) (void)hipFree(b->d_terrain_index);
-    b->d_terrain_index = (int *)device_ptr;
-    b->terrain_index_owned = false;
+    b->d_terrain_index.borrow((int *)device_ptr);
     return 0;
 }
 int phys_batch_set_terrain(phys_batch_t *b, const int *ids, int on_device, int env0, int n, void *stream) {
-    if (!b || !ids || env0 < 0 || n < 0 || (size_t)env0 + (size_t)n > (size_t)b->nenv) { phys_set_last_error("phys_batch_set_terrain: bad arguments"); return -1; }
+    if (!b || !ids || !range_ok(b, env0, n)) { phys_set_last_error("phys_batch_set_terrain: bad arguments"); return -1; }
     if (b->nterrain <= 0) { phys_set_last_error("phys_batch_set_terrain: no bank of terrains (phys_batch_set_hfield_bank)"); return -1; }
     if (!on_device)
         for (int i = 0; i < n; ++i)
@@ -1047,8 +990,7 @@ int phys_batch_set_terrain(phys_batch_t *b, const int *ids, int on_device, int e
     (void)hipSetDevice(b->device);
     if (!ensure_terrain_index(b)) return -1;
     if (n == 0) return 0;
-    hipStream_t s = stream ? (hipStream_t)stream : b->stream;
-    note_stream(b, s);
+    hipStream_t s = launch_stream(b, stream);
     if (!hip_ok(hipMemcpyAsync(b->d_terrain_index + env0, ids, sizeof(int) * (size_t)n, on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s), "hipMemcpy(terrain ids)")) return -1;
     /* (host ids: the caller's array may go away once the call returns) */
     return on_device || hip_ok(hipStreamSynchronize(s), "terrain ids sync") ? 0 : -1;
@@ -1069,19 +1011,13 @@ int phys_batch_scan_configure(phys_batch_t *b, const double *offsets_xy, int npo
     }
     (void)hipSetDevice(b->device);
     if (!quiesce(b)) return -1;
-    double *off = nullptr, *out = nullptr;
-    const size_t obytes = sizeof(double) * 2 * (size_t)npoints, fbytes = sizeof(double) * (size_t)npoints * (size_t)b->nenv;
-    if (!hip_ok(hipMalloc((void **)&off, obytes), "hipMalloc(scan pattern)")) return -1;
-    if (!hip_ok(hipMemcpy(off, offsets_xy, obytes, hipMemcpyHostToDevice), "hipMemcpy(scan pattern)")) { (void)hipFree(off); return -1; }
+    DevBuf<double> off, out;
+    if (!off.alloc(2 * (size_t)npoints, false, "scan pattern")) return -1;
+    if (!hip_ok(hipMemcpy(off, offsets_xy, sizeof(double) * 2 * (size_t)npoints, hipMemcpyHostToDevice), "hipMemcpy(scan pattern)")) return -1;
     /* the field takes the pattern's size: a buffer of the batch's own of the new size (a caller's binding is dropped: bind again) */
-    if (!hip_ok(hipMalloc((void **)&out, fbytes), "hipMalloc(height scan)") || !hip_ok(hipMemset(out, 0, fbytes), "hipMemset(height scan)")) {
-        (void)hipFree(off); if (out) (void)hipFree(out);
-        return -1;
-    }
-    if (b->d_scan_offsets) (void)hipFree(b->d_scan_offsets);
-    if (b->owned[PHYS_F_HEIGHT_SCAN] && b->d_field[PHYS_F_HEIGHT_SCAN]) (void)hipFree(b->d_field[PHYS_F_HEIGHT_SCAN]);
-    b->d_scan_offsets = off;
-    b->d_field[PHYS_F_HEIGHT_SCAN] = out; b->owned[PHYS_F_HEIGHT_SCAN] = true;
+    if (!out.alloc((size_t)npoints * (size_t)b->nenv, true, "height scan")) return -1;
+    b->d_scan_offsets = std::move(off);
+    b->d_field[PHYS_F_HEIGHT_SCAN] = std::move(out);
     b->dim[PHYS_F_HEIGHT_SCAN] = npoints; b->stride[PHYS_F_HEIGHT_SCAN] = npoints;
     b->scan_points = npoints; b->scan_body = body; b->scan_range = range;
     return 0;
@@ -1089,7 +1025,7 @@ int phys_batch_scan_configure(phys_batch_t *b, const double *offsets_xy, int npo
 int phys_batch_height_scan(phys_batch_t *b, int env0, int n, void *stream) {
     if (!b) return -1;
     if (b->scan_points <= 0 || !b->d_field[PHYS_F_HEIGHT_SCAN]) { phys_set_last_error("phys_batch_height_scan: call phys_batch_scan_configure first"); return -1; }
-    if (env0 < 0 || n < 0 || (size_t)env0 + (size_t)n > (size_t)b->nenv) { phys_set_last_error("phys_batch_height_scan: env range out of bounds"); return -1; }
+    if (!range_ok(b, env0, n)) { phys_set_last_error("phys_batch_height_scan: env range out of bounds"); return -1; }
     (void)hipSetDevice(b->device);
     if (n == 0) return 0;
     ck::ScanIO io;
@@ -1102,8 +1038,7 @@ int phys_batch_height_scan(phys_batch_t *b, int env0, int n, void *stream) {
     io.hfield = b->d_hfield; io.hfield_stride = b->hfield_stride;
     if (b->nterrain > 0) { io.hfield_index = b->d_terrain_index; io.hfield_nterrain = b->nterrain; }
     io.warn = b->d_warn;
-    hipStream_t s = stream ? (hipStream_t)stream : b->stream;
-    note_stream(b, s);
+    hipStream_t s = launch_stream(b, stream);
     hipLaunchKernelGGL(ck::cassie_scan_kernel, dim3((unsigned)(n < ck::SCAN_GRID ? n : ck::SCAN_GRID)), dim3(WV_WAVE), 0, s, io);
     return hip_ok(hipGetLastError(), "cassie_scan_kernel launch") ? 0 : -1;
 }
@@ -1119,18 +1054,15 @@ int phys_batch_enable_ext(phys_batch_t *b, int on) {
     (void)hipSetDevice(b->device);
     if (!quiesce(b)) return -1;
     if (on && !b->d_ext) {
-        if (!hip_ok(hipMalloc((void **)&b->d_ext, sizeof(cm_ext_t) * (size_t)b->nenv), "hipMalloc(ext)")) return -1;
+        if (!b->d_ext.alloc((size_t)b->nenv, false, "ext")) return -1;
         if (!hip_ok(hipMemsetAsync(b->d_ext, 0, sizeof(cm_ext_t) * (size_t)b->nenv, b->stream), "hipMemset(ext)") ||
             !hip_ok(hipStreamSynchronize(b->stream), "ext sync")) return -1;
-    } else if (!on && b->d_ext) {
-        (void)hipFree(b->d_ext);
-        b->d_ext = nullptr;
-    }
+    } else if (!on) b->d_ext.reset();
     return 0;
 }
 
 int phys_batch_download_ext(phys_batch_t *b, cm_ext_t *host, int env0, int n) {
-    if (!b || !host || !b->d_ext || env0 < 0 || n < 0 || env0 + n > b->nenv) return -1;
+    if (!b || !host || !b->d_ext || !range_ok(b, env0, n)) return -1;
     (void)hipSetDevice(b->device);
     return hip_ok(hipMemcpyAsync(host, b->d_ext + env0, sizeof(cm_ext_t) * (size_t)n, hipMemcpyDeviceToHost, b->stream), "ext download") &&
                    hip_ok(hipStreamSynchronize(b->stream), "ext sync")
@@ -1138,7 +1070,7 @@ int phys_batch_download_ext(phys_batch_t *b, cm_ext_t *host, int env0, int n) {
 }
 
 int phys_batch_download_ext_async(phys_batch_t *b, cm_ext_t *host, int env0, int n) {
-    if (!b || !host || !b->d_ext || env0 < 0 || n < 0 || env0 + n > b->nenv) return -1;
+    if (!b || !host || !b->d_ext || !range_ok(b, env0, n)) return -1;
     (void)hipSetDevice(b->device);
     return hip_ok(hipMemcpyAsync(host, b->d_ext + env0, sizeof(cm_ext_t) * (size_t)n, hipMemcpyDeviceToHost, b->stream), "ext download") ? 0 : -1;
 }
@@ -1146,13 +1078,12 @@ int phys_batch_download_ext_async(phys_batch_t *b, cm_ext_t *host, int env0, int
 int phys_batch_derive(phys_batch_t *b, const int ids[6], void *stream) {
     if (!b || !ids) return -1;
     (void)hipSetDevice(b->device);
-    hipStream_t s = stream ? (hipStream_t)stream : b->stream;
+    hipStream_t s = launch_stream(b, stream);
     for (int f : {PHYS_F_DERIVED, PHYS_F_QM}) {
         if (b->d_field[f]) continue;
-        const size_t bytes = sizeof(double) * (size_t)b->nenv * b->dim[f];
-        if (!hip_ok(hipMalloc((void **)&b->d_field[f], bytes), "hipMalloc(derived)")) return -1;
-        if (!hip_ok(hipMemsetAsync(b->d_field[f], 0, bytes, s), "hipMemset(derived)")) return -1;
-        b->owned[f] = true;
+        const size_t count = (size_t)b->nenv * b->dim[f];
+        if (!b->d_field[f].alloc(count, false, "derived")) return -1;
+        if (!hip_ok(hipMemsetAsync(b->d_field[f], 0, sizeof(double) * count, s), "hipMemset(derived)")) return -1;
     }
     const bool had_ext = b->d_ext != nullptr;
     if (!had_ext && phys_batch_enable_ext(b, 1) != 0) return -1;
@@ -1197,17 +1128,16 @@ static bool ensure_envparams(phys_batch *b) {
     if (b->d_envparams) return true;
     if (b->model_stride != 0) { phys_set_last_error("per-env parameter blocks and per-env models (phys_batch_set_model with env >= 0) do not mix"); return false; }
     if (!quiesce(b)) return false;
-    cm_envparams_t *all = nullptr;
-    if (!hip_ok(hipMalloc((void **)&all, sizeof(cm_envparams_t) * (size_t)b->nenv), "hipMalloc(env parameters)")) return false;
+    DevBuf<cm_envparams_t> all;
+    if (!all.alloc((size_t)b->nenv, false, "env parameters")) return false;
     std::vector<cm_envparams_t> tmp((size_t)b->nenv, b->host_model.params);
-    if (!hip_ok(hipMemcpy(all, tmp.data(), sizeof(cm_envparams_t) * tmp.size(), hipMemcpyHostToDevice), "hipMemcpy(env parameters)")) { (void)hipFree(all); return false; }
-    b->d_envparams = all;
+    if (!hip_ok(hipMemcpy(all, tmp.data(), sizeof(cm_envparams_t) * tmp.size(), hipMemcpyHostToDevice), "hipMemcpy(env parameters)")) return false;
+    b->d_envparams = std::move(all);
     return true;
 }
 static int launch_setconst(phys_batch *b, int env0, int n, int derive_inertial, hipStream_t s) {
     ck::SetConstIO io;
     io.model = b->d_models; io.params = b->d_envparams; io.env0 = env0; io.nenv = n; io.derive_inertial = derive_inertial;
-    note_stream(b, s);
     /* one wave per env, at most a few thousand workgroups walking the range (58 KB of LDS each: two to a CU) */
     hipLaunchKernelGGL(ck::cassie_setconst_kernel, dim3((unsigned)(n < 2048 ? n : 2048)), dim3(WV_WAVE), 0, s, io);
     return hip_ok(hipGetLastError(), "cassie_setconst_kernel launch") ? 0 : -1;
@@ -1218,25 +1148,24 @@ static int read_from_blocks(phys_batch *b, int *host_word, size_t off, hipStream
     static const int one = 1;
     if (*host_word) return 0;
     *host_word = 1;
-    return hip_ok(hipMemcpyAsync((char *)b->d_models + off, &one, sizeof one, hipMemcpyHostToDevice, s), "hipMemcpy(model word)") ? 0 : -1;
+    return hip_ok(hipMemcpyAsync((char *)b->d_models.get() + off, &one, sizeof one, hipMemcpyHostToDevice, s), "hipMemcpy(model word)") ? 0 : -1;
 }
 int phys_batch_randomize(phys_batch_t *b, int param, const double *values, int on_device, int env0, int n, void *stream) {
-    if (!b || !values || param < 0 || param >= CM_P_COUNT || env0 < 0 || n < 0 || env0 + n > b->nenv) { phys_set_last_error("phys_batch_randomize: bad arguments"); return -1; }
+    if (!b || !values || param < 0 || param >= CM_P_COUNT || !range_ok(b, env0, n)) { phys_set_last_error("phys_batch_randomize: bad arguments"); return -1; }
     (void)hipSetDevice(b->device);
     if (!ensure_envparams(b)) return -1;
     if (n == 0) return 0;
-    hipStream_t s = stream ? (hipStream_t)stream : b->stream;
+    hipStream_t s = launch_stream(b, stream);
     const int dim = phys_batch_param_dim(b, param);
     const double *src = values;
-    double *staged = nullptr;
+    DevBuf<double> staged;
     if (!on_device) {
-        const size_t bytes = sizeof(double) * (size_t)n * dim;
-        if (!hip_ok(hipMalloc((void **)&staged, bytes), "hipMalloc(parameter rows)")) return -1;
-        if (!hip_ok(hipMemcpyAsync(staged, values, bytes, hipMemcpyHostToDevice, s), "hipMemcpy(parameter rows)")) { (void)hipFree(staged); return -1; }
+        const size_t count = (size_t)n * dim;
+        if (!staged.alloc(count, false, "parameter rows")) return -1;
+        if (!hip_ok(hipMemcpyAsync(staged, values, sizeof(double) * count, hipMemcpyHostToDevice, s), "hipMemcpy(parameter rows)")) return -1;
         src = staged;
     }
-    note_stream(b, s);
-    hipLaunchKernelGGL(ck::cassie_param_scatter_kernel, dim3((unsigned)(n < 1024 ? n : 1024)), dim3(WV_WAVE), 0, s, b->d_envparams,
+    hipLaunchKernelGGL(ck::cassie_param_scatter_kernel, dim3((unsigned)(n < 1024 ? n : 1024)), dim3(WV_WAVE), 0, s, b->d_envparams.get(),
                        (int)(PARAM_TABLE[param].off / sizeof(double)), dim, src, env0, n);
     int rc = hip_ok(hipGetLastError(), "cassie_param_scatter_kernel launch") ? 0 : -1;
     /* friction needs no set_const in the reference (mj_contactParam mixes the geoms' values at every step): the pairs' mixed
@@ -1253,18 +1182,18 @@ int phys_batch_randomize(phys_batch_t *b, int param, const double *values, int o
         rc = launch_setconst(b, env0, n, ck::SETCONST_SPRINGS, s);
         if (rc == 0) rc = read_from_blocks(b, &b->host_model.env_springs, offsetof(cm_model_t, env_springs), s);
     }
-    if (staged) { if (!hip_ok(hipStreamSynchronize(s), "randomize sync")) rc = -1; (void)hipFree(staged); }
+    if (staged && !hip_ok(hipStreamSynchronize(s), "randomize sync")) rc = -1;
     return rc;
 }
 int phys_batch_set_const(phys_batch_t *b, int env0, int n, void *stream) {
-    if (!b || env0 < 0 || n < 0 || env0 + n > b->nenv) return -1;
+    if (!b || !range_ok(b, env0, n)) return -1;
     (void)hipSetDevice(b->device);
     if (!ensure_envparams(b)) return -1;
     if (n == 0) return 0;
-    return launch_setconst(b, env0, n, ck::SETCONST_ALL, stream ? (hipStream_t)stream : b->stream);
+    return launch_setconst(b, env0, n, ck::SETCONST_ALL, launch_stream(b, stream));
 }
 int phys_batch_download_params(phys_batch_t *b, cm_envparams_t *host, int env0, int n) {
-    if (!b || !host || env0 < 0 || n < 0 || env0 + n > b->nenv) return -1;
+    if (!b || !host || !range_ok(b, env0, n)) return -1;
     (void)hipSetDevice(b->device);
     if (!quiesce(b)) return -1;
     if (!b->d_envparams) { for (int e = 0; e < n; ++e) host[e] = b->host_model.params; return 0; }
@@ -1374,7 +1303,7 @@ int phys_batch_debug_handover_pending(phys_batch_t *b) {
     std::vector<int> h(2 * (size_t)b->nenv);
     long total = 0;
     if (!quiesce(b)) return -1;
-    for (int *d : {b->d_handover_count, b->d_handover_count2}) {
+    for (int *d : {b->d_handover_count.get(), b->d_handover_count2.get()}) {
         if (!d) continue;
         if (!hip_ok(hipMemcpy(h.data(), d, sizeof(int) * h.size(), hipMemcpyDeviceToHost), "hand-over count download")) return -1;
         /* (a range in the in-place form keeps other things in its first list's words: the in-place count since the order kernel's last
@@ -1387,10 +1316,10 @@ int phys_batch_debug_handover_pending(phys_batch_t *b) {
 
 /* envs the 63-row pass of the last stepping launch over [env0, ...) handed on to the 127-row pass (what that pass reported) */
 int phys_batch_wide_pass_envs(phys_batch_t *b, int env0) {
-    if (!b || env0 < 0 || env0 >= b->nenv || !b->h_handover_seen2) return -1;
+    if (!b || env0 < 0 || env0 >= b->nenv || !b->handover_seen2.host()) return -1;
     (void)hipSetDevice(b->device);
     if (!quiesce(b)) return -1;
-    return *(volatile int *)(b->h_handover_seen2 + env0);
+    return *(volatile int *)(b->handover_seen2.host() + env0);
 }
 
 int phys_batch_set_balance(phys_batch_t *b, int on) {
@@ -1426,13 +1355,12 @@ int phys_batch_profile_substeps(phys_batch_t *b, int nsub, long long *host_stamp
     if (!b || !host_stamps || nsub < 1) return -1;
     (void)hipSetDevice(b->device);
     const size_t bytes = sizeof(long long) * ck::NSTAMP * (size_t)b->nenv;
-    if (!hip_ok(hipMalloc((void **)&b->d_prof, bytes), "hipMalloc(prof)")) return -1;
+    if (!b->d_prof.alloc(ck::NSTAMP * (size_t)b->nenv, false, "prof")) return -1;
     (void)hipMemsetAsync(b->d_prof, 0, bytes, b->stream);
     int rc = launch(b, nsub, 1, b->stream);
     bool ok = rc == 0 && hip_ok(hipStreamSynchronize(b->stream), "sync") &&
               hip_ok(hipMemcpy(host_stamps, b->d_prof, bytes, hipMemcpyDeviceToHost), "prof download");
-    (void)hipFree(b->d_prof);
-    b->d_prof = nullptr;
+    b->d_prof.reset();
     return ok ? 0 : -1;
 }
 
