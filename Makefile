@@ -115,10 +115,24 @@ $(PKG)/bin/cassiesim: $(PKG)/apps/cassiesim.c $(PRODUCT)
 oracle/libcassie_oracle.so: oracle/cassie_oracle.c oracle/cassie_oracle.h $(CSRC)/cm_model.h
 	gcc -O2 -std=gnu11 -fPIC -shared -fopenmp -I$(CSRC) -Ioracle oracle/cassie_oracle.c -o $@ -lm
 
-# (emu_terrain.cpp includes emu_episodes.cpp, which includes emu_runtime.cpp: one translation unit, the entry points of the episode and
-# scan kernels use the runtime's workgroup loop)
-tests/emu/libcassie_emu.so: tests/emu/emu_terrain.cpp tests/emu/emu_episodes.cpp tests/emu/emu_runtime.cpp tests/emu/wave.h $(wildcard tests/device/wave_bodies.h) $(wildcard $(CSRC)/*.h) $(wildcard $(CSRC)/*.inc)
-	g++ -O2 -std=c++17 -fPIC -shared -Wl,-Bsymbolic -Itests/emu -I$(CSRC) -Itests/device tests/emu/emu_terrain.cpp -o $@
+# the wave emulator: the scheduler (emu_runtime), the step kernel (emu_step: the one unit that instantiates it, and most of the build
+# time) and the small kernels and probes (emu_kernels), compiled in parallel.  Baseline x86-64, no -march, no FMA contraction: the
+# emulator's bit-exactness rests on these flags
+# (the emulator's sources live in the test tree too: an older tests/, whose emulator is one chain of .cpp files that include each other
+# from emu_terrain.cpp down, builds as it did -- one translation unit)
+EMU_FLAGS := -O2 -std=c++17 -fPIC -Itests/emu -I$(CSRC) -Itests/device
+EMU_DEPS  := $(wildcard tests/emu/*.h) $(wildcard tests/device/wave_bodies.h) $(wildcard $(CSRC)/*.h) $(wildcard $(CSRC)/*.inc)
+ifeq ($(wildcard tests/emu/emu_terrain.cpp),)
+EMU_OBJS := $(OBJD)/emu/emu_runtime.o $(OBJD)/emu/emu_step.o $(OBJD)/emu/emu_kernels.o
+$(OBJD)/emu/%.o: tests/emu/%.cpp $(EMU_DEPS)
+	@mkdir -p $(OBJD)/emu
+	g++ $(EMU_FLAGS) -c $< -o $@
+tests/emu/libcassie_emu.so: $(EMU_OBJS)
+	g++ -shared -Wl,-Bsymbolic $(EMU_OBJS) -o $@
+else
+tests/emu/libcassie_emu.so: $(wildcard tests/emu/*.cpp) $(EMU_DEPS)
+	g++ $(EMU_FLAGS) -shared -Wl,-Bsymbolic tests/emu/emu_terrain.cpp -o $@
+endif
 
 # the wave primitives and the kernel's numerical helpers one at a time (tests/test_wave_primitives.py): the bodies of
 # wave_bodies.h for gfx950, with the product's flags -- the emulator library above runs the same bodies

@@ -275,6 +275,10 @@ static const ck::StepLauncher CASSIE_ALL_FORMS[ck::FORM_COUNT] = {launch_step<32
 static const ck::StepLauncher TRAY_HFIELD_FORMS[ck::FORM_COUNT] = {launch_step<40, TopoCassieTray38, ck::FEAT_ALL>};
 static const ck::StepLauncher GENERIC32_FORMS[ck::FORM_COUNT] = {launch_step<32, TopoRuntime, ck::FEAT_ALL>};
 static const ck::StepLauncher GENERIC40_FORMS[ck::FORM_COUNT] = {launch_step<40, TopoRuntime, ck::FEAT_ALL>};
+/* ... by family (ck::pick_family) */
+static const ck::StepLauncher *const FAMILY_FORMS[ck::FAMILY_COUNT] = {
+    CASSIE_FORMS<0>, CASSIE_FORMS<ck::FEAT_HFIELD>, CASSIE_ALL_FORMS, TRAY_FORMS, TRAY_HFIELD_FORMS, GENERIC32_FORMS, GENERIC40_FORMS,
+};
 
 constexpr int SMALL_BATCH_NSUB = 4;  /* substeps per launch up to which a small batch skips the fast kernel + passes (three launches) for one instantiation alone */
 constexpr int SMALL_BATCH = 512;     /* envs up to which that holds (half the chip's workgroup slots) */
@@ -374,30 +378,19 @@ static int launch(phys_batch *b, int nsub, int integrate, hipStream_t s, bool sc
             ++b->ev_used;
         }
     }
-    /* the compile-time-topology instantiations are used only when the model's dof tree is exactly theirs */
     const cm_model_t &hm = b->host_model;
-    auto matches = [&](const unsigned long long *table, int nv, int body_levels) {
-        /* (kin_simple, and a body tree no deeper than theirs: the record-based local transforms and the round count of the
-         * recursion in their kinematics stage) */
-        if (b->generic_kernel || hm.nv != nv || !hm.kin_simple || hm.maxdepth > body_levels) return false;
-        for (int k = 0; k < nv; ++k) if (hm.dof_ancmask[k] != table[k]) return false;
-        return true;
-    };
-    /* ... and the collision code of an instantiation is what the model's pair list needs (FEAT_*): plain cassie.xml has
-     * neither height-field nor whole-wave (plane-box / box-box) pairs */
-    const bool hf = hm.nhfpair > 0 || hm.hfield_geom >= 0, wp = hm.npair > hm.npair_simple;
     /* the family, and the forms of this launch (step_plan.h) */
-    const ck::StepLauncher *family;
+    const ck::StepFamily fam = ck::pick_family(hm, b->generic_kernel);
+    const ck::StepLauncher *family = FAMILY_FORMS[fam];
     ck::StepForms forms = {ck::FORM_ALONE, ck::FORM_ALONE, false, FAST_ROWS - 4};
     /* (inplace_stay_rows: once in the 63-row code an env stays there until a substep needs at most FAST_ROWS - 4 rows again -- the
      * margin keeps an env that hovers about the fast code's capacity from changing codes every substep) */
-    if (matches(TopoCassie32::table, TopoCassie32::nv, TopoCassie32::body_levels) && !wp) {
+    if (fam == ck::CASSIE || fam == ck::CASSIE_HFIELD) {
         /* stepping launches go through the row-capped fast instantiation first; the 63-row pass behind it finishes the envs that met
          * a substep with more rows, and -- for a model with the wide caps (CM_FLAG_HFPRISM) -- the 127-row pass behind that one what
          * is left.  Forward / read-out passes take one instantiation alone, and so does a small batch stepping a few substeps per
          * launch (somebody's control loop around a handful of envs): one launch instead of two or three -- a launch costs what four
          * substeps' difference between the kernels saves */
-        family = hf ? CASSIE_FORMS<ck::FEAT_HFIELD> : CASSIE_FORMS<0>;
         forms.wide = hm.maxefc > CM_MAXEFC_NARROW;
         if (!b->fast_rows || !integrate || io.ext || (n <= SMALL_BATCH && nsub <= SMALL_BATCH_NSUB))
             /* (alone and a LARGE grid -- phys_batch_derive / forward passes of a whole batch, the fast kernel switched off -- with 63-row
@@ -406,16 +399,13 @@ static int launch(phys_batch *b, int nsub, int integrate, hipStream_t s, bool sc
             forms.first = forms.wide ? ck::FORM_WIDE : n > SMALL_BATCH ? ck::FORM_ALONE : ck::FORM_ALONE_2W;
         else if (b->waves_per_env == 2) { forms.first = ck::FORM_FAST_2W; forms.mid = ck::FORM_MID_WALK_2W; }
         else forms.first = ck::FORM_FAST;     /* (behind it the one-wave 63-row pass looks every env's record up: FORM_ALONE) */
-    } else if (matches(TopoCassie32::table, TopoCassie32::nv, TopoCassie32::body_levels)) family = CASSIE_ALL_FORMS;
-    else if (matches(TopoCassieTray38::table, TopoCassieTray38::nv, TopoCassieTray38::body_levels) && !hf) {
+    } else if (fam == ck::TRAY) {
         /* the 40-dof model: a fast instantiation of 47 rows (the boxes resting on the tray take it to 32 .. 40 routinely) with the 63-row
          * one behind it walking the list, both in the two-wave form by default (waves_per_env_tray) -- or the 63-row one alone */
-        family = TRAY_FORMS;
         const bool plain = integrate && !io.ext, two = plain && b->waves_per_env_tray == 2;
         if (plain && b->fast_rows) { forms.first = two ? ck::FORM_FAST_2W : ck::FORM_FAST; forms.mid = two ? ck::FORM_MID_WALK_2W : ck::FORM_MID_WALK; }
         else forms.first = two ? ck::FORM_ALONE_2W : ck::FORM_ALONE;
-    } else if (matches(TopoCassieTray38::table, TopoCassieTray38::nv, TopoCassieTray38::body_levels)) family = TRAY_HFIELD_FORMS;
-    else family = hm.nv > 32 ? GENERIC40_FORMS : GENERIC32_FORMS;
+    }
     /* a fast kernel first: its record of completed substeps, its launch in chunks, the hand-over lists of the passes behind it, its form */
     ck::HandoverLists hl = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     ck::StepGrids grids = {(unsigned)n, (unsigned)n, (unsigned)n};

@@ -32,6 +32,36 @@ enum StepForm {
     FORM_COUNT
 };
 
+/* the model families: which instantiations step a model, by its dof tree and the collision code its pair list needs */
+enum StepFamily {
+    CASSIE,             /* the Cassie dof tree, neither height-field nor whole-wave (plane-box / box-box) pairs: all three tiers */
+    CASSIE_HFIELD,      /* ... with height-field pairs: all three tiers */
+    CASSIE_ALL,         /* ... with whole-wave pairs: one instantiation alone */
+    TRAY,               /* the 40-dof tray model's tree without height-field pairs: fast (47 rows) and 63 rows */
+    TRAY_HFIELD,        /* ... with height-field pairs: one instantiation alone */
+    GENERIC32,          /* any other model: the dof tree read from the model at run time, up to 32 dofs */
+    GENERIC40,          /* ... more than 32 */
+    FAMILY_COUNT
+};
+
+/* the compile-time-topology instantiations are used only when the model's dof tree is exactly theirs (kin_simple, and a body tree no
+ * deeper than theirs: the record-based local transforms and the round count of the recursion in their kinematics stage) */
+template <class TOPO>
+inline bool topo_matches(const cm_model_t &m) {
+    if (m.nv != TOPO::nv || !m.kin_simple || m.maxdepth > TOPO::body_levels) return false;
+    for (int k = 0; k < TOPO::nv; ++k) if (m.dof_ancmask[k] != TOPO::table[k]) return false;
+    return true;
+}
+
+/* ... and the collision code of an instantiation is what the model's pair list needs (FEAT_*); generic_only: the run-time topology
+ * whatever the tree (phys_batch's generic_kernel, the emulator's force_runtime_topology) */
+inline StepFamily pick_family(const cm_model_t &m, bool generic_only) {
+    const bool hf = m.nhfpair > 0 || m.hfield_geom >= 0, wp = m.npair > m.npair_simple;
+    if (!generic_only && topo_matches<TopoCassie32>(m)) return wp ? CASSIE_ALL : hf ? CASSIE_HFIELD : CASSIE;
+    if (!generic_only && topo_matches<TopoCassieTray38>(m)) return hf ? TRAY_HFIELD : TRAY;
+    return m.nv > 32 ? GENERIC40 : GENERIC32;
+}
+
 /* the forms a launch takes: `first` is one of the FORM_FAST* forms (the tiers behind it follow) or the form that steps every env alone */
 struct StepForms {
     int first;

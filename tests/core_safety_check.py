@@ -38,14 +38,11 @@ def live(u, q, w, L, ch8, telemetry=None, fresh=True):
 def restated(u, q, w, L, sto):
     """csrc/pk_safety.h (what the kernel's drive-level pass calls) -> (tau [n][10], message bits [n])."""
     import emu_py
-    lib = emu_py.lib()
     n = len(sto)
     a = lambda x, dt=np.float64: np.ascontiguousarray(x, dtype=dt)
     u, q, w, L, sto = a(u), a(q), a(w), a(L), a(sto, np.uint8)
     tau, msg = np.zeros((n, 10)), np.zeros(n, dtype=np.int32)
-    lib.emu_core_safety.argtypes = [ctypes.c_int] + [ctypes.c_void_p] * 7
-    lib.emu_core_safety.restype = None
-    lib.emu_core_safety(n, u.ctypes.data, q.ctypes.data, w.ctypes.data, L.ctypes.data, sto.ctypes.data, tau.ctypes.data, msg.ctypes.data)
+    emu_py.core_safety(n, u, q, w, L, sto, tau, msg)
     return tau, msg
 
 

@@ -1,22 +1,96 @@
-"""ctypes access to the CPU wave emulator running the real physics_kernel.h -- test infrastructure only."""
+"""ctypes access to the CPU wave emulator running the real physics_kernel.h -- test infrastructure only.  The one binding of
+tests/emu/libcassie_emu.so (tests/wave_check.py loads it besides, for the wc_* entries it shares with the device's library).
+
+A call is handed everything it reads in one block (tests/emu/emu_api.h) -- the arrays and the emulator's settings; the library keeps
+nothing from call to call.  `with settings(fast_rows=1, chunks=3) as run:` changes what the calls inside the block are handed, and
+`run` adds up what they report (fast_bails, wide_envs, chunk_fault)."""
+import contextlib
 import ctypes
 import os
 
 import numpy as np
 
-from cassie_amd._lib import CmDriveState, CmModel, REPO_DIR
+from cassie_amd._lib import CmDriveState, CmEpisodeRules, CmModel, REPO_DIR
 
 _lib = None
+_vp, _ci, _ul = ctypes.c_void_p, ctypes.c_int, ctypes.c_ulong
+
+
+class Settings(ctypes.Structure):
+    _fields_ = [(f, _ci) for f in ("two_waves", "fast_rows", "inplace", "inplace_stay_rows", "chunks", "resume_grid", "wave_schedule",
+                                   "force_runtime_topology", "force_guarded_pgs", "poison_lds")] + \
+               [("poison_lo", _ul), ("poison_hi", _ul), ("skip_com_init", _ci), ("producer_xcc", _ci)]
+
+
+class StepArgs(ctypes.Structure):
+    _fields_ = [("model", ctypes.POINTER(CmModel)), ("nenv", _ci), ("nsub", _ci), ("integrate", _ci)] + \
+               [(f, _vp) for f in ("qpos", "qvel", "qacc_warmstart", "time", "ctrl", "qfrc_applied", "xfrc_applied", "qacc", "sensordata",
+                                   "actuator_velocity", "warn", "info", "xpos", "xquat", "pd_ptarget", "pd_kp", "pd_kd")] + \
+               [("drive_mode", _ci)] + [(f, _vp) for f in ("drive_state", "drive_cmd", "meas", "pd_dtarget", "pd_torque", "envparams", "hfield")] + \
+               [("hfield_stride", _ul), ("hfield_index", _vp), ("nterrain", _ci), ("settings", Settings)]
+
+
+class StepResult(ctypes.Structure):
+    _fields_ = [(f, _ci) for f in ("fast_bails", "wide_envs", "chunk_fault")]
+
+
+API = (Settings, StepArgs, StepResult)          # by emu_sizeof_api's / emu_offsetof_api's `which`
+DEFAULTS = dict(resume_grid=2, chunks=1)        # the settings that are not zero by default
 
 
 def lib():
     global _lib
     if _lib is None:
-        _lib = ctypes.CDLL(os.path.join(REPO_DIR, "tests", "emu", "libcassie_emu.so"))
-        _lib.emu_phys_run.argtypes = [ctypes.POINTER(CmModel)] + [ctypes.c_int] * 3 + [ctypes.c_void_p] * 18
-        _lib.emu_set_drive_io.argtypes = [ctypes.c_int] + [ctypes.c_void_p] * 5
-        _lib.emu_derive.argtypes = [ctypes.POINTER(CmModel), ctypes.c_int] + [ctypes.c_void_p] * 14
+        L = ctypes.CDLL(os.path.join(REPO_DIR, "tests", "emu", "libcassie_emu.so"))
+        L.emu_sizeof_api.restype, L.emu_offsetof_api.restype = _ul, ctypes.c_long
+        for which, T in enumerate(API):
+            assert ctypes.sizeof(T) == L.emu_sizeof_api(which), T
+            offsets = [L.emu_offsetof_api(which, k) for k in range(len(T._fields_) + 1)]
+            assert offsets == [getattr(T, f).offset for f, _ in T._fields_] + [-1], T
+        L.emu_phys_run.argtypes = [ctypes.POINTER(StepArgs), ctypes.POINTER(StepResult)]
+        L.emu_derive.argtypes = [ctypes.POINTER(StepArgs), _vp, _vp, _vp, ctypes.POINTER(StepResult)]
+        L.emu_pick_family.argtypes = [ctypes.POINTER(CmModel), _ci]
+        L.emu_set_const.argtypes = [ctypes.POINTER(CmModel), _vp, _ci, _ci]
+        L.emu_sizeof_envparams.restype = _ul
+        L.emu_end_episodes.argtypes = ([ctypes.POINTER(CmModel), ctypes.POINTER(CmEpisodeRules)] + [_ci] * 4 + [_vp, _ci] * 3 + [_vp] * 13 +
+                                       [_vp, _ci] + [_vp] * 2)
+        L.emu_sizeof_episode_rules.restype, L.emu_offsetof_episode_rules.restype = _ul, ctypes.c_long
+        L.emu_height_scan.argtypes = [ctypes.POINTER(CmModel), _vp, _ci, _ci, _ci, _vp, _ci, _ci, ctypes.c_double, _vp, _ci, _vp, _ci, _vp, _ul, _vp, _ci, _vp]
+        L.emu_core_safety.argtypes, L.emu_core_safety.restype = [_ci] + [_vp] * 7, None
+        _lib = L
     return _lib
+
+
+class Counters:
+    """What emulated step calls reported, added up."""
+
+    def __init__(self):
+        self.fast_bails = self.wide_envs = self.chunk_fault = 0
+
+    def add(self, r):
+        self.fast_bails += r.fast_bails
+        self.wide_envs += r.wide_envs
+        self.chunk_fault |= r.chunk_fault
+
+
+_active = []    # the settings() blocks we are inside: (overrides, counters), outermost first
+
+
+@contextlib.contextmanager
+def settings(**kw):
+    """The emulator's settings (emu_api.h: emu_settings) of the calls made inside the block, on top of those of the blocks around it;
+    yields the Counters of those calls."""
+    assert all(hasattr(Settings, k) for k in kw), kw
+    run = Counters()
+    _active.append((kw, run))
+    try:
+        yield run
+    finally:
+        _active.pop()
+
+
+def _ptr(a):
+    return None if a is None else a.ctypes.data if isinstance(a, np.ndarray) else ctypes.addressof(a)
 
 
 class EmuBatch:
@@ -36,38 +110,114 @@ class EmuBatch:
         self.xpos = z(pod.nbody * 3)
         self.xquat = z(pod.nbody * 4)
         self.pd_ptarget = self.pd_kp = self.pd_kd = None
-        self.hfield = None          # float32 [nrow * ncol] shared by all envs
+        # the height field, float32: one grid [nrow * ncol] shared by all envs; with hfield_stride (floats between the grids) every env's
+        # own (hfield_index None) or a bank of nterrain grids that hfield_index [nenv] (int32) picks from
+        self.hfield, self.hfield_stride, self.hfield_index, self.nterrain = None, 0, None, 0
         # drive-level I/O (mode 0 = off): filter histories / delay lines, commands [nenv][nu + 1], measurement block
         self.drive_mode = 0
         self.drive_state = (CmDriveState * nenv)()
         self.drive_cmd = z(pod.nu + 1)
         self.meas = z(56)
         self.pd_dtarget = self.pd_torque = None
+        self.envparams = None       # [nenv] cm_envparams_t (a ctypes array), or None: the model's own
+        self.settings = {}          # this batch's own settings, on top of the settings() blocks around the call
+        self.counters = Counters()  # what this batch's calls reported so far
+
+    def _args(self, nsub, integrate):
+        a = StepArgs(model=ctypes.pointer(self.pod), nenv=self.nenv, nsub=nsub, integrate=integrate, drive_mode=self.drive_mode,
+                     hfield_stride=self.hfield_stride, nterrain=self.nterrain)
+        for f in ("qpos", "qvel", "qacc_warmstart", "time", "ctrl", "qfrc_applied", "xfrc_applied", "qacc", "sensordata", "actuator_velocity",
+                  "warn", "info", "xpos", "xquat", "pd_ptarget", "pd_kp", "pd_kd", "drive_state", "drive_cmd", "meas", "pd_dtarget",
+                  "pd_torque", "envparams", "hfield", "hfield_index"):
+            setattr(a, f, _ptr(getattr(self, f)))
+        for kw in [DEFAULTS] + [k for k, _ in _active] + [self.settings]:
+            for k, v in kw.items():
+                setattr(a.settings, k, v)
+        return a
+
+    def _report(self, result):
+        for c in [self.counters] + [run for _, run in _active]:
+            c.add(result)
+        return result
 
     def _run(self, nsub, integrate):
-        p = lambda a: None if a is None else a.ctypes.data
-        lib().emu_set_drive_io(self.drive_mode, ctypes.addressof(self.drive_state), p(self.drive_cmd), p(self.meas),
-                               p(self.pd_dtarget), p(self.pd_torque))
-        lib().emu_phys_run(ctypes.byref(self.pod), self.nenv, nsub, integrate, p(self.qpos), p(self.qvel),
-                           p(self.qacc_warmstart), p(self.time), p(self.ctrl), p(self.qfrc_applied),
-                           p(self.xfrc_applied), p(self.qacc), p(self.sensordata), p(self.actuator_velocity),
-                           p(self.warn), p(self.info), p(self.xpos), p(self.xquat), p(self.pd_ptarget), p(self.pd_kp),
-                           p(self.pd_kd), p(self.hfield))
+        result = StepResult()
+        rc = lib().emu_phys_run(ctypes.byref(self._args(nsub, integrate)), ctypes.byref(result))
+        assert rc == 0
+        return self._report(result)
 
     def derive(self, ids):
         """phys_batch_derive on the emulator: -> (derived [nenv][CM_DRV_DIM], qM [nenv][nv][nv])."""
         from cassie_amd import phys as P
-        p = lambda a: None if a is None else a.ctypes.data
         derived = np.zeros((self.nenv, P.DRV_DIM))
         qM = np.zeros((self.nenv, self.pod.nv, self.pod.nv))
         idarr = np.asarray(ids, dtype=np.int32)
-        lib().emu_derive(ctypes.byref(self.pod), self.nenv, p(self.qpos), p(self.qvel), p(self.qacc_warmstart), p(self.time), p(self.ctrl),
-                         p(self.qacc), p(self.sensordata), p(self.actuator_velocity), p(self.warn), p(self.info), p(self.hfield),
-                         p(idarr), p(derived), p(qM))
+        result = StepResult()
+        lib().emu_derive(ctypes.byref(self._args(1, 0)), _ptr(idarr), _ptr(derived), _ptr(qM), ctypes.byref(result))
+        self._report(result)
         return derived, qM
 
     def step(self, nsub=1):
-        self._run(nsub, 1)
+        return self._run(nsub, 1)
 
     def forward(self):
-        self._run(1, 0)
+        return self._run(1, 0)
+
+
+def pick_family(pod, generic_only=False):
+    """ck::pick_family (csrc/step_plan.h) -> the index of the family in ck::StepFamily."""
+    return lib().emu_pick_family(ctypes.byref(pod), 1 if generic_only else 0)
+
+
+def set_const(pod, blocks, nenv, mode):
+    """phys_batch_set_const on the emulator: the device's set_const kernel on the [nenv] parameter blocks (a ctypes array), in place."""
+    assert lib().emu_set_const(ctypes.byref(pod), ctypes.addressof(blocks), nenv, mode) == 0
+
+
+def end_episodes(state, pod, r, env0, n, restart, bank=None, pick=None, force=None, grid=0, block=None):
+    """The emulated episode kernel on `state` (in place); r: the rules, as tests/episode_check.py's dict.  block: a
+    [nenv][nq + nv + nsd] array whose column blocks ARE the state's qpos / qvel / sensordata (strided binding); otherwise the three
+    are dense."""
+    for k, a in state.items():
+        assert a is None or a.flags.c_contiguous or block is not None, k
+    if block is not None:
+        w = block.shape[1]
+        qp, qv, sd = block.ctypes.data, block.ctypes.data + 8 * pod.nq, block.ctypes.data + 8 * (pod.nq + pod.nv)
+        sq = sqv = ssd = w
+    else:
+        qp, qv, sd = _ptr(state["qpos"]), _ptr(state["qvel"]), _ptr(state["sensordata"])
+        sq, sqv, ssd = pod.nq, pod.nv, pod.nsensordata
+    pick = None if pick is None else np.ascontiguousarray(pick, dtype=np.int32)
+    force = None if force is None else np.ascontiguousarray(force, dtype=np.int32)
+    rules = CmEpisodeRules(min_height=r["min_height"], min_upright=r["min_upright"], max_steps=r["max_steps"],
+                           warn_mask=r["warn_mask"], nonfinite=1 if r["nonfinite"] else 0)
+    rc = lib().emu_end_episodes(ctypes.byref(pod), ctypes.byref(rules), env0, n, 1 if restart else 0, grid,
+                                qp, sq, qv, sqv, sd, ssd, _ptr(state["qacc_warmstart"]), _ptr(state["ctrl"]), _ptr(state["qacc"]), _ptr(state["time"]),
+                                _ptr(state["actuator_velocity"]), _ptr(state["meas"]), _ptr(state["drive"]), _ptr(state["warn"]),
+                                _ptr(state["done"]), _ptr(state["reason"]), _ptr(state["steps"]), _ptr(state["count"]), _ptr(state["terminal"]),
+                                _ptr(bank), 0 if bank is None else bank.shape[0], _ptr(pick), _ptr(force))
+    assert rc == 0
+
+
+def height_scan(pod, qpos, offsets, body, scan_range, blocks=None, hfield=None, stride=0, index=None, nterrain=0, env0=0, n=None, grid=0,
+                out=None, warn=None):
+    """The emulated scan kernel -> (values [nenv][P], warn [nenv]).  hfield: float32, one grid / nenv grids / a bank; blocks: per-env
+    parameter blocks whose geometry the scan reads (the model is then told to, like a batch that has randomised geometry)."""
+    nenv, npts = qpos.shape[0], offsets.shape[0]
+    n = nenv - env0 if n is None else n
+    offsets = np.ascontiguousarray(offsets, dtype=np.float64)
+    qpos = np.ascontiguousarray(qpos, dtype=np.float64)
+    out = np.full((nenv, npts), np.nan) if out is None else out
+    warn = np.zeros(nenv, dtype=np.int32) if warn is None else warn
+    model = CmModel.from_buffer_copy(pod)
+    model.env_geom = 1 if blocks is not None else 0
+    index = None if index is None else np.ascontiguousarray(index, dtype=np.int32)
+    rc = lib().emu_height_scan(ctypes.byref(model), _ptr(blocks), env0, n, grid, _ptr(offsets), npts, body, scan_range, _ptr(qpos),
+                               qpos.shape[1], _ptr(out), out.shape[1], _ptr(hfield), stride, _ptr(index), nterrain, _ptr(warn))
+    assert rc == 0
+    return out, warn
+
+
+def core_safety(n, u, q, w, L, sto, tau, msg):
+    """cassie_core_sim's safety layer as the step kernel computes it (csrc/pk_safety.h): n samples, into tau [n][10] and msg [n]."""
+    lib().emu_core_safety(n, _ptr(u), _ptr(q), _ptr(w), _ptr(L), _ptr(sto), _ptr(tau), _ptr(msg))

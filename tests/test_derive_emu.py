@@ -21,11 +21,8 @@ def test_derived_block_against_first_principles(cassie, two_waves):
     """(two_waves: the forward pass with the read-out enabled through the full instantiation's two-wave form -- what a
     cassie_sim_t, a batch of one env with the read-out on, runs since round 4)"""
     import emu_py
-    emu_py.lib().emu_two_waves(two_waves)
-    try:
+    with emu_py.settings(two_waves=two_waves):
         _derived_block(cassie)
-    finally:
-        emu_py.lib().emu_two_waves(0)
 
 
 def _derived_block(cassie):

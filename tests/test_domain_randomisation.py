@@ -13,16 +13,8 @@ from cassie_amd._lib import CmEnvParams, CmModel
 from oracle_py import Oracle
 
 
-def _emu():
-    L = emu_py.lib()
-    L.emu_set_const.argtypes = [ctypes.POINTER(CmModel), ctypes.c_void_p, ctypes.c_int, ctypes.c_int]
-    L.emu_set_envparams.argtypes = [ctypes.c_void_p]
-    L.emu_sizeof_envparams.restype = ctypes.c_ulong
-    return L
-
-
 def test_parameter_block_layout_is_shared_by_header_emulator_and_library():
-    assert _emu().emu_sizeof_envparams() == ctypes.sizeof(CmEnvParams)
+    assert emu_py.lib().emu_sizeof_envparams() == ctypes.sizeof(CmEnvParams)
     # the model's own block is what the compile derives for the model's own parameters
     for name in ("cassie", "cassie_tray_box"):
         pod = Model(name).pod
@@ -42,7 +34,7 @@ def test_device_set_const_reproduces_the_host_compile_bit_for_bit(name):
     pod0 = Model(name).pod
     params = rc.random_params(hosts.m, nenv, seed=11)
     blocks = rc.new_blocks(pod0, nenv, params)
-    _emu().emu_set_const(ctypes.byref(pod0), ctypes.addressof(blocks), nenv, 1)
+    emu_py.set_const(pod0, blocks, nenv, 1)
     for e in range(nenv):
         want = hosts.pod(params, e)
         rc.assert_blocks_equal(blocks[e], want.params, pod0, "%s env %d" % (name, e))
@@ -56,7 +48,7 @@ def test_device_set_const_reproduces_the_host_compile_bit_for_bit(name):
             same[0].meaninertia = -1.0
         else:
             np.ctypeslib.as_array(getattr(same[0], f)).reshape(-1)[:] = -1.0
-    _emu().emu_set_const(ctypes.byref(pod0), ctypes.addressof(same), 1, 1)
+    emu_py.set_const(pod0, same, 1, 1)
     rc.assert_blocks_equal(same[0], pod0.params, pod0, name + " unchanged parameters")
 
 
@@ -67,7 +59,7 @@ def test_friction_alone_needs_no_set_const():
     pod0 = Model("cassie").pod
     params = rc.random_params(hosts.m, 2, seed=5, mass=0.0, ipos=0.0, damping=0.0)
     blocks = rc.new_blocks(pod0, 2, params)
-    _emu().emu_set_const(ctypes.byref(pod0), ctypes.addressof(blocks), 2, 0)
+    emu_py.set_const(pod0, blocks, 2, 0)
     for e in range(2):
         want = hosts.pod(params, e, set_const=False)
         rc.assert_blocks_equal(blocks[e], want.params, pod0, "env %d" % e)
@@ -84,23 +76,19 @@ def test_step_kernel_reads_the_env_block_like_a_per_env_model(name, two_waves):
     pod0 = model.pod
     params = rc.random_params(hosts.m, nenv, seed=3)
     blocks = rc.new_blocks(pod0, nenv, params)
-    L = _emu()
-    L.emu_set_const(ctypes.byref(pod0), ctypes.addressof(blocks), nenv, 1)
-    L.emu_two_waves(two_waves)
-    L.emu_fast_rows(1)
+    emu_py.set_const(pod0, blocks, nenv, 1)
     rng = np.random.default_rng(1)
     hi = np.array([pod0.act_ctrlrange[u][1] for u in range(pod0.nu)])
     ctrl = 0.6 * hi * rng.uniform(-1, 1, (nenv, pod0.nu))
     q0 = model.qpos_init()
     if name == "cassie_tray_box":
         q0 = np.array(pod0.qpos0[: pod0.nq]); q0[7:35] = model.qpos_init()[7:35]
-    try:
+    with emu_py.settings(two_waves=two_waves, fast_rows=1):
         a = emu_py.EmuBatch(pod0, nenv)
         a.qpos[:] = q0; a.ctrl[:] = ctrl
-        L.emu_set_envparams(ctypes.addressof(blocks))
+        a.envparams = blocks
         for _ in range(nlaunch):
             a.step(nsub)
-        L.emu_set_envparams(None)
         for e in range(nenv):
             pe = hosts.pod(params, e)
             b = emu_py.EmuBatch(pe, 1)
@@ -119,7 +107,3 @@ def test_step_kernel_reads_the_env_block_like_a_per_env_model(name, two_waves):
         for _ in range(nlaunch):
             c.step(nsub)
         assert np.max(np.abs(c.qpos[0] - a.qpos[0])) > 1e-6
-    finally:
-        L.emu_set_envparams(None)
-        L.emu_two_waves(0)
-        L.emu_fast_rows(0)

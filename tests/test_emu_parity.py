@@ -100,8 +100,7 @@ def test_divergence_flag_is_sticky_and_state_untouched(cassie, two_waves):
     """A NaN in the state (caught at the top of the substep) and a diverged qacc (caught behind the solve -- in the two-wave form
     by wave 1, which tells wave 0 at the substep's last barrier): sticky flag, state left as it is."""
     import emu_py
-    emu_py.lib().emu_two_waves(two_waves); emu_py.lib().emu_fast_rows(two_waves)
-    try:
+    with emu_py.settings(two_waves=two_waves, fast_rows=two_waves):
         emu = EmuBatch(cassie.pod, 1)
         emu.qpos[:] = cassie.qpos_init()
         emu.qvel[0, 3] = np.nan
@@ -120,8 +119,6 @@ def test_divergence_flag_is_sticky_and_state_untouched(cassie, two_waves):
         assert np.array_equal(q, emu.qpos) and np.array_equal(v, emu.qvel)
         emu.forward()                                     # (a forward pass over the same state: same verdict, no hang)
         assert emu.warn[0] & 8
-    finally:
-        emu_py.lib().emu_two_waves(0); emu_py.lib().emu_fast_rows(0)
 
 
 def test_on_device_pd_mode(cassie):
@@ -156,11 +153,8 @@ def test_runtime_topology_instantiation_matches_static_one(cassie):
         x.qpos[:] = cassie.qpos_init()
         x.ctrl[:] = [1.0, -2.0, 3.0, -4.0, 0.5, -1.0, 2.0, -3.0, 4.0, -0.5]
     a.step(40)
-    emu_py.lib().emu_force_runtime_topology(1)
-    try:
+    with emu_py.settings(force_runtime_topology=1):
         b.step(40)
-    finally:
-        emu_py.lib().emu_force_runtime_topology(0)
     assert np.abs(a.qpos - b.qpos).max() < 1e-11 and np.abs(a.qvel - b.qvel).max() < 1e-9
 
 
@@ -175,11 +169,8 @@ def test_guarded_pgs_sweep_agrees_with_the_speculative_one(cassie):
         x.qpos[:] = cassie.qpos_init()
         x.ctrl[:] = [1.0, -2.0, 3.0, -4.0, 0.5, -1.0, 2.0, -3.0, 4.0, -0.5]
     a.step(60)
-    emu_py.lib().emu_force_guarded_pgs(1)
-    try:
+    with emu_py.settings(force_guarded_pgs=1):
         b.step(60)
-    finally:
-        emu_py.lib().emu_force_guarded_pgs(0)
     assert np.abs(a.qpos - b.qpos).max() < 1e-11 and np.abs(a.qvel - b.qvel).max() < 1e-9
 
 
@@ -252,8 +243,7 @@ def test_kernel_never_reads_lds_it_has_not_written(cassie):
     pod = cassie.pod
     out = []
     for poison in (0, 1):
-        emu_py.lib().emu_poison_lds(poison)
-        try:
+        with emu_py.settings(poison_lds=poison):
             emu = EmuBatch(pod, 2)
             emu.qpos[:] = cassie.qpos_init()
             emu.qpos[1, 2] -= 0.02
@@ -263,17 +253,13 @@ def test_kernel_never_reads_lds_it_has_not_written(cassie):
             emu.step(1)
             emu.step(40)
             out.append((emu.qpos.copy(), emu.qvel.copy(), emu.sensordata.copy(), emu.warn.copy(), emu.info.copy()))
-        finally:
-            emu_py.lib().emu_poison_lds(0)
     assert not out[1][3].any() and out[1][4][:, 0].max() >= 1          # no divergence flag, contacts happened
     for a, b in zip(out[0], out[1]):
         assert np.array_equal(a, b)
     # the check is not vacuous: with the round-2 bug reinstated (the emulator's test hook skips the once-per-launch
     # initialisation of the centre-of-mass rows) the poisoned run differs from the clean one or raises the divergence flag
     def fifty(poison, skip):
-        emu_py.lib().emu_skip_com_init(skip)
-        emu_py.lib().emu_poison_lds(poison)
-        try:
+        with emu_py.settings(skip_com_init=skip, poison_lds=poison):
             emu = EmuBatch(pod, 2)
             emu.qpos[:] = cassie.qpos_init()
             emu.qpos[1, 2] -= 0.02
@@ -281,9 +267,6 @@ def test_kernel_never_reads_lds_it_has_not_written(cassie):
             emu.pd_ptarget = np.ascontiguousarray(bench.pd_targets([3, 4], 1)[0])
             emu.step(50)
             return emu.qpos.copy(), emu.warn.copy()
-        finally:
-            emu_py.lib().emu_poison_lds(0)
-            emu_py.lib().emu_skip_com_init(0)
     clean, buggy = fifty(0, 0), fifty(1, 1)
     assert buggy[1].any() or not np.array_equal(clean[0], buggy[0])
 
@@ -303,8 +286,7 @@ def test_lds_poison_on_the_other_models_and_modes(name, steps, drive, built):
         hf = np.random.default_rng(99).random((200, 200)).astype(np.float32).ravel()
     out = []
     for poison in (0, 1):
-        emu_py.lib().emu_poison_lds(poison)
-        try:
+        with emu_py.settings(poison_lds=poison):
             emu = EmuBatch(pod, 1)
             emu.qpos[:] = model.qpos_init()
             if hf is not None:
@@ -320,8 +302,6 @@ def test_lds_poison_on_the_other_models_and_modes(name, steps, drive, built):
             for _ in range(steps // 10):
                 emu.step(10)
             out.append((emu.qpos.copy(), emu.qvel.copy(), emu.sensordata.copy(), emu.meas.copy(), emu.warn.copy(), emu.info.copy()))
-        finally:
-            emu_py.lib().emu_poison_lds(0)
     assert not out[1][4].any() and out[1][5][0, 0] >= 1
     for a, b in zip(out[0], out[1]):
         assert np.array_equal(a, b)
@@ -357,8 +337,7 @@ def test_row_capped_fast_kernel_hands_over_mid_launch_and_changes_nothing(cassie
         tg[:, e, :] = bench.PD_OFFSET + np.random.default_rng(4321 + e).uniform(-10, 10, (6, 10))
     out, bails = [], 0
     for fast in (0, 1):
-        emu_py.lib().emu_fast_rows(fast)
-        try:
+        with emu_py.settings(fast_rows=fast) as run:
             emu = EmuBatch(pod, n)
             emu.qpos[:] = cassie.qpos_init()
             emu.qpos[:, 2] -= 0.2                               # start in contact so that rows are plenty from the first step
@@ -373,10 +352,8 @@ def test_row_capped_fast_kernel_hands_over_mid_launch_and_changes_nothing(cassie
                 rows.append(emu.info[:, 1].copy())
             out.append((emu.qpos.copy(), emu.qvel.copy(), emu.qacc_warmstart.copy(), emu.sensordata.copy(), emu.meas.copy(), emu.info.copy(),
                         emu.warn.copy(), emu.time.copy(), [device_state_bytes(emu.drive_state[e]) for e in range(n)], np.array(rows)))
-            if fast:
-                bails = emu_py.lib().emu_fast_bails()
-        finally:
-            emu_py.lib().emu_fast_rows(0)
+        if fast:
+            bails = run.fast_bails
     assert out[0][9].max() > 31 and out[0][9].min() <= 31          # launches on both sides of the fast kernel's capacity
     assert bails > 0                                                # and the hand-over really happened
     for a, b in zip(out[0], out[1]):
@@ -389,15 +366,14 @@ def test_row_capped_fast_kernel_hands_over_mid_launch_and_changes_nothing(cassie
 # ---- the two-wave form (NW = 2): wave 1 runs the mass-matrix stage group beside wave 0's collision / velocity / row stages ----
 def _two_wave_workload(model, drive, fast, two_waves, schedule, poison=False, nlaunch=5, nsub=12, stress=True):
     """A few fused launches of the benchmark's PD workload (optionally with the +-10 rad stress targets, which force hand-overs
-    between the row-capped and the full instantiation); returns everything a launch leaves behind, as bytes."""
+    between the row-capped and the full instantiation); returns everything a launch leaves behind, as bytes, the solver statistics of
+    every launch and the number of envs the workload's launches handed over."""
     import bench
     import emu_py
     from cassie_amd import phys as P
     from hostchain_py import device_state_bytes
-    lib = emu_py.lib()
     pod, n = model.pod, 2
-    lib.emu_fast_rows(1 if fast else 0); lib.emu_two_waves(1 if two_waves else 0); lib.emu_wave_schedule(schedule); lib.emu_poison_lds(1 if poison else 0)
-    try:
+    with emu_py.settings(fast_rows=1 if fast else 0, two_waves=1 if two_waves else 0, wave_schedule=schedule, poison_lds=1 if poison else 0):
         emu = EmuBatch(pod, n)
         emu.qpos[:] = model.qpos_init()
         emu.qpos[:, 2] -= 0.15
@@ -420,9 +396,7 @@ def _two_wave_workload(model, drive, fast, two_waves, schedule, poison=False, nl
         emu.forward()                                    # a forward-only pass goes through the same kernel (integrate = 0)
         return [emu.qpos.tobytes(), emu.qvel.tobytes(), emu.qacc_warmstart.tobytes(), emu.qacc.tobytes(), emu.sensordata.tobytes(),
                 emu.actuator_velocity.tobytes(), emu.meas.tobytes(), emu.warn.tobytes(), emu.time.tobytes(), emu.xpos.tobytes(), emu.xquat.tobytes(),
-                np.array(rows).tobytes(), [device_state_bytes(emu.drive_state[e]) for e in range(n)]], np.array(rows), lib.emu_fast_bails()
-    finally:
-        lib.emu_fast_rows(0); lib.emu_two_waves(0); lib.emu_wave_schedule(0); lib.emu_poison_lds(0)
+                np.array(rows).tobytes(), [device_state_bytes(emu.drive_state[e]) for e in range(n)]], np.array(rows), emu.counters.fast_bails
 
 
 @pytest.mark.parametrize("drive", [False, True])
@@ -435,11 +409,8 @@ def test_two_wave_form_is_bit_for_bit_the_one_wave_form_under_every_wave_schedul
     assert rows[:, :, 1].max() > 31 and rows[:, :, 1].min() <= 31
     import emu_py
     for schedule in (0, 1, 2):
-        emu_py.lib().emu_resume_grid((2, 1, 3)[schedule])      # workgroups of the pass that walks the hand-over list
-        try:
+        with emu_py.settings(resume_grid=(2, 1, 3)[schedule]):      # workgroups of the pass that walks the hand-over list
             got, _, bails = _two_wave_workload(cassie, drive, fast=True, two_waves=True, schedule=schedule)
-        finally:
-            emu_py.lib().emu_resume_grid(2)
         assert bails > 0
         assert got == ref, schedule
     # the full instantiation alone, two waves
@@ -479,22 +450,17 @@ def test_tray_fast_instantiation_is_bit_for_bit_the_full_one(built):
         # (the second round: every limited joint inside its limit's margin all the time -- 16 more rows while the robot still stands)
         for j in range(model.pod.njnt):
             model.pod.jnt_margin[j] = 10.0 if stress and model.pod.jnt_limited[j] else margins[j]
-        ref, rows, before = _two_wave_workload(model, True, fast=False, two_waves=False, schedule=0, nlaunch=3, nsub=10, stress=stress)
+        ref, rows, _ = _two_wave_workload(model, True, fast=False, two_waves=False, schedule=0, nlaunch=3, nsub=10, stress=stress)
         got, _, bails = _two_wave_workload(model, True, fast=True, two_waves=False, schedule=0, poison=True, nlaunch=3, nsub=10, stress=stress)
-        bails -= before       # (the emulator's count of handed-over envs runs on from test to test)
         assert got == ref, stress
         if stress:
             assert rows[:, :, 1].max() > 47 and bails > 0, (rows[:, :, 1].max(), bails)
         else:
             assert 16 < rows[:, :, 1].max() <= 47 and bails == 0, (rows[:, :, 1].max(), bails)
     # the walking pass in its two-wave form (what phys_batch.hip launches behind the fast kernel)
-    emu_py.lib().emu_resume_grid(1)
-    before = emu_py.lib().emu_fast_bails()
-    try:
+    with emu_py.settings(resume_grid=1):
         got, _, bails = _two_wave_workload(model, True, fast=True, two_waves=True, schedule=1, nlaunch=3, nsub=10, stress=True)
-    finally:
-        emu_py.lib().emu_resume_grid(2)
-    assert got == ref and bails > before
+    assert got == ref and bails > 0
 
 
 @pytest.mark.parametrize("name", ["cassie", "cassie_hfield", "cassie_tray_box"])
@@ -506,28 +472,20 @@ def test_launch_in_chunks_is_bit_for_bit_the_launch_in_one_piece(name, built):
     from cassie_amd import Model
     import emu_py
     model = Model(name)
-    lib = emu_py.lib()
     for stress in ((False, True) if name != "cassie_tray_box" else (False,)):   # (the 40-dof model's 47-row instantiation is not left under these targets: covered above)
-        ref, rows, before = _two_wave_workload(model, True, fast=True, two_waves=False, schedule=0, nlaunch=3, nsub=11, stress=stress)
+        ref, rows, _ = _two_wave_workload(model, True, fast=True, two_waves=False, schedule=0, nlaunch=3, nsub=11, stress=stress)
         for chunks, two_waves in ((4, False), (3, True), (2, True)):
-            lib.emu_chunks(chunks)
-            try:
+            with emu_py.settings(chunks=chunks):
                 got, _, bails = _two_wave_workload(model, True, fast=True, two_waves=two_waves, schedule=1, poison=True, nlaunch=3, nsub=11, stress=stress)
-            finally:
-                lib.emu_chunks(1)
             assert got == ref, (chunks, two_waves, stress)
             if stress:
-                assert bails > before
-            before = bails
+                assert bails > 0
     # more chunks than substeps (the trailing chunks have nothing to do), and a chunk of a single substep
     if name == "cassie":
         for nsub in (2, 5):
             ref, _, _ = _two_wave_workload(model, True, fast=True, two_waves=True, schedule=0, nlaunch=4, nsub=nsub, stress=False)
-            lib.emu_chunks(4)
-            try:
+            with emu_py.settings(chunks=4):
                 got, _, _ = _two_wave_workload(model, True, fast=True, two_waves=True, schedule=2, nlaunch=4, nsub=nsub, stress=False)
-            finally:
-                lib.emu_chunks(1)
             assert got == ref, nsub
 
 
@@ -536,20 +494,14 @@ def test_a_chunk_that_finds_its_producer_on_another_xcd_flags_the_env_and_tells_
     word carries the producer's XCD and the consumer checks it.  With the emulator's producers publishing from "XCD 3" (consumers
     run on 0) every env must carry WARN_CHUNK_PLACEMENT (16) and the launcher's fault word must be set; with producers on 0 neither."""
     import emu_py
-    lib = emu_py.lib()
-    lib.emu_chunks(3)
-    try:
-        lib.emu_producer_xcc(0)
+    with emu_py.settings(chunks=3, producer_xcc=0) as run:
         got, _, _ = _two_wave_workload(cassie, True, fast=True, two_waves=True, schedule=1, nlaunch=2, nsub=9, stress=False)
-        warn = np.frombuffer(got[7], dtype=np.int32)
-        assert not (warn & 16).any() and lib.emu_chunk_fault() == 0
-        lib.emu_producer_xcc(3)
+    warn = np.frombuffer(got[7], dtype=np.int32)
+    assert not (warn & 16).any() and run.chunk_fault == 0
+    with emu_py.settings(chunks=3, producer_xcc=3) as run:
         got, _, _ = _two_wave_workload(cassie, True, fast=True, two_waves=True, schedule=1, nlaunch=2, nsub=9, stress=False)
-        warn = np.frombuffer(got[7], dtype=np.int32)
-        assert (warn & 16).all() and lib.emu_chunk_fault() == 1
-    finally:
-        lib.emu_producer_xcc(0)
-        lib.emu_chunks(1)
+    warn = np.frombuffer(got[7], dtype=np.int32)
+    assert (warn & 16).all() and run.chunk_fault == 1
 
 
 def test_127_row_instantiation_is_the_63_row_one_bit_for_bit_where_both_hold_the_substep(cassie):
@@ -580,19 +532,14 @@ def test_three_tiers_equal_the_127_row_instantiation_alone_bit_for_bit(built):
     from cassie_amd import Model
     from cassie_amd import phys as P
     import emu_py
-    lib = emu_py.lib()
     model = Model("cassie_hfield")
     model.set_flag(P.FLAG_HFPRISM, True)
     ref, rows, _ = _two_wave_workload(model, True, fast=False, two_waves=True, schedule=0, nlaunch=3, nsub=12, stress=False)
     assert rows[:, :, 1].max() > 63 and rows[:, :, 1].min() <= 31, (rows[:, :, 1].min(), rows[:, :, 1].max())
     for schedule, two_waves, chunks in ((0, True, 1), (1, True, 1), (2, True, 1), (1, False, 1), (2, True, 3)):
-        before = lib.emu_wide_envs()
-        lib.emu_resume_grid((2, 1, 3)[schedule]); lib.emu_chunks(chunks)
-        try:
+        with emu_py.settings(resume_grid=(2, 1, 3)[schedule], chunks=chunks) as run:
             got, _, _ = _two_wave_workload(model, True, fast=True, two_waves=two_waves, schedule=schedule, poison=True, nlaunch=3, nsub=12, stress=False)
-        finally:
-            lib.emu_resume_grid(2); lib.emu_chunks(1)
-        assert lib.emu_wide_envs() > before, "no env reached the 127-row pass"
+        assert run.wide_envs > 0, "no env reached the 127-row pass"
         assert got == ref, (schedule, two_waves, chunks)
 
 
@@ -610,11 +557,8 @@ def test_guarded_sweeps_across_both_waves_reproduce_the_fast_ones(cassie):
         for x in (a, b):
             x.qpos[:] = q0
         a.step(10)
-        emu_py.lib().emu_force_guarded_pgs(1)
-        try:
+        with emu_py.settings(force_guarded_pgs=1):
             b.step(10)
-        finally:
-            emu_py.lib().emu_force_guarded_pgs(0)
     finally:
         pod.maxcon, pod.maxefc = keep
     assert a.info[0, 1] > 64 and a.info[0, 3] == 0 and b.info[0, 3] > 0
@@ -630,17 +574,13 @@ def test_in_place_form_equals_the_pass_behind_the_kernel_bit_for_bit(cassie, dri
     the same instructions either way, so everything a launch leaves must be identical: under the stress targets (hand-overs in the
     middle of fused launches), all three wave schedules, NaN-poisoned LDS, and with the launch in chunks."""
     import emu_py
-    lib = emu_py.lib()
     ref, rows, bails0 = _two_wave_workload(cassie, drive, fast=True, two_waves=True, schedule=0)
     assert rows[:, :, 1].max() > 31, "the workload never left the 31-row tier"
     # (stay: PhysIO::inplace_stay_rows -- 0 = back to the fast code after every substep, r = the env stays in the 63-row code until a
     # substep needs at most r rows again: 27 is what the product launches with, 31 the narrowest margin, 12 practically never back)
     for schedule, chunks, stay in ((0, 1, 0), (1, 1, 27), (2, 1, 31), (1, 3, 27), (0, 2, 12)):
-        lib.emu_inplace(1); lib.emu_chunks(chunks); lib.emu_inplace_stay_rows(stay)
-        try:
+        with emu_py.settings(inplace=1, chunks=chunks, inplace_stay_rows=stay):
             got, _, _ = _two_wave_workload(cassie, drive, fast=True, two_waves=True, schedule=schedule, poison=True)
-        finally:
-            lib.emu_inplace(0); lib.emu_chunks(1); lib.emu_inplace_stay_rows(0)
         assert got == ref, (schedule, chunks, stay)
     # ... and the one-wave form of the full kernel alone agrees too (the yardstick of every form)
     alone, _, _ = _two_wave_workload(cassie, drive, fast=False, two_waves=False, schedule=0)
@@ -653,17 +593,12 @@ def test_in_place_form_hands_on_to_the_127_row_pass(built):
     from cassie_amd import Model
     from cassie_amd import phys as P
     import emu_py
-    lib = emu_py.lib()
     model = Model("cassie_hfield")
     model.set_flag(P.FLAG_HFPRISM, True)
     ref, rows, _ = _two_wave_workload(model, True, fast=False, two_waves=True, schedule=0, nlaunch=3, nsub=12, stress=False)
     assert rows[:, :, 1].max() > 63 and rows[:, :, 1].min() <= 31
     for schedule, chunks, stay in ((0, 1, 0), (2, 3, 27), (1, 1, 31)):
-        before = lib.emu_wide_envs()
-        lib.emu_inplace(1); lib.emu_chunks(chunks); lib.emu_resume_grid((2, 1, 3)[schedule]); lib.emu_inplace_stay_rows(stay)
-        try:
+        with emu_py.settings(inplace=1, chunks=chunks, resume_grid=(2, 1, 3)[schedule], inplace_stay_rows=stay) as run:
             got, _, _ = _two_wave_workload(model, True, fast=True, two_waves=True, schedule=schedule, poison=True, nlaunch=3, nsub=12, stress=False)
-        finally:
-            lib.emu_inplace(0); lib.emu_chunks(1); lib.emu_resume_grid(2); lib.emu_inplace_stay_rows(0)
-        assert lib.emu_wide_envs() > before, "no env reached the 127-row pass"
+        assert run.wide_envs > 0, "no env reached the 127-row pass"
         assert got == ref, (schedule, chunks, stay)

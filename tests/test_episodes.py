@@ -20,44 +20,7 @@ RULES = ec.rules(min_height=0.4, min_upright=0.5, max_steps=7, warn_mask=P.WARN_
 NROWS = 5
 
 
-def _emu():
-    from cassie_amd._lib import CmEpisodeRules
-    L = emu_py.lib()
-    L.emu_end_episodes.argtypes = ([ctypes.POINTER(CmModel), ctypes.POINTER(CmEpisodeRules)] + [ctypes.c_int] * 4 +
-                                   [ctypes.c_void_p, ctypes.c_int] * 3 + [ctypes.c_void_p] * 13 + [ctypes.c_void_p, ctypes.c_int] +
-                                   [ctypes.c_void_p] * 2)
-    L.emu_sizeof_episode_rules.restype = ctypes.c_ulong
-    L.emu_offsetof_episode_rules.restype = ctypes.c_long
-    return L
-
-
-def _c_rules(r):
-    from cassie_amd._lib import CmEpisodeRules
-    return CmEpisodeRules(min_height=r["min_height"], min_upright=r["min_upright"], max_steps=r["max_steps"],
-                          warn_mask=r["warn_mask"], nonfinite=1 if r["nonfinite"] else 0)
-
-
-def emu_end_episodes(state, pod, r, env0, n, restart, bank=None, pick=None, force=None, grid=0, block=None):
-    """The emulated kernel on `state` (in place).  block: a [nenv][nq + nv + nsd] array whose column blocks ARE the state's qpos /
-    qvel / sensordata (strided binding); otherwise the three are dense."""
-    p = lambda a: None if a is None else a.ctypes.data
-    for k, a in state.items():
-        assert a is None or a.flags.c_contiguous or block is not None, k
-    if block is not None:
-        w = block.shape[1]
-        qp, qv, sd = block.ctypes.data, block.ctypes.data + 8 * pod.nq, block.ctypes.data + 8 * (pod.nq + pod.nv)
-        sq = sqv = ssd = w
-    else:
-        qp, qv, sd = p(state["qpos"]), p(state["qvel"]), p(state["sensordata"])
-        sq, sqv, ssd = pod.nq, pod.nv, pod.nsensordata
-    pick = None if pick is None else np.ascontiguousarray(pick, dtype=np.int32)
-    force = None if force is None else np.ascontiguousarray(force, dtype=np.int32)
-    rc = _emu().emu_end_episodes(ctypes.byref(pod), ctypes.byref(_c_rules(r)), env0, n, 1 if restart else 0, grid,
-                                 qp, sq, qv, sqv, sd, ssd, p(state["qacc_warmstart"]), p(state["ctrl"]), p(state["qacc"]), p(state["time"]),
-                                 p(state["actuator_velocity"]), p(state["meas"]), p(state["drive"]), p(state["warn"]),
-                                 p(state["done"]), p(state["reason"]), p(state["steps"]), p(state["count"]), p(state["terminal"]),
-                                 p(bank), 0 if bank is None else bank.shape[0], p(pick), p(force))
-    assert rc == 0
+emu_end_episodes = emu_py.end_episodes
 
 
 # hand-placed envs: (name, what to do to the upright, mid-episode env, reason bits expected under RULES)
@@ -268,7 +231,7 @@ def test_rules_off_at_their_neutral_values(built):
 def test_rules_struct_layout_and_exported_symbols(built):
     """cm_episode_rules_t as ctypes derives it from cm_model.h against the compiled layout, and the new entry points in the product."""
     from cassie_amd._lib import CmEpisodeRules
-    L = _emu()
+    L = emu_py.lib()
     assert ctypes.sizeof(CmEpisodeRules) == L.emu_sizeof_episode_rules() == 32
     for which, f in enumerate(("min_height", "min_upright", "max_steps", "warn_mask", "nonfinite")):
         assert getattr(CmEpisodeRules, f).offset == L.emu_offsetof_episode_rules(which), f

@@ -18,13 +18,6 @@ from oracle_py import Oracle
 SETCONST_ALL, SETCONST_GEOMETRY, SETCONST_SPRINGS = 1, 2, 3
 
 
-def _emu():
-    L = emu_py.lib()
-    L.emu_set_const.argtypes = [ctypes.POINTER(CmModel), ctypes.c_void_p, ctypes.c_int, ctypes.c_int]
-    L.emu_set_envparams.argtypes = [ctypes.c_void_p]
-    return L
-
-
 def _reading_blocks(pod, geom, springs):
     """A copy of the shared model that tells the step kernel to read geometry / springs from the env's block (what
     phys_batch_randomize sets on a batch's shared model once it has randomised them)."""
@@ -59,7 +52,7 @@ def test_device_derives_geometry_and_springs_like_the_host_compile(name, mode):
                SETCONST_SPRINGS: ("dof_stiffness", "dof_springref")}[mode]
     for e in range(nenv):
         gc.garble_derived(blocks[e], derived)
-    _emu().emu_set_const(ctypes.byref(pod0), ctypes.addressof(blocks), nenv, mode)
+    emu_py.set_const(pod0, blocks, nenv, mode)
     reach0 = pod0.body_reach[pod0.root_body[0]]
     moved = False
     for e in range(nenv):
@@ -113,25 +106,21 @@ def test_cassie_five_envs_300_steps_each_on_its_own_geometry_and_springs(cassie)
     rb = pod0.geom_rbound[box] + pod0.geom_margin[box] + 0.01
     assert pod0.body_reach[root] + rb < d - 0.05 and d + 0.05 < pods[4].body_reach[root] + rb
     blocks = gc.new_blocks(pod0, nenv, params)
-    L = _emu()
-    L.emu_set_const(ctypes.byref(pod0), ctypes.addressof(blocks), nenv, SETCONST_ALL)
+    emu_py.set_const(pod0, blocks, nenv, SETCONST_ALL)
     for e in range(nenv):
         gc.assert_geo_equal(blocks[e], pods[e], pod0, "env %d" % e)
     emu = emu_py.EmuBatch(_reading_blocks(pod0, 1, 1), nenv)
     emu.qpos[:] = q0
     orc = [Oracle(pods[e], q0) for e in range(nenv)]
     box_contacts = [0] * nenv
-    try:
-        L.emu_set_envparams(ctypes.addressof(blocks))
-        for s in range(nsteps):
-            emu.step()
-            for e, o in enumerate(orc):
-                o.step()
-                assert (emu.info[e, 0], emu.info[e, 1]) == (o.d.ncon, o.d.nefc), (e, s)
-                n = sum(1 for i in range(o.d.ncon) if box in (o.d.contact[i].geom1, o.d.contact[i].geom2) or 1 in (o.d.contact[i].geom1, o.d.contact[i].geom2))
-                box_contacts[e] = max(box_contacts[e], n)
-    finally:
-        L.emu_set_envparams(None)
+    emu.envparams = blocks
+    for s in range(nsteps):
+        emu.step()
+        for e, o in enumerate(orc):
+            o.step()
+            assert (emu.info[e, 0], emu.info[e, 1]) == (o.d.ncon, o.d.nefc), (e, s)
+            n = sum(1 for i in range(o.d.ncon) if box in (o.d.contact[i].geom1, o.d.contact[i].geom2) or 1 in (o.d.contact[i].geom1, o.d.contact[i].geom2))
+            box_contacts[e] = max(box_contacts[e], n)
     for e in range(nenv):
         assert np.max(np.abs(emu.qpos[e] - orc[e].qpos)) < 1e-8, e
     assert not emu.warn.any()
@@ -158,15 +147,14 @@ def test_hfield_terrain_geom_shifted_per_env(built):
     hosts = gc.HostGeomEnvModels("cassie_hfield")
     pods = [hosts.pod(params, e) for e in range(nenv)]
     blocks = gc.new_blocks(pod0, nenv, params)
-    L = _emu()
-    L.emu_set_const(ctypes.byref(pod0), ctypes.addressof(blocks), nenv, SETCONST_GEOMETRY)
+    emu_py.set_const(pod0, blocks, nenv, SETCONST_GEOMETRY)
     oracle_py.set_hfield(h)
     emu = emu_py.EmuBatch(_reading_blocks(pod0, 1, 0), nenv)
     emu.qpos[:] = q0
     emu.hfield = h.ravel().copy()
     try:
         orc = [Oracle(pods[e], q0) for e in range(nenv)]
-        L.emu_set_envparams(ctypes.addressof(blocks))
+        emu.envparams = blocks
         seen = [0] * nenv
         for s in range(nsteps):
             emu.step()
@@ -175,7 +163,6 @@ def test_hfield_terrain_geom_shifted_per_env(built):
                 assert (emu.info[e, 0], emu.info[e, 1]) == (o.d.ncon, o.d.nefc), (e, s)
                 seen[e] = max(seen[e], o.d.ncon)
     finally:
-        L.emu_set_envparams(None)
         oracle_py.set_hfield(None)
     assert min(seen) >= 2
     for e in range(nenv):

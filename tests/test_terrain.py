@@ -23,37 +23,13 @@ SETCONST_GEOMETRY = 2
 RANGE = 2.5
 
 
-def _emu():
-    L = emu_py.lib()
-    vp, ci = ctypes.c_void_p, ctypes.c_int
-    L.emu_height_scan.argtypes = [ctypes.POINTER(CmModel), vp, ci, ci, ci, vp, ci, ci, ctypes.c_double, vp, ci, vp, ci, vp, ctypes.c_ulong, vp, ci, vp]
-    L.emu_phys_run_terrain.argtypes = [ctypes.POINTER(CmModel), ci, ci] + [vp] * 11 + [ctypes.c_ulong, vp, ci]
-    L.emu_set_const.argtypes = [ctypes.POINTER(CmModel), vp, ci, ci]
-    return L
-
-
 def _pelvis(pod):
     return pod.root_body[0]
 
 
-def emu_scan(pod, qpos, offsets, scan_range=RANGE, blocks=None, hfield=None, stride=0, index=None, nterrain=0, env0=0, n=None, grid=0,
-             out=None, warn=None):
-    """The emulated kernel -> (values [nenv][P], warn [nenv]).  hfield: float32, one grid / nenv grids / a bank; blocks: per-env
-    parameter blocks whose geometry the scan reads (the model is then told to, like a batch that has randomised geometry)."""
-    nenv, npts = qpos.shape[0], offsets.shape[0]
-    n = nenv - env0 if n is None else n
-    offsets = np.ascontiguousarray(offsets, dtype=np.float64)
-    qpos = np.ascontiguousarray(qpos, dtype=np.float64)
-    out = np.full((nenv, npts), np.nan) if out is None else out
-    warn = np.zeros(nenv, dtype=np.int32) if warn is None else warn
-    model = CmModel.from_buffer_copy(pod)
-    model.env_geom = 1 if blocks is not None else 0
-    p = lambda a: None if a is None else a.ctypes.data
-    index = None if index is None else np.ascontiguousarray(index, dtype=np.int32)
-    rc = _emu().emu_height_scan(ctypes.byref(model), None if blocks is None else ctypes.addressof(blocks), env0, n, grid, p(offsets), npts,
-                                _pelvis(pod), scan_range, p(qpos), qpos.shape[1], p(out), out.shape[1], p(hfield), stride, p(index), nterrain, p(warn))
-    assert rc == 0
-    return out, warn
+def emu_scan(pod, qpos, offsets, scan_range=RANGE, **kw):
+    """The emulated kernel -> (values [nenv][P], warn [nenv]) (emu_py.height_scan), from the pelvis."""
+    return emu_py.height_scan(pod, qpos, offsets, _pelvis(pod), scan_range, **kw)
 
 
 def _yaw_quat(a):
@@ -83,7 +59,7 @@ def _blocks(pod, gp, gq):
     params = gc.own_params(pod, nenv)
     params["geom_pos"], params["geom_quat"] = gp.reshape(nenv, -1).copy(), gq.reshape(nenv, -1).copy()
     blocks = gc.new_blocks(pod, nenv, params)
-    _emu().emu_set_const(ctypes.byref(pod), ctypes.addressof(blocks), nenv, SETCONST_GEOMETRY)
+    emu_py.set_const(pod, blocks, nenv, SETCONST_GEOMETRY)
     return blocks
 
 
@@ -284,12 +260,9 @@ def test_scanned_surface_is_the_one_the_narrow_phase_collides_with(built, kind):
 
 # ------------------------------------------------------------------ 4. the terrain index in the step kernel ----
 def _run_terrain(pod, state, nsub, hfield, stride, index=None, nterrain=0):
-    p = lambda a: None if a is None else a.ctypes.data
-    index = None if index is None else np.ascontiguousarray(index, dtype=np.int32)
-    rc = _emu().emu_phys_run_terrain(ctypes.byref(pod), state.nenv, nsub, p(state.qpos), p(state.qvel), p(state.qacc_warmstart), p(state.time),
-                                     p(state.ctrl), p(state.qacc), p(state.sensordata), p(state.actuator_velocity), p(state.warn), p(state.info),
-                                     p(hfield), stride, p(index), nterrain)
-    assert rc == 0
+    state.hfield, state.hfield_stride, state.nterrain = hfield, stride, nterrain
+    state.hfield_index = None if index is None else np.ascontiguousarray(index, dtype=np.int32)
+    state.step(nsub)
 
 
 def _fresh(hf, nenv):
@@ -324,9 +297,7 @@ def test_stepping_on_a_bank_equals_stepping_on_the_same_grid_as_the_envs_own(bui
     n = pod.hfield_nrow * pod.hfield_ncol
     bank = _step_bank(pod, 3)
     index = np.array([2, 0, 1, 2], dtype=np.int32)
-    L = _emu()
-    L.emu_fast_rows(1 if fast else 0); L.emu_two_waves(1 if fast else 0); L.emu_chunks(2 if fast else 1)
-    try:
+    with emu_py.settings(fast_rows=1 if fast else 0, two_waves=1 if fast else 0, chunks=2 if fast else 1):
         a, b = _fresh(hf, nenv), _fresh(hf, nenv)
         own = np.ascontiguousarray(bank[index]).reshape(-1)
         for _ in range(6):
@@ -340,13 +311,11 @@ def test_stepping_on_a_bank_equals_stepping_on_the_same_grid_as_the_envs_own(bui
         for _ in range(6):
             _run_terrain(pod, c, 50, bank.reshape(-1), n, bad, len(bank))
             _run_terrain(pod, d, 50, bank.reshape(-1), n, np.clip(bad, 0, len(bank) - 1), len(bank))
-        bit = L.emu_warn_bit(0)
+        bit = emu_py.lib().emu_warn_bit(0)
         assert bit == P.WARN_TERRAIN_INDEX == 32
         assert list(c.warn & bit) == [bit, bit, 0, bit] and not (d.warn & bit).any()
         c.warn &= ~np.int32(bit)
         assert _same(c, d)
-    finally:
-        L.emu_fast_rows(0); L.emu_two_waves(0); L.emu_chunks(1)
 
 
 def test_no_index_is_todays_entry_point_bit_for_bit(built):
@@ -382,7 +351,7 @@ def test_tilted_height_field_geom_is_left_out_and_flagged(built):
     got, warn = emu_scan(pod, qpos, offsets, blocks=_blocks(pod, gp, gq), hfield=grid.reshape(-1))
     want, near, tilted = tc.scan(pod, qpos, offsets, RANGE, gp, gq, np.tile(grid, (nenv, 1, 1)))
     assert list(tilted) == [False, True, False, True]
-    bit = _emu().emu_warn_bit(1)
+    bit = emu_py.lib().emu_warn_bit(1)
     assert bit == P.WARN_SCAN_TILTED == 64 and list(warn) == [0, bit, 0, bit]
     tc.compare(got, want, near)
     assert np.all(got[1] == RANGE) and np.all(got[3] == RANGE)      # no other static geom in this model: a miss everywhere
