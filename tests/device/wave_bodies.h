@@ -1,17 +1,27 @@
 /*
- * wave_bodies.h -- TEST-ONLY bodies that exercise the wavefront primitives (wave.h) and the kernel's small numerical
- * helpers (pk_math.h, pk_factor_solve.h) one at a time, written against wv:: and ck:: exactly as the step kernel is.
+ * wave_bodies.h -- TEST-ONLY bodies that exercise, one at a time and written against wv:: and ck:: exactly as the step
+ * kernel is:
+ *   - the wavefront primitives of wave.h (sums, DPP moves, readlane / writelane, shuffles, ballot, the matrix core, max_raw,
+ *     the reciprocal and reciprocal-square-root seeds);
+ *   - the elementary functions of pk_math.h (normalize4_fast, normalize3_fast, sincos_reduced / sincos_bounded);
+ *   - all of pk_factor_solve.h: fast_rcp, the two L^T D L factorisations in both forms (factor_pair_in_registers for the
+ *     run-time topology, factor_pair_by_height for Cassie-32 and the packed tray model, interleaved and split), the packed rows
+ *     read back as the kernel stages them (stage_factor_row / stage_factor_h of pk_stages.h) into solve_forward /
+ *     solve_backward, and one sweep of pgs_rows and of pgs_rows_fast at the three row counts the kernel instantiates.
+ * Not covered here: wide_solve and the convergence logic around the sweeps (they need the step kernel's shared state).
  *
  * The same source is compiled twice: for gfx950 with the product's flags (wave_check.hip: one workgroup of one wave per
  * trial) and into the CPU wave emulator (tests/emu/emu_runtime.cpp: the body runs through the emulator's rendezvous
  * scheduler).  tests/wave_check.py loads either and tests/test_wave_primitives.py compares both with exact references.
  *
  * A body gets its trial's slice of the buffers: input k of lane l is in[64 k + l], output k of lane l is out[64 k + l].
- * WAVE_CHECK_BODIES lists every body as X(name, inputs per lane, outputs per lane).
+ * WAVE_CHECK_BODIES lists every body as X(name, inputs per lane, outputs per lane).  The bodies of WAVE_CHECK_AUX_BODIES take
+ * a third argument: a read-only block of bytes every trial of a call shares (wc::FactorAux: the model the factorisations read).
  */
 #ifndef CASSIE_WAVE_BODIES_H
 #define CASSIE_WAVE_BODIES_H
 
+#include <cstddef>
 #include <cstring>
 
 #define WAVE_CHECK_BODIES(X) \
@@ -30,9 +40,157 @@
     X(fast_rcp, 1, 1)        \
     X(normalize4_fast, 4, 4) \
     X(normalize3_fast, 3, 4) \
-    X(sincos, 1, 4)
+    X(sincos, 1, 4)          \
+    X(solve_rt, 2 * 40 + 3, 2)     \
+    X(solve_cassie, 2 * 32 + 3, 2) \
+    X(solve_tray, 2 * 40 + 3, 2)   \
+    X(pgs_guarded32, 32 + 5, 3)    \
+    X(pgs_guarded48, 48 + 5, 3)    \
+    X(pgs_guarded64, 64 + 5, 3)    \
+    X(pgs_fast32, 32 + 5, 2)       \
+    X(pgs_fast48, 48 + 5, 2)       \
+    X(pgs_fast64, 64 + 5, 2)
+
+#define WAVE_CHECK_AUX_BODIES(X)                                                       \
+    X(factor_rt, 2 * 40, (wc::factor_set_rows<40, ck::TopoRuntime>()))                \
+    X(factor_cassie, 2 * 32, (2 * wc::factor_set_rows<32, ck::TopoCassie32>()))       \
+    X(factor_tray, 2 * 40, (2 * wc::factor_set_rows<40, ck::TopoCassieTray38>()))
 
 namespace wc {
+
+/* what the factorisations read of a model: the auxiliary block of the factor_* bodies.  P = the model's own parameter block. */
+struct FactorAux { cm_model_t model; double h; };
+/* the part of EnvShared the factorisations and the solves' staging touch: LDS on the device, one static block in the emulator
+ * (whose trials run one after the other) */
+template <int NVP, class TOPO>
+struct FactorShared {
+    double Lp[ck::LPack<TOPO, NVP>::count], LHp[ck::LPack<TOPO, NVP>::count];
+    double dinv[NVP], dinvH[NVP], rsd[NVP];
+};
+/* NaN into every word, so that a slot nobody wrote shows (LDS is not initialised, and the emulator's block is the last trial's) */
+template <class SH> WV_DEVICE void poison(SH &S) {
+    double *p = (double *)&S;
+    wv::sync();
+    for (int i = wv::lane(); i < (int)(sizeof(SH) / sizeof(double)); i += 64) p[i] = __builtin_nan("");
+    wv::sync();
+}
+/* one set of a factor body's outputs, in rows of 64: Lp, LHp (rows_of_pack each), dinv, dinvH, rsd, col[NVP], colh[NVP] */
+template <int NVP, class TOPO> constexpr int rows_of_pack() { return (ck::LPack<TOPO, NVP>::count + 63) / 64; }
+template <int NVP, class TOPO> constexpr int factor_set_rows() { return 2 * rows_of_pack<NVP, TOPO>() + 3 + 2 * NVP; }
+template <int NVP, class TOPO, class SH>
+WV_DEVICE void factor_write(const SH &S, const double (&col)[NVP], const double (&colh)[NVP], double *out) {
+    constexpr int C = ck::LPack<TOPO, NVP>::count, R = rows_of_pack<NVP, TOPO>();
+    const int l = wv::lane();
+    wv::sync();
+    for (int i = l; i < C; i += 64) { out[i] = S.Lp[i]; out[R * 64 + i] = S.LHp[i]; }
+    if (l < NVP) { out[2 * R * 64 + l] = S.dinv[l]; out[(2 * R + 1) * 64 + l] = S.dinvH[l]; out[(2 * R + 2) * 64 + l] = S.rsd[l]; }
+#pragma unroll
+    for (int i = 0; i < NVP; ++i) { out[(2 * R + 3 + i) * 64 + l] = col[i]; out[(2 * R + 3 + NVP + i) * 64 + l] = colh[i]; }
+}
+/* the two matrices, one column per lane: inputs i and NVP + i of lane j are M[i][j] and (M + hB)[i][j] less their diagonal
+ * terms, i >= j (the rest is never read) */
+template <int NVP> WV_DEVICE void factor_read(const double *in, double (&col)[NVP], double (&colh)[NVP]) {
+    const int l = wv::lane();
+#pragma unroll
+    for (int i = 0; i < NVP; ++i) { col[i] = in[i * 64 + l]; colh[i] = in[(NVP + i) * 64 + l]; }
+}
+/* factor_pair_in_registers on the run-time topology: nv, the ancestor masks, armature and damping are the aux model's.  The
+ * factors stay in col / colh (entry (k, j) in col[k] of lane j); Lp / LHp of the output set stay NaN. */
+WV_DEVICE void factor_rt(const double *in, double *out, const void *aux) {
+    WV_SHARED FactorShared<40, ck::TopoRuntime> S;
+    const FactorAux *a = (const FactorAux *)aux;
+    const ck::ModelPtr m = (ck::ModelPtr)&a->model;
+    const ck::ParamPtr P = (ck::ParamPtr)&m->params;
+    double col[40], colh[40];
+    factor_read<40>(in, col, colh);
+    poison(S);
+    ck::factor_pair_in_registers<40, ck::TopoRuntime>(m, P, a->h, col, colh, wv::lane(), m->nv, S.dinv, S.rsd, S.dinvH);
+    factor_write<40, ck::TopoRuntime>(S, col, colh, out);
+}
+/* factor_pair_by_height: both factorisations interleaved (the first output set), then, on a fresh copy of the inputs and a
+ * poisoned block, that of M followed by that of M + hB as the two-wave form runs them (the second set) */
+template <int NVP, class TOPO> WV_DEVICE void factor_static(const double *in, double *out, const void *aux) {
+    WV_SHARED FactorShared<NVP, TOPO> S;
+    const FactorAux *a = (const FactorAux *)aux;
+    const ck::ModelPtr m = (ck::ModelPtr)&a->model;
+    const ck::ParamPtr P = (ck::ParamPtr)&m->params;
+    const double h = a->h;
+    const int l = wv::lane();
+    double col[NVP], colh[NVP];
+    factor_read<NVP>(in, col, colh);
+    poison(S);
+    ck::factor_pair_by_height<NVP, TOPO, 2>(m, P, h, S, col, colh, l);
+    factor_write<NVP, TOPO>(S, col, colh, out);
+    factor_read<NVP>(in, col, colh);
+    poison(S);
+    ck::factor_pair_by_height<NVP, TOPO, 0>(m, P, h, S, col, colh, l);
+    ck::factor_pair_by_height<NVP, TOPO, 1>(m, P, h, S, col, colh, l);
+    factor_write<NVP, TOPO>(S, col, colh, out + factor_set_rows<NVP, TOPO>() * 64);
+}
+WV_DEVICE void factor_cassie(const double *in, double *out, const void *aux) { factor_static<32, ck::TopoCassie32>(in, out, aux); }
+WV_DEVICE void factor_tray(const double *in, double *out, const void *aux) { factor_static<40, ck::TopoCassieTray38>(in, out, aux); }
+
+/* solve_forward on z with the factor of inputs 0 .. NVP - 1, solve_backward on w with that of inputs NVP .. 2 NVP - 1 (entry
+ * (k, j) of a unit-triangular factor = input k of lane j, as the factorisations leave it; parked in Lp / LHp the way they park
+ * it, and staged into the lane's row / column the way the kernel stages it); then z, w, nv (read by the run-time form only) */
+template <int NVP, class TOPO> WV_DEVICE void solve_body(const double *in, double *out) {
+    typedef ck::LPack<TOPO, NVP> LP;
+    WV_SHARED FactorShared<NVP, TOPO> S;
+    const int l = wv::lane();
+    const int nv = TOPO::is_static ? TOPO::nv : (int)wv::readlane(in[(2 * NVP + 2) * 64 + l], 0);
+    poison(S);
+#pragma unroll
+    for (int k = 0; k < NVP; ++k) {
+        const int at = LP::row_slot(k, l);
+        S.Lp[at] = in[k * 64 + l];
+        S.LHp[at] = in[(NVP + k) * 64 + l];
+    }
+    wv::sync();
+    const bool isdof = l < nv;
+    double lrow[NVP], lcol[NVP], lrowh[NVP];
+    ck::stage_factor_row<NVP, TOPO>(S, l, isdof, lrow);
+    ck::stage_factor_h<NVP, TOPO, 0>(S, l, isdof, nv, lcol, lrowh);
+    out[l] = ck::solve_forward<NVP, TOPO>(in[2 * NVP * 64 + l], lrow, l, nv);
+    out[64 + l] = ck::solve_backward<NVP, TOPO>(in[(2 * NVP + 1) * 64 + l], lcol, l, nv);
+}
+WV_DEVICE void solve_rt(const double *in, double *out) { solve_body<40, ck::TopoRuntime>(in, out); }
+WV_DEVICE void solve_cassie(const double *in, double *out) { solve_body<32, ck::TopoCassie32>(in, out); }
+WV_DEVICE void solve_tray(const double *in, double *out) { solve_body<40, ck::TopoCassieTray38>(in, out); }
+
+/* one sweep of the projected Gauss-Seidel chain, lane = row, in the scaled domain the solve stage hands it: inputs 0 .. N - 1
+ * are the lane's brow, then nrows (the same in every lane), Aii, flo, f, sres */
+template <int N> WV_DEVICE void pgs_guarded(const double *in, double *out) {
+    const int l = wv::lane();
+    double brow[N];
+#pragma unroll
+    for (int t = 0; t < N; ++t) brow[t] = in[t * 64 + l];
+    const int nrows = (int)wv::readlane(in[N * 64 + l], 0); /* wave-uniform, in a scalar register as the kernel's is */
+    const double Aii = in[(N + 1) * 64 + l], flo = in[(N + 2) * 64 + l];
+    double f = in[(N + 3) * 64 + l], sres = in[(N + 4) * 64 + l], improvement = 0;
+    ck::pgs_rows<0, N>(brow, nrows, l, Aii, 0.5 * Aii, flo, f, sres, improvement);
+    out[l] = f;
+    out[64 + l] = sres;
+    out[128 + l] = improvement;
+}
+template <int N> WV_DEVICE void pgs_fast(const double *in, double *out) {
+    const int l = wv::lane();
+    double brow[N];
+#pragma unroll
+    for (int t = 0; t < N; ++t) brow[t] = in[t * 64 + l];
+    const int nrows = (int)wv::readlane(in[N * 64 + l], 0); /* wave-uniform, in a scalar register as the kernel's is */
+    const double flo = in[(N + 2) * 64 + l], f = in[(N + 3) * 64 + l];
+    double sres = in[(N + 4) * 64 + l], mys = 0;
+    ck::pgs_rows_fast<0, N>(brow, nrows, l, flo - f, sres, mys);
+    out[l] = sres;
+    out[64 + l] = mys;
+}
+static_assert(ck::FAST_ROWS + 1 == 32 && ck::FAST_ROWS_TRAY + 1 == 48 && ck::NROW == 64, "the row counts the kernel instantiates the sweeps at");
+WV_DEVICE void pgs_guarded32(const double *in, double *out) { pgs_guarded<32>(in, out); }
+WV_DEVICE void pgs_guarded48(const double *in, double *out) { pgs_guarded<48>(in, out); }
+WV_DEVICE void pgs_guarded64(const double *in, double *out) { pgs_guarded<64>(in, out); }
+WV_DEVICE void pgs_fast32(const double *in, double *out) { pgs_fast<32>(in, out); }
+WV_DEVICE void pgs_fast48(const double *in, double *out) { pgs_fast<48>(in, out); }
+WV_DEVICE void pgs_fast64(const double *in, double *out) { pgs_fast<64>(in, out); }
 
 /* the wave-uniform sum, stored by every lane */
 WV_DEVICE void wave_sum(const double *in, double *out) {
@@ -170,7 +328,31 @@ WV_DEVICE void sincos(const double *in, double *out) {
 extern "C" int wc_shape(const char *name, int *nin, int *nout) {
 #define WC_SHAPE(n, i, o) if (!strcmp(name, #n)) { *nin = i; *nout = o; return 0; }
     WAVE_CHECK_BODIES(WC_SHAPE)
+    WAVE_CHECK_AUX_BODIES(WC_SHAPE)
 #undef WC_SHAPE
+    return -1;
+}
+/* (host) the size of the auxiliary block a factor_* body reads, and where h sits in it */
+extern "C" unsigned long wc_sizeof_factor_aux(void) { return sizeof(wc::FactorAux); }
+extern "C" unsigned long wc_offsetof_factor_aux_h(void) { return offsetof(wc::FactorAux, h); }
+/* (host) the three dof trees (which: 0 = run-time at 40 dofs, 1 = Cassie-32, 2 = the packed tray model): the padded size and the
+ * words of a packed factor, the ancestor mask and elimination height of dof k (0 for the run-time tree: the model's own), and
+ * the slot of entry (k, i) in Lp / LHp, -1 where the row keeps none */
+extern "C" int wc_tree_size(int which, int *nvp, int *nv, int *count) {
+    if (which == 0) { *nvp = 40; *nv = 0; *count = ck::LPack<ck::TopoRuntime, 40>::count; }
+    else if (which == 1) { *nvp = 32; *nv = ck::TopoCassie32::nv; *count = ck::LPack<ck::TopoCassie32, 32>::count; }
+    else if (which == 2) { *nvp = 40; *nv = ck::TopoCassieTray38::nv; *count = ck::LPack<ck::TopoCassieTray38, 40>::count; }
+    else return -1;
+    return 0;
+}
+extern "C" unsigned long long wc_tree_mask(int which, int k) {
+    return which == 1 ? (k >= 0 && k < 32 ? ck::TopoCassie32::table[k] : 0ull) : which == 2 ? (k >= 0 && k < 40 ? ck::TopoCassieTray38::table[k] : 0ull) : 0ull;
+}
+extern "C" int wc_tree_slot(int which, int k, int i) {
+    if (k < 0 || i < 0 || i >= k) return -1;
+    if (which == 0) return k < 40 ? ck::LPack<ck::TopoRuntime, 40>::idx(k, i) : -1;
+    if (which == 1) return k < 32 ? ck::LPack<ck::TopoCassie32, 32>::idx(k, i) : -1;
+    if (which == 2) return k < 40 && ck::LPack<ck::TopoCassieTray38, 40>::has(k, i) ? ck::LPack<ck::TopoCassieTray38, 40>::idx(k, i) : -1;
     return -1;
 }
 #endif

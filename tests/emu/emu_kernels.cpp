@@ -202,3 +202,19 @@ static int wc_run(void (*body)(const double *, double *), const double *in, doub
 #define WC_ENTRY(name, nin, nout) \
     extern "C" int wc_##name(const double *in, double *out, int ntrial) { return wc_run(wc::name, in, out, ntrial, nin, nout); }
 WAVE_CHECK_BODIES(WC_ENTRY)
+/* ... and those that read an auxiliary block every trial of the call shares */
+static const void *g_wc_aux;
+static void (*g_wc_aux_body)(const double *, double *, const void *);
+static void wc_aux_trial() { g_wc_aux_body(g_wc_in + (size_t)wv::env_id() * g_wc_nin * 64, g_wc_out + (size_t)wv::env_id() * g_wc_nout * 64, g_wc_aux); }
+static int wc_aux_run(void (*body)(const double *, double *, const void *), const double *in, double *out, int ntrial, int nin, int nout,
+                      const void *aux, unsigned long aux_bytes) {
+    if (!aux || aux_bytes < sizeof(wc::FactorAux)) return 1; /* (hipErrorInvalidValue, as the device's launcher answers) */
+    g_wc_aux_body = body; g_wc_aux = aux; g_wc_in = in; g_wc_out = out; g_wc_nin = nin; g_wc_nout = nout;
+    emu::run_grid(wc_aux_trial, ntrial);
+    return 0;
+}
+#define WC_AUX_ENTRY(name, nin, nout)                                                                                    \
+    extern "C" int wc_##name(const double *in, double *out, int ntrial, const void *aux, unsigned long aux_bytes) {     \
+        return wc_aux_run(wc::name, in, out, ntrial, nin, nout, aux, aux_bytes);                                         \
+    }
+WAVE_CHECK_AUX_BODIES(WC_AUX_ENTRY)
