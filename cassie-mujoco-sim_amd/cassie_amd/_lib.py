@@ -144,6 +144,10 @@ def _declare(L):
         L.phys_batch_set_terrain.argtypes = [vp, vp, c.c_int, c.c_int, c.c_int, vp]
         L.phys_batch_scan_configure.argtypes = [vp, vp, c.c_int, c.c_int, c.c_double]
         L.phys_batch_height_scan.argtypes = [vp, c.c_int, c.c_int, vp]
+    if hasattr(L, "phys_batch_depth_image"):   # (absent from older variant builds selected with CASSIE_LIB)
+        L.phys_batch_depth_configure.argtypes = [vp, c.c_int, vp, vp, c.c_int, c.c_int, c.c_double, c.c_double, c.c_double]
+        L.phys_batch_depth_bind_pose.argtypes = [vp, vp]
+        L.phys_batch_depth_image.argtypes = [vp, c.c_int, c.c_int, vp]
     if hasattr(L, "phys_batch_download_progress"):   # (absent from older variant builds selected with CASSIE_LIB)
         L.phys_batch_download_progress.argtypes = [vp, vp]
     L.phys_batch_set_all_outputs_every_substep.argtypes = [vp, c.c_int]

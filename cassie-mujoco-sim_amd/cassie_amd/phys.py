@@ -15,7 +15,7 @@ from ._lib import CmDriveState, CmEnvParams, CmEpisodeRules, CmModel, MODEL_DIR,
 # field ids (enum in cassie_phys.h)
 (F_QPOS, F_QVEL, F_QACC_WARMSTART, F_TIME, F_CTRL, F_QFRC_APPLIED, F_XFRC_APPLIED, F_QACC, F_SENSORDATA,
  F_ACTUATOR_VELOCITY, F_XPOS, F_XQUAT, F_PD_PTARGET, F_PD_KP, F_PD_KD, F_BODY_CFRC, F_DRIVE_CMD, F_MEAS, F_PD_DTARGET,
- F_PD_TORQUE, F_DERIVED, F_QM, F_HEIGHT_SCAN) = range(23)
+ F_PD_TORQUE, F_DERIVED, F_QM, F_HEIGHT_SCAN, F_DEPTH) = range(24)
 
 # layout of the derived block F_DERIVED (CM_DRV_* in cm_model.h); MAXV = CM_MAXV
 MAXV = 40
@@ -34,6 +34,7 @@ WARN_CHUNK_PLACEMENT = 16   # a chunk of a stepping launch found its predecessor
 WARN_TERRAIN_INDEX = 32     # the env's terrain index lay outside the bank and was clamped to it
 WARN_SCAN_TILTED = 64       # height scan: the env's height-field geom is tilted out of the world's z axis and was left out
 SCAN_MAXPOINTS = 1024
+DEPTH_MAXPIXELS = 16384
 
 # per-env physical parameters (CM_P_* in cm_model.h): what Batch.randomize takes
 (P_BODY_MASS, P_BODY_IPOS, P_BODY_INERTIA, P_DOF_DAMPING, P_GEOM_FRICTION,
@@ -164,7 +165,7 @@ class Batch:
         return lib().phys_batch_device_ptr(self._h, field)
 
     def bind(self, field, device_ptr, row_stride=None):
-        """Aliases a field to caller-owned HBM; `row_stride` (doubles, qpos / qvel / sensordata / the height scan only) lets the field be a
+        """Aliases a field to caller-owned HBM; `row_stride` (doubles, qpos / qvel / sensordata / the height scan / the depth image only) lets the field be a
         column block of a wider tensor, e.g. one [nenv][nq + nv + nsensordata] observation block."""
         rc = (lib().phys_batch_bind(self._h, field, device_ptr) if row_stride is None
               else lib().phys_batch_bind_strided(self._h, field, device_ptr, int(row_stride)))
@@ -318,6 +319,40 @@ class Batch:
         n = self.nenv - env0 if n is None else n
         if lib().phys_batch_height_scan(self._h, int(env0), int(n), stream) != 0:
             raise RuntimeError("height_scan failed: " + (lib().phys_last_error() or b"").decode())
+
+    def configure_depth(self, body, cam_pos, cam_quat, width, height, fovy_deg, near, far):
+        """The depth camera: rigidly mounted on `body` (a child of the world: Cassie's pelvis) at cam_pos [3], cam_quat [4] (w, x, y, z) in
+        the body's frame, looking along -z of its own frame with +x right and +y up (MuJoCo's convention); `height` rows of `width`
+        pixels (width * height <= DEPTH_MAXPIXELS), vertical field of view fovy_deg in degrees, 0 < near < far.  Sizes F_DEPTH to
+        height * width doubles per env, row-major, row 0 at the top (bind a tensor after this call)."""
+        p, q = np.ascontiguousarray(cam_pos, dtype=np.float64), np.ascontiguousarray(cam_quat, dtype=np.float64)
+        if p.shape != (3,) or q.shape != (4,) or not np.linalg.norm(q) > 0:
+            raise ValueError("configure_depth: cam_pos [3] and a non-zero cam_quat [4]")
+        if int(width) < 1 or int(height) < 1 or int(width) * int(height) > DEPTH_MAXPIXELS:
+            raise ValueError("configure_depth: 1 <= width, height and width * height <= %d" % DEPTH_MAXPIXELS)
+        if not 0 < float(fovy_deg) < 180:
+            raise ValueError("configure_depth: the field of view must lie in (0, 180) degrees")
+        if not 0 < float(near) < float(far):
+            raise ValueError("configure_depth: 0 < near < far")
+        if not 0 < int(body) < self.pod.nbody:
+            raise ValueError("configure_depth: no such body")
+        if lib().phys_batch_depth_configure(self._h, int(body), p.ctypes.data, q.ctypes.data, int(width), int(height),
+                                            float(np.radians(float(fovy_deg))), float(near), float(far)) != 0:
+            raise ValueError("configure_depth failed: " + (lib().phys_last_error() or b"").decode())
+
+    def bind_depth_pose(self, device_ptr):
+        """Per-env camera extrinsics: float64 [nenv][7] (pos, quat; normalised by the kernel) in HBM, e.g. a torch tensor's data_ptr(), in
+        the place of configure_depth's cam_pos / cam_quat; None returns to the shared pose."""
+        if lib().phys_batch_depth_bind_pose(self._h, device_ptr) != 0:
+            raise RuntimeError("bind_depth_pose failed: " + (lib().phys_last_error() or b"").decode())
+
+    def depth_image(self, env0=0, n=None, stream=None):
+        """One launch on `stream` (default: the batch's own), in order with the step launches there: F_DEPTH of envs [env0, env0 + n) =
+        per pixel the depth along the optical axis of the nearest static collision geom (plane, box, height field) in [near, far], `far`
+        where the ray meets none."""
+        n = self.nenv - env0 if n is None else n
+        if lib().phys_batch_depth_image(self._h, int(env0), int(n), stream) != 0:
+            raise RuntimeError("depth_image failed: " + (lib().phys_last_error() or b"").decode())
 
     def set_pd_mode(self, on=True):
         lib().phys_batch_set_pd_mode(self._h, 1 if on else 0)

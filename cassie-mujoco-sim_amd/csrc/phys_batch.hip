@@ -20,6 +20,7 @@
 
 #include "cassie_phys.h"
 #include "device_mem.h"
+#include "depth_kernel.h"
 #include "small_kernels.h"
 #include "step_launch.h"
 
@@ -55,6 +56,10 @@ struct phys_batch {
     DevBuf<double> d_scan_offsets;
     int scan_points = 0, scan_body = 0;
     double scan_range = 0;
+    /* the depth image (phys_batch_depth_configure): the camera, and the caller's per-env extrinsics when bound (phys_batch_depth_bind_pose) */
+    int depth_width = 0, depth_height = 0, depth_body = 0;
+    double depth_tan_half = 0, depth_near = 0, depth_far = 0, depth_cam_pos[3] = {0, 0, 0}, depth_cam_quat[4] = {1, 0, 0, 0};
+    DevBuf<const double> d_depth_pose;
     hipStream_t stream = nullptr;
     hipStream_t recent_streams[4] = {nullptr, nullptr, nullptr, nullptr}; /* streams of the most recent launches (callers may pass
                                        their own, and ranges of one batch may be in flight on several at once) */
@@ -448,7 +453,7 @@ static void note_field_in_use(phys_batch *b, int field) {
 /* rows [env0, env0 + n) of a field between a dense host array and HBM (dense, or strided when the field is a column
  * block of a caller-owned tensor), asynchronously on the batch's stream */
 static bool copy_rows(phys_batch *b, int field, void *host, int env0, int n, bool to_device, const char *what) {
-    if (!b->d_field[field]) { phys_set_last_error("this field is allocated by phys_batch_derive (PHYS_F_HEIGHT_SCAN: phys_batch_scan_configure); call it first"); return false; }
+    if (!b->d_field[field]) { phys_set_last_error("this field is allocated by phys_batch_derive (PHYS_F_HEIGHT_SCAN: phys_batch_scan_configure, PHYS_F_DEPTH: phys_batch_depth_configure); call it first"); return false; }
     const size_t row = (size_t)b->dim[field], st = (size_t)b->stride[field];
     double *dev = b->d_field[field] + st * env0;
     if (n == 0) return true;
@@ -519,13 +524,14 @@ phys_batch_t *phys_batch_create(const cm_model_t *model, int nenv, int device) {
     const int d[PHYS_F_COUNT] = {model->nq, model->nv, model->nv, 1, model->nu, model->nv, model->nbody * 6,
                                  model->nv, model->nsensordata, model->nu, model->nbody * 3, model->nbody * 4,
                                  model->nu, model->nu, model->nu, model->nbody * 3,
-                                 model->nu + 1, CM_MEAS_DIM, model->nu, model->nu, CM_DRV_DIM, model->nv * model->nv, 0};
+                                 model->nu + 1, CM_MEAS_DIM, model->nu, model->nu, CM_DRV_DIM, model->nv * model->nv, 0, 0};
     const size_t n = (size_t)nenv;
     bool ok = true;
     for (int f = 0; f < PHYS_F_COUNT; ++f) {
         b->dim[f] = d[f]; b->stride[f] = d[f];
         if (f == PHYS_F_DERIVED || f == PHYS_F_QM) continue; /* large and optional: allocated by the first phys_batch_derive */
         if (f == PHYS_F_HEIGHT_SCAN) continue;              /* sized and allocated by phys_batch_scan_configure */
+        if (f == PHYS_F_DEPTH) continue;                    /* ... by phys_batch_depth_configure */
         ok = ok && b->d_field[f].alloc(n * (d[f] > 0 ? d[f] : 1), true, "field");
     }
     ok = ok && b->d_models.alloc(1, false, "model");
@@ -721,13 +727,14 @@ int phys_batch_bind(phys_batch_t *b, int field, void *device_ptr) {
 int phys_batch_bind_strided(phys_batch_t *b, int field, void *device_ptr, int row_stride) {
     if (!b || !device_ptr || field < 0 || field >= PHYS_F_COUNT) return -1;
     if (row_stride != b->dim[field]) {
-        const bool may = field == PHYS_F_QPOS || field == PHYS_F_QVEL || field == PHYS_F_SENSORDATA || field == PHYS_F_HEIGHT_SCAN;
+        const bool may = field == PHYS_F_QPOS || field == PHYS_F_QVEL || field == PHYS_F_SENSORDATA || field == PHYS_F_HEIGHT_SCAN || field == PHYS_F_DEPTH;
         if (!may || row_stride < b->dim[field]) {
-            phys_set_last_error("phys_batch_bind_strided: only qpos / qvel / sensordata / the height scan take a row stride, and it must be >= the field's dim");
+            phys_set_last_error("phys_batch_bind_strided: only qpos / qvel / sensordata / the height scan / the depth image take a row stride, and it must be >= the field's dim");
             return -1;
         }
     }
     if (field == PHYS_F_HEIGHT_SCAN && b->scan_points <= 0) { phys_set_last_error("phys_batch_bind: configure the scan first (phys_batch_scan_configure sizes PHYS_F_HEIGHT_SCAN)"); return -1; }
+    if (field == PHYS_F_DEPTH && b->depth_width <= 0) { phys_set_last_error("phys_batch_bind: configure the depth image first (phys_batch_depth_configure sizes PHYS_F_DEPTH)"); return -1; }
     (void)hipSetDevice(b->device);
     /* no stream synchronisation: launches already queued keep the pointers they were given, and hipFree of the
      * replaced buffer waits for the device by itself */
@@ -987,15 +994,19 @@ int phys_batch_set_terrain(phys_batch_t *b, const int *ids, int on_device, int e
 }
 
 /* ------------------------------------------------ the height scan ---- */
+/* the body a scan pattern or a camera hangs on: a child of the world whose pose follows from qpos alone */
+static bool body_pose_from_qpos(const phys_batch *b, int body) {
+    const cm_model_t &m = b->host_model;
+    if (body <= 0 || body >= m.nbody) return false;
+    const int rt = m.body_kin[body].rot_type;
+    return m.kin_simple && m.body_parentid[body] == 0 && b->model_stride == 0 && (rt == CM_JNT_BALL || rt == CM_JNT_FREE || rt == -1);
+}
 int phys_batch_scan_configure(phys_batch_t *b, const double *offsets_xy, int npoints, int body, double range) {
     if (!b || !offsets_xy || npoints <= 0 || npoints > ck::SCAN_MAXPOINTS || !(range > 0)) {
         phys_set_last_error("phys_batch_scan_configure: 1 .. 1024 points and a positive range");
         return -1;
     }
-    const cm_model_t &m = b->host_model;
-    const int rt = body > 0 && body < m.nbody ? m.body_kin[body].rot_type : CM_JNT_HINGE;
-    if (body <= 0 || body >= m.nbody || !m.kin_simple || m.body_parentid[body] != 0 || b->model_stride != 0 ||
-        (rt != CM_JNT_BALL && rt != CM_JNT_FREE && rt != -1)) {
+    if (!body_pose_from_qpos(b, body)) {
         phys_set_last_error("phys_batch_scan_configure: the body must be a child of the world whose joints are slides and at most a ball or free joint (a shared kin_simple model)");
         return -1;
     }
@@ -1031,6 +1042,69 @@ int phys_batch_height_scan(phys_batch_t *b, int env0, int n, void *stream) {
     hipStream_t s = launch_stream(b, stream);
     hipLaunchKernelGGL(ck::cassie_scan_kernel, dim3((unsigned)(n < ck::SCAN_GRID ? n : ck::SCAN_GRID)), dim3(WV_WAVE), 0, s, io);
     return hip_ok(hipGetLastError(), "cassie_scan_kernel launch") ? 0 : -1;
+}
+
+/* ------------------------------------------------ the depth image ---- */
+int phys_batch_depth_configure(phys_batch_t *b, int body, const double *cam_pos, const double *cam_quat, int width, int height, double fovy,
+                               double znear, double zfar) {
+    if (!b || !cam_pos || !cam_quat || width < 1 || height < 1 || (long long)width * height > ck::DEPTH_MAXPIXELS) {
+        phys_set_last_error("phys_batch_depth_configure: an image of 1 .. 16384 pixels and a camera pose");
+        return -1;
+    }
+    if (!(fovy > 0 && fovy < 3.14159265358979323846) || !(znear > 0 && znear < zfar)) {
+        phys_set_last_error("phys_batch_depth_configure: 0 < fovy < pi (radians) and 0 < near < far");
+        return -1;
+    }
+    const double qn = cam_quat[0] * cam_quat[0] + cam_quat[1] * cam_quat[1] + cam_quat[2] * cam_quat[2] + cam_quat[3] * cam_quat[3];
+    if (!(qn > 0)) { phys_set_last_error("phys_batch_depth_configure: the camera's quaternion is zero"); return -1; }
+    if (!body_pose_from_qpos(b, body)) {
+        phys_set_last_error("phys_batch_depth_configure: the body must be a child of the world whose joints are slides and at most a ball or free joint (a shared kin_simple model)");
+        return -1;
+    }
+    (void)hipSetDevice(b->device);
+    if (!quiesce(b)) return -1;
+    /* the field takes the image's size: a buffer of the batch's own of the new size (a caller's binding is dropped: bind again) */
+    DevBuf<double> out;
+    if (!out.alloc((size_t)width * (size_t)height * (size_t)b->nenv, true, "depth image")) return -1;
+    b->d_field[PHYS_F_DEPTH] = std::move(out);
+    b->dim[PHYS_F_DEPTH] = width * height; b->stride[PHYS_F_DEPTH] = width * height;
+    b->depth_width = width; b->depth_height = height; b->depth_body = body;
+    b->depth_tan_half = tan(0.5 * fovy); b->depth_near = znear; b->depth_far = zfar;
+    for (int k = 0; k < 3; ++k) b->depth_cam_pos[k] = cam_pos[k];
+    for (int k = 0; k < 4; ++k) b->depth_cam_quat[k] = cam_quat[k];
+    return 0;
+}
+int phys_batch_depth_bind_pose(phys_batch_t *b, const void *device_ptr) {
+    if (!b) return -1;
+    (void)hipSetDevice(b->device);
+    /* (as phys_batch_bind: launches already queued keep the pointer they were given) */
+    b->d_depth_pose.borrow((const double *)device_ptr);
+    return 0;
+}
+int phys_batch_depth_image(phys_batch_t *b, int env0, int n, void *stream) {
+    if (!b) return -1;
+    if (b->depth_width <= 0 || !b->d_field[PHYS_F_DEPTH]) { phys_set_last_error("phys_batch_depth_image: call phys_batch_depth_configure first"); return -1; }
+    if (!range_ok(b, env0, n)) { phys_set_last_error("phys_batch_depth_image: env range out of bounds"); return -1; }
+    (void)hipSetDevice(b->device);
+    if (n == 0) return 0;
+    ck::DepthIO io;
+    memset(&io, 0, sizeof io);
+    io.models = b->d_models; io.model_stride = b->model_stride; io.envparams = b->d_envparams;
+    io.env0 = env0; io.n = n; io.body = b->depth_body; io.width = b->depth_width; io.height = b->depth_height;
+    io.tan_half = b->depth_tan_half; io.znear = b->depth_near; io.zfar = b->depth_far;
+    for (int k = 0; k < 3; ++k) io.cam_pos[k] = b->depth_cam_pos[k];
+    for (int k = 0; k < 4; ++k) io.cam_quat[k] = b->depth_cam_quat[k];
+    io.pose = b->d_depth_pose;
+    io.qpos = b->d_field[PHYS_F_QPOS]; io.sq = b->stride[PHYS_F_QPOS];
+    io.out = b->d_field[PHYS_F_DEPTH]; io.sout = b->stride[PHYS_F_DEPTH];
+    io.hfield = b->d_hfield; io.hfield_stride = b->hfield_stride;
+    if (b->nterrain > 0) { io.hfield_index = b->d_terrain_index; io.hfield_nterrain = b->nterrain; }
+    io.warn = b->d_warn;
+    const int T = ck::DEPTH_TILE;
+    const long long jobs = (long long)n * (((b->depth_width + T - 1) / T) * ((b->depth_height + T - 1) / T));
+    hipStream_t s = launch_stream(b, stream);
+    hipLaunchKernelGGL(ck::cassie_depth_kernel, dim3((unsigned)(jobs < ck::DEPTH_GRID ? jobs : ck::DEPTH_GRID)), dim3(WV_WAVE), 0, s, io);
+    return hip_ok(hipGetLastError(), "cassie_depth_kernel launch") ? 0 : -1;
 }
 
 int phys_batch_sync(phys_batch_t *b) {

@@ -591,6 +591,47 @@ WV_GLOBAL void __launch_bounds__(WV_WAVE) cassie_episode_kernel(EpisodeIO io) {
     }
 }
 
+/* The world pose of a body that is a child of the world in a kin_simple model, from the env's qpos alone -- up to CM_MAXSLIDE slides and
+ * a ball or free joint, whose quaternion is normalised here, as in the step kernel's kinematics stage (the height scan and the depth
+ * image both start from it: no forward pass) */
+WV_DEVICE void static_body_pose(ModelPtr m, int body, const double *q, double *bp, double *bq) {
+    const auto *kr = &m->body_kin[body];
+    for (int k = 0; k < 3; ++k) bp[k] = kr->pos[k];
+    for (int k = 0; k < 4; ++k) bq[k] = kr->quat[k];
+    for (int sl = 0; sl < kr->nslide; ++sl) {
+        const double d = q[kr->slide_qadr[sl]] - kr->slide_ref[sl];
+        for (int k = 0; k < 3; ++k) bp[k] += kr->slide_axis_p[sl][k] * d;
+    }
+    if (kr->rot_type == CM_JNT_BALL || kr->rot_type == CM_JNT_FREE) {
+        const int qa = kr->rot_qadr, qo = kr->rot_type == CM_JNT_FREE ? qa + 3 : qa;
+        double qj[4] = {q[qo], q[qo + 1], q[qo + 2], q[qo + 3]}, q0[4] = {bq[0], bq[1], bq[2], bq[3]}, R[9], r[3];
+        normalize4(qj);
+        if (kr->rot_type == CM_JNT_FREE) for (int k = 0; k < 3; ++k) bp[k] = q[qa + k];
+        mulquat(bq, q0, qj);
+        const double jp[3] = {kr->rot_pos[0], kr->rot_pos[1], kr->rot_pos[2]};
+        quat2mat(R, bq);
+        mulmatvec3(r, R, jp);
+        for (int k = 0; k < 3; ++k) bp[k] = bp[k] + kr->rot_pos_p[k] - r[k];
+    }
+}
+/* The world pose (position gp, rotation R, row-major) of geom g of a body welded to the world: the geom's own pose from PG (the env's
+ * block or the model's), composed with the static bodies between it and the world */
+WV_DEVICE void static_geom_pose(ModelPtr m, ParamPtr PG, int g, double *gp, double *R) {
+    for (int k = 0; k < 3; ++k) gp[k] = PG->geom_pos[g][k];
+    for (int k = 0; k < 9; ++k) R[k] = PG->geom_mat[g][k];
+    for (int a = m->geom_bodyid[g]; a > 0; a = m->body_parentid[a]) {
+        double Rn[9], pn[3];
+        double Rb[9];
+        for (int k = 0; k < 9; ++k) Rb[k] = m->body_mat[a][k];
+        for (int r_ = 0; r_ < 3; ++r_) {
+            for (int c = 0; c < 3; ++c) Rn[3 * r_ + c] = Rb[3 * r_] * R[c] + Rb[3 * r_ + 1] * R[3 + c] + Rb[3 * r_ + 2] * R[6 + c];
+            pn[r_] = m->body_pos[a][r_] + (Rb[3 * r_] * gp[0] + Rb[3 * r_ + 1] * gp[1] + Rb[3 * r_ + 2] * gp[2]);
+        }
+        for (int k = 0; k < 9; ++k) R[k] = Rn[k];
+        for (int k = 0; k < 3; ++k) gp[k] = pn[k];
+    }
+}
+
 /* The height scan (phys_batch_height_scan, include/cassie_phys.h), one wave per env, lanes over the scan points (a loop for more than
  * 64): point j of the pattern, given in the HEADING frame of a body -- origin at the body's world x, y, turned about world z by the
  * yaw of the body's world quaternion -- is the world point (X, Y); the env's value for it is clamp(z_body - S(X, Y), -range, range),
@@ -626,24 +667,8 @@ WV_GLOBAL void __launch_bounds__(WV_WAVE) cassie_scan_kernel(ScanIO io) {
         const ModelPtr m = (ModelPtr)(io.models + (size_t)env * io.model_stride);
         const ParamPtr PG = (io.envparams && m->env_geom) ? (ParamPtr)(io.envparams + (size_t)env) : (ParamPtr)&m->params;
         const double *q = io.qpos + (size_t)env * io.sq;
-        /* the body's world pose from qpos (wave-uniform) */
-        const auto *kr = &m->body_kin[io.body];
-        double bp[3] = {kr->pos[0], kr->pos[1], kr->pos[2]}, bq[4] = {kr->quat[0], kr->quat[1], kr->quat[2], kr->quat[3]};
-        for (int sl = 0; sl < kr->nslide; ++sl) {
-            const double d = q[kr->slide_qadr[sl]] - kr->slide_ref[sl];
-            for (int k = 0; k < 3; ++k) bp[k] += kr->slide_axis_p[sl][k] * d;
-        }
-        if (kr->rot_type == CM_JNT_BALL || kr->rot_type == CM_JNT_FREE) {
-            const int qa = kr->rot_qadr, qo = kr->rot_type == CM_JNT_FREE ? qa + 3 : qa;
-            double qj[4] = {q[qo], q[qo + 1], q[qo + 2], q[qo + 3]}, q0[4] = {bq[0], bq[1], bq[2], bq[3]}, R[9], r[3];
-            normalize4(qj);
-            if (kr->rot_type == CM_JNT_FREE) for (int k = 0; k < 3; ++k) bp[k] = q[qa + k];
-            mulquat(bq, q0, qj);
-            const double jp[3] = {kr->rot_pos[0], kr->rot_pos[1], kr->rot_pos[2]};
-            quat2mat(R, bq);
-            mulmatvec3(r, R, jp);
-            for (int k = 0; k < 3; ++k) bp[k] = bp[k] + kr->rot_pos_p[k] - r[k];
-        }
+        double bp[3], bq[4];
+        static_body_pose(m, io.body, q, bp, bq);                  /* (wave-uniform) */
         const double ys = 2.0 * (bq[0] * bq[3] + bq[1] * bq[2]), yc = 1.0 - 2.0 * (bq[2] * bq[2] + bq[3] * bq[3]);
         const double yn = sqrt(ys * ys + yc * yc);
         const double cy = yn > 0.0 ? yc / yn : 1.0, sy = yn > 0.0 ? ys / yn : 0.0;
@@ -661,19 +686,7 @@ WV_GLOBAL void __launch_bounds__(WV_WAVE) cassie_scan_kernel(ScanIO io) {
                 const int gb = m->geom_bodyid[g], gt = m->geom_type[g];
                 if (m->body_weldid[gb] != 0 || (gt != CM_GEOM_PLANE && gt != CM_GEOM_BOX && gt != CM_GEOM_HFIELD)) continue;
                 double gp[3], R[9];
-                for (int k = 0; k < 3; ++k) gp[k] = PG->geom_pos[g][k];
-                for (int k = 0; k < 9; ++k) R[k] = PG->geom_mat[g][k];
-                for (int a = gb; a > 0; a = m->body_parentid[a]) { /* (a static body between the geom and the world) */
-                    double Rn[9], pn[3];
-                    double Rb[9];
-                    for (int k = 0; k < 9; ++k) Rb[k] = m->body_mat[a][k];
-                    for (int r_ = 0; r_ < 3; ++r_) {
-                        for (int c = 0; c < 3; ++c) Rn[3 * r_ + c] = Rb[3 * r_] * R[c] + Rb[3 * r_ + 1] * R[3 + c] + Rb[3 * r_ + 2] * R[6 + c];
-                        pn[r_] = m->body_pos[a][r_] + (Rb[3 * r_] * gp[0] + Rb[3 * r_ + 1] * gp[1] + Rb[3 * r_ + 2] * gp[2]);
-                    }
-                    for (int k = 0; k < 9; ++k) R[k] = Rn[k];
-                    for (int k = 0; k < 3; ++k) gp[k] = pn[k];
-                }
+                static_geom_pose(m, PG, g, gp, R);
                 const double dx = X - gp[0], dy = Y - gp[1];
                 bool has = false;
                 double z = 0.0;

@@ -87,6 +87,8 @@ enum { PHYS_F_QPOS, PHYS_F_QVEL, PHYS_F_QACC_WARMSTART, PHYS_F_TIME, PHYS_F_CTRL
        PHYS_F_DERIVED,    /* [CM_DRV_DIM]: the derived block of phys_batch_derive (layout: CM_DRV_* in cm_model.h) */
        PHYS_F_QM,         /* [nv * nv]: dense joint-space inertia matrix (mj_fullM role), written by phys_batch_derive */
        PHYS_F_HEIGHT_SCAN, /* [npoints]: the height scan of phys_batch_height_scan (sized by phys_batch_scan_configure) */
+       PHYS_F_DEPTH,      /* [height * width], row-major, row 0 at the top: the depth image of phys_batch_depth_image (sized by
+                             phys_batch_depth_configure) */
        PHYS_F_COUNT };
 
 /* mj_makeData (reference :441-447) for nenv environments on HIP device `device`;
@@ -185,6 +187,46 @@ int phys_batch_set_terrain(phys_batch_t *b, const int *ids, int on_device, int e
  *                               conversion are the caller's. */
 int phys_batch_scan_configure(phys_batch_t *b, const double *offsets_xy, int npoints, int body, double range);
 int phys_batch_height_scan(phys_batch_t *b, int env0, int n, void *stream);
+/* The DEPTH IMAGE: what a body-mounted pinhole camera sees of the env's static collision geometry, one ray per pixel, on the device
+ * (the role of the reference's `egocentric` camera and cassie_vis_draw_depth, with no renderer and no OpenGL context).
+ *   phys_batch_depth_configure  the camera is rigidly mounted on `body` (the scan's restriction: a child of the world whose joints are
+ *                               slides and at most one ball or free joint, in a shared kin_simple model; its world pose is computed as
+ *                               the scan computes it, the joint quaternion normalised), at cam_pos[3], cam_quat[4] (w, x, y, z;
+ *                               normalised by the kernel) in the body's frame.  MuJoCo's camera convention: it looks along -z of its
+ *                               frame, +x is right, +y is up.  The image has `height` rows of `width` pixels, row 0 at the top,
+ *                               1 <= width, height and width * height <= 16384; fovy is the VERTICAL field of view in RADIANS;
+ *                               0 < near < far.  Sizes PHYS_F_DEPTH to width * height doubles per env, row-major, in a buffer of the
+ *                               batch's own (bind a tensor AFTER configuring; phys_batch_bind_strided takes a row stride for this
+ *                               field).  Waits for the batch's streams; reconfiguring is allowed.  -1 + phys_last_error() on failure.
+ *   phys_batch_depth_bind_pose  optional per-env extrinsics, [nenv][7] doubles in DEVICE memory (pos, quat; the quaternion is normalised
+ *                               by the kernel), indexed by the absolute env: they replace cam_pos / cam_quat for that env (camera-mount
+ *                               randomisation is one statement on a tensor).  NULL: back to the shared pose.
+ *   phys_batch_depth_image      one launch on `stream` (NULL: the batch's own), in order with the step launches there, for envs
+ *                               [env0, env0 + n).  Pixel (r, c) has the camera-frame direction
+ *                                   d = (a T (2 (c + 1/2) / width - 1), T (1 - 2 (r + 1/2) / height), -1),  T = tan(fovy / 2), a = width / height,
+ *                               NOT normalised, so the ray parameter t of o + t R d is the metric depth ALONG THE OPTICAL AXIS (what a
+ *                               linearised depth buffer holds).  The pixel's value is the smallest t in [near, far] at which the ray
+ *                               meets a static collision geom of the env, `far` where there is none; intersections at t < near are
+ *                               ignored, as a near plane clips them.  The geoms are those the scan sees -- on a body welded to the
+ *                               world (static parent bodies composed), poses the env's own once geometry is randomised (CM_P_GEOM_POS /
+ *                               CM_P_GEOM_QUAT), the model's otherwise:
+ *                                 plane         the crossing of the infinite plane, from either side;
+ *                                 box           slab test in the box's frame: the hit is at the entry t0; an origin inside the box
+ *                                               (t0 < near <= t1) gives `near`;
+ *                                 height field  the triangulated surface of the narrow phase, as in the scan (vertices on the grid scaled
+ *                                               by hfield_size, cells split into v00 v10 v01 and v11 v01 v10, at geom z + sz * grid), for
+ *                                               ANY pose of the geom, tilted included (the ray is taken into the geom's frame): the first
+ *                                               intersection with any triangle, from either face.  Side walls and the base below the
+ *                                               surface are not rendered; a ray outside the footprint misses.  The grid is the env's own
+ *                                               (shared, per env, or the bank's terrain of the env's index; an index outside the bank is
+ *                                               clamped and raises WARN_TERRAIN_INDEX).
+ *                               Spheres, capsules, cylinders and everything on moving bodies -- the robot's own legs, the tray and cube
+ *                               of cassie_tray_box -- are not seen.  Noise, history, fp32 conversion and inverse-depth encodings are the
+ *                               caller's.  A batch that never configures the depth image runs exactly as before. */
+int phys_batch_depth_configure(phys_batch_t *b, int body, const double *cam_pos, const double *cam_quat, int width, int height, double fovy,
+                               double znear, double zfar);
+int phys_batch_depth_bind_pose(phys_batch_t *b, const void *device_ptr);
+int phys_batch_depth_image(phys_batch_t *b, int env0, int n, void *stream);
 /* host <-> HBM copies of whole fields or of a row range [env0, env0 + n) */
 int phys_batch_upload(phys_batch_t *b, int field, const double *host, int env0, int n);
 int phys_batch_download(phys_batch_t *b, int field, double *host, int env0, int n);
@@ -198,7 +240,7 @@ int phys_batch_download_warn(phys_batch_t *b, int *host_warn, int *host_info /* 
 /* raw device pointer of a field (for torch / RCCL interop); bind replaces it with caller-owned HBM */
 void *phys_batch_device_ptr(phys_batch_t *b, int field);
 int phys_batch_bind(phys_batch_t *b, int field, void *device_ptr);
-/* same with a row stride in doubles (>= the field's dim) for PHYS_F_QPOS / QVEL / SENSORDATA / HEIGHT_SCAN, so that they can be
+/* same with a row stride in doubles (>= the field's dim) for PHYS_F_QPOS / QVEL / SENSORDATA / HEIGHT_SCAN / DEPTH, so that they can be
  * column blocks of ONE caller-owned [nenv][nq + nv + nsensordata] observation tensor -- the buffer an RCCL all-gather
  * sends as is; uploads / downloads of a strided field are 2-D copies */
 int phys_batch_bind_strided(phys_batch_t *b, int field, void *device_ptr, int row_stride);
