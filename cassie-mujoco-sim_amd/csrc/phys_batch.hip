@@ -23,16 +23,10 @@
 #include "depth_kernel.h"
 #include "small_kernels.h"
 #include "step_launch.h"
+#include "step_policy.h"
 
 void phys_set_last_error(const char *s);
 
-/* stepping launches of the fast instantiations in chunks (PhysIO::nchunk): chunks per env-launch, for launches of at least
- * CHUNK_MIN_ENVS envs (two jobs per workgroup slot: below that there is no queue whose end could be evened out) and chunks of at
- * least CHUNK_MIN_SUBSTEPS substeps */
-/* Defaults by measurement (profiles/round4/chunks_ab.txt): a launch over the whole batch has nothing to fill the end of its queue
- * with: 4 chunks (+7 %); launches over env ranges (phys_batch_step_range: other ranges' launches fill in) gain nothing from more
- * than 2 in steady state, and as much as the whole-batch launch when they stand alone between two synchronisations. */
-constexpr int DEFAULT_CHUNKS_WHOLE = 7 /* (round 6; 4 before: jobs of 7 substeps leave the shortest end of a queue, profiles/round6/one_stream_chunks.txt) */, DEFAULT_CHUNKS_RANGE = 2, CHUNK_MIN_ENVS = 2048, CHUNK_MIN_SUBSTEPS = 5;
 constexpr int DEFAULT_TRAY_WAVES = 2; /* the 40-dof model's default form (by measurement: round 5, 17.77 against 15.72 M with one wave, profiles/round5/tray_two_waves_ab.txt; round 4 had it at -7.5 %) */
 
 struct phys_batch {
@@ -71,28 +65,26 @@ struct phys_batch {
     DevBuf<cm_drive_state_t> d_drive; /* [nenv], allocated when a drive mode is first selected */
     bool use_pd_dtarget = false, use_pd_torque = false;
     DevBuf<long long> d_prof;
-    /* launch-order balancing (see ck::cassie_order_kernel) */
     bool all_outputs = false;       /* measurement aid: see PhysIO::all_outputs_every_substep */
+    DevBuf<cm_ext_t> d_ext;
+
+    /* ---- the launcher's (launch(): the rules are step_policy.h's, these are the settings they read and the state they keep) ---- */
+    bool fast_rows = true;          /* use the row-capped fast instantiation where one exists (phys_batch_set_fast_rows) */
+    int waves_per_env = 2;          /* two-wave form of the fast instantiations (phys_batch_set_waves_per_env) */
+    int waves_per_env_tray = DEFAULT_TRAY_WAVES; /* ... of the 40-dof instantiations (CASSIE_TRAY_TWO_WAVES=0/1 overrides the default: A/B aid) */
+    int inplace_mode = 2;           /* form of the two-wave fast kernel (phys_batch_set_inplace; ck::next_inplace) */
+    long long form_launches[2] = {0, 0};   /* stepping launches of the two-wave fast kernel in the plain / the in-place form (diagnostics) */
+    /* launch-order balancing (see ck::cassie_order_kernel) */
     bool balance = true;
     DevBuf<unsigned> d_cost, d_cost_wall; /* per-env span of the last launch in 64 shader clocks / in 100 MHz ticks */
-    DevBuf<int> d_order;
-    /* d_order holds a permutation of the env ids of every range it was last sorted for (the order kernel sorts one launch's
-     * range [env0, env0 + n) at a time) and the identity everywhere else.  A launch may use the array only for a range that is
-     * exactly one of these segments, or that lies wholly in identity territory: any other range would step envs outside itself
-     * and skip envs inside it.  launch() keeps the list and puts overlapping segments back to the identity first. */
-    struct OrderSeg { int env0, n, launches_since_sort; };
-    std::vector<OrderSeg> order_segs;
-    std::vector<int> order_ident;   /* 0 .. nenv - 1, the source of those resets */
-    DevBuf<cm_ext_t> d_ext;
-    /* per-kernel timing (phys_batch_kernel_timing): event pairs around the kernel of every stepping launch that does the work */
-    bool timing = false;
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_pool;
-    size_t ev_used = 0;
+    DevBuf<int> d_order;            /* a permutation of the env ids of every range it was last sorted for, the identity elsewhere */
+    std::vector<int> order_ident;   /* 0 .. nenv - 1, the source of the resets of retired ranges' segments */
+    ck::RangeTable ranges;          /* the env ranges stepping launches went over: their order segment, form, launches since a sort */
     DevBuf<int> d_progress;         /* [nenv] substeps completed by the row-capped fast instantiation (PhysIO::progress) */
     /* stepping launches of the fast instantiations in chunks (PhysIO::nchunk): chunks per env-launch asked for (1 = off), the
      * words the chunks of an env hand over through, and the tag of the last chunked launch */
-    int chunks = DEFAULT_CHUNKS_WHOLE, chunks_range = DEFAULT_CHUNKS_RANGE; /* (launches over the whole batch / over an env range) */
-    bool chunks_default = true;    /* nobody has asked for a chunk count: a range's SHORT launches go as three (see launch) */
+    int chunks = ck::DEFAULT_CHUNKS_WHOLE, chunks_range = ck::DEFAULT_CHUNKS_RANGE; /* (launches over the whole batch / over an env range) */
+    bool chunks_default = true;    /* nobody has asked for a chunk count: a range's SHORT launches go as three (ck::launch_chunks) */
     DevBuf<int> d_chunk_flag;
     int chunk_seq = 0;
     bool chunks_allowed = true;     /* (false: this device does not place workgroup w on XCD w % 8 -- launches stay in one piece) */
@@ -104,26 +96,15 @@ struct phys_batch {
     HostWords chunk_fault;
     bool chunk_fault_reported = false;
     /* the hand-over list (PhysIO::handover_list): env ids per range, [count, ticket] pairs indexed by a range's first env, and
-     * -- in pinned host memory the device writes -- the number of envs the last launch of a range handed over */
-    DevBuf<int> d_handover_list, d_handover_count;
-    HostWords handover_seen;
-    /* ... and the same for the second list: what the 63-row pass hands on to the 127-row pass (models on the Cassie dof tree) */
-    DevBuf<int> d_handover_list2, d_handover_count2;
-    HostWords handover_seen2;
-    bool fast_rows = true;          /* use the row-capped fast instantiation where one exists (phys_batch_set_fast_rows) */
-    /* Which form of the two-wave fast kernel a range's launches take (phys_batch_set_inplace): 0 = the kernel + the list-walking pass
-     * behind it, 1 = the kernel that finishes the substeps it cannot hold in place, 2 (default) = per range by what its recent launches
-     * needed.  The in-place form costs the default workload 1.8 % (both codes share one register allocation) and gains 8 - 24 % where
-     * envs leave the fast tier at all (profiles/round6/inplace_ab.txt): a range switches to it once a launch handed envs over
-     * and back after INPLACE_QUIET reports in a row in which no env needed the wider code.  h_handover_seen[env0] is the signal in both
-     * forms (the pass reports the list's length; in the in-place form the order kernel reports the kernel's count, or the run of
-     * reports without one -- counted on the device, in stream order, because the launcher may run far ahead of it). */
-    int inplace_mode = 2;
-    struct RangeForm { int env0; bool inplace; };
-    std::vector<RangeForm> range_forms;
-    long long form_launches[2] = {0, 0};   /* stepping launches of the two-wave fast kernel in the plain / the in-place form (diagnostics) */
-    int waves_per_env = 2;          /* two-wave form of the fast instantiations (phys_batch_set_waves_per_env) */
-    int waves_per_env_tray = DEFAULT_TRAY_WAVES; /* ... of the 40-dof instantiations (CASSIE_TRAY_TWO_WAVES=0/1 overrides the default: A/B aid) */
+     * -- in pinned host memory the device writes -- the number of envs the last launch of a range handed over; the same for the
+     * second list: what the 63-row pass hands on to the 127-row pass (models on the Cassie dof tree) */
+    DevBuf<int> d_handover_list, d_handover_count, d_handover_list2, d_handover_count2;
+    HostWords handover_seen, handover_seen2;
+    /* per-kernel timing (phys_batch_kernel_timing): event pairs around the kernel of every stepping launch that does the work */
+    bool timing = false;
+    std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_pool;
+    size_t ev_used = 0;
+
     DevBuf<double> d_scratch_out;    /* [nenv][nv + nsensordata + nu]: where phys_batch_forward_kinematics sends qacc / sensordata / actuator_velocity */
     /* episodes on the device (phys_batch_end_episodes): the rules, the per-env arrays PHYS_EP_* and the bank of start states */
     bool episodes = false;
@@ -140,8 +121,6 @@ static bool hip_ok(hipError_t e, const char *what) {
     fprintf(stderr, "cassie_phys: %s\n", msg.c_str());
     return false;
 }
-
-static bool stream_may_chunk(phys_batch *b, hipStream_t s);
 
 static ck::PhysIO make_io(phys_batch *b, int nsub, int integrate) {
     ck::PhysIO io;
@@ -229,22 +208,6 @@ static void fill_state_block(const phys_batch *b, IO &io) {
     io.drive = b->d_drive;
 }
 
-/* The launch-order array for the range [env0, env0 + n): returns the range's segment record (created if the range lies in
- * identity territory), after resetting every segment that overlaps the range without coinciding with it (stream-ordered
- * copies on the launch's stream; ranges in flight on other streams must not overlap this one anyway -- their state would race). */
-static phys_batch::OrderSeg *order_segment_for(phys_batch *b, int env0, int n, hipStream_t s) {
-    for (auto &g : b->order_segs) if (g.env0 == env0 && g.n == n) return &g;
-    for (size_t i = 0; i < b->order_segs.size();) {
-        const auto g = b->order_segs[i];
-        if (g.env0 < env0 + n && env0 < g.env0 + g.n) {
-            if (!hip_ok(hipMemcpyAsync(b->d_order + g.env0, b->order_ident.data() + g.env0, sizeof(int) * (size_t)g.n, hipMemcpyHostToDevice, s), "hipMemcpy(order reset)")) return nullptr;
-            b->order_segs.erase(b->order_segs.begin() + (long)i);
-        } else ++i;
-    }
-    b->order_segs.push_back({env0, n, 0});
-    return &b->order_segs.back();
-}
-
 /* The step kernel's instantiations per model family, by form (step_plan.h; null: the family has no such form).  Each is instantiated
  * explicitly in one of the kernels_*.hip translation units. */
 using ck::launch_step;
@@ -285,191 +248,10 @@ static const ck::StepLauncher *const FAMILY_FORMS[ck::FAMILY_COUNT] = {
     CASSIE_FORMS<0>, CASSIE_FORMS<ck::FEAT_HFIELD>, CASSIE_ALL_FORMS, TRAY_FORMS, TRAY_HFIELD_FORMS, GENERIC32_FORMS, GENERIC40_FORMS,
 };
 
-constexpr int SMALL_BATCH_NSUB = 4;  /* substeps per launch up to which a small batch skips the fast kernel + passes (three launches) for one instantiation alone */
-constexpr int SMALL_BATCH = 512;     /* envs up to which that holds (half the chip's workgroup slots) */
-
-/* The launch of the fast kernel over the range [env0, env0 + n) in chunks of at least CHUNK_MIN_SUBSTEPS substeps (PhysIO::nchunk,
- * chunk_seq, chunk_flag, chunk_fault), where the launch is long enough and the stream places workgroups round the XCDs */
-static void set_chunks(phys_batch *b, ck::PhysIO &io, int n, int nsub, hipStream_t s) {
-    io.nchunk = 1;
-    /* (n % 8: workgroup w runs on XCD w % 8, so the chunks of an env -- workgroups n apart -- share an XCD and its L2) */
-    if (!b->chunks_allowed || (n == b->nenv ? b->chunks : b->chunks_range) <= 1 || n < CHUNK_MIN_ENVS || n % 8 != 0 || nsub < 2 * CHUNK_MIN_SUBSTEPS ||
-        !stream_may_chunk(b, s))
-        return;
-    /* (round 6: a range's launch of 15 .. 25 substeps -- a consumer that fences every few substeps, the driver's 20-step regions --
-     * as three chunks instead of two: nothing fills the end of such a launch's queue, finer jobs shorten it, + 1.5 %; at 50
-     * substeps between fences three cost 0.6 %, profiles/round6/chunks3_ab.txt) */
-    const int range_chunks = b->chunks_default && nsub <= 25 ? 3 : b->chunks_range;
-    const int most = nsub / CHUNK_MIN_SUBSTEPS, asked = n == b->nenv ? b->chunks : range_chunks;
-    io.nchunk = asked < most ? asked : most;
-    if (b->chunk_seq >= (1 << 24)) { /* (the tag has 25 bits: start over once NOTHING is in flight on the device -- the words of
-                                       * envs in flight on a stream this batch does not remember must not be cleared under them --
-                                       * and the clearing itself is complete before the next chunk can publish) */
-        (void)hipDeviceSynchronize();
-        (void)hipMemsetAsync(b->d_chunk_flag, 0, sizeof(int) * (size_t)b->nenv, s);
-        (void)hipStreamSynchronize(s);
-        b->chunk_seq = 0;
-    }
-    io.chunk_seq = ++b->chunk_seq;
-    io.chunk_flag = b->d_chunk_flag;
-    io.chunk_fault = b->chunk_fault.dev();
-}
-
-/* The hand-over lists of the range [env0, env0 + n) and the grids of the passes that walk them: twice what the range's last launch
- * handed over (the launcher learns that a launch late, through host memory) plus 16, at most one workgroup per env; the 127-row pass
- * behind that one likewise, plus 8.  (A floor of 256 workgroups under both grids was measured: no gain on the prism workload, -0.6 %
- * on config 2, profiles/round5.) */
-static void range_lists(phys_batch *b, int env0, int n, bool wide, ck::HandoverLists &hl, ck::StepGrids &g) {
-    hl.list1 = b->d_handover_list; hl.count1 = b->d_handover_count + 2 * (size_t)env0; hl.seen1 = b->handover_seen.dev() + env0;
-    if (wide) { hl.list2 = b->d_handover_list2; hl.count2 = b->d_handover_count2 + 2 * (size_t)env0; hl.seen2 = b->handover_seen2.dev() + env0; }
-    const int seen = b->handover_seen.host()[env0], seen2 = wide ? b->handover_seen2.host()[env0] : 0;
-    const int seen12 = seen > seen2 ? seen : seen2; /* (the first pass is never smaller than the second: it feeds it) */
-    const long want = 2L * (seen12 > 0 ? seen12 : 0) + 16, want2 = 2L * (seen2 > 0 ? seen2 : 0) + 8;
-    g.mid = (unsigned)(want < n ? want : n);
-    g.wide = (unsigned)(want2 < n ? want2 : n);
-}
-
-/* Whether the two-wave fast kernel of the range starting at env0 takes its in-place form (see phys_batch::inplace_mode); auto_ok: the
- * order kernel runs behind the range's launches (auto mode needs it: it reports the in-place count) */
-static bool range_inplace(phys_batch *b, int env0, bool auto_ok, int *count1, hipStream_t s) {
-    constexpr int INPLACE_QUIET = 8;
-    phys_batch::RangeForm *rf = nullptr;
-    for (auto &r : b->range_forms) if (r.env0 == env0) rf = &r;
-    if (!rf) { b->range_forms.push_back({env0, false}); rf = &b->range_forms.back(); }
-    const bool was = rf->inplace;
-    /* the range's word in host memory: > 0 = env-launches the last reporting launch handed over (plain form: the pass behind the
-     * kernel writes it) or finished in place (the order kernel does); -k = the last k reports of the in-place form had none */
-    const int seen = *(volatile int *)(b->handover_seen.host() + env0);
-    if (b->inplace_mode != 2 || !auto_ok) rf->inplace = b->inplace_mode == 1;
-    else if (!rf->inplace) { if (seen > 0) rf->inplace = true; }
-    else if (seen <= -INPLACE_QUIET) rf->inplace = false;
-    if (was != rf->inplace) {
-        /* the first list's count word changes its meaning with the form: start the new form from zero (stream-ordered) */
-        (void)hipMemsetAsync(count1, 0, 2 * sizeof(int), s);
-        b->handover_seen.host()[env0] = 0;
-    }
-    ++b->form_launches[rf->inplace ? 1 : 0];
-    return rf->inplace;
-}
-
-static int launch(phys_batch *b, int nsub, int integrate, hipStream_t s, bool scratch_outputs = false, int env0 = 0, int n = -1) {
-    ck::PhysIO io = make_io(b, nsub, integrate);
-    if (n < 0) n = b->nenv;
-    io.env0 = env0; io.nenv = n;
-    phys_batch::OrderSeg *seg = nullptr;
-    if (io.order && !integrate) { io.order = nullptr; io.cost = nullptr; io.cost_wall = nullptr; } /* forward / read-out passes: one substep, nothing to balance (identity order) */
-    if (io.order) {
-        seg = order_segment_for(b, env0, n, s);
-        if (!seg) { io.order = nullptr; io.cost = nullptr; io.cost_wall = nullptr; }
-    }
-    if (scratch_outputs) {
-        /* a read-out pass: the step outputs the caller's fields hold (sensordata and actuator_velocity of the last STEP feed
-         * the encoder / motor models of the next one; qacc) stay as they are */
-        const cm_model_t &m = b->host_model;
-        io.qacc = b->d_scratch_out; io.sv = m.nv;
-        io.sensordata = b->d_scratch_out + (size_t)b->nenv * m.nv; io.ssd = m.nsensordata;
-        io.actuator_velocity = io.sensordata + (size_t)b->nenv * m.nsensordata;
-    }
-    note_stream(b, s);
-    hipEvent_t ev_after = nullptr;
-    if (b->timing && integrate) {
-        if (b->ev_used == b->ev_pool.size() && b->ev_pool.size() < 65536) { /* (launches beyond that between two queries go untimed) */
-            hipEvent_t a = nullptr, c = nullptr;
-            if (hipEventCreate(&a) == hipSuccess && hipEventCreate(&c) == hipSuccess) b->ev_pool.emplace_back(a, c);
-        }
-        if (b->ev_used < b->ev_pool.size()) {
-            (void)hipEventRecord(b->ev_pool[b->ev_used].first, s);
-            ev_after = b->ev_pool[b->ev_used].second;
-            ++b->ev_used;
-        }
-    }
-    const cm_model_t &hm = b->host_model;
-    /* the family, and the forms of this launch (step_plan.h) */
-    const ck::StepFamily fam = ck::pick_family(hm, b->generic_kernel);
-    const ck::StepLauncher *family = FAMILY_FORMS[fam];
-    ck::StepForms forms = {ck::FORM_ALONE, ck::FORM_ALONE, false, FAST_ROWS - 4};
-    /* (inplace_stay_rows: once in the 63-row code an env stays there until a substep needs at most FAST_ROWS - 4 rows again -- the
-     * margin keeps an env that hovers about the fast code's capacity from changing codes every substep) */
-    if (fam == ck::CASSIE || fam == ck::CASSIE_HFIELD) {
-        /* stepping launches go through the row-capped fast instantiation first; the 63-row pass behind it finishes the envs that met
-         * a substep with more rows, and -- for a model with the wide caps (CM_FLAG_HFPRISM) -- the 127-row pass behind that one what
-         * is left.  Forward / read-out passes take one instantiation alone, and so does a small batch stepping a few substeps per
-         * launch (somebody's control loop around a handful of envs): one launch instead of two or three -- a launch costs what four
-         * substeps' difference between the kernels saves */
-        forms.wide = hm.maxefc > CM_MAXEFC_NARROW;
-        if (!b->fast_rows || !integrate || io.ext || (n <= SMALL_BATCH && nsub <= SMALL_BATCH_NSUB))
-            /* (alone and a LARGE grid -- phys_batch_derive / forward passes of a whole batch, the fast kernel switched off -- with 63-row
-             * caps: the one-wave form, whose 421 registers leave room for four envs per CU; the two-wave 512-register form halves that
-             * and only pays where the chip is not full anyway, profiles/round6/alone_pass_ab.txt) */
-            forms.first = forms.wide ? ck::FORM_WIDE : n > SMALL_BATCH ? ck::FORM_ALONE : ck::FORM_ALONE_2W;
-        else if (b->waves_per_env == 2) { forms.first = ck::FORM_FAST_2W; forms.mid = ck::FORM_MID_WALK_2W; }
-        else forms.first = ck::FORM_FAST;     /* (behind it the one-wave 63-row pass looks every env's record up: FORM_ALONE) */
-    } else if (fam == ck::TRAY) {
-        /* the 40-dof model: a fast instantiation of 47 rows (the boxes resting on the tray take it to 32 .. 40 routinely) with the 63-row
-         * one behind it walking the list, both in the two-wave form by default (waves_per_env_tray) -- or the 63-row one alone */
-        const bool plain = integrate && !io.ext, two = plain && b->waves_per_env_tray == 2;
-        if (plain && b->fast_rows) { forms.first = two ? ck::FORM_FAST_2W : ck::FORM_FAST; forms.mid = two ? ck::FORM_MID_WALK_2W : ck::FORM_MID_WALK; }
-        else forms.first = two ? ck::FORM_ALONE_2W : ck::FORM_ALONE;
-    }
-    /* a fast kernel first: its record of completed substeps, its launch in chunks, the hand-over lists of the passes behind it, its form */
-    ck::HandoverLists hl = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    ck::StepGrids grids = {(unsigned)n, (unsigned)n, (unsigned)n};
-    if (ck::is_fast_form(forms.first)) {
-        io.progress = b->d_progress;
-        set_chunks(b, io, n, nsub, s);
-        range_lists(b, env0, n, forms.wide, hl, grids);
-        if (forms.first == ck::FORM_FAST_2W && family[ck::FORM_FAST_INPLACE] && range_inplace(b, env0, io.order && seg, hl.count1, s))
-            forms.first = ck::FORM_FAST_INPLACE;
-    }
-    const ck::StepPlan plan = ck::plan_step(io, forms, hl, grids);
-    for (int i = 0; i < plan.n; ++i) {
-        const ck::StepPass &p = plan.pass[i];
-        if (!family[p.form]) { (void)hip_ok(hipErrorInvalidDeviceFunction, "cassie_step_kernel launch (no instantiation of this form)"); return -1; }
-        family[p.form](p.grid, s, p.io);
-        if (!hip_ok(hipGetLastError(), "cassie_step_kernel launch")) return -1;
-        if (i == 0 && ev_after) (void)hipEventRecord(ev_after, s);   /* (the first kernel of the launch does the work: per-kernel timing) */
-    }
-    /* the next launch's order from this one's per-env cost: after every long launch, now and then after short ones.  (Round 6: "long" is
-     * more than 25 substeps, not 8 -- the sort is 20 - 25 us at the end of the launch's stream, 0.7 % of a fenced 20-substep launch, and the
-     * order itself is worth nothing either way since launches go in chunks: profiles/round6/launch_order_ab.txt.)  It reports the in-place
-     * count of the range when the in-place form ran. */
-    if (io.order && integrate && (nsub > 25 || ++seg->launches_since_sort >= 16)) {
-        seg->launches_since_sort = 0;
-        const bool inplace = forms.first == ck::FORM_FAST_INPLACE;
-        hipLaunchKernelGGL(ck::cassie_order_kernel, dim3(1), dim3(ck::ORDER_THREADS), 0, s, b->d_cost, b->d_order, n, env0,
-                           inplace ? hl.count1 : (int *)nullptr, inplace ? hl.seen1 : (volatile int *)nullptr);
-        if (!hip_ok(hipGetLastError(), "cassie_order_kernel launch")) return -1;
-    }
-    return 0;
-}
-
-/* optional inputs are handed to the kernel only once somebody uploaded or bound them */
-static void note_field_in_use(phys_batch *b, int field) {
-    if (field == PHYS_F_QFRC_APPLIED || field == PHYS_F_XFRC_APPLIED) b->use_applied = true;
-    if (field == PHYS_F_PD_DTARGET) b->use_pd_dtarget = true;
-    if (field == PHYS_F_PD_TORQUE) b->use_pd_torque = true;
-}
-
-/* rows [env0, env0 + n) of a field between a dense host array and HBM (dense, or strided when the field is a column
- * block of a caller-owned tensor), asynchronously on the batch's stream */
-static bool copy_rows(phys_batch *b, int field, void *host, int env0, int n, bool to_device, const char *what) {
-    if (!b->d_field[field]) { phys_set_last_error("this field is allocated by phys_batch_derive (PHYS_F_HEIGHT_SCAN: phys_batch_scan_configure, PHYS_F_DEPTH: phys_batch_depth_configure); call it first"); return false; }
-    const size_t row = (size_t)b->dim[field], st = (size_t)b->stride[field];
-    double *dev = b->d_field[field] + st * env0;
-    if (n == 0) return true;
-    if (st == row)
-        return hip_ok(to_device ? hipMemcpyAsync(dev, host, sizeof(double) * row * n, hipMemcpyHostToDevice, b->stream)
-                                : hipMemcpyAsync(host, dev, sizeof(double) * row * n, hipMemcpyDeviceToHost, b->stream), what);
-    return hip_ok(to_device ? hipMemcpy2DAsync(dev, sizeof(double) * st, host, sizeof(double) * row, sizeof(double) * row, n, hipMemcpyHostToDevice, b->stream)
-                            : hipMemcpy2DAsync(host, sizeof(double) * row, dev, sizeof(double) * st, sizeof(double) * row, n, hipMemcpyDeviceToHost, b->stream), what);
-}
-
-extern "C" {
-
 /* A launch in chunks hands an env's state from one workgroup to another through the L2 both share (wave.h: publish_global): the
  * chunks of an env are workgroups a multiple of 8 apart, and workgroup w runs on XCD w % 8.  That assignment is checked here, once
  * per batch of a size that could be chunked: a grid of 1024 workgroups reports where it ran. */
-__global__ void __launch_bounds__(128) cassie_xcd_probe_kernel(int *xcc) {
+extern "C" __global__ void __launch_bounds__(128) cassie_xcd_probe_kernel(int *xcc) {
     if (threadIdx.x == 0) xcc[blockIdx.x] = (int)(wv::hw_id() >> 32) & 7;
 }
 /* does the queue behind stream s place workgroup w on XCD w % 8 (in the sense that workgroups 8 apart share an XCD)?  A grid of 1024
@@ -502,6 +284,150 @@ static bool stream_may_chunk(phys_batch *b, hipStream_t s) {
     if (b->probed_streams.size() < 64) b->probed_streams.emplace_back(s, ok);
     return ok;
 }
+
+/* The launch of the fast kernel over n envs in chunks (PhysIO::nchunk, chunk_seq, chunk_flag, chunk_fault): as many as the policy
+ * gives a launch of this length (ck::launch_chunks), where the stream places workgroups round the XCDs -- asked last: the first
+ * question about a stream is a probe launch and a synchronisation */
+static void set_chunks(phys_batch *b, ck::PhysIO &io, int n, int nsub, hipStream_t s) {
+    const int nchunk = b->chunks_allowed ? ck::launch_chunks(n, b->nenv, nsub, b->chunks, b->chunks_range, b->chunks_default) : 1;
+    io.nchunk = 1;
+    if (nchunk <= 1 || !stream_may_chunk(b, s)) return;
+    io.nchunk = nchunk;
+    if (b->chunk_seq >= (1 << 24)) { /* (the tag has 25 bits: start over once NOTHING is in flight on the device -- the words of
+                                       * envs in flight on a stream this batch does not remember must not be cleared under them --
+                                       * and the clearing itself is complete before the next chunk can publish) */
+        (void)hipDeviceSynchronize();
+        (void)hipMemsetAsync(b->d_chunk_flag, 0, sizeof(int) * (size_t)b->nenv, s);
+        (void)hipStreamSynchronize(s);
+        b->chunk_seq = 0;
+    }
+    io.chunk_seq = ++b->chunk_seq;
+    io.chunk_flag = b->d_chunk_flag;
+    io.chunk_fault = b->chunk_fault.dev();
+}
+
+/* The first list's count word and the `seen` word of the range starting at env0 change their meaning with the form of the range's
+ * fast kernel (ck::LaunchRange): start the new form from zero (stream-ordered).  (The host's store to the seen word is not ordered
+ * against passes or order kernels of the old form still queued, which may write it after: that delays or repeats a change of form,
+ * the results are the same bits either way.) */
+static void reset_range_words(phys_batch *b, int env0, hipStream_t s) {
+    (void)hipMemsetAsync(b->d_handover_count + 2 * (size_t)env0, 0, 2 * sizeof(int), s);
+    b->handover_seen.host()[env0] = 0;
+}
+
+/* The record of the range [env0, env0 + n) of a stepping launch on stream s (ck::RangeTable::claim), after undoing, in stream order,
+ * what the records it retired stood for: their segment of the order array goes back to the identity, the words of one that was in
+ * the in-place form start over as a count and a ticket */
+static ck::LaunchRange *claim_range(phys_batch *b, int env0, int n, hipStream_t s) {
+    std::vector<ck::LaunchRange> retired;
+    ck::LaunchRange *range = b->ranges.claim(env0, n, retired);
+    for (const ck::LaunchRange &g : retired) {
+        if (b->d_order && !hip_ok(hipMemcpyAsync(b->d_order + g.env0, b->order_ident.data() + g.env0, sizeof(int) * (size_t)g.n, hipMemcpyHostToDevice, s), "hipMemcpy(order reset)")) return nullptr;
+        if (g.inplace) reset_range_words(b, g.env0, s);
+    }
+    return range;
+}
+
+/* per-kernel timing: records the event in front of a stepping launch and returns the one that goes behind its first kernel (or null) */
+static hipEvent_t timing_begin(phys_batch *b, hipStream_t s) {
+    if (b->ev_used == b->ev_pool.size() && b->ev_pool.size() < 65536) { /* (launches beyond that between two queries go untimed) */
+        hipEvent_t a = nullptr, c = nullptr;
+        if (hipEventCreate(&a) == hipSuccess && hipEventCreate(&c) == hipSuccess) b->ev_pool.emplace_back(a, c);
+    }
+    if (b->ev_used == b->ev_pool.size()) return nullptr;
+    (void)hipEventRecord(b->ev_pool[b->ev_used].first, s);
+    return b->ev_pool[b->ev_used++].second;
+}
+
+/* One launch: the PhysIO, the range's record, the policy's answers (step_policy.h), the plan (step_plan.h), its passes, the report */
+static int launch(phys_batch *b, int nsub, int integrate, hipStream_t s, bool scratch_outputs = false, int env0 = 0, int n = -1) {
+    ck::PhysIO io = make_io(b, nsub, integrate);
+    if (n < 0) n = b->nenv;
+    io.env0 = env0; io.nenv = n;
+    if (!integrate) { io.order = nullptr; io.cost = nullptr; io.cost_wall = nullptr; } /* forward / read-out passes: one substep, nothing to balance (identity order) */
+    if (scratch_outputs) {
+        /* a read-out pass: the step outputs the caller's fields hold (sensordata and actuator_velocity of the last STEP feed
+         * the encoder / motor models of the next one; qacc) stay as they are */
+        const cm_model_t &m = b->host_model;
+        io.qacc = b->d_scratch_out; io.sv = m.nv;
+        io.sensordata = b->d_scratch_out + (size_t)b->nenv * m.nv; io.ssd = m.nsensordata;
+        io.actuator_velocity = io.sensordata + (size_t)b->nenv * m.nsensordata;
+    }
+    note_stream(b, s);
+    /* the family, and the forms of this launch while its range is in the plain form */
+    const cm_model_t &hm = b->host_model;
+    const ck::StepFamily fam = ck::pick_family(hm, b->generic_kernel);
+    const ck::StepLauncher *family = FAMILY_FORMS[fam];
+    const bool has_inplace = family[ck::FORM_FAST_INPLACE] != nullptr;
+    auto forms_if = [&](bool inplace) {
+        return ck::launch_forms(fam, has_inplace, hm.maxefc, integrate, io.ext != nullptr, n, nsub, b->fast_rows, b->waves_per_env, b->waves_per_env_tray, inplace);
+    };
+    ck::StepForms forms = forms_if(false);
+    const bool fast = ck::is_fast_form(forms.first);
+    /* the range's record: of a stepping launch that uses the order array or a fast kernel (forward / read-out passes claim nothing) */
+    ck::LaunchRange *range = nullptr;
+    if (integrate && (io.order || fast) && !(range = claim_range(b, env0, n, s))) return -1;
+    const hipEvent_t ev_after = b->timing && integrate ? timing_begin(b, s) : nullptr;
+    /* a fast kernel first: its record of completed substeps, its launch in chunks, the hand-over lists of the passes behind it, its form */
+    ck::HandoverLists hl = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    ck::StepGrids grids = {(unsigned)n, (unsigned)n, (unsigned)n};
+    if (fast) {
+        io.progress = b->d_progress;
+        set_chunks(b, io, n, nsub, s);
+        hl.list1 = b->d_handover_list; hl.count1 = b->d_handover_count + 2 * (size_t)env0; hl.seen1 = b->handover_seen.dev() + env0;
+        if (forms.wide) { hl.list2 = b->d_handover_list2; hl.count2 = b->d_handover_count2 + 2 * (size_t)env0; hl.seen2 = b->handover_seen2.dev() + env0; }
+        const int seen = *(volatile int *)(b->handover_seen.host() + env0);
+        grids = ck::pass_grids(n, seen, forms.wide ? b->handover_seen2.host()[env0] : 0, forms.wide);
+        if (forms.first == ck::FORM_FAST_2W && has_inplace) {
+            const bool was = range->inplace;
+            range->inplace = ck::next_inplace(was, seen, b->inplace_mode, io.order != nullptr);
+            if (was != range->inplace) reset_range_words(b, env0, s);
+            ++b->form_launches[range->inplace ? 1 : 0];
+            forms = forms_if(range->inplace);
+        }
+    }
+    const ck::StepPlan plan = ck::plan_step(io, forms, hl, grids);
+    for (int i = 0; i < plan.n; ++i) {
+        const ck::StepPass &p = plan.pass[i];
+        if (!family[p.form]) { (void)hip_ok(hipErrorInvalidDeviceFunction, "cassie_step_kernel launch (no instantiation of this form)"); return -1; }
+        family[p.form](p.grid, s, p.io);
+        if (!hip_ok(hipGetLastError(), "cassie_step_kernel launch")) return -1;
+        if (i == 0 && ev_after) (void)hipEventRecord(ev_after, s);   /* (the first kernel of the launch does the work: per-kernel timing) */
+    }
+    /* the next launch's order from this one's per-env cost, when it is due (ck::order_kernel_due); it reports the in-place count of the
+     * range when the in-place form ran */
+    if (io.order && ck::order_kernel_due(nsub, ++range->launches_since_sort)) {
+        range->launches_since_sort = 0;
+        const bool inplace = forms.first == ck::FORM_FAST_INPLACE;
+        hipLaunchKernelGGL(ck::cassie_order_kernel, dim3(1), dim3(ck::ORDER_THREADS), 0, s, b->d_cost, b->d_order, n, env0,
+                           inplace ? hl.count1 : (int *)nullptr, inplace ? hl.seen1 : (volatile int *)nullptr);
+        if (!hip_ok(hipGetLastError(), "cassie_order_kernel launch")) return -1;
+    }
+    return 0;
+}
+
+/* optional inputs are handed to the kernel only once somebody uploaded or bound them */
+static void note_field_in_use(phys_batch *b, int field) {
+    if (field == PHYS_F_QFRC_APPLIED || field == PHYS_F_XFRC_APPLIED) b->use_applied = true;
+    if (field == PHYS_F_PD_DTARGET) b->use_pd_dtarget = true;
+    if (field == PHYS_F_PD_TORQUE) b->use_pd_torque = true;
+}
+
+/* rows [env0, env0 + n) of a field between a dense host array and HBM (dense, or strided when the field is a column
+ * block of a caller-owned tensor), asynchronously on the batch's stream */
+static bool copy_rows(phys_batch *b, int field, void *host, int env0, int n, bool to_device, const char *what) {
+    if (!b->d_field[field]) { phys_set_last_error("this field is allocated by phys_batch_derive (PHYS_F_HEIGHT_SCAN: phys_batch_scan_configure, PHYS_F_DEPTH: phys_batch_depth_configure); call it first"); return false; }
+    const size_t row = (size_t)b->dim[field], st = (size_t)b->stride[field];
+    double *dev = b->d_field[field] + st * env0;
+    if (n == 0) return true;
+    if (st == row)
+        return hip_ok(to_device ? hipMemcpyAsync(dev, host, sizeof(double) * row * n, hipMemcpyHostToDevice, b->stream)
+                                : hipMemcpyAsync(host, dev, sizeof(double) * row * n, hipMemcpyDeviceToHost, b->stream), what);
+    return hip_ok(to_device ? hipMemcpy2DAsync(dev, sizeof(double) * st, host, sizeof(double) * row, sizeof(double) * row, n, hipMemcpyHostToDevice, b->stream)
+                            : hipMemcpy2DAsync(host, sizeof(double) * row, dev, sizeof(double) * st, sizeof(double) * row, n, hipMemcpyDeviceToHost, b->stream), what);
+}
+
+extern "C" {
 
 phys_batch_t *phys_batch_create(const cm_model_t *model, int nenv, int device) {
     if (!model || nenv <= 0) { phys_set_last_error("phys_batch_create: bad arguments"); return nullptr; }
@@ -1310,7 +1236,7 @@ int phys_batch_set_fast_rows(phys_batch_t *b, int on) {
 int phys_batch_debug_inplace_ranges(const phys_batch_t *b) {
     if (!b) return -1;
     int k = 0;
-    for (const auto &r : b->range_forms) k += r.inplace ? 1 : 0;
+    for (const auto &r : b->ranges.ranges) k += r.inplace ? 1 : 0;
     return k;
 }
 
@@ -1372,7 +1298,7 @@ int phys_batch_debug_handover_pending(phys_batch_t *b) {
         if (!hip_ok(hipMemcpy(h.data(), d, sizeof(int) * h.size(), hipMemcpyDeviceToHost), "hand-over count download")) return -1;
         /* (a range in the in-place form keeps other things in its first list's words: the in-place count since the order kernel's last
          * report and the run of quiet reports) */
-        if (d == b->d_handover_count) for (const auto &r : b->range_forms) if (r.inplace) h[2 * (size_t)r.env0] = h[2 * (size_t)r.env0 + 1] = 0;
+        if (d == b->d_handover_count) for (const auto &r : b->ranges.ranges) if (r.inplace) h[2 * (size_t)r.env0] = h[2 * (size_t)r.env0 + 1] = 0;
         for (int v : h) total += v < 0 ? -(long)v : v;
     }
     return total > 0x7fffffff ? 0x7fffffff : (int)total;

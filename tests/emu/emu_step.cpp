@@ -1,14 +1,15 @@
 /*
  * emu_step.cpp -- TEST-ONLY: the step kernel on the wave emulator (tests/emu/wave.h, emu_runtime.cpp).  The one translation unit that
  * instantiates ck::cassie_step_kernel: the bodies, their tables by form (step_plan.h), the family of a model (ck::pick_family) and the
- * one function that fills PhysIO from a call's argument block and runs ck::plan_step's passes.
+ * one function that fills PhysIO from a call's argument block and runs ck::plan_step's passes.  The launcher's policy and range table
+ * (step_policy.h) are exported for tests at the end; the emulator's own launches do not go through them.
  */
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <vector>
 
-#include "step_plan.h"
+#include "step_policy.h"
 #include "emu_runtime.h"
 
 static ck::PhysIO g_io;
@@ -83,8 +84,9 @@ int emu::run_step(const emu_step_args &a, emu_step_result &r, cm_ext_t *ext) {
     const ck::StepFamily fam = ck::pick_family(*model, !ext && set.force_runtime_topology);
     const bool cassie32 = fam == ck::CASSIE || fam == ck::CASSIE_HFIELD || fam == ck::CASSIE_ALL, tray38 = fam == ck::TRAY;
     const EmuForm *bodies = FAMILY_BODIES[fam];
-    /* the forms, as phys_batch.hip picks them (with this call's settings): the row-capped fast instantiation for every env, then
-     * the passes behind it -- a list-walking one as ONE small grid (here: resume_grid workgroups) -- or one instantiation alone */
+    /* the forms, chosen by this call's settings alone (NOT by the launcher's policy, step_policy.h: a test must be able to force every
+     * form at a handful of envs): the row-capped fast instantiation for every env, then the passes behind it -- a list-walking one as
+     * ONE small grid (here: resume_grid workgroups) -- or one instantiation alone */
     ck::StepForms forms = {ck::FORM_ALONE, ck::FORM_ALONE, false, set.inplace_stay_rows};
     std::vector<int> progress, list, list2, chunk_flag;
     int count[2] = {0, 0}, count2[2] = {0, 0};
@@ -128,3 +130,32 @@ int emu::run_step(const emu_step_args &a, emu_step_result &r, cm_ext_t *ext) {
 extern "C" int emu_phys_run(const emu_step_args *args, emu_step_result *result) { return emu::run_step(*args, *result); }
 /* ck::pick_family (step_plan.h), for tests */
 extern "C" int emu_pick_family(const cm_model_t *model, int generic_only) { return ck::pick_family(*model, generic_only != 0); }
+/* the launcher's policy (step_policy.h), for tests: forms -> {first, mid, wide, stay_rows}, grids -> {envs, mid, wide} */
+extern "C" void emu_launch_forms(int fam, int has_inplace, int maxefc, int integrate, int ext, int n, int nsub, int fast_rows, int waves_per_env,
+                                 int waves_per_env_tray, int inplace, int *out) {
+    const ck::StepForms f = ck::launch_forms(fam, has_inplace != 0, maxefc, integrate, ext != 0, n, nsub, fast_rows != 0, waves_per_env, waves_per_env_tray, inplace != 0);
+    out[0] = f.first; out[1] = f.mid; out[2] = f.wide ? 1 : 0; out[3] = f.stay_rows;
+}
+extern "C" int emu_launch_chunks(int n, int nenv, int nsub, int chunks, int chunks_range, int chunks_default) {
+    return ck::launch_chunks(n, nenv, nsub, chunks, chunks_range, chunks_default != 0);
+}
+extern "C" void emu_pass_grids(int n, int seen1, int seen2, int wide, unsigned *out) {
+    const ck::StepGrids g = ck::pass_grids(n, seen1, seen2, wide != 0);
+    out[0] = g.envs; out[1] = g.mid; out[2] = g.wide;
+}
+extern "C" int emu_next_inplace(int was, int seen, int mode, int auto_ok) { return ck::next_inplace(was != 0, seen, mode, auto_ok != 0) ? 1 : 0; }
+extern "C" int emu_order_kernel_due(int nsub, int launches_since_sort) { return ck::order_kernel_due(nsub, launches_since_sort) ? 1 : 0; }
+extern "C" void emu_policy_defaults(int *out) { out[0] = ck::DEFAULT_CHUNKS_WHOLE; out[1] = ck::DEFAULT_CHUNKS_RANGE; }
+/* ck::RangeTable::claim on the caller's table: records [*nrec][4] = {env0, n, inplace, launches_since_sort} (room for one more), updated
+ * in place; retired [as many as there were records][4]; -> the index of the claimed record */
+extern "C" int emu_ranges_claim(int *records, int *nrec, int env0, int n, int *retired, int *nretired) {
+    ck::RangeTable t;
+    for (int i = 0; i < *nrec; ++i) t.ranges.push_back({records[4 * i], records[4 * i + 1], records[4 * i + 2] != 0, records[4 * i + 3]});
+    std::vector<ck::LaunchRange> gone;
+    const ck::LaunchRange *r = t.claim(env0, n, gone);
+    const auto put = [](int *to, const ck::LaunchRange &g) { to[0] = g.env0; to[1] = g.n; to[2] = g.inplace ? 1 : 0; to[3] = g.launches_since_sort; };
+    for (size_t i = 0; i < t.ranges.size(); ++i) put(records + 4 * i, t.ranges[i]);
+    for (size_t i = 0; i < gone.size(); ++i) put(retired + 4 * i, gone[i]);
+    *nrec = (int)t.ranges.size(); *nretired = (int)gone.size();
+    return (int)(r - t.ranges.data());
+}

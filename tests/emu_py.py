@@ -50,6 +50,10 @@ def lib():
         L.emu_phys_run.argtypes = [ctypes.POINTER(StepArgs), ctypes.POINTER(StepResult)]
         L.emu_derive.argtypes = [ctypes.POINTER(StepArgs), _vp, _vp, _vp, ctypes.POINTER(StepResult)]
         L.emu_pick_family.argtypes = [ctypes.POINTER(CmModel), _ci]
+        L.emu_launch_forms.argtypes, L.emu_launch_forms.restype = [_ci] * 11 + [_vp], None
+        L.emu_pass_grids.argtypes, L.emu_pass_grids.restype = [_ci] * 4 + [_vp], None
+        L.emu_policy_defaults.argtypes, L.emu_policy_defaults.restype = [_vp], None
+        L.emu_ranges_claim.argtypes = [_vp, _vp, _ci, _ci, _vp, _vp]
         L.emu_set_const.argtypes = [ctypes.POINTER(CmModel), _vp, _ci, _ci]
         L.emu_sizeof_envparams.restype = _ul
         L.emu_end_episodes.argtypes = ([ctypes.POINTER(CmModel), ctypes.POINTER(CmEpisodeRules)] + [_ci] * 4 + [_vp, _ci] * 3 + [_vp] * 13 +
@@ -167,6 +171,57 @@ class EmuBatch:
 def pick_family(pod, generic_only=False):
     """ck::pick_family (csrc/step_plan.h) -> the index of the family in ck::StepFamily."""
     return lib().emu_pick_family(ctypes.byref(pod), 1 if generic_only else 0)
+
+
+def launch_forms(fam, has_inplace=True, maxefc=63, integrate=1, ext=False, n=4096, nsub=50, fast_rows=True, waves_per_env=2,
+                 waves_per_env_tray=2, inplace=False):
+    """ck::launch_forms (csrc/step_policy.h) -> (first, mid, wide, stay_rows), the forms as indices in ck::StepForm."""
+    out = np.zeros(4, dtype=np.int32)
+    lib().emu_launch_forms(fam, int(has_inplace), maxefc, integrate, int(ext), n, nsub, int(fast_rows), waves_per_env, waves_per_env_tray,
+                           int(inplace), _ptr(out))
+    return int(out[0]), int(out[1]), bool(out[2]), int(out[3])
+
+
+def launch_chunks(n, nenv, nsub, chunks=None):
+    """ck::launch_chunks; chunks: what phys_batch_set_chunks was given, None: nobody asked (the defaults)."""
+    d = np.zeros(2, dtype=np.int32)
+    lib().emu_policy_defaults(_ptr(d))
+    whole, rng = (int(d[0]), int(d[1])) if chunks is None else (chunks, chunks)
+    return lib().emu_launch_chunks(n, nenv, nsub, whole, rng, 1 if chunks is None else 0)
+
+
+def pass_grids(n, seen1, seen2, wide):
+    """ck::pass_grids -> (mid, wide): the workgroups of the passes that walk the first / the second list."""
+    out = np.zeros(3, dtype=np.uint32)
+    lib().emu_pass_grids(n, seen1, seen2, int(wide), _ptr(out))
+    assert out[0] == n
+    return int(out[1]), int(out[2])
+
+
+def next_inplace(was, seen, mode, auto_ok=True):
+    return bool(lib().emu_next_inplace(int(was), seen, mode, int(auto_ok)))
+
+
+def order_kernel_due(nsub, launches_since_sort):
+    return bool(lib().emu_order_kernel_due(nsub, launches_since_sort))
+
+
+class RangeTable:
+    """ck::RangeTable: `records` are lists [env0, n, inplace, launches_since_sort], the caller's to edit between claims."""
+
+    def __init__(self):
+        self.records = []
+
+    def claim(self, env0, n):
+        """-> (the claimed record: one of self.records, the retired records)"""
+        k = len(self.records)
+        rec, gone = np.zeros((k + 1, 4), dtype=np.int32), np.zeros((k + 1, 4), dtype=np.int32)
+        rec[:k] = np.asarray(self.records, dtype=np.int32).reshape(k, 4)
+        nrec, ngone = ctypes.c_int(k), ctypes.c_int(0)
+        at = lib().emu_ranges_claim(_ptr(rec), ctypes.addressof(nrec), env0, n, _ptr(gone), ctypes.addressof(ngone))
+        kept = {(r[0], r[1]): r for r in self.records}             # (a record that survives stays the same list)
+        self.records = [kept.get((int(r[0]), int(r[1])), [int(v) for v in r]) for r in rec[: nrec.value]]
+        return self.records[at], [tuple(int(v) for v in g) for g in gone[: ngone.value]]
 
 
 def set_const(pod, blocks, nenv, mode):

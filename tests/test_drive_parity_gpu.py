@@ -598,6 +598,55 @@ def test_launch_order_survives_a_change_of_the_range_partition(cassie):
             assert a.tobytes() == c.tobytes()
 
 
+def test_form_and_hand_over_words_survive_a_change_of_the_range_partition(cassie):
+    """The partition of the batch changes while envs leave the fast tier and every range picks the form of its fast kernel itself
+    (phys_batch_set_inplace(2)): whole batch, halves on two streams, ranges that straddle the halves, whole batch again -- eight policy
+    steps each, the host seeing every launch's report (eight, because under these targets the first env of the 4096 needs more than 31
+    rows in policy step 4, the next ones from step 13 on: a block must hold a hand-over and the launch after it).  A range is (env0, n): the ranges a launch overlaps are retired with their form
+    and their hand-over words, the new one starts in the plain form and goes in place after its own first report.  Same bits as
+    whole-batch stepping in the plain form, nothing left in the lists, the in-place form at work under every partition, and never more
+    ranges in place than the partition has."""
+    import torch
+    n, per_block = 4096, 8
+    blocks = [[(0, n)], [(0, n // 2), (n // 2, n // 2)], [(0, 1500), (1500, n - 1500)], [(0, n)]]
+    tg = _stress_targets(np.arange(n), per_block * len(blocks))      # joints slammed into their limits: envs leave the 31-row tier
+
+    def run(mode, schedule):
+        b = Batch(cassie, n)
+        try:
+            b.set_inplace(mode)
+            b.set(P.F_QPOS, np.tile(cassie.qpos_init(), (n, 1)))
+            b.set(P.F_PD_KP, np.tile(bench.PD_KP, (n, 1)))
+            b.set(P.F_PD_KD, np.tile(bench.PD_KD, (n, 1)))
+            b.forward()
+            b.set_drive_mode(P.DRIVE_PD)
+            streams = (torch.cuda.Stream(), torch.cuda.Stream())
+            in_place_launches = []
+            for k, cut in enumerate(schedule):
+                before = b.form_launches()[1]
+                for p in range(per_block * k, per_block * (k + 1)):
+                    b.set(P.F_PD_PTARGET, tg[p])
+                    for i, (first, cnt) in enumerate(cut):
+                        if (first, cnt) == (0, n):
+                            b.step(bench.HOLD)
+                        else:
+                            b.step_range(first, cnt, bench.HOLD, streams[i % 2].cuda_stream)
+                    b.sync()                                         # (waits for the callers' streams too)
+                    assert b.inplace_ranges() <= len(cut), (k, p, b.inplace_ranges())
+                in_place_launches.append(b.form_launches()[1] - before)
+            assert b.handover_pending() == 0
+            return in_place_launches, [b.get(P.F_QPOS), b.get(P.F_QVEL), b.get(P.F_QACC_WARMSTART), b.get(P.F_SENSORDATA), b.get(P.F_MEAS),
+                                       b.get(P.F_TIME), b.warnings()[1][:, :3].copy()]
+        finally:
+            b.close()
+    plain, want = run(0, [[(0, n)]] * len(blocks))
+    in_place, got = run(2, blocks)
+    assert not any(plain)
+    assert all(k > 0 for k in in_place), in_place
+    for a, c in zip(want, got):
+        assert a.tobytes() == c.tobytes()
+
+
 def test_fast_kernel_form_follows_what_the_range_needs(built):
     """phys_batch_set_inplace(2), the default: a range whose launch handed envs over takes the in-place form of the fast kernel from the
     next launch on, and goes back to the plain form after eight launches in which no env left the fast tier -- with the same bits as the
