@@ -97,6 +97,7 @@ def _declare(L):
     L.phys_batch_clear_warn.argtypes = [vp, c.c_int, c.c_int]
     L.phys_batch_step.argtypes = [vp, c.c_int, vp]
     L.phys_batch_forward.argtypes = [vp, vp]
+    L.phys_batch_forward_kinematics.argtypes = [vp, vp]
     L.phys_batch_sync.argtypes = [vp]
     L.phys_batch_set_pd_mode.argtypes = [vp, c.c_int]
     L.phys_batch_set_drive_mode.argtypes = [vp, c.c_int]
@@ -148,6 +149,14 @@ def _declare(L):
         L.phys_batch_depth_configure.argtypes = [vp, c.c_int, vp, vp, c.c_int, c.c_int, c.c_double, c.c_double, c.c_double]
         L.phys_batch_depth_bind_pose.argtypes = [vp, vp]
         L.phys_batch_depth_image.argtypes = [vp, c.c_int, c.c_int, vp]
+    if hasattr(L, "phys_batch_depth_set_geoms"):   # (likewise)
+        L.phys_batch_depth_set_geoms.argtypes = [vp, c.c_uint]
+        L.phys_batch_depth_default_geoms.argtypes = [vp]
+        L.phys_batch_depth_default_geoms.restype = c.c_uint
+        L.phys_batch_depth_all_geoms.argtypes = [vp]
+        L.phys_batch_depth_all_geoms.restype = c.c_uint
+        L.phys_batch_depth_bind_ids.argtypes = [vp, vp]
+        L.phys_batch_debug_depth_launches.argtypes = [vp, c.POINTER(c.c_longlong), c.POINTER(c.c_longlong)]
     if hasattr(L, "phys_batch_download_progress"):   # (absent from older variant builds selected with CASSIE_LIB)
         L.phys_batch_download_progress.argtypes = [vp, vp]
     L.phys_batch_set_all_outputs_every_substep.argtypes = [vp, c.c_int]

@@ -228,6 +228,12 @@ class Batch:
         if lib().phys_batch_forward(self._h, stream) != 0:
             raise RuntimeError("forward failed: " + (lib().phys_last_error() or b"").decode())
 
+    def forward_kinematics(self, stream=None):
+        """The forward pass with qacc / sensordata / actuator_velocity sent to scratch: refreshes F_XPOS / F_XQUAT (and the other
+        position-level outputs) from qpos and leaves the fields a policy reads alone.  Not in a drive mode."""
+        if lib().phys_batch_forward_kinematics(self._h, stream) != 0:
+            raise RuntimeError("forward_kinematics failed: " + (lib().phys_last_error() or b"").decode())
+
     def set_hfield(self, data, env=None):
         """Height-field samples for all envs (env=None, one shared grid) or for one env only (per-env terrain)."""
         a = np.ascontiguousarray(data, dtype=np.float32)
@@ -346,10 +352,46 @@ class Batch:
         if lib().phys_batch_depth_bind_pose(self._h, device_ptr) != 0:
             raise RuntimeError("bind_depth_pose failed: " + (lib().phys_last_error() or b"").decode())
 
+    def depth_default_geoms(self):
+        """The mask of the geoms a depth image shows by default: the planes, boxes and height field on bodies welded to the world."""
+        return int(lib().phys_batch_depth_default_geoms(self._h))
+
+    def depth_all_geoms(self):
+        """The mask of every compiled collision geom."""
+        return int(lib().phys_batch_depth_all_geoms(self._h))
+
+    def depth_geoms(self, mask=None, *, moving=None):
+        """Which geoms the depth image shows: bit g of `mask` = compiled collision geom g (the order of pod.geom_fullid), or
+        moving=True for all of them -- the robot's own legs, the tray and the cube included, drawn where F_XPOS / F_XQUAT have the
+        bodies: as the last step launch or forward pass left them, NOT refreshed by reset_envs, end_episodes or set(F_QPOS) -- or
+        moving=False for the default.  configure_depth restores the default.  -> the mask now in force."""
+        if (mask is None) == (moving is None):
+            raise ValueError("depth_geoms: a mask or moving=True / False")
+        if mask is None:
+            mask = self.depth_all_geoms() if moving else self.depth_default_geoms()
+        mask = int(mask)
+        if mask < 0 or mask >> self.pod.ngeom:
+            raise ValueError("depth_geoms: the mask names a geom at or above ngeom = %d" % self.pod.ngeom)
+        if lib().phys_batch_depth_set_geoms(self._h, mask) != 0:
+            raise RuntimeError("depth_geoms failed: " + (lib().phys_last_error() or b"").decode())
+        return mask
+
+    def bind_depth_ids(self, device_ptr):
+        """The hit-id image: int32 [nenv][height * width] in HBM, contiguous, e.g. a torch tensor's data_ptr(): per pixel the compiled
+        index of the geom that gave the depth, -1 where the depth is `far`.  None unbinds; configure_depth drops the binding."""
+        if lib().phys_batch_depth_bind_ids(self._h, device_ptr) != 0:
+            raise RuntimeError("bind_depth_ids failed: " + (lib().phys_last_error() or b"").decode())
+
+    def depth_launches(self):
+        """Diagnostics: (launches of the static depth kernel, launches of the scene kernel) so far."""
+        a, b = ctypes.c_longlong(0), ctypes.c_longlong(0)
+        lib().phys_batch_debug_depth_launches(self._h, ctypes.byref(a), ctypes.byref(b))
+        return a.value, b.value
+
     def depth_image(self, env0=0, n=None, stream=None):
         """One launch on `stream` (default: the batch's own), in order with the step launches there: F_DEPTH of envs [env0, env0 + n) =
-        per pixel the depth along the optical axis of the nearest static collision geom (plane, box, height field) in [near, far], `far`
-        where the ray meets none."""
+        per pixel the depth along the optical axis of the nearest rendered geom (by default the static planes, boxes and height field;
+        depth_geoms chooses others) in [near, far], `far` where the ray meets none."""
         n = self.nenv - env0 if n is None else n
         if lib().phys_batch_depth_image(self._h, int(env0), int(n), stream) != 0:
             raise RuntimeError("depth_image failed: " + (lib().phys_last_error() or b"").decode())

@@ -1,7 +1,9 @@
 /*
  * depth_kernel.h -- the egocentric depth image (phys_batch_depth_image, include/cassie_phys.h: the definition is there): one ray
- * per pixel of a pinhole camera mounted on a body, against the env's static collision geometry.  Written with the wv:: primitives
- * only, workgroups of one wave: phys_batch.hip launches it, the wave emulator (tests/emu/emu_depth.cpp) runs the same text.
+ * per pixel of a pinhole camera mounted on a body, against the env's static collision geometry (cassie_depth_kernel) or against any
+ * chosen set of its collision geoms, the moving bodies' included (cassie_depth_scene_kernel).  Written with the wv:: primitives only,
+ * workgroups of one wave: phys_batch.hip launches them, the wave emulator (tests/emu/emu_depth.cpp, emu_depth_scene.cpp) runs the same
+ * text.
  */
 #ifndef CASSIE_DEPTH_KERNEL_H
 #define CASSIE_DEPTH_KERNEL_H
@@ -34,6 +36,27 @@ constexpr int DEPTH_GRID = 2048, DEPTH_TILE = 8, DEPTH_MAXPIXELS = 16384;
  * between them (barycentric coordinates, dimensionless), a cell whose corners touch the ray's z-interval is not skipped (metres) */
 constexpr double DEPTH_EDGE_EPS = 1e-12, DEPTH_CULL_PAD = 1e-9;
 
+/* THE SCENE KERNEL (cassie_depth_scene_kernel) renders the geoms of the mask DepthIO::geoms: besides the static planes, boxes and
+ * height field also spheres and capsules, and spheres, capsules and boxes on moving bodies, whose world pose is that of the body as
+ * the last step launch or forward pass stored it (xpos / xquat, used as stored) composed with the geom's own pose from PG.  It is the
+ * same per-pixel body as the static kernel's (depth_jobs.inc, with a compile-time switch): the static kernel keeps its text.
+ *
+ * The geoms' world frames are needed once per job, not once per lane: lane g builds geom g's (position and rotation, 12 doubles) and
+ * the geom loop, whose index is wave-uniform, reads them with wv::readlane -- 24 v_readlane_b32 into scalars per rendered geom, no
+ * LDS, no barrier, nothing to allocate at launch, and the emulator runs it as it stands.  (LDS would cost a write, a wait and 24
+ * ds_reads per geom and lane for values that are the wave's, not the lane's.)  The size and the bounding radius are the model's, at a
+ * wave-uniform address: scalar loads, not lane reads.
+ *
+ * A solid (sphere, capsule, box) is convex: the ray meets it over an interval [t0, t1], and the pixel takes t0 where t0 >= near, `near`
+ * where t0 < near <= t1, nothing otherwise.  A lane runs a solid's test only where its ray meets the geom's bounding sphere
+ * (geom_rbound + DEPTH_CULL_PAD) over an interval that reaches `near` and starts in front of the lane's best so far; a wave in which
+ * no lane does skips the geom (wv::ballot, a uniform branch).  The solid lies inside the bound, so the cull changes no value; for the
+ * sphere the bound (unpadded) is the test.  The quadratics are solved about the ray's point of closest approach, tc = -(o.d) / (d.d),
+ * q = o + tc d, t = tc -+ sqrt((r^2 - q.q) / (d.d)): r^2 - q.q is a difference of terms of the size of r^2, not of |o|^2.  The
+ * capsule is the cylinder side (the same in x, y, a root kept where |z| <= h) and the two spheres at z = -+h: the interval runs from
+ * the smallest to the largest of the roots kept; a ray along the axis (dx^2 + dy^2 == 0) has the spheres alone.  A NaN pose fails
+ * every comparison: the geom is unseen, and nothing is indexed by these values. */
+
 struct DepthIO {
     const cm_model_t *models; int model_stride;
     const cm_envparams_t *envparams;   /* null, or one block per env (PhysIO::envparams) */
@@ -45,6 +68,11 @@ struct DepthIO {
     double *out; int sout;             /* [nenv][height * width] with a row stride in doubles */
     const float *hfield; size_t hfield_stride; const int *hfield_index; int hfield_nterrain;   /* as in PhysIO */
     int *warn;
+    /* the scene kernel's (all zero: the static kernel's behaviour) */
+    unsigned geoms;                    /* bit g: compiled geom g is rendered */
+    const double *xpos, *xquat;        /* [nenv][nbody][3 / 4] body poses in the world, rows sxp / sxq doubles apart */
+    int sxp, sxq;
+    int *ids;                          /* null, or [nenv][height * width]: the geom that gave the value, -1 where it is `far` */
 };
 
 /* the ray o + t d against the triangle a, a + e1, a + e2 (Moeller-Trumbore, either face): t, or -1 where it misses */
@@ -116,70 +144,44 @@ WV_DEVICE double depth_ray_hfield(const float *grid, int nr, int nc, double sx, 
     return miss;
 }
 
-WV_GLOBAL void __launch_bounds__(WV_WAVE) cassie_depth_kernel(DepthIO io) {
-    const int lane = wv::lane();
-    const int W = io.width, H = io.height;
-    const int tiles_x = (W + DEPTH_TILE - 1) / DEPTH_TILE, tiles = tiles_x * ((H + DEPTH_TILE - 1) / DEPTH_TILE);
-    const long long njobs = (long long)io.n * tiles;
-    for (long long job = wv::env_id(); job < njobs; job += wv::grid_size()) {
-        const int env = io.env0 + (int)(job / tiles), tile = (int)(job % tiles);
-        const ModelPtr m = (ModelPtr)(io.models + (size_t)env * io.model_stride);
-        const ParamPtr PG = (io.envparams && m->env_geom) ? (ParamPtr)(io.envparams + (size_t)env) : (ParamPtr)&m->params;
-        /* the camera's world pose (wave-uniform) */
-        double bp[3], bq[4], Rb[9], cp[3], cq[4], wq[4], Rc[9], off[3];
-        static_body_pose(m, io.body, io.qpos + (size_t)env * io.sq, bp, bq);
-        const double *own = io.pose ? io.pose + (size_t)env * 7 : nullptr;
-        for (int k = 0; k < 3; ++k) cp[k] = own ? own[k] : io.cam_pos[k];
-        for (int k = 0; k < 4; ++k) cq[k] = own ? own[3 + k] : io.cam_quat[k];
-        normalize4(cq);
-        quat2mat(Rb, bq);
-        mulmatvec3(off, Rb, cp);
-        mulquat(wq, bq, cq);
-        quat2mat(Rc, wq);
-        const double o[3] = {bp[0] + off[0], bp[1] + off[1], bp[2] + off[2]};
-        /* this lane's pixel and its ray */
-        const int r = (tile / tiles_x) * DEPTH_TILE + (lane >> 3), c = (tile % tiles_x) * DEPTH_TILE + (lane & 7);
-        const bool mine = r < H && c < W;
-        const double aspect = (double)W / (double)H;
-        const double dc[3] = {aspect * io.tan_half * (2.0 * (c + 0.5) / W - 1.0), io.tan_half * (1.0 - 2.0 * (r + 0.5) / H), -1.0};
-        double D[3];
-        mulmatvec3(D, Rc, dc);
-        bool clamped;
-        const float *grid = terrain_grid(io.hfield, io.hfield_stride, io.hfield_index, io.hfield_nterrain, env, &clamped);
-        double best = io.zfar;
-        for (int g = 0; g < m->ngeom; ++g) {              /* (the same trip for every lane: the geom's pose is the wave's, not the lane's) */
-            const int gt = m->geom_type[g];
-            if (m->body_weldid[m->geom_bodyid[g]] != 0 || (gt != CM_GEOM_PLANE && gt != CM_GEOM_BOX && gt != CM_GEOM_HFIELD)) continue;
-            double gp[3], R[9], og[3], dg[3];
-            static_geom_pose(m, PG, g, gp, R);
-            const double rel[3] = {o[0] - gp[0], o[1] - gp[1], o[2] - gp[2]};
-            mulmatTvec3(og, R, rel);
-            mulmatTvec3(dg, R, D);
-            double t = io.zfar + 1.0;
-            if (!mine) {                                    /* (a lane past the image's edge has no ray) */
-            } else if (gt == CM_GEOM_PLANE) {
-                if (dg[2] != 0.0) t = -og[2] / dg[2];
-            } else if (gt == CM_GEOM_BOX) {
-                double t0 = -1e300, t1 = 1e300;
-                bool inside = true;
-                for (int k = 0; k < 3; ++k) {
-                    const double s = m->geom_size[g][k];
-                    if (dg[k] != 0.0) {
-                        const double ta = (-s - og[k]) / dg[k], tb = (s - og[k]) / dg[k];
-                        const double lo = ta < tb ? ta : tb, hi = ta < tb ? tb : ta;
-                        t0 = lo > t0 ? lo : t0; t1 = hi < t1 ? hi : t1;
-                    } else if (fabs(og[k]) > s) inside = false;
-                }
-                if (inside && t0 <= t1) t = t0 >= io.znear ? t0 : (t1 >= io.znear ? io.znear : t);
-            } else if (grid && m->hfield_nrow >= 2 && m->hfield_ncol >= 2) {
-                t = depth_ray_hfield(grid, m->hfield_nrow, m->hfield_ncol, m->hfield_size[0], m->hfield_size[1], m->hfield_size[2], og, dg,
-                                     io.znear, io.zfar);
-            }
-            if (t >= io.znear && t < best) best = t;
-        }
-        if (mine) io.out[(size_t)env * io.sout + (size_t)r * W + c] = best;
-        if (clamped && tile == 0 && lane == 0) wv::atomic_or(io.warn + env, WARN_TERRAIN_INDEX);
+/* the roots of |o + t d|^2 = r2 for a ray with d.d = dd (2-D: pass z components of zero): false where there are none */
+WV_DEVICE bool depth_ray_round(const double *o, const double *d, double dd, double r2, double *ta, double *tb) {
+    const double tc = -dot3(o, d) / dd;
+    const double q[3] = {o[0] + tc * d[0], o[1] + tc * d[1], o[2] + tc * d[2]};
+    const double h2 = r2 - dot3(q, q);
+    if (!(h2 >= 0.0)) return false;
+    const double s = sqrt(h2 / dd);
+    *ta = tc - s; *tb = tc + s;
+    return true;
+}
+
+/* the interval of the ray (geom frame) within the capsule of radius r, half-length h along z: false where it misses */
+WV_DEVICE bool depth_ray_capsule(const double *o, const double *d, double r, double h, double *t0, double *t1) {
+    double lo = 1e300, hi = -1e300, ta, tb;
+    const double r2 = r * r, dd = dot3(d, d), a = d[0] * d[0] + d[1] * d[1];
+    const double o2[3] = {o[0], o[1], 0.0}, d2[3] = {d[0], d[1], 0.0};
+    if (a != 0.0 && depth_ray_round(o2, d2, a, r2, &ta, &tb)) {
+        if (fabs(o[2] + ta * d[2]) <= h) { lo = ta < lo ? ta : lo; hi = ta > hi ? ta : hi; }
+        if (fabs(o[2] + tb * d[2]) <= h) { lo = tb < lo ? tb : lo; hi = tb > hi ? tb : hi; }
     }
+    for (int e = 0; e < 2; ++e) {
+        const double oc[3] = {o[0], o[1], e ? o[2] - h : o[2] + h};
+        if (depth_ray_round(oc, d, dd, r2, &ta, &tb)) { lo = ta < lo ? ta : lo; hi = tb > hi ? tb : hi; }
+    }
+    *t0 = lo; *t1 = hi;
+    return lo <= hi;
+}
+
+/* the value a convex solid met over [t0, t1] gives the pixel: the entry, `near` where the near plane cuts the solid, else `miss` */
+WV_DEVICE double depth_convex(double t0, double t1, double znear, double miss) { return t0 >= znear ? t0 : (t1 >= znear ? znear : miss); }
+
+WV_GLOBAL void __launch_bounds__(WV_WAVE) cassie_depth_kernel(DepthIO io) {
+    constexpr bool SCENE = false;
+#include "depth_jobs.inc"
+}
+WV_GLOBAL void __launch_bounds__(WV_WAVE) cassie_depth_scene_kernel(DepthIO io) {
+    constexpr bool SCENE = true;
+#include "depth_jobs.inc"
 }
 
 }  // namespace ck

@@ -54,6 +54,11 @@ struct phys_batch {
     int depth_width = 0, depth_height = 0, depth_body = 0;
     double depth_tan_half = 0, depth_near = 0, depth_far = 0, depth_cam_pos[3] = {0, 0, 0}, depth_cam_quat[4] = {1, 0, 0, 0};
     DevBuf<const double> d_depth_pose;
+    /* ... the geoms it renders (phys_batch_depth_set_geoms; the default until then), the caller's hit-id image when bound
+     * (phys_batch_depth_bind_ids), and how many launches each of the two kernels has had (phys_batch_debug_depth_launches) */
+    unsigned depth_geoms = 0;
+    DevBuf<int> d_depth_ids;
+    long long depth_launches[2] = {0, 0};
     hipStream_t stream = nullptr;
     hipStream_t recent_streams[4] = {nullptr, nullptr, nullptr, nullptr}; /* streams of the most recent launches (callers may pass
                                        their own, and ranges of one batch may be in flight on several at once) */
@@ -971,6 +976,15 @@ int phys_batch_height_scan(phys_batch_t *b, int env0, int n, void *stream) {
 }
 
 /* ------------------------------------------------ the depth image ---- */
+static unsigned depth_all_geoms(const cm_model_t &m) { return m.ngeom >= 32 ? 0xffffffffu : (1u << m.ngeom) - 1u; }
+static unsigned depth_default_geoms(const cm_model_t &m) {
+    unsigned mask = 0;
+    for (int g = 0; g < m.ngeom; ++g) {
+        const int gt = m.geom_type[g];
+        if (m.body_weldid[m.geom_bodyid[g]] == 0 && (gt == CM_GEOM_PLANE || gt == CM_GEOM_BOX || gt == CM_GEOM_HFIELD)) mask |= 1u << g;
+    }
+    return mask;
+}
 int phys_batch_depth_configure(phys_batch_t *b, int body, const double *cam_pos, const double *cam_quat, int width, int height, double fovy,
                                double znear, double zfar) {
     if (!b || !cam_pos || !cam_quat || width < 1 || height < 1 || (long long)width * height > ck::DEPTH_MAXPIXELS) {
@@ -998,6 +1012,31 @@ int phys_batch_depth_configure(phys_batch_t *b, int body, const double *cam_pos,
     b->depth_tan_half = tan(0.5 * fovy); b->depth_near = znear; b->depth_far = zfar;
     for (int k = 0; k < 3; ++k) b->depth_cam_pos[k] = cam_pos[k];
     for (int k = 0; k < 4; ++k) b->depth_cam_quat[k] = cam_quat[k];
+    b->depth_geoms = depth_default_geoms(b->host_model);
+    b->d_depth_ids.reset();             /* (the image may have another size: bind the ids again) */
+    return 0;
+}
+unsigned phys_batch_depth_default_geoms(const phys_batch_t *b) { return b ? depth_default_geoms(b->host_model) : 0u; }
+unsigned phys_batch_depth_all_geoms(const phys_batch_t *b) { return b ? depth_all_geoms(b->host_model) : 0u; }
+int phys_batch_depth_set_geoms(phys_batch_t *b, unsigned mask) {
+    if (!b) return -1;
+    if (b->depth_width <= 0) { phys_set_last_error("phys_batch_depth_set_geoms: call phys_batch_depth_configure first (it restores the default set)"); return -1; }
+    if (mask & ~depth_all_geoms(b->host_model)) { phys_set_last_error("phys_batch_depth_set_geoms: the mask names a geom at or above ngeom"); return -1; }
+    /* (as phys_batch_bind: launches already queued keep the mask they were given) */
+    b->depth_geoms = mask;
+    return 0;
+}
+int phys_batch_depth_bind_ids(phys_batch_t *b, void *device_ptr) {
+    if (!b) return -1;
+    if (b->depth_width <= 0) { phys_set_last_error("phys_batch_depth_bind_ids: call phys_batch_depth_configure first (it sizes the image)"); return -1; }
+    (void)hipSetDevice(b->device);
+    b->d_depth_ids.borrow((int *)device_ptr);
+    return 0;
+}
+int phys_batch_debug_depth_launches(const phys_batch_t *b, long long *static_kernel, long long *scene_kernel) {
+    if (!b) return -1;
+    if (static_kernel) *static_kernel = b->depth_launches[0];
+    if (scene_kernel) *scene_kernel = b->depth_launches[1];
     return 0;
 }
 int phys_batch_depth_bind_pose(phys_batch_t *b, const void *device_ptr) {
@@ -1029,8 +1068,21 @@ int phys_batch_depth_image(phys_batch_t *b, int env0, int n, void *stream) {
     const int T = ck::DEPTH_TILE;
     const long long jobs = (long long)n * (((b->depth_width + T - 1) / T) * ((b->depth_height + T - 1) / T));
     hipStream_t s = launch_stream(b, stream);
-    hipLaunchKernelGGL(ck::cassie_depth_kernel, dim3((unsigned)(jobs < ck::DEPTH_GRID ? jobs : ck::DEPTH_GRID)), dim3(WV_WAVE), 0, s, io);
-    return hip_ok(hipGetLastError(), "cassie_depth_kernel launch") ? 0 : -1;
+    const dim3 grid((unsigned)(jobs < ck::DEPTH_GRID ? jobs : ck::DEPTH_GRID));
+    /* the static kernel unless the caller has chosen other geoms than the default or wants the ids: the default image is the static
+     * kernel's, bit for bit and at its cost */
+    const bool scene = b->depth_geoms != depth_default_geoms(b->host_model) || b->d_depth_ids;
+    ++b->depth_launches[scene ? 1 : 0];
+    if (!scene) {
+        hipLaunchKernelGGL(ck::cassie_depth_kernel, grid, dim3(WV_WAVE), 0, s, io);
+        return hip_ok(hipGetLastError(), "cassie_depth_kernel launch") ? 0 : -1;
+    }
+    io.geoms = b->depth_geoms;
+    io.xpos = b->d_field[PHYS_F_XPOS]; io.xquat = b->d_field[PHYS_F_XQUAT];
+    io.sxp = 3 * b->host_model.nbody; io.sxq = 4 * b->host_model.nbody;   /* (rows as the step kernel writes them: make_io's sb) */
+    io.ids = b->d_depth_ids;
+    hipLaunchKernelGGL(ck::cassie_depth_scene_kernel, grid, dim3(WV_WAVE), 0, s, io);
+    return hip_ok(hipGetLastError(), "cassie_depth_scene_kernel launch") ? 0 : -1;
 }
 
 int phys_batch_sync(phys_batch_t *b) {

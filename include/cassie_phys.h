@@ -220,13 +220,63 @@ int phys_batch_height_scan(phys_batch_t *b, int env0, int n, void *stream);
  *                                               surface are not rendered; a ray outside the footprint misses.  The grid is the env's own
  *                                               (shared, per env, or the bank's terrain of the env's index; an index outside the bank is
  *                                               clamped and raises WARN_TERRAIN_INDEX).
- *                               Spheres, capsules, cylinders and everything on moving bodies -- the robot's own legs, the tray and cube
- *                               of cassie_tray_box -- are not seen.  Noise, history, fp32 conversion and inverse-depth encodings are the
- *                               caller's.  A batch that never configures the depth image runs exactly as before. */
+ *                               BY DEFAULT spheres, capsules, cylinders and everything on moving bodies -- the robot's own legs, the
+ *                               tray and cube of cassie_tray_box -- are not seen; phys_batch_depth_set_geoms (below) chooses other
+ *                               geoms.  Noise, history, fp32 conversion and inverse-depth encodings are the caller's.  A batch that
+ *                               never configures the depth image runs exactly as before.
+ *   phys_batch_depth_set_geoms  WHICH GEOMS ARE RENDERED: bit g of `mask` set = compiled collision geom g is (CM_MAXGEOM is 32: one word
+ *                               holds every geom; compiled order is that of cm_model_t::geom_fullid, as for CM_P_GEOM_FRICTION).  The
+ *                               default -- phys_batch_depth_default_geoms: the planes, boxes and height field on bodies welded to the
+ *                               world, the set described above -- holds until this call is made and is restored by
+ *                               phys_batch_depth_configure; phys_batch_depth_all_geoms is every compiled geom.  Configure first; a bit
+ *                               at or above ngeom fails with -1 + phys_last_error().  Launches already queued keep their mask.  A batch
+ *                               that never makes the call (or makes it with the default) and binds no ids produces, bit for bit, the
+ *                               image described above, with the same kernel.  With any other mask, or with ids bound:
+ *                                 geom poses    of a geom on a body welded to the world (body_weldid == 0) as above.  Of a geom g on a
+ *                                               moving body B the world pose is p = xpos[B] + R(xquat[B]) geom_pos[g] and
+ *                                               R = R(xquat[B]) geom_mat[g], xpos / xquat the env's rows of PHYS_F_XPOS / PHYS_F_XQUAT
+ *                                               USED AS STORED (not normalised, not recomputed), geom_pos / geom_mat the env's own once
+ *                                               geometry is randomised, the model's otherwise.  The camera's pose keeps coming from qpos.
+ *                                 STALENESS     PHYS_F_XPOS / PHYS_F_XQUAT are written by the last substep of a stepping launch
+ *                                               (phys_batch_step, phys_batch_step_range; also phys_batch_profile_step /
+ *                                               _profile_substeps / _time_steps, which step) and by the forward passes
+ *                                               (phys_batch_forward, phys_batch_forward_kinematics), for the envs of that launch -- and
+ *                                               by an upload or a binding of the two fields themselves.  NOTHING ELSE refreshes them:
+ *                                               not phys_batch_reset_envs, not phys_batch_end_episodes with restart, not an upload of
+ *                                               qpos, not phys_batch_drive_pass.  After one of those the camera (qpos) is at the new
+ *                                               state and the moving geoms are drawn where the bodies WERE; the next stepping launch or
+ *                                               forward pass puts them right.  A fresh batch holds zeros there: run a forward pass first.
+ *                                               (A stepping launch stores the poses its last substep computed from the qpos that substep
+ *                                               STARTED from: behind a step launch the bodies are drawn one substep behind the camera.)
+ *                                 solids        a sphere, capsule or box is convex: the ray o + t d (geom frame, d not normalised) meets
+ *                                               it over an interval [t0, t1]; the pixel takes t0 if t0 >= near, `near` if t0 < near <= t1
+ *                                               (the origin is inside, or the near plane cuts the solid), else the solid is missed.
+ *                                                 sphere   radius size[0]: the roots of |o + t d|^2 = r^2;
+ *                                                 capsule  radius size[0], half-length size[1] along the geom's z: the cylinder side
+ *                                                          x^2 + y^2 = r^2 for |z| <= h and the two spheres at z = -+h; the interval
+ *                                                          runs from the smallest entry to the largest exit over the pieces hit;
+ *                                                 box      the slab test above, also on a moving body.
+ *                                               Static spheres and capsules are rendered like moving ones.  Planes and height fields on
+ *                                               MOVING bodies (none of the supported models has one) and any other kind of geom are not
+ *                                               rendered whatever the mask says.
+ *                                 the value     the smallest such t < far over the rendered geoms, `far` where there is none.
+ *                                 NaN poses     a NaN in xpos / xquat fails every comparison made for that geom: it is unseen.  Nothing
+ *                                               indexes memory by these values.
+ *   phys_batch_depth_bind_ids   optional HIT-ID image: int32 [nenv][height * width] in DEVICE memory, contiguous, indexed by the
+ *                               absolute env.  A pixel holds the compiled index of the geom that gave the pixel's value, -1 where the
+ *                               value is `far`; ties go to the lower index.  (Mask the robot out, train on a self / other segmentation.)
+ *                               Configure first; NULL unbinds; phys_batch_depth_configure drops the binding (the size may change).
+ *   phys_batch_debug_depth_launches  diagnostics: the depth launches so far of the static kernel and of the scene kernel (the one that
+ *                               takes a mask and ids). */
 int phys_batch_depth_configure(phys_batch_t *b, int body, const double *cam_pos, const double *cam_quat, int width, int height, double fovy,
                                double znear, double zfar);
 int phys_batch_depth_bind_pose(phys_batch_t *b, const void *device_ptr);
 int phys_batch_depth_image(phys_batch_t *b, int env0, int n, void *stream);
+int phys_batch_depth_set_geoms(phys_batch_t *b, unsigned mask);
+unsigned phys_batch_depth_default_geoms(const phys_batch_t *b);
+unsigned phys_batch_depth_all_geoms(const phys_batch_t *b);
+int phys_batch_depth_bind_ids(phys_batch_t *b, void *device_ptr);
+int phys_batch_debug_depth_launches(const phys_batch_t *b, long long *static_kernel, long long *scene_kernel);
 /* host <-> HBM copies of whole fields or of a row range [env0, env0 + n) */
 int phys_batch_upload(phys_batch_t *b, int field, const double *host, int env0, int n);
 int phys_batch_download(phys_batch_t *b, int field, double *host, int env0, int n);

@@ -1,19 +1,25 @@
 #!/usr/bin/env python3
 """What a depth image per policy step costs config 4's loop -- 4096 cassie_hfield.xml envs, CM_DRIVE_PD_SAFE, 50 fused substeps per
 launch, the batch as two env ranges on two streams, a bank of 64 terrains with a random per-env index, restarts on bench.py's
-schedule (tools/terrain_rate.py's `bank` leg) -- in three settings in one session, fenced timed regions:
+schedule (tools/terrain_rate.py's `bank` leg) -- in four settings in one session, fenced timed regions:
 
-  no_depth       the loop alone.  THE YARDSTICK (the step kernels are those of tools/terrain_rate.py's bank leg).
-  depth_64x48    the same plus a 64 x 48 depth image per range and policy step (phys_batch_depth_image).
-  depth_128x128  ... a 128 x 128 one.
+  no_depth               the loop alone.  THE YARDSTICK (the step kernels are those of tools/terrain_rate.py's bank leg).
+  depth_64x48            the same plus a 64 x 48 depth image per range and policy step (phys_batch_depth_image): the default geoms,
+                         the static kernel.
+  depth_64x48_all_geoms  ... with every geom in the mask (Batch.depth_geoms(moving=True)): the scene kernel, the robot's own sphere
+                         and capsules drawn where the step launch in front of it left the bodies.
+  depth_128x128          the default geoms, 128 x 128.
+
+--parent-lib PATH runs the depth_64x48 leg once more in a child process against another build of the library (the parent commit's):
+the static kernel must not have become slower, and the yardstick for that is the parent in the same session, not a file.
 
 The camera is the reference's `egocentric` one in spirit: on the pelvis, pitched 45 degrees down, fovy 65.5, near 0.01, far 5.  Also
-times the depth launch alone over the whole batch on an idle device, for both sizes, and records the kernel's registers, scratch and
+times the depth launch alone over the whole batch on an idle device, for every leg, and records both kernels' registers, scratch and
 LDS as the compiler reports them (hipcc -Rpass-analysis=kernel-resource-usage on csrc/depth_kernel.h; null where hipcc is absent).
 Prints one JSON line; `--out` also writes it to a file.  Needs a GPU.
 
     python tools/depth_rate.py [--envs 4096] [--launches 20] [--warmup 10] [--repeats 10] [--only NAME] [--out profiles/depth_rate.json]
-                               [--resources-only]
+                               [--resources-only] [--parent-lib PATH]
 """
 import argparse
 import json
@@ -40,7 +46,9 @@ from cassie_amd import phys as P  # noqa: E402
 from terrain_rate import NTERRAIN, terrain  # noqa: E402
 
 NSUB = bench.HOLD
-SETTINGS = {"no_depth": None, "depth_64x48": (64, 48), "depth_128x128": (128, 128)}
+SETTINGS = {"no_depth": None, "depth_64x48": (64, 48), "depth_64x48_all_geoms": (64, 48), "depth_128x128": (128, 128)}
+ALL_GEOMS = {"depth_64x48_all_geoms"}
+KERNELS = ("cassie_depth_kernel", "cassie_depth_scene_kernel")
 CAM_POS, FOVY, NEAR, FAR, PITCH = (0.1, 0.0, 0.25), 65.5, 0.01, 5.0, 45.0
 
 
@@ -65,17 +73,22 @@ def kernel_resources():
                  "-I" + os.path.join(REPO, "cassie-mujoco-sim_amd", "csrc"), "-ffp-contract=on", "-mllvm", "-amdgpu-sched-strategy=iterative-ilp",
                  "-mllvm", "-disable-machine-licm", "--cuda-device-only", "-Rpass-analysis=kernel-resource-usage"]
         r = subprocess.run([hipcc] + flags + ["-c", src, "-o", os.path.join(tmp, "depth.o")], capture_output=True, text=True, timeout=600)
-    text = r.stderr[r.stderr.find("cassie_depth_kernel"):]
-    val = lambda key: int(re.search(key + r"[^:\n]*: *(\d+)", text).group(1))
-    try:
-        return {"vgprs": val("VGPRs"), "sgprs": val("TotalSGPRs"), "scratch_bytes_per_lane": val("ScratchSize"), "lds_bytes": val("LDS Size"),
-                "waves_per_simd": val("Occupancy"), "vgpr_spills": val("VGPRs Spill"), "sgpr_spills": val("SGPRs Spill"),
-                "compiled": "csrc/depth_kernel.h alone, with the Makefile's HIPFLAGS (phys_batch.hip includes the same header)"}
-    except AttributeError:
-        return None
+    out = {"compiled": "csrc/depth_kernel.h alone, with the Makefile's HIPFLAGS (phys_batch.hip includes the same header)"}
+    for kernel in KERNELS:
+        at = re.search(r"Function Name: \w*%d%sE" % (len(kernel), kernel), r.stderr)
+        if not at:
+            return None
+        text = r.stderr[at.start():]
+        val = lambda key: int(re.search(key + r"[^:\n]*: *(\d+)", text).group(1))
+        try:
+            out[kernel] = {"vgprs": val("VGPRs"), "sgprs": val("TotalSGPRs"), "scratch_bytes_per_lane": val("ScratchSize"), "lds_bytes": val("LDS Size"),
+                           "waves_per_simd": val("Occupancy"), "vgpr_spills": val("VGPRs Spill"), "sgpr_spills": val("SGPRs Spill")}
+        except AttributeError:
+            return None
+    return out
 
 
-def regions(model, n, size, launches, warmup, repeats):
+def regions(model, n, size, launches, warmup, repeats, all_geoms=False):
     pod = model.pod
     b = Batch(model, n)
     try:
@@ -95,6 +108,8 @@ def regions(model, n, size, launches, warmup, repeats):
         init_row = torch.from_numpy(np.concatenate([model.qpos_init(), sens0])).cuda()
         if size:
             b.configure_depth(pod.root_body[0], CAM_POS, camera_quat(PITCH), size[0], size[1], FOVY, NEAR, FAR)
+            if all_geoms:
+                b.depth_geoms(moving=True)
         b.sync()
         torch.cuda.synchronize()
         streams, half = [torch.cuda.Stream(), torch.cuda.Stream()], n // 2
@@ -142,6 +157,10 @@ def regions(model, n, size, launches, warmup, repeats):
             info["image"] = [size[0], size[1]]
             info["depth_value_range"] = [float(v.min()), float(v.max())]
             info["fraction_of_rays_that_hit"] = float((v < FAR).mean())
+            try:
+                info["launches_static_kernel_scene_kernel"] = list(b.depth_launches())
+            except AttributeError:          # (--parent-lib: a build of the library from before the scene kernel)
+                pass
         return info
     finally:
         b.close()
@@ -155,7 +174,8 @@ def main():
     ap.add_argument("--repeats", type=int, default=10)
     ap.add_argument("--only", choices=list(SETTINGS), default=None, help="one setting only (e.g. under a kernel trace)")
     ap.add_argument("--out", default=None, help="also write the JSON line to this file")
-    ap.add_argument("--resources-only", action="store_true", help="the kernel's resources alone: no leg is run (needs hipcc, no GPU)")
+    ap.add_argument("--resources-only", action="store_true", help="the kernels' resources alone: no leg is run (needs hipcc, no GPU)")
+    ap.add_argument("--parent-lib", default=None, help="another build of the library (the parent commit's): its depth_64x48 leg, in a child process")
     a = ap.parse_args()
     model = None if a.resources_only else Model("cassie_hfield")
     out = {"tool": "depth_rate", "model": "cassie_hfield", "envs": a.envs, "substeps_per_launch": NSUB, "launches_per_region": a.launches,
@@ -163,15 +183,27 @@ def main():
            "mode": "CM_DRIVE_PD_SAFE, 50 fused substeps per launch, two env ranges on two streams, a bank of terrains with a per-env index, "
                    "restarts on the benchmark's schedule (config 4); the depth image per range behind its step launch",
            "camera": {"body": "pelvis", "pos": list(CAM_POS), "pitch_down_deg": PITCH, "fovy_deg": FOVY, "near": NEAR, "far": FAR},
-           "yardstick": "no_depth", "kernel": "cassie_depth_kernel", "kernel_resources": kernel_resources()}
+           "yardstick": "no_depth", "kernels": list(KERNELS), "kernel_resources": kernel_resources()}
+    if a.parent_lib and not a.resources_only:
+        # (first, in a process of its own: one library per process; this process has not touched the GPU yet)
+        cmd = [sys.executable, os.path.abspath(__file__), "--only", "depth_64x48", "--envs", str(a.envs), "--launches", str(a.launches),
+               "--warmup", str(a.warmup), "--repeats", str(a.repeats)]
+        r = subprocess.run(cmd, env=dict(os.environ, CASSIE_LIB=os.path.abspath(a.parent_lib)), capture_output=True, text=True, timeout=900)
+        if r.returncode != 0:
+            sys.exit("the --parent-lib leg failed:\n" + r.stderr[-2000:])
+        out["parent_depth_64x48"] = json.loads(r.stdout.strip().splitlines()[-1])["depth_64x48"]
     for name, size in SETTINGS.items():
         if a.only in (None, name) and not a.resources_only:
-            out[name] = regions(model, a.envs, size, a.launches, a.warmup, a.repeats)
+            out[name] = regions(model, a.envs, size, a.launches, a.warmup, a.repeats, all_geoms=name in ALL_GEOMS)
     if "no_depth" in out:
         base = out["no_depth"]["env_steps_per_s_median"]
         for name in SETTINGS:
             if name != "no_depth" and name in out:
                 out[name]["cost_of_the_loop_percent"] = 100.0 * (1.0 - out[name]["env_steps_per_s_median"] / base)
+    if "parent_depth_64x48" in out and "depth_64x48" in out:
+        par, med = out["parent_depth_64x48"], out["depth_64x48"]["env_steps_per_s_median"]
+        out["static_leg_median_within_the_parents_regions"] = bool(par["env_steps_per_s_min"] <= med <= par["env_steps_per_s_max"])
+        out["static_leg_median_over_parent_median"] = med / par["env_steps_per_s_median"]
     line = json.dumps(out)
     print(line)
     if a.out:
