@@ -136,6 +136,13 @@ def _declare(L):
         L.phys_batch_end_episodes.argtypes = [vp, c.c_int, c.c_int, c.c_int, vp, vp, vp]
         L.phys_batch_download_episodes.argtypes = [vp, c.c_int, vp]
         L.phys_sizeof_episode_rules.restype = c.c_size_t
+    if hasattr(L, "phys_batch_place_configure"):   # (absent from older variant builds selected with CASSIE_LIB)
+        L.phys_batch_place_configure.argtypes = [vp, c.c_int, vp, c.c_int, c.c_double]
+        L.phys_batch_place_ptr.restype = vp
+        L.phys_batch_place_ptr.argtypes = [vp, c.c_int]
+        L.phys_batch_place_bind.argtypes = [vp, c.c_int, vp]
+        L.phys_batch_place_upload.argtypes = [vp, c.c_int, vp, c.c_int, c.c_int]
+        L.phys_batch_place_download.argtypes = [vp, c.c_int, vp]
     if hasattr(L, "phys_batch_set_hfield_bank"):   # (absent from older variant builds selected with CASSIE_LIB)
         L.phys_batch_set_hfield_bank.argtypes = [vp, vp, c.c_int, c.c_int, c.c_int]
         L.phys_batch_nterrain.argtypes = [vp]

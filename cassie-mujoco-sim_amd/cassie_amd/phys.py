@@ -33,6 +33,7 @@ WARN_CONTACT_FULL, WARN_CONSTRAINT_FULL, WARN_UNSUPPORTED_PAIR, WARN_DIVERGED = 
 WARN_CHUNK_PLACEMENT = 16   # a chunk of a stepping launch found its predecessor on another XCD: the env's state may be stale, discard its results
 WARN_TERRAIN_INDEX = 32     # the env's terrain index lay outside the bank and was clamped to it
 WARN_SCAN_TILTED = 64       # height scan: the env's height-field geom is tilted out of the world's z axis and was left out
+WARN_PLACE_MISS = 128       # placed restart: the footprint met no ground anywhere, the env was put down at ground_ref
 SCAN_MAXPOINTS = 1024
 DEPTH_MAXPIXELS = 16384
 
@@ -47,6 +48,9 @@ SIZE_NGEOM = 5               # PHYS_NGEOM: geoms in the host model's full list
 # episodes on the device: bits of an env's reason word (CM_DONE_* in cm_model.h) and the per-env arrays (PHYS_EP_* in cassie_phys.h)
 DONE_HEIGHT, DONE_UPRIGHT, DONE_TIME, DONE_WARN, DONE_NONFINITE, DONE_FORCED = 1, 2, 4, 8, 16, 32
 EP_DONE, EP_REASON, EP_STEPS, EP_COUNT, EP_TERMINAL = range(5)
+# placed restarts: the per-env arrays (PHYS_PLACE_* in cassie_phys.h)
+PLACE_POSE, PLACE_NEXT_TERRAIN, PLACE_GROUND = range(3)
+PLACE_MAXPOINTS = 1024
 
 # joint configuration the reference writes at init (reference src/cassiemujoco.c:1023-1028)
 QPOS_INIT_JOINTS = np.array(
@@ -481,10 +485,60 @@ class Batch:
         the int32 device array force_ptr[n] is non-zero), writes EP_DONE / EP_REASON, and for the envs that ended keeps the
         terminal state, counts the episode and -- with `restart` -- restarts them from bank row pick_ptr[i] (int32 device array
         [n]; default (env + episodes ended) % rows): state from the row, time / ctrl / warm start / drive-level state /
-        measurement block zero, warning word clear."""
+        measurement block zero, warning word clear.
+
+        Once configure_placement has named an anchor, a restart is PLACED (include/cassie_phys.h: "placed restarts"): the env first takes
+        its next terrain (PLACE_NEXT_TERRAIN, if bound and a bank is set), the row's moving root bodies -- the pelvis, the cube of
+        cassie_tray_box -- are turned by the env's yaw about the vertical through the anchor and shifted by (dx, dy, dz + G - ground_ref),
+        G = the highest ground under the placed footprint (PLACE_GROUND[env]; ground_ref without a footprint or where nothing is hit,
+        then with WARN_PLACE_MISS); their linear qvel / qacc entries, the framequat and the magnetometer are turned along, every other
+        entry is the row's (the accelerometer, qacc and rangefinders are those of the ground the row was recorded on until the first
+        substep replaces them); the warning word is cleared and then holds WARN_TERRAIN_INDEX / WARN_SCAN_TILTED / WARN_PLACE_MISS as
+        the placement raised them.  The pose (0, 0, 0, 0) with no footprint leaves what an unplaced restart leaves."""
         n = self.nenv - env0 if n is None else n
         if lib().phys_batch_end_episodes(self._h, int(env0), int(n), 1 if restart else 0, pick_ptr, force_ptr, stream) != 0:
             raise RuntimeError("end_episodes failed: " + (lib().phys_last_error() or b"").decode())
+
+    # ---- placed restarts (phys_batch_place_configure) ----
+    def configure_placement(self, anchor, footprint_xy=None, ground_ref=0.0):
+        """Restarts of end_episodes are placed from now on: `anchor` is a child of the world whose pose follows from qpos alone (Cassie's
+        pelvis: pod.root_body[0]); footprint_xy [P][2] (P <= PLACE_MAXPOINTS; None or empty: no ground following) are the points, in the
+        anchor's heading frame after placement, under which the ground is looked up; ground_ref is the world z of the ground the bank's
+        rows were recorded on.  anchor <= 0 turns placement off again.  Waits for the batch's streams."""
+        a = np.zeros((0, 2)) if footprint_xy is None else np.ascontiguousarray(footprint_xy, dtype=np.float64)
+        if a.size == 0:
+            a = a.reshape(0, 2)
+        if a.ndim != 2 or a.shape[1] != 2:
+            raise ValueError("configure_placement: footprint_xy must be [P][2]")
+        if lib().phys_batch_place_configure(self._h, int(anchor), a.ctypes.data if a.shape[0] else None, a.shape[0], float(ground_ref)) != 0:
+            raise ValueError("configure_placement failed: " + (lib().phys_last_error() or b"").decode())
+
+    def placement_ptr(self, which):
+        """Device pointer of a placement array: PLACE_POSE float64 [nenv][4] (dx, dy, dz, yaw), PLACE_GROUND float64 [nenv], or the bound
+        PLACE_NEXT_TERRAIN int32 [nenv] (None while none is bound: the batch keeps none of its own)."""
+        return lib().phys_batch_place_ptr(self._h, int(which))
+
+    def bind_placement(self, which, device_ptr):
+        """Caller-owned HBM (a torch tensor's data_ptr()) in the place of a placement array; None un-binds: the batch's own array again
+        (zeros), for PLACE_NEXT_TERRAIN none -- restarts then leave the terrain index alone."""
+        if lib().phys_batch_place_bind(self._h, int(which), device_ptr) != 0:
+            raise RuntimeError("bind_placement failed: " + (lib().phys_last_error() or b"").decode())
+
+    def set_placement(self, poses, env0=0):
+        """Host upload of spawn poses [n][4] = (dx, dy, dz, yaw) for envs env0 ... into PLACE_POSE (the batch's own array or the bound
+        one); waits for the batch's streams."""
+        a = np.ascontiguousarray(poses, dtype=np.float64).reshape(-1, 4)
+        if env0 < 0 or env0 + a.shape[0] > self.nenv:
+            raise ValueError("set_placement: envs [%d, %d) are not in the batch" % (env0, env0 + a.shape[0]))
+        if lib().phys_batch_place_upload(self._h, PLACE_POSE, a.ctypes.data, int(env0), a.shape[0]) != 0:
+            raise RuntimeError("set_placement failed: " + (lib().phys_last_error() or b"").decode())
+
+    def placement_ground(self):
+        """PLACE_GROUND downloaded: the ground height found at every env's last placed restart; waits for the batch's streams."""
+        out = np.zeros(self.nenv)
+        if lib().phys_batch_place_download(self._h, PLACE_GROUND, out.ctypes.data) != 0:
+            raise RuntimeError("placement_ground failed: " + (lib().phys_last_error() or b"").decode())
+        return out
 
     def episode_ptr(self, which):
         """Device pointer of an episode array (EP_DONE / EP_REASON / EP_STEPS / EP_COUNT: int32 [nenv]; EP_TERMINAL: float64

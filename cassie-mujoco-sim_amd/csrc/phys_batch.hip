@@ -117,6 +117,13 @@ struct phys_batch {
     DevBuf<char> d_ep[PHYS_EP_ARRAYS]; /* (ints, or doubles: PHYS_EP_TERMINAL; the batch's own or a caller's) */
     DevBuf<const double> d_ep_bank;    /* (a copy of the host's rows, or the caller's device rows) */
     int ep_bank_rows = 0;
+    /* placed restarts (phys_batch_place_configure): the anchor (0: off), the footprint and the table of what a placement moves
+     * (worked out of the model once) in HBM, and the per-env arrays PHYS_PLACE_* (the batch's own or a caller's; no next-terrain array unless bound) */
+    int place_anchor = 0, place_points = 0;
+    double place_ground_ref = 0;
+    DevBuf<ck::PlaceTable> d_place_table;
+    DevBuf<double> d_place_offsets, d_place_pose, d_place_ground;
+    DevBuf<int> d_place_next;
 };
 
 static bool hip_ok(hipError_t e, const char *what) {
@@ -842,6 +849,7 @@ int phys_batch_episode_bind(phys_batch_t *b, int which, void *device_ptr) {
     b->d_ep[which].borrow((char *)device_ptr);
     return 0;
 }
+static bool ensure_place_arrays(phys_batch *b);
 int phys_batch_end_episodes(phys_batch_t *b, int env0, int n, int restart, const int *pick, const int *force, void *stream) {
     if (!b) return -1;
     if (!b->episodes) { phys_set_last_error("phys_batch_end_episodes: call phys_batch_episodes_enable first"); return -1; }
@@ -860,9 +868,24 @@ int phys_batch_end_episodes(phys_batch_t *b, int env0, int n, int restart, const
     io.done = (int *)b->d_ep[PHYS_EP_DONE].get(); io.reason = (int *)b->d_ep[PHYS_EP_REASON].get(); io.steps = (int *)b->d_ep[PHYS_EP_STEPS].get();
     io.count = (int *)b->d_ep[PHYS_EP_COUNT].get(); io.terminal = (double *)b->d_ep[PHYS_EP_TERMINAL].get();
     io.bank = b->d_ep_bank; io.pick = pick; io.force = force;
+    const bool placed = restart && b->place_anchor > 0;
+    if (placed) {
+        if (b->model_stride != 0) { phys_set_last_error("phys_batch_end_episodes: placed restarts and per-env models (phys_batch_set_model with env >= 0) do not mix"); return -1; }
+        if (!ensure_place_arrays(b)) return -1;
+        io.place_anchor = b->place_anchor; io.place_npoints = b->place_points; io.place_ground_ref = b->place_ground_ref;
+        io.place_table = b->d_place_table;
+        io.place_offsets = b->d_place_offsets; io.place_pose = b->d_place_pose; io.place_ground = b->d_place_ground;
+        /* what the surface reads, as phys_batch_height_scan hands it over; the next terrains count only while a bank is set */
+        io.model = b->d_models; io.envparams = b->d_envparams;
+        io.hfield = b->d_hfield; io.hfield_stride = b->hfield_stride;
+        if (b->nterrain > 0) { io.hfield_index = b->d_terrain_index; io.hfield_nterrain = b->nterrain; io.place_next = b->d_place_next; }
+    }
     hipStream_t s = launch_stream(b, stream);
-    hipLaunchKernelGGL(ck::cassie_episode_kernel, dim3((unsigned)(n < ck::EPISODE_GRID ? n : ck::EPISODE_GRID)), dim3(WV_WAVE), 0, s, io);
-    return hip_ok(hipGetLastError(), "cassie_episode_kernel launch") ? 0 : -1;
+    /* (one launch either way, on the same few workgroups: EPISODE_GRID's reason holds for both kernels) */
+    const dim3 grid((unsigned)(n < ck::EPISODE_GRID ? n : ck::EPISODE_GRID));
+    if (placed) hipLaunchKernelGGL(ck::cassie_episode_place_kernel, grid, dim3(WV_WAVE), 0, s, io);
+    else hipLaunchKernelGGL(ck::cassie_episode_kernel, grid, dim3(WV_WAVE), 0, s, io);
+    return hip_ok(hipGetLastError(), placed ? "cassie_episode_place_kernel launch" : "cassie_episode_kernel launch") ? 0 : -1;
 }
 int phys_batch_download_episodes(phys_batch_t *b, int which, void *host) {
     if (!b || !host || which < 0 || which >= PHYS_EP_ARRAYS || !b->d_ep[which]) { phys_set_last_error("phys_batch_download_episodes: bad arguments, or episodes not enabled"); return -1; }
@@ -973,6 +996,83 @@ int phys_batch_height_scan(phys_batch_t *b, int env0, int n, void *stream) {
     hipStream_t s = launch_stream(b, stream);
     hipLaunchKernelGGL(ck::cassie_scan_kernel, dim3((unsigned)(n < ck::SCAN_GRID ? n : ck::SCAN_GRID)), dim3(WV_WAVE), 0, s, io);
     return hip_ok(hipGetLastError(), "cassie_scan_kernel launch") ? 0 : -1;
+}
+
+/* ------------------------------------------------ placed restarts ---- */
+/* the batch's own pose (zeros) and ground arrays, unless the caller's are bound */
+static bool ensure_place_arrays(phys_batch *b) {
+    if (!b->d_place_pose && !b->d_place_pose.alloc(4 * (size_t)b->nenv, true, "placement poses")) return false;
+    if (!b->d_place_ground && !b->d_place_ground.alloc((size_t)b->nenv, true, "placement ground")) return false;
+    return true;
+}
+int phys_batch_place_configure(phys_batch_t *b, int anchor, const double *offsets_xy, int npoints, double ground_ref) {
+    if (!b) return -1;
+    (void)hipSetDevice(b->device);
+    if (anchor <= 0) {           /* off again: restarts copy the row verbatim */
+        if (!quiesce(b)) return -1;
+        b->place_anchor = 0;
+        return 0;
+    }
+    if (npoints < 0 || npoints > ck::PLACE_MAXPOINTS || (npoints > 0 && !offsets_xy) || !(ground_ref == ground_ref)) {
+        phys_set_last_error("phys_batch_place_configure: a footprint of 0 .. 1024 points and a ground height");
+        return -1;
+    }
+    if (b->model_stride != 0) { phys_set_last_error("phys_batch_place_configure: not with per-env models (phys_batch_set_model with env >= 0)"); return -1; }
+    ck::PlaceTable tab;
+    memset(&tab, 0, sizeof tab);
+    if (const char *why = ck::place_classify(b->host_model, anchor, tab)) {
+        phys_set_last_error((std::string("phys_batch_place_configure: ") + why).c_str());
+        return -1;
+    }
+    if (!quiesce(b)) return -1;  /* (launches in flight may be reading the footprint that goes away) */
+    DevBuf<double> off;
+    DevBuf<ck::PlaceTable> dtab;
+    if (!dtab.alloc(1, false, "placement table")) return -1;
+    if (!hip_ok(hipMemcpy(dtab, &tab, sizeof tab, hipMemcpyHostToDevice), "hipMemcpy(placement table)")) return -1;
+    if (npoints > 0) {
+        if (!off.alloc(2 * (size_t)npoints, false, "placement footprint")) return -1;
+        if (!hip_ok(hipMemcpy(off, offsets_xy, sizeof(double) * 2 * (size_t)npoints, hipMemcpyHostToDevice), "hipMemcpy(placement footprint)")) return -1;
+    }
+    if (!ensure_place_arrays(b)) return -1;
+    b->d_place_offsets = std::move(off);
+    b->d_place_table = std::move(dtab);
+    b->place_anchor = anchor; b->place_points = npoints; b->place_ground_ref = ground_ref;
+    return 0;
+}
+void *phys_batch_place_ptr(phys_batch_t *b, int which) {
+    if (!b || which < 0 || which >= PHYS_PLACE_ARRAYS) return nullptr;
+    (void)hipSetDevice(b->device);
+    if (which == PHYS_PLACE_NEXT_TERRAIN) return (void *)b->d_place_next.get();   /* (null unless bound: the batch keeps none of its own) */
+    if (!ensure_place_arrays(b)) return nullptr;
+    return which == PHYS_PLACE_POSE ? (void *)b->d_place_pose.get() : (void *)b->d_place_ground.get();
+}
+int phys_batch_place_bind(phys_batch_t *b, int which, void *device_ptr) {
+    if (!b || which < 0 || which >= PHYS_PLACE_ARRAYS) { phys_set_last_error("phys_batch_place_bind: bad arguments"); return -1; }
+    (void)hipSetDevice(b->device);
+    /* (as phys_batch_bind: launches already queued keep the pointer they were given; hipFree waits for the device by itself.  NULL:
+     * the batch's own array again -- zeros -- or, for the next terrains, none) */
+    if (which == PHYS_PLACE_NEXT_TERRAIN) b->d_place_next.borrow((int *)device_ptr);
+    else {
+        DevBuf<double> &d = which == PHYS_PLACE_POSE ? b->d_place_pose : b->d_place_ground;
+        d.borrow((double *)device_ptr);
+        if (!device_ptr && !ensure_place_arrays(b)) return -1;
+    }
+    return 0;
+}
+
+static size_t place_row_bytes(int which) { return which == PHYS_PLACE_POSE ? 4 * sizeof(double) : which == PHYS_PLACE_GROUND ? sizeof(double) : sizeof(int); }
+int phys_batch_place_upload(phys_batch_t *b, int which, const void *host, int env0, int n) {
+    if (!b || !host || which < 0 || which >= PHYS_PLACE_ARRAYS || !range_ok(b, env0, n)) { phys_set_last_error("phys_batch_place_upload: bad arguments"); return -1; }
+    char *dst = (char *)phys_batch_place_ptr(b, which);
+    if (!dst) { phys_set_last_error("phys_batch_place_upload: no such array (bind the next terrains first)"); return -1; }
+    const size_t row = place_row_bytes(which);
+    return quiesce(b) && hip_ok(hipMemcpy(dst + row * (size_t)env0, host, row * (size_t)n, hipMemcpyHostToDevice), "placement array upload") ? 0 : -1;
+}
+int phys_batch_place_download(phys_batch_t *b, int which, void *host) {
+    if (!b || !host || which < 0 || which >= PHYS_PLACE_ARRAYS) { phys_set_last_error("phys_batch_place_download: bad arguments"); return -1; }
+    const char *src = (const char *)phys_batch_place_ptr(b, which);
+    if (!src) { phys_set_last_error("phys_batch_place_download: no such array (bind the next terrains first)"); return -1; }
+    return quiesce(b) && hip_ok(hipMemcpy(host, src, place_row_bytes(which) * (size_t)b->nenv, hipMemcpyDeviceToHost), "placement array download") ? 0 : -1;
 }
 
 /* ------------------------------------------------ the depth image ---- */

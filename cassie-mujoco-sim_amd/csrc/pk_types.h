@@ -26,7 +26,8 @@ constexpr int NSTAMP = 48;   /* 0..15 stage boundaries, 16..32 sub-stage stamps,
 enum { WARN_CONTACT_FULL = 1, WARN_CONSTRAINT_FULL = 2, WARN_UNSUPPORTED_PAIR = 4, WARN_DIVERGED = 8,
        WARN_CHUNK_PLACEMENT = 16 /* a chunk of a launch found the chunk before it on another XCD (cassie_step_kernel): state possibly stale */,
        WARN_TERRAIN_INDEX = 32   /* the env's terrain index (PhysIO::hfield_index) lay outside the bank: clamped to its first / last terrain */,
-       WARN_SCAN_TILTED = 64     /* phys_batch_height_scan: the env's height-field geom is tilted out of the world's z axis and was left out of the scan */ };
+       WARN_SCAN_TILTED = 64     /* phys_batch_height_scan: the env's height-field geom is tilted out of the world's z axis and was left out of the scan */,
+       WARN_PLACE_MISS = 128     /* a placed restart (phys_batch_place_configure) whose footprint met no ground: the env was put down at ground_ref */ };
 
 #ifndef WV_OCC
 #define WV_OCC

@@ -155,8 +155,9 @@ int phys_batch_set_hfield_env(phys_batch_t *b, int env, const float *data, int n
  *                                phys_last_error() for an id outside it; returns once the copy is done) or device memory (asynchronous),
  *                                in order on `stream` (NULL: the batch's own) like phys_batch_randomize.
  * An index outside the bank that reaches the device is CLAMPED to [0, nterrain - 1], never followed, and raises bit 32 of the env's
- * warning word (WARN_TERRAIN_INDEX).  The bank's terrains must agree where restarted envs are put down: start states do not follow
- * the terrain's height.  A batch that never sets a bank runs exactly as before. */
+ * warning word (WARN_TERRAIN_INDEX).  Start states follow the terrain's height only through PLACED RESTARTS (phys_batch_place_configure,
+ * below): without them a restart copies its bank row verbatim, and the bank's terrains must agree where restarted envs are put down.
+ * A batch that never sets a bank runs exactly as before. */
 int phys_batch_set_hfield_bank(phys_batch_t *b, const float *grids, int on_device, int nterrain, int n);
 int phys_batch_nterrain(const phys_batch_t *b);   /* terrains of the bank in use, 0 = none */
 void *phys_batch_terrain_index_ptr(phys_batch_t *b);
@@ -356,6 +357,70 @@ int phys_batch_end_episodes(phys_batch_t *b, int env0, int n, int restart, const
 /* one whole episode array to the host (int32 [nenv], or double [nenv][nq + nv] for PHYS_EP_TERMINAL); waits for the batch's streams */
 int phys_batch_download_episodes(phys_batch_t *b, int which, void *host);
 size_t phys_sizeof_episode_rules(void);
+/* PLACED RESTARTS: a restarted env is put down at a pose of its own, on the ground it finds there -- a curriculum's envs no longer all
+ * restart at the row's spot and heading, a terrain (or a stair box moved under the spawn point) no longer buries or drops the robot,
+ * and the env's NEXT terrain is chosen inside the restart, which can therefore see the ground it is about to stand on.  Still one
+ * launch per env range per policy step, no host read.
+ *
+ * phys_batch_place_configure(b, anchor, offsets_xy, npoints, ground_ref), once per batch (it waits for the batch's streams, like
+ * phys_batch_scan_configure; anchor <= 0 turns placement off again):
+ *   anchor        a body that is a child of the world and whose pose follows from qpos alone (the height scan's restriction:
+ *                 Cassie's pelvis);
+ *   offsets_xy    a footprint o[npoints][2], 0 <= npoints <= 1024, host memory; npoints == 0: no ground following;
+ *   ground_ref    the world z of the ground the bank's rows were recorded on.
+ * Per-env arrays in HBM, indexed by the absolute env, the batch's own (phys_batch_place_ptr) or a caller's (phys_batch_place_bind; NULL
+ * un-binds), handled like the episode arrays:
+ *   PHYS_PLACE_POSE          double [nenv][4] = (dx, dy, dz, yaw)   input; the batch's own array starts as zeros
+ *   PHYS_PLACE_NEXT_TERRAIN  int32  [nenv]                          optional input: used only while bound and a bank of terrains is set
+ *                                                                   (the batch has none of its own: NULL = unused)
+ *   PHYS_PLACE_GROUND        double [nenv]                          output: the ground height G found at the env's last placed restart
+ *
+ * With placement configured, step 4 of phys_batch_end_episodes -- the restart of an env that ended; `row` is the bank row step 4 picks
+ * -- becomes:
+ *   1. Terrain.  If a next-terrain array is bound (and a bank is set): index[env] = clamp(next[env], 0, nterrain - 1); an id outside the
+ *      bank raises WARN_TERRAIN_INDEX.  The step launches queued behind on the stream read the new index.  (With no array bound the
+ *      index stays; if the ground lookup of step 3 has to clamp it, that raises the bit as well.)
+ *   2. Anchor.  a = (ax, ay): the anchor's world x, y in the row (its pose from the row's qpos, as the scan computes it, the joint
+ *      quaternion normalised); psi its heading by the scan's formula, atan2(2 (w z + x y), 1 - 2 (y y + z z)).
+ *   3. Ground.  The footprint's world points are F_j = (ax + dx, ay + dy) + Rz(psi + yaw) o_j: the heading frame of the anchor AFTER
+ *      placement, the height scan's own convention.  G = max_j S(F_j) over the points that hit, S exactly the height scan's surface
+ *      (phys_batch_height_scan above): static planes, boxes and the height field; the env's own geom poses once geometry is
+ *      randomised; the env's terrain grid after step 1; a tilted height-field geom is left out and raises WARN_SCAN_TILTED.  If no
+ *      point hits, or npoints == 0, G = ground_ref; with npoints > 0 and no hit, bit 128 of the warning word (WARN_PLACE_MISS) is
+ *      raised too.  PHYS_PLACE_GROUND[env] = G.
+ *   4. Rigid motion.  T(p) = p + (dx, dy, h) + (Rz(yaw) - I)(p - (ax, ay, p_z)), h = dz + G - ground_ref: a turn by yaw about the
+ *      vertical through the anchor, then a shift.  Every MOVING ROOT body (a child of the world with at least one joint: the pelvis,
+ *      and the cube of cassie_tray_box.xml) gets T applied to its world pose in the row: position T(p), quaternion Qz(yaw) (x) q,
+ *      Qz(yaw) = (cos yaw/2, 0, 0, sin yaw/2), q the body's joint quaternion as the row has it (not normalised).  Only the joint
+ *      coordinates of those roots change; every other qpos entry is the row's.  A moving root must have a free joint, or three slides
+ *      along the world's x, y and z (one each) followed by a ball at the body's origin, the body frame the world's at qpos0 (the pelvis
+ *      of all three models) -- the make-ups whose joint coordinates can take ANY world pose; anything else makes the configure call
+ *      fail with -1 and a phys_last_error() message.
+ *   5. qvel and qacc.  The linear entries of those roots are world-frame vectors and are turned by Rz(yaw): the free joint's first
+ *      three entries, or the slides' velocities taken together as a vector.  Angular entries (ball or free: body-local) and everything
+ *      else are the row's.
+ *   6. sensordata.  framequat becomes Qz(yaw) (x) value; magnetometer becomes R_s'^T B, clamped at the sensor's cutoff as the step
+ *      does, R_s' the rotation of Qz(yaw) (x) (bq_row (x) sensor_squat), bq_row the world quaternion of the sensor's body in the row, B
+ *      the model's magnetic field -- for yaw != 0; a yaw of exactly 0 turns no frame and leaves the row's words.  Both need the
+ *      sensor's site on a moving root body (configure fails with -1 otherwise; at most eight such sensors).  Every other entry is the
+ *      row's: joint and actuator positions, gyro, accelerometer, rangefinder.  THE ACCELEROMETER, QACC (up to the turn of step 5) AND THE
+ *      RANGEFINDERS ARE THEREFORE THOSE OF THE GROUND THE ROW WAS RECORDED ON, contact forces included; the first substep replaces
+ *      them.  The rest of step 4 is unchanged: time, ctrl, warm start zero; measurement block and drive-level state zero once a drive
+ *      mode is in use; steps = 0.
+ *   7. Warning word: cleared as before, then the bits of steps 1 and 3 are set.
+ * IDENTITY: the pose (0, 0, 0, 0) with npoints == 0 leaves exactly what an unplaced restart leaves (as compared with ==: -0.0 may
+ * stand for 0.0) -- the turn is applied as (Rz(yaw) - I), which adds exact zeros at yaw = 0.  A batch that never configures placement
+ * runs phys_batch_end_episodes exactly as before, with the same kernel; so does a call with restart == 0.
+ * Not done: roll and pitch are not aligned to a slope, the legs are not bent to the ground, per-env MODELS (phys_batch_set_model with
+ * env >= 0) are refused, by the configure call and by phys_batch_end_episodes. */
+enum { PHYS_PLACE_POSE, PHYS_PLACE_NEXT_TERRAIN, PHYS_PLACE_GROUND, PHYS_PLACE_ARRAYS };
+int phys_batch_place_configure(phys_batch_t *b, int anchor, const double *offsets_xy, int npoints, double ground_ref);
+void *phys_batch_place_ptr(phys_batch_t *b, int which);
+int phys_batch_place_bind(phys_batch_t *b, int which, void *device_ptr);
+/* host rows [n] of a placement array (4 doubles, 1 int32 or 1 double each) into envs [env0, env0 + n) of the array in use, and one whole
+ * array to the host; both wait for the batch's streams.  -1 for PHYS_PLACE_NEXT_TERRAIN while none is bound. */
+int phys_batch_place_upload(phys_batch_t *b, int which, const void *host, int env0, int n);
+int phys_batch_place_download(phys_batch_t *b, int which, void *host);
 /* the read-out half of mj_forward -- what the reference's getters obtain from mj_kinematics / mj_comPos / mj_comVel /
  * mj_fwdPosition (reference src/cassiemujoco.c:1223-1301, :1604-1770): xpos / xquat / the ext read-out / body_cfrc of the
  * current state, while the fields qacc, sensordata and actuator_velocity keep what the last STEP left (the encoder and
