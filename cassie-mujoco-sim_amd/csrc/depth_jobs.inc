@@ -11,8 +11,8 @@
     const long long njobs = (long long)io.n * tiles;
     for (long long job = wv::env_id(); job < njobs; job += wv::grid_size()) {
         const int env = io.env0 + (int)(job / tiles), tile = (int)(job % tiles);
-        const ModelPtr m = (ModelPtr)(io.models + (size_t)env * io.model_stride);
-        const ParamPtr PG = (io.envparams && m->env_geom) ? (ParamPtr)(io.envparams + (size_t)env) : (ParamPtr)&m->params;
+        const ModelPtr m = env_model(io.models, io.model_stride, env);
+        const ParamPtr PG = env_geometry(io.envparams, m, (size_t)env);
         /* the camera's world pose (wave-uniform) */
         double bp[3], bq[4], Rb[9], cp[3], cq[4], wq[4], Rc[9], off[3];
         static_body_pose(m, io.body, io.qpos + (size_t)env * io.sq, bp, bq);

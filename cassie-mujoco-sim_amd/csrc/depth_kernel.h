@@ -8,7 +8,7 @@
 #ifndef CASSIE_DEPTH_KERNEL_H
 #define CASSIE_DEPTH_KERNEL_H
 
-#include "small_kernels.h"
+#include "surface_kernels.h"
 
 namespace ck {
 

@@ -20,8 +20,7 @@
 
 #include "cassie_phys.h"
 #include "device_mem.h"
-#include "depth_kernel.h"
-#include "small_kernels.h"
+#include "small_launch.h"
 #include "step_launch.h"
 #include "step_policy.h"
 
@@ -46,19 +45,12 @@ struct phys_batch {
      * (PhysIO::hfield_index; the array is created on first use and may be the caller's) */
     int nterrain = 0;
     DevBuf<int> d_terrain_index;
-    /* the height scan (phys_batch_scan_configure): the pattern in HBM, its body and range */
+    /* what the kernels around the step kernel are configured with (small_launch.h: the records a launch's arguments are built from);
+     * a pointer into one of the batch's buffers is filled in at the launch, from the buffer */
+    ck::ScanCfg scan = {};          /* the height scan (phys_batch_scan_configure): its pattern is d_scan_offsets */
     DevBuf<double> d_scan_offsets;
-    int scan_points = 0, scan_body = 0;
-    double scan_range = 0;
-    /* the depth image (phys_batch_depth_configure): the camera, and the caller's per-env extrinsics when bound (phys_batch_depth_bind_pose) */
-    int depth_width = 0, depth_height = 0, depth_body = 0;
-    double depth_tan_half = 0, depth_near = 0, depth_far = 0, depth_cam_pos[3] = {0, 0, 0}, depth_cam_quat[4] = {1, 0, 0, 0};
-    DevBuf<const double> d_depth_pose;
-    /* ... the geoms it renders (phys_batch_depth_set_geoms; the default until then), the caller's hit-id image when bound
-     * (phys_batch_depth_bind_ids), and how many launches each of the two kernels has had (phys_batch_debug_depth_launches) */
-    unsigned depth_geoms = 0;
-    DevBuf<int> d_depth_ids;
-    long long depth_launches[2] = {0, 0};
+    ck::DepthCfg depth = {};        /* the depth image (phys_batch_depth_configure, _bind_pose, _set_geoms, _bind_ids: the caller's arrays) */
+    long long depth_launches[2] = {0, 0}; /* launches of the static / the scene kernel (phys_batch_debug_depth_launches) */
     hipStream_t stream = nullptr;
     hipStream_t recent_streams[4] = {nullptr, nullptr, nullptr, nullptr}; /* streams of the most recent launches (callers may pass
                                        their own, and ranges of one batch may be in flight on several at once) */
@@ -111,19 +103,16 @@ struct phys_batch {
     size_t ev_used = 0;
 
     DevBuf<double> d_scratch_out;    /* [nenv][nv + nsensordata + nu]: where phys_batch_forward_kinematics sends qacc / sensordata / actuator_velocity */
-    /* episodes on the device (phys_batch_end_episodes): the rules, the per-env arrays PHYS_EP_* and the bank of start states */
+    /* episodes on the device (phys_batch_end_episodes): the rules, the bank's rows (ep), the per-env arrays PHYS_EP_* and the bank */
     bool episodes = false;
-    cm_episode_rules_t ep_rules;
+    ck::EpisodeCfg ep = {};
     DevBuf<char> d_ep[PHYS_EP_ARRAYS]; /* (ints, or doubles: PHYS_EP_TERMINAL; the batch's own or a caller's) */
     DevBuf<const double> d_ep_bank;    /* (a copy of the host's rows, or the caller's device rows) */
-    int ep_bank_rows = 0;
     /* placed restarts (phys_batch_place_configure): the anchor (0: off), the footprint and the table of what a placement moves
-     * (worked out of the model once) in HBM, and the per-env arrays PHYS_PLACE_* (the batch's own or a caller's; no next-terrain array unless bound) */
-    int place_anchor = 0, place_points = 0;
-    double place_ground_ref = 0;
+     * (worked out of the model once) in HBM, and the per-env arrays PHYS_PLACE_* (the batch's own or a caller's; the next terrains the caller's only) */
+    ck::PlaceCfg place = {};
     DevBuf<ck::PlaceTable> d_place_table;
     DevBuf<double> d_place_offsets, d_place_pose, d_place_ground;
-    DevBuf<int> d_place_next;
 };
 
 static bool hip_ok(hipError_t e, const char *what) {
@@ -207,17 +196,23 @@ static bool strided_ok(const phys_batch *b, int first, int stride, int count) {
     return first >= 0 && stride >= 1 && count >= 0 && (count == 0 || (size_t)first + (size_t)(count - 1) * (size_t)stride < (size_t)b->nenv);
 }
 
-/* what ResetIO and EpisodeIO share: sizes, row strides and the state arrays a restart writes */
-template <class IO>
-static void fill_state_block(const phys_batch *b, IO &io) {
-    const cm_model_t &m = b->host_model;
-    io.nq = m.nq; io.nv = m.nv; io.nu = m.nu; io.nsd = m.nsensordata;
-    io.sq = b->stride[PHYS_F_QPOS]; io.sqv = b->stride[PHYS_F_QVEL]; io.ssd = b->stride[PHYS_F_SENSORDATA];
-    io.qpos = b->d_field[PHYS_F_QPOS]; io.qvel = b->d_field[PHYS_F_QVEL]; io.warm = b->d_field[PHYS_F_QACC_WARMSTART];
-    io.ctrl = b->d_field[PHYS_F_CTRL]; io.qacc = b->d_field[PHYS_F_QACC]; io.time = b->d_field[PHYS_F_TIME];
-    io.sens = b->d_field[PHYS_F_SENSORDATA]; io.actvel = b->d_field[PHYS_F_ACTUATOR_VELOCITY];
-    io.meas = b->d_drive ? b->d_field[PHYS_F_MEAS].get() : nullptr;
-    io.drive = b->d_drive;
+/* what the kernels around the step kernel read of the batch (small_launch.h), as make_io hands the same to the step kernel */
+static ck::BatchView view_of(const phys_batch *b) {
+    ck::BatchView v = {b->d_models, b->model_stride, b->d_envparams, b->d_hfield, b->hfield_stride, b->d_terrain_index, b->nterrain};
+    ck::view_sizes(v, b->host_model);
+    v.sq = b->stride[PHYS_F_QPOS]; v.sqv = b->stride[PHYS_F_QVEL]; v.ssd = b->stride[PHYS_F_SENSORDATA];
+    v.qpos = b->d_field[PHYS_F_QPOS]; v.qvel = b->d_field[PHYS_F_QVEL]; v.warm = b->d_field[PHYS_F_QACC_WARMSTART];
+    v.ctrl = b->d_field[PHYS_F_CTRL]; v.qacc = b->d_field[PHYS_F_QACC]; v.time = b->d_field[PHYS_F_TIME];
+    v.sens = b->d_field[PHYS_F_SENSORDATA]; v.actvel = b->d_field[PHYS_F_ACTUATOR_VELOCITY];
+    v.meas = b->d_drive ? b->d_field[PHYS_F_MEAS].get() : nullptr;
+    v.drive = b->d_drive; v.warn = b->d_warn;
+    v.xpos = b->d_field[PHYS_F_XPOS]; v.xquat = b->d_field[PHYS_F_XQUAT];
+    return v;
+}
+/* the refusal of an entry point: its name in front of a check's message (small_launch.h) */
+static int refuse(const char *entry, const char *why) {
+    phys_set_last_error((std::string(entry) + ": " + why).c_str());
+    return -1;
 }
 
 /* The step kernel's instantiations per model family, by form (step_plan.h; null: the family has no such form).  Each is instantiated
@@ -671,8 +666,8 @@ int phys_batch_bind_strided(phys_batch_t *b, int field, void *device_ptr, int ro
             return -1;
         }
     }
-    if (field == PHYS_F_HEIGHT_SCAN && b->scan_points <= 0) { phys_set_last_error("phys_batch_bind: configure the scan first (phys_batch_scan_configure sizes PHYS_F_HEIGHT_SCAN)"); return -1; }
-    if (field == PHYS_F_DEPTH && b->depth_width <= 0) { phys_set_last_error("phys_batch_bind: configure the depth image first (phys_batch_depth_configure sizes PHYS_F_DEPTH)"); return -1; }
+    if (field == PHYS_F_HEIGHT_SCAN && b->scan.npoints <= 0) { phys_set_last_error("phys_batch_bind: configure the scan first (phys_batch_scan_configure sizes PHYS_F_HEIGHT_SCAN)"); return -1; }
+    if (field == PHYS_F_DEPTH && b->depth.width <= 0) { phys_set_last_error("phys_batch_bind: configure the depth image first (phys_batch_depth_configure sizes PHYS_F_DEPTH)"); return -1; }
     (void)hipSetDevice(b->device);
     /* no stream synchronisation: launches already queued keep the pointers they were given, and hipFree of the
      * replaced buffer waits for the device by itself */
@@ -790,13 +785,8 @@ int phys_batch_reset_envs(phys_batch_t *b, int first, int stride, int count, con
     if (!b || !qpos_row || !strided_ok(b, first, stride, count)) return -1;
     (void)hipSetDevice(b->device);
     if (count == 0) return 0;
-    ck::ResetIO io;
-    memset(&io, 0, sizeof io);
-    fill_state_block(b, io);
-    io.first = first; io.stride = stride; io.count = count;
-    io.qpos_row = qpos_row; io.sens_row = sens_row;
     hipStream_t s = launch_stream(b, stream);
-    hipLaunchKernelGGL(ck::cassie_reset_kernel, dim3(count < 4 ? count : 4), dim3(WV_WAVE), 0, s, io);
+    hipLaunchKernelGGL(ck::cassie_reset_kernel, dim3(ck::reset_grid(count)), dim3(WV_WAVE), 0, s, ck::make_reset_io(view_of(b), first, stride, count, qpos_row, sens_row));
     return hip_ok(hipGetLastError(), "cassie_reset_kernel launch") ? 0 : -1;
 }
 
@@ -815,7 +805,7 @@ int phys_batch_episodes_enable(phys_batch_t *b, const cm_episode_rules_t *rules)
         if (!hip_ok(hipDeviceSynchronize(), "episode arrays sync")) return -1;
         b->episodes = true;
     }
-    b->ep_rules = *rules; /* (passed to every launch by value: launches already queued keep the rules they were given) */
+    b->ep.rules = *rules; /* (passed to every launch by value: launches already queued keep the rules they were given) */
     return 0;
 }
 int phys_batch_episode_row_dim(const phys_batch_t *b) {
@@ -827,7 +817,7 @@ int phys_batch_episodes_set_bank(phys_batch_t *b, const double *rows, int on_dev
     if (!b || !rows || nrows <= 0) { phys_set_last_error("phys_batch_episodes_set_bank: bad arguments"); return -1; }
     (void)hipSetDevice(b->device);
     if (!quiesce(b)) return -1; /* (launches in flight may be reading the bank that goes away) */
-    b->d_ep_bank.reset(); b->ep_bank_rows = 0;
+    b->d_ep_bank.reset(); b->ep.nrows = 0;
     if (on_device) b->d_ep_bank.borrow(rows);
     else {
         const size_t count = (size_t)nrows * (size_t)phys_batch_episode_row_dim(b);
@@ -836,7 +826,7 @@ int phys_batch_episodes_set_bank(phys_batch_t *b, const double *rows, int on_dev
         if (!hip_ok(hipMemcpy((void *)d.get(), rows, sizeof(double) * count, hipMemcpyHostToDevice), "hipMemcpy(reset bank)")) return -1;
         b->d_ep_bank = std::move(d);
     }
-    b->ep_bank_rows = nrows;
+    b->ep.nrows = nrows;
     return 0;
 }
 void *phys_batch_episode_ptr(phys_batch_t *b, int which) {
@@ -854,35 +844,24 @@ int phys_batch_end_episodes(phys_batch_t *b, int env0, int n, int restart, const
     if (!b) return -1;
     if (!b->episodes) { phys_set_last_error("phys_batch_end_episodes: call phys_batch_episodes_enable first"); return -1; }
     if (!range_ok(b, env0, n)) { phys_set_last_error("phys_batch_end_episodes: env range out of bounds"); return -1; }
-    if (restart && (!b->d_ep_bank || b->ep_bank_rows <= 0)) { phys_set_last_error("phys_batch_end_episodes: restart needs a bank of start states (phys_batch_episodes_set_bank)"); return -1; }
+    if (restart && (!b->d_ep_bank || b->ep.nrows <= 0)) { phys_set_last_error("phys_batch_end_episodes: restart needs a bank of start states (phys_batch_episodes_set_bank)"); return -1; }
     for (int a = 0; a < PHYS_EP_ARRAYS; ++a) if (!b->d_ep[a]) { phys_set_last_error("phys_batch_end_episodes: an episode array is missing"); return -1; }
     (void)hipSetDevice(b->device);
     if (n == 0) return 0;
-    ck::EpisodeIO io;
-    memset(&io, 0, sizeof io);
-    fill_state_block(b, io);
-    io.env0 = env0; io.n = n; io.restart = restart ? 1 : 0; io.nrows = b->ep_bank_rows;
-    io.row_dim = phys_batch_episode_row_dim(b);
-    io.rules = b->ep_rules;
-    io.warn = b->d_warn;
-    io.done = (int *)b->d_ep[PHYS_EP_DONE].get(); io.reason = (int *)b->d_ep[PHYS_EP_REASON].get(); io.steps = (int *)b->d_ep[PHYS_EP_STEPS].get();
-    io.count = (int *)b->d_ep[PHYS_EP_COUNT].get(); io.terminal = (double *)b->d_ep[PHYS_EP_TERMINAL].get();
-    io.bank = b->d_ep_bank; io.pick = pick; io.force = force;
-    const bool placed = restart && b->place_anchor > 0;
+    const bool placed = restart && b->place.anchor > 0;
     if (placed) {
         if (b->model_stride != 0) { phys_set_last_error("phys_batch_end_episodes: placed restarts and per-env models (phys_batch_set_model with env >= 0) do not mix"); return -1; }
         if (!ensure_place_arrays(b)) return -1;
-        io.place_anchor = b->place_anchor; io.place_npoints = b->place_points; io.place_ground_ref = b->place_ground_ref;
-        io.place_table = b->d_place_table;
-        io.place_offsets = b->d_place_offsets; io.place_pose = b->d_place_pose; io.place_ground = b->d_place_ground;
-        /* what the surface reads, as phys_batch_height_scan hands it over; the next terrains count only while a bank is set */
-        io.model = b->d_models; io.envparams = b->d_envparams;
-        io.hfield = b->d_hfield; io.hfield_stride = b->hfield_stride;
-        if (b->nterrain > 0) { io.hfield_index = b->d_terrain_index; io.hfield_nterrain = b->nterrain; io.place_next = b->d_place_next; }
     }
+    ck::EpisodeCfg e = b->ep;
+    ck::PlaceCfg place = b->place;
+    place.table = b->d_place_table; place.offsets = b->d_place_offsets; place.pose = b->d_place_pose; place.ground = b->d_place_ground;
+    e.bank = b->d_ep_bank;
+    e.done = (int *)b->d_ep[PHYS_EP_DONE].get(); e.reason = (int *)b->d_ep[PHYS_EP_REASON].get(); e.steps = (int *)b->d_ep[PHYS_EP_STEPS].get();
+    e.count = (int *)b->d_ep[PHYS_EP_COUNT].get(); e.terminal = (double *)b->d_ep[PHYS_EP_TERMINAL].get();
+    const ck::EpisodeIO io = ck::make_episode_io(view_of(b), e, placed ? &place : nullptr, env0, n, restart, pick, force);
     hipStream_t s = launch_stream(b, stream);
-    /* (one launch either way, on the same few workgroups: EPISODE_GRID's reason holds for both kernels) */
-    const dim3 grid((unsigned)(n < ck::EPISODE_GRID ? n : ck::EPISODE_GRID));
+    const dim3 grid((unsigned)ck::episode_grid(n));   /* (one launch either way, on the same few workgroups) */
     if (placed) hipLaunchKernelGGL(ck::cassie_episode_place_kernel, grid, dim3(WV_WAVE), 0, s, io);
     else hipLaunchKernelGGL(ck::cassie_episode_kernel, grid, dim3(WV_WAVE), 0, s, io);
     return hip_ok(hipGetLastError(), placed ? "cassie_episode_place_kernel launch" : "cassie_episode_kernel launch") ? 0 : -1;
@@ -948,22 +927,10 @@ int phys_batch_set_terrain(phys_batch_t *b, const int *ids, int on_device, int e
 }
 
 /* ------------------------------------------------ the height scan ---- */
-/* the body a scan pattern or a camera hangs on: a child of the world whose pose follows from qpos alone */
-static bool body_pose_from_qpos(const phys_batch *b, int body) {
-    const cm_model_t &m = b->host_model;
-    if (body <= 0 || body >= m.nbody) return false;
-    const int rt = m.body_kin[body].rot_type;
-    return m.kin_simple && m.body_parentid[body] == 0 && b->model_stride == 0 && (rt == CM_JNT_BALL || rt == CM_JNT_FREE || rt == -1);
-}
 int phys_batch_scan_configure(phys_batch_t *b, const double *offsets_xy, int npoints, int body, double range) {
-    if (!b || !offsets_xy || npoints <= 0 || npoints > ck::SCAN_MAXPOINTS || !(range > 0)) {
-        phys_set_last_error("phys_batch_scan_configure: 1 .. 1024 points and a positive range");
-        return -1;
-    }
-    if (!body_pose_from_qpos(b, body)) {
-        phys_set_last_error("phys_batch_scan_configure: the body must be a child of the world whose joints are slides and at most a ball or free joint (a shared kin_simple model)");
-        return -1;
-    }
+    if (!b) return refuse("phys_batch_scan_configure", ck::SCAN_SIZE_REFUSAL);
+    ck::ScanCfg cfg;
+    if (const char *why = ck::scan_configure(b->host_model, b->model_stride, offsets_xy, npoints, body, range, cfg)) return refuse("phys_batch_scan_configure", why);
     (void)hipSetDevice(b->device);
     if (!quiesce(b)) return -1;
     DevBuf<double> off, out;
@@ -974,27 +941,20 @@ int phys_batch_scan_configure(phys_batch_t *b, const double *offsets_xy, int npo
     b->d_scan_offsets = std::move(off);
     b->d_field[PHYS_F_HEIGHT_SCAN] = std::move(out);
     b->dim[PHYS_F_HEIGHT_SCAN] = npoints; b->stride[PHYS_F_HEIGHT_SCAN] = npoints;
-    b->scan_points = npoints; b->scan_body = body; b->scan_range = range;
+    b->scan = cfg;
     return 0;
 }
 int phys_batch_height_scan(phys_batch_t *b, int env0, int n, void *stream) {
     if (!b) return -1;
-    if (b->scan_points <= 0 || !b->d_field[PHYS_F_HEIGHT_SCAN]) { phys_set_last_error("phys_batch_height_scan: call phys_batch_scan_configure first"); return -1; }
+    if (b->scan.npoints <= 0 || !b->d_field[PHYS_F_HEIGHT_SCAN]) { phys_set_last_error("phys_batch_height_scan: call phys_batch_scan_configure first"); return -1; }
     if (!range_ok(b, env0, n)) { phys_set_last_error("phys_batch_height_scan: env range out of bounds"); return -1; }
     (void)hipSetDevice(b->device);
     if (n == 0) return 0;
-    ck::ScanIO io;
-    memset(&io, 0, sizeof io);
-    io.models = b->d_models; io.model_stride = b->model_stride; io.envparams = b->d_envparams;
-    io.env0 = env0; io.n = n; io.npoints = b->scan_points; io.body = b->scan_body; io.range = b->scan_range;
-    io.offsets = b->d_scan_offsets;
-    io.qpos = b->d_field[PHYS_F_QPOS]; io.sq = b->stride[PHYS_F_QPOS];
-    io.out = b->d_field[PHYS_F_HEIGHT_SCAN]; io.sout = b->stride[PHYS_F_HEIGHT_SCAN];
-    io.hfield = b->d_hfield; io.hfield_stride = b->hfield_stride;
-    if (b->nterrain > 0) { io.hfield_index = b->d_terrain_index; io.hfield_nterrain = b->nterrain; }
-    io.warn = b->d_warn;
     hipStream_t s = launch_stream(b, stream);
-    hipLaunchKernelGGL(ck::cassie_scan_kernel, dim3((unsigned)(n < ck::SCAN_GRID ? n : ck::SCAN_GRID)), dim3(WV_WAVE), 0, s, io);
+    ck::ScanCfg scan = b->scan;
+    scan.offsets = b->d_scan_offsets;
+    hipLaunchKernelGGL(ck::cassie_scan_kernel, dim3((unsigned)ck::scan_grid(n)), dim3(WV_WAVE), 0, s,
+                       ck::make_scan_io(view_of(b), scan, b->d_field[PHYS_F_HEIGHT_SCAN], b->stride[PHYS_F_HEIGHT_SCAN], env0, n));
     return hip_ok(hipGetLastError(), "cassie_scan_kernel launch") ? 0 : -1;
 }
 
@@ -1010,20 +970,11 @@ int phys_batch_place_configure(phys_batch_t *b, int anchor, const double *offset
     (void)hipSetDevice(b->device);
     if (anchor <= 0) {           /* off again: restarts copy the row verbatim */
         if (!quiesce(b)) return -1;
-        b->place_anchor = 0;
+        b->place.anchor = 0;
         return 0;
     }
-    if (npoints < 0 || npoints > ck::PLACE_MAXPOINTS || (npoints > 0 && !offsets_xy) || !(ground_ref == ground_ref)) {
-        phys_set_last_error("phys_batch_place_configure: a footprint of 0 .. 1024 points and a ground height");
-        return -1;
-    }
-    if (b->model_stride != 0) { phys_set_last_error("phys_batch_place_configure: not with per-env models (phys_batch_set_model with env >= 0)"); return -1; }
     ck::PlaceTable tab;
-    memset(&tab, 0, sizeof tab);
-    if (const char *why = ck::place_classify(b->host_model, anchor, tab)) {
-        phys_set_last_error((std::string("phys_batch_place_configure: ") + why).c_str());
-        return -1;
-    }
+    if (const char *why = ck::place_configure(b->host_model, b->model_stride, anchor, offsets_xy, npoints, ground_ref, tab)) return refuse("phys_batch_place_configure", why);
     if (!quiesce(b)) return -1;  /* (launches in flight may be reading the footprint that goes away) */
     DevBuf<double> off;
     DevBuf<ck::PlaceTable> dtab;
@@ -1036,13 +987,13 @@ int phys_batch_place_configure(phys_batch_t *b, int anchor, const double *offset
     if (!ensure_place_arrays(b)) return -1;
     b->d_place_offsets = std::move(off);
     b->d_place_table = std::move(dtab);
-    b->place_anchor = anchor; b->place_points = npoints; b->place_ground_ref = ground_ref;
+    b->place.anchor = anchor; b->place.npoints = npoints; b->place.ground_ref = ground_ref;
     return 0;
 }
 void *phys_batch_place_ptr(phys_batch_t *b, int which) {
     if (!b || which < 0 || which >= PHYS_PLACE_ARRAYS) return nullptr;
     (void)hipSetDevice(b->device);
-    if (which == PHYS_PLACE_NEXT_TERRAIN) return (void *)b->d_place_next.get();   /* (null unless bound: the batch keeps none of its own) */
+    if (which == PHYS_PLACE_NEXT_TERRAIN) return (void *)b->place.next;   /* (null unless bound: the batch keeps none of its own) */
     if (!ensure_place_arrays(b)) return nullptr;
     return which == PHYS_PLACE_POSE ? (void *)b->d_place_pose.get() : (void *)b->d_place_ground.get();
 }
@@ -1051,7 +1002,7 @@ int phys_batch_place_bind(phys_batch_t *b, int which, void *device_ptr) {
     (void)hipSetDevice(b->device);
     /* (as phys_batch_bind: launches already queued keep the pointer they were given; hipFree waits for the device by itself.  NULL:
      * the batch's own array again -- zeros -- or, for the next terrains, none) */
-    if (which == PHYS_PLACE_NEXT_TERRAIN) b->d_place_next.borrow((int *)device_ptr);
+    if (which == PHYS_PLACE_NEXT_TERRAIN) b->place.next = (const int *)device_ptr;
     else {
         DevBuf<double> &d = which == PHYS_PLACE_POSE ? b->d_place_pose : b->d_place_ground;
         d.borrow((double *)device_ptr);
@@ -1076,31 +1027,11 @@ int phys_batch_place_download(phys_batch_t *b, int which, void *host) {
 }
 
 /* ------------------------------------------------ the depth image ---- */
-static unsigned depth_all_geoms(const cm_model_t &m) { return m.ngeom >= 32 ? 0xffffffffu : (1u << m.ngeom) - 1u; }
-static unsigned depth_default_geoms(const cm_model_t &m) {
-    unsigned mask = 0;
-    for (int g = 0; g < m.ngeom; ++g) {
-        const int gt = m.geom_type[g];
-        if (m.body_weldid[m.geom_bodyid[g]] == 0 && (gt == CM_GEOM_PLANE || gt == CM_GEOM_BOX || gt == CM_GEOM_HFIELD)) mask |= 1u << g;
-    }
-    return mask;
-}
 int phys_batch_depth_configure(phys_batch_t *b, int body, const double *cam_pos, const double *cam_quat, int width, int height, double fovy,
                                double znear, double zfar) {
-    if (!b || !cam_pos || !cam_quat || width < 1 || height < 1 || (long long)width * height > ck::DEPTH_MAXPIXELS) {
-        phys_set_last_error("phys_batch_depth_configure: an image of 1 .. 16384 pixels and a camera pose");
-        return -1;
-    }
-    if (!(fovy > 0 && fovy < 3.14159265358979323846) || !(znear > 0 && znear < zfar)) {
-        phys_set_last_error("phys_batch_depth_configure: 0 < fovy < pi (radians) and 0 < near < far");
-        return -1;
-    }
-    const double qn = cam_quat[0] * cam_quat[0] + cam_quat[1] * cam_quat[1] + cam_quat[2] * cam_quat[2] + cam_quat[3] * cam_quat[3];
-    if (!(qn > 0)) { phys_set_last_error("phys_batch_depth_configure: the camera's quaternion is zero"); return -1; }
-    if (!body_pose_from_qpos(b, body)) {
-        phys_set_last_error("phys_batch_depth_configure: the body must be a child of the world whose joints are slides and at most a ball or free joint (a shared kin_simple model)");
-        return -1;
-    }
+    if (!b) return refuse("phys_batch_depth_configure", ck::DEPTH_SIZE_REFUSAL);
+    ck::DepthCfg cfg;
+    if (const char *why = ck::depth_configure(b->host_model, b->model_stride, body, cam_pos, cam_quat, width, height, fovy, znear, zfar, cfg)) return refuse("phys_batch_depth_configure", why);
     (void)hipSetDevice(b->device);
     if (!quiesce(b)) return -1;
     /* the field takes the image's size: a buffer of the batch's own of the new size (a caller's binding is dropped: bind again) */
@@ -1108,29 +1039,24 @@ int phys_batch_depth_configure(phys_batch_t *b, int body, const double *cam_pos,
     if (!out.alloc((size_t)width * (size_t)height * (size_t)b->nenv, true, "depth image")) return -1;
     b->d_field[PHYS_F_DEPTH] = std::move(out);
     b->dim[PHYS_F_DEPTH] = width * height; b->stride[PHYS_F_DEPTH] = width * height;
-    b->depth_width = width; b->depth_height = height; b->depth_body = body;
-    b->depth_tan_half = tan(0.5 * fovy); b->depth_near = znear; b->depth_far = zfar;
-    for (int k = 0; k < 3; ++k) b->depth_cam_pos[k] = cam_pos[k];
-    for (int k = 0; k < 4; ++k) b->depth_cam_quat[k] = cam_quat[k];
-    b->depth_geoms = depth_default_geoms(b->host_model);
-    b->d_depth_ids.reset();             /* (the image may have another size: bind the ids again) */
+    cfg.pose = b->depth.pose;           /* (the default geoms again, and no ids -- the image may have another size: bind them again) */
+    b->depth = cfg;
     return 0;
 }
-unsigned phys_batch_depth_default_geoms(const phys_batch_t *b) { return b ? depth_default_geoms(b->host_model) : 0u; }
-unsigned phys_batch_depth_all_geoms(const phys_batch_t *b) { return b ? depth_all_geoms(b->host_model) : 0u; }
+unsigned phys_batch_depth_default_geoms(const phys_batch_t *b) { return b ? ck::depth_default_geoms(b->host_model) : 0u; }
+unsigned phys_batch_depth_all_geoms(const phys_batch_t *b) { return b ? ck::depth_all_geoms(b->host_model) : 0u; }
 int phys_batch_depth_set_geoms(phys_batch_t *b, unsigned mask) {
     if (!b) return -1;
-    if (b->depth_width <= 0) { phys_set_last_error("phys_batch_depth_set_geoms: call phys_batch_depth_configure first (it restores the default set)"); return -1; }
-    if (mask & ~depth_all_geoms(b->host_model)) { phys_set_last_error("phys_batch_depth_set_geoms: the mask names a geom at or above ngeom"); return -1; }
+    if (b->depth.width <= 0) { phys_set_last_error("phys_batch_depth_set_geoms: call phys_batch_depth_configure first (it restores the default set)"); return -1; }
+    if (const char *why = ck::check_depth_geoms(b->host_model, mask)) return refuse("phys_batch_depth_set_geoms", why);
     /* (as phys_batch_bind: launches already queued keep the mask they were given) */
-    b->depth_geoms = mask;
+    b->depth.geoms = mask;
     return 0;
 }
 int phys_batch_depth_bind_ids(phys_batch_t *b, void *device_ptr) {
     if (!b) return -1;
-    if (b->depth_width <= 0) { phys_set_last_error("phys_batch_depth_bind_ids: call phys_batch_depth_configure first (it sizes the image)"); return -1; }
-    (void)hipSetDevice(b->device);
-    b->d_depth_ids.borrow((int *)device_ptr);
+    if (b->depth.width <= 0) { phys_set_last_error("phys_batch_depth_bind_ids: call phys_batch_depth_configure first (it sizes the image)"); return -1; }
+    b->depth.ids = (int *)device_ptr;
     return 0;
 }
 int phys_batch_debug_depth_launches(const phys_batch_t *b, long long *static_kernel, long long *scene_kernel) {
@@ -1141,48 +1067,23 @@ int phys_batch_debug_depth_launches(const phys_batch_t *b, long long *static_ker
 }
 int phys_batch_depth_bind_pose(phys_batch_t *b, const void *device_ptr) {
     if (!b) return -1;
-    (void)hipSetDevice(b->device);
-    /* (as phys_batch_bind: launches already queued keep the pointer they were given) */
-    b->d_depth_pose.borrow((const double *)device_ptr);
+    b->depth.pose = (const double *)device_ptr;   /* (as phys_batch_bind: launches already queued keep the pointer they were given) */
     return 0;
 }
 int phys_batch_depth_image(phys_batch_t *b, int env0, int n, void *stream) {
     if (!b) return -1;
-    if (b->depth_width <= 0 || !b->d_field[PHYS_F_DEPTH]) { phys_set_last_error("phys_batch_depth_image: call phys_batch_depth_configure first"); return -1; }
+    if (b->depth.width <= 0 || !b->d_field[PHYS_F_DEPTH]) { phys_set_last_error("phys_batch_depth_image: call phys_batch_depth_configure first"); return -1; }
     if (!range_ok(b, env0, n)) { phys_set_last_error("phys_batch_depth_image: env range out of bounds"); return -1; }
     (void)hipSetDevice(b->device);
     if (n == 0) return 0;
-    ck::DepthIO io;
-    memset(&io, 0, sizeof io);
-    io.models = b->d_models; io.model_stride = b->model_stride; io.envparams = b->d_envparams;
-    io.env0 = env0; io.n = n; io.body = b->depth_body; io.width = b->depth_width; io.height = b->depth_height;
-    io.tan_half = b->depth_tan_half; io.znear = b->depth_near; io.zfar = b->depth_far;
-    for (int k = 0; k < 3; ++k) io.cam_pos[k] = b->depth_cam_pos[k];
-    for (int k = 0; k < 4; ++k) io.cam_quat[k] = b->depth_cam_quat[k];
-    io.pose = b->d_depth_pose;
-    io.qpos = b->d_field[PHYS_F_QPOS]; io.sq = b->stride[PHYS_F_QPOS];
-    io.out = b->d_field[PHYS_F_DEPTH]; io.sout = b->stride[PHYS_F_DEPTH];
-    io.hfield = b->d_hfield; io.hfield_stride = b->hfield_stride;
-    if (b->nterrain > 0) { io.hfield_index = b->d_terrain_index; io.hfield_nterrain = b->nterrain; }
-    io.warn = b->d_warn;
-    const int T = ck::DEPTH_TILE;
-    const long long jobs = (long long)n * (((b->depth_width + T - 1) / T) * ((b->depth_height + T - 1) / T));
     hipStream_t s = launch_stream(b, stream);
-    const dim3 grid((unsigned)(jobs < ck::DEPTH_GRID ? jobs : ck::DEPTH_GRID));
-    /* the static kernel unless the caller has chosen other geoms than the default or wants the ids: the default image is the static
-     * kernel's, bit for bit and at its cost */
-    const bool scene = b->depth_geoms != depth_default_geoms(b->host_model) || b->d_depth_ids;
+    const bool scene = ck::depth_scene_kernel(b->host_model, b->depth);
+    const ck::DepthIO io = ck::make_depth_io(view_of(b), b->depth, b->d_field[PHYS_F_DEPTH], b->stride[PHYS_F_DEPTH], env0, n, scene);
+    const dim3 grid((unsigned)ck::depth_grid(n, b->depth.width, b->depth.height));
     ++b->depth_launches[scene ? 1 : 0];
-    if (!scene) {
-        hipLaunchKernelGGL(ck::cassie_depth_kernel, grid, dim3(WV_WAVE), 0, s, io);
-        return hip_ok(hipGetLastError(), "cassie_depth_kernel launch") ? 0 : -1;
-    }
-    io.geoms = b->depth_geoms;
-    io.xpos = b->d_field[PHYS_F_XPOS]; io.xquat = b->d_field[PHYS_F_XQUAT];
-    io.sxp = 3 * b->host_model.nbody; io.sxq = 4 * b->host_model.nbody;   /* (rows as the step kernel writes them: make_io's sb) */
-    io.ids = b->d_depth_ids;
-    hipLaunchKernelGGL(ck::cassie_depth_scene_kernel, grid, dim3(WV_WAVE), 0, s, io);
-    return hip_ok(hipGetLastError(), "cassie_depth_scene_kernel launch") ? 0 : -1;
+    if (scene) hipLaunchKernelGGL(ck::cassie_depth_scene_kernel, grid, dim3(WV_WAVE), 0, s, io);
+    else hipLaunchKernelGGL(ck::cassie_depth_kernel, grid, dim3(WV_WAVE), 0, s, io);
+    return hip_ok(hipGetLastError(), scene ? "cassie_depth_scene_kernel launch" : "cassie_depth_kernel launch") ? 0 : -1;
 }
 
 int phys_batch_sync(phys_batch_t *b) {
@@ -1230,13 +1131,8 @@ int phys_batch_derive(phys_batch_t *b, const int ids[6], void *stream) {
     const bool had_ext = b->d_ext != nullptr;
     if (!had_ext && phys_batch_enable_ext(b, 1) != 0) return -1;
     int rc = launch(b, 1, 0, s); /* forward: the read-out of the current state */
-    ck::DeriveIO io;
-    memset(&io, 0, sizeof io);
-    io.models = b->d_models; io.model_stride = b->model_stride; io.nenv = b->nenv; io.envparams = b->d_envparams;
-    io.ext = b->d_ext; io.xpos = b->d_field[PHYS_F_XPOS]; io.xquat = b->d_field[PHYS_F_XQUAT];
-    io.derived = b->d_field[PHYS_F_DERIVED]; io.qM = b->d_field[PHYS_F_QM];
-    for (int i = 0; i < 6; ++i) io.ids[i] = ids[i];
-    hipLaunchKernelGGL(ck::cassie_derive_kernel, dim3(b->nenv), dim3(WV_WAVE), 0, s, io);
+    hipLaunchKernelGGL(ck::cassie_derive_kernel, dim3(b->nenv), dim3(WV_WAVE), 0, s,
+                       ck::make_derive_io(view_of(b), b->nenv, b->d_ext, b->d_field[PHYS_F_DERIVED], b->d_field[PHYS_F_QM], ids));
     rc |= hip_ok(hipGetLastError(), "cassie_derive_kernel launch") ? 0 : -1;
     if (!had_ext) {
         /* the read-out buffer is 20 KB per env and makes every step write it: keep it only for the caller who asked for it */
@@ -1278,10 +1174,8 @@ static bool ensure_envparams(phys_batch *b) {
     return true;
 }
 static int launch_setconst(phys_batch *b, int env0, int n, int derive_inertial, hipStream_t s) {
-    ck::SetConstIO io;
-    io.model = b->d_models; io.params = b->d_envparams; io.env0 = env0; io.nenv = n; io.derive_inertial = derive_inertial;
-    /* one wave per env, at most a few thousand workgroups walking the range (58 KB of LDS each: two to a CU) */
-    hipLaunchKernelGGL(ck::cassie_setconst_kernel, dim3((unsigned)(n < 2048 ? n : 2048)), dim3(WV_WAVE), 0, s, io);
+    hipLaunchKernelGGL(ck::cassie_setconst_kernel, dim3((unsigned)ck::setconst_grid(n)), dim3(WV_WAVE), 0, s,
+                       ck::make_setconst_io(b->d_models, b->d_envparams, env0, n, derive_inertial));
     return hip_ok(hipGetLastError(), "cassie_setconst_kernel launch") ? 0 : -1;
 }
 /* the shared model's cm_model_t::env_geom / env_springs word (at `off`): from now on the step kernel reads that group from the blocks
@@ -1307,7 +1201,7 @@ int phys_batch_randomize(phys_batch_t *b, int param, const double *values, int o
         if (!hip_ok(hipMemcpyAsync(staged, values, sizeof(double) * count, hipMemcpyHostToDevice, s), "hipMemcpy(parameter rows)")) return -1;
         src = staged;
     }
-    hipLaunchKernelGGL(ck::cassie_param_scatter_kernel, dim3((unsigned)(n < 1024 ? n : 1024)), dim3(WV_WAVE), 0, s, b->d_envparams.get(),
+    hipLaunchKernelGGL(ck::cassie_param_scatter_kernel, dim3((unsigned)ck::param_scatter_grid(n)), dim3(WV_WAVE), 0, s, b->d_envparams.get(),
                        (int)(PARAM_TABLE[param].off / sizeof(double)), dim, src, env0, n);
     int rc = hip_ok(hipGetLastError(), "cassie_param_scatter_kernel launch") ? 0 : -1;
     /* friction needs no set_const in the reference (mj_contactParam mixes the geoms' values at every step): the pairs' mixed

@@ -1,0 +1,206 @@
+/*
+ * small_launch.h -- how the kernels around the step kernel (small_kernels.h, surface_kernels.h, depth_kernel.h, episode_kernels.h) are
+ * launched: the records a kernel's arguments are built from, one builder per kernel that returns its filled argument struct for an env
+ * range, the grid of every launch, and the checks of what a caller configures, each returning the message of its refusal (null: fine).
+ * Pure host code, no HIP runtime calls, in the spirit of step_policy.h: the launcher (phys_batch.hip) keeps the records in the batch,
+ * prefixes a message with its entry point's name and launches what a builder returns on the grid given here; the wave emulator's entry
+ * points (tests/emu) fill the same records from their arguments and go through the same builders, grids and checks, so a CPU test of
+ * one of these kernels also runs the launcher's refusals, grid and choice of kernel (tests/test_small_launch.py pins them one by one).
+ * No field of ScanIO, DepthIO, EpisodeIO, ResetIO, DeriveIO or SetConstIO is assigned anywhere else.
+ */
+#ifndef CASSIE_SMALL_LAUNCH_H
+#define CASSIE_SMALL_LAUNCH_H
+
+#include <cmath>
+#include <cstring>
+
+#include "depth_kernel.h"
+#include "episode_kernels.h"
+#include "small_kernels.h"
+
+namespace ck {
+
+/* ---- the records ---- */
+
+/* What the kernels read of the batch, whatever they compute.  The surface source: the model(s), the envs' parameter blocks (null: the
+ * model's own), the height field(s) and -- while a bank of terrains is set, hfield_nterrain > 0 -- the envs' index into it, which a
+ * placed restart WRITES; all as the fields of PhysIO of the same names.  The state rows: the model's sizes, the doubles between the rows
+ * of qpos / qvel / sensordata, the arrays a restart writes (meas, drive: null until a drive mode is in use), the sticky warning word, and
+ * the body poses the last step launch or forward pass stored (rows of 3 nbody / 4 nbody doubles). */
+struct BatchView {
+    const cm_model_t *models; int model_stride;
+    const cm_envparams_t *envparams;
+    const float *hfield; size_t hfield_stride; int *hfield_index; int hfield_nterrain;
+    int nq, nv, nu, nsd, nbody, sq, sqv, ssd;
+    double *qpos, *qvel, *warm, *ctrl, *qacc, *time, *sens, *actvel, *meas;
+    cm_drive_state_t *drive;
+    int *warn;
+    const double *xpos, *xquat;
+};
+/* the sizes of a view from the (host's copy of the) shared model, with dense rows */
+inline void view_sizes(BatchView &v, const cm_model_t &m) {
+    v.nq = m.nq; v.nv = m.nv; v.nu = m.nu; v.nsd = m.nsensordata; v.nbody = m.nbody; v.sq = m.nq; v.sqv = m.nv; v.ssd = m.nsensordata;
+}
+/* the height scan (phys_batch_scan_configure; npoints 0: not configured): the pattern [npoints][2], its body and range */
+struct ScanCfg { int npoints, body; double range; const double *offsets; };
+/* the depth image (phys_batch_depth_configure; width 0: not configured): the camera on its body, tan(fovy / 2), the caller's per-env
+ * extrinsics (null: the shared pose), the geoms it renders and the caller's hit-id image (null: none) */
+struct DepthCfg { int width, height, body; double tan_half, znear, zfar, cam_pos[3], cam_quat[4]; const double *pose; unsigned geoms; int *ids; };
+/* placed restarts (phys_batch_place_configure; anchor 0: off): the footprint [npoints][2], the table of what a placement moves, and the
+ * per-env arrays: poses [nenv][4], next terrains [nenv] (null: none bound), ground heights [nenv] */
+struct PlaceCfg { int anchor, npoints; double ground_ref; const PlaceTable *table; const double *offsets, *pose; const int *next; double *ground; };
+/* episodes (phys_batch_episodes_enable): the rules, the per-env arrays and the bank of start states [nrows][episode_row_dim] */
+struct EpisodeCfg { cm_episode_rules_t rules; int *done, *reason, *steps, *count; double *terminal; const double *bank; int nrows; };
+
+/* ---- the checks ---- */
+
+/* the body a scan pattern or a camera hangs on: a child of the world whose pose follows from qpos alone (static_body_pose) */
+inline const char *check_body_pose_from_qpos(const cm_model_t &m, int model_stride, int body) {
+    const int rt = body > 0 && body < m.nbody ? m.body_kin[body].rot_type : 0;
+    const bool ok = body > 0 && body < m.nbody && m.kin_simple && m.body_parentid[body] == 0 && model_stride == 0 && (rt == CM_JNT_BALL || rt == CM_JNT_FREE || rt == -1);
+    return ok ? nullptr : "the body must be a child of the world whose joints are slides and at most a ball or free joint (a shared kin_simple model)";
+}
+/* (what the launcher also answers a call without a batch) */
+constexpr const char *SCAN_SIZE_REFUSAL = "1 .. 1024 points and a positive range", *DEPTH_SIZE_REFUSAL = "an image of 1 .. 16384 pixels and a camera pose";
+/* the height scan's configuration; fills c but for where the pattern lies once a kernel reads it, which the caller names */
+inline const char *scan_configure(const cm_model_t &m, int model_stride, const double *offsets_xy, int npoints, int body, double range, ScanCfg &c) {
+    if (!offsets_xy || npoints <= 0 || npoints > SCAN_MAXPOINTS || !(range > 0)) return SCAN_SIZE_REFUSAL;
+    if (const char *why = check_body_pose_from_qpos(m, model_stride, body)) return why;
+    c = {npoints, body, range, nullptr};
+    return nullptr;
+}
+/* the geoms a depth image may render (every compiled geom) and those it renders by default (the static planes, boxes and height field:
+ * what the static kernel sees); a mask must name none at or above ngeom */
+inline unsigned depth_all_geoms(const cm_model_t &m) { return m.ngeom >= 32 ? 0xffffffffu : (1u << m.ngeom) - 1u; }
+inline unsigned depth_default_geoms(const cm_model_t &m) {
+    unsigned mask = 0;
+    for (int g = 0; g < m.ngeom; ++g) {
+        const int gt = m.geom_type[g];
+        if (m.body_weldid[m.geom_bodyid[g]] == 0 && (gt == CM_GEOM_PLANE || gt == CM_GEOM_BOX || gt == CM_GEOM_HFIELD)) mask |= 1u << g;
+    }
+    return mask;
+}
+inline const char *check_depth_geoms(const cm_model_t &m, unsigned mask) { return mask & ~depth_all_geoms(m) ? "the mask names a geom at or above ngeom" : nullptr; }
+/* the depth image's configuration (fovy in radians); fills c: the default geoms, no per-env pose, no ids */
+inline const char *depth_configure(const cm_model_t &m, int model_stride, int body, const double *cam_pos, const double *cam_quat, int width, int height,
+                                   double fovy, double znear, double zfar, DepthCfg &c) {
+    if (!cam_pos || !cam_quat || width < 1 || height < 1 || (long long)width * height > DEPTH_MAXPIXELS) return DEPTH_SIZE_REFUSAL;
+    if (!(fovy > 0 && fovy < 3.14159265358979323846) || !(znear > 0 && znear < zfar)) return "0 < fovy < pi (radians) and 0 < near < far";
+    const double qn = cam_quat[0] * cam_quat[0] + cam_quat[1] * cam_quat[1] + cam_quat[2] * cam_quat[2] + cam_quat[3] * cam_quat[3];
+    if (!(qn > 0)) return "the camera's quaternion is zero";
+    if (const char *why = check_body_pose_from_qpos(m, model_stride, body)) return why;
+    c = {width, height, body, tan(0.5 * fovy), znear, zfar, {cam_pos[0], cam_pos[1], cam_pos[2]}, {cam_quat[0], cam_quat[1], cam_quat[2], cam_quat[3]},
+         nullptr, depth_default_geoms(m), nullptr};
+    return nullptr;
+}
+/* a placement's configuration; fills the table (place_classify, episode_kernels.h) */
+inline const char *place_configure(const cm_model_t &m, int model_stride, int anchor, const double *offsets_xy, int npoints, double ground_ref, PlaceTable &tab) {
+    if (npoints < 0 || npoints > PLACE_MAXPOINTS || (npoints > 0 && !offsets_xy) || !(ground_ref == ground_ref)) return "a footprint of 0 .. 1024 points and a ground height";
+    if (model_stride != 0) return "not with per-env models (phys_batch_set_model with env >= 0)";
+    memset(&tab, 0, sizeof tab);
+    return place_classify(m, anchor, tab);
+}
+
+/* ---- the grids ---- */
+
+/* one workgroup per CU walks the range: an env's scan is a chain of dependent reads */
+inline int scan_grid(int n) { return n < SCAN_GRID ? n : SCAN_GRID; }
+/* a few workgroups walk the range, with or without placement: the launch runs behind a range's step launch while the other range's step
+ * kernel fills the chip, where every workgroup waits for a wave slot to free (cassie_reset_kernel) */
+inline int episode_grid(int n) { return n < EPISODE_GRID ? n : EPISODE_GRID; }
+/* a job is (env, tile of DEPTH_TILE x DEPTH_TILE pixels); a fixed grid walks the job list (a first choice: depth_kernel.h) */
+inline int depth_grid(int n, int width, int height) {
+    const int T = DEPTH_TILE;
+    const long long jobs = (long long)n * (((width + T - 1) / T) * ((height + T - 1) / T));
+    return (int)(jobs < DEPTH_GRID ? jobs : DEPTH_GRID);
+}
+/* a few workgroups walk the envs: one workgroup per env made the kernel a 0.5 ms stall of its stream on a saturated GPU (cassie_reset_kernel) */
+inline int reset_grid(int count) { return count < 4 ? count : 4; }
+/* one wave per env, at most a few thousand workgroups walking the range (58 KB of LDS each: two to a CU) */
+inline int setconst_grid(int n) { return n < 2048 ? n : 2048; }
+/* a few workgroups walk the rows (cassie_param_scatter_kernel) */
+inline int param_scatter_grid(int n) { return n < 1024 ? n : 1024; }
+
+/* ---- the builders ---- */
+
+/* what ScanIO, DepthIO and EpisodeIO share: where the surface comes from (the terrain index counts only while a bank is set) */
+template <class IO>
+inline void fill_surface(IO &io, const BatchView &v) {
+    io.envparams = v.envparams; io.hfield = v.hfield; io.hfield_stride = v.hfield_stride;
+    if (v.hfield_nterrain > 0) { io.hfield_index = v.hfield_index; io.hfield_nterrain = v.hfield_nterrain; }
+}
+/* what ResetIO and EpisodeIO share: sizes, row strides and the state arrays a restart writes */
+template <class IO>
+inline void fill_state(IO &io, const BatchView &v) {
+    io.nq = v.nq; io.nv = v.nv; io.nu = v.nu; io.nsd = v.nsd; io.sq = v.sq; io.sqv = v.sqv; io.ssd = v.ssd;
+    io.qpos = v.qpos; io.qvel = v.qvel; io.warm = v.warm; io.ctrl = v.ctrl; io.qacc = v.qacc; io.time = v.time;
+    io.sens = v.sens; io.actvel = v.actvel; io.meas = v.meas; io.drive = v.drive;
+}
+template <class IO>
+inline IO zeroed() { IO io; memset(&io, 0, sizeof io); return io; }
+
+inline ScanIO make_scan_io(const BatchView &v, const ScanCfg &c, double *out, int sout, int env0, int n) {
+    ScanIO io = zeroed<ScanIO>();
+    fill_surface(io, v);
+    io.models = v.models; io.model_stride = v.model_stride;
+    io.env0 = env0; io.n = n; io.npoints = c.npoints; io.body = c.body; io.range = c.range; io.offsets = c.offsets;
+    io.qpos = v.qpos; io.sq = v.sq; io.out = out; io.sout = sout; io.warn = v.warn;
+    return io;
+}
+/* The static kernel unless the caller has chosen other geoms than the default or wants the ids: the default image is the static
+ * kernel's, bit for bit and at its cost.  (Any other mask goes to the scene kernel, also one that renders the same geoms.) */
+inline bool depth_scene_kernel(const cm_model_t &m, const DepthCfg &c) { return c.geoms != depth_default_geoms(m) || c.ids; }
+/* scene: for cassie_depth_scene_kernel; else its fields stay zero (the static kernel reads none of them) */
+inline DepthIO make_depth_io(const BatchView &v, const DepthCfg &c, double *out, int sout, int env0, int n, bool scene) {
+    DepthIO io = zeroed<DepthIO>();
+    fill_surface(io, v);
+    io.models = v.models; io.model_stride = v.model_stride;
+    io.env0 = env0; io.n = n; io.body = c.body; io.width = c.width; io.height = c.height;
+    io.tan_half = c.tan_half; io.znear = c.znear; io.zfar = c.zfar;
+    for (int k = 0; k < 3; ++k) io.cam_pos[k] = c.cam_pos[k];
+    for (int k = 0; k < 4; ++k) io.cam_quat[k] = c.cam_quat[k];
+    io.pose = c.pose;
+    io.qpos = v.qpos; io.sq = v.sq; io.out = out; io.sout = sout; io.warn = v.warn;
+    if (scene) { io.geoms = c.geoms; io.xpos = v.xpos; io.xquat = v.xquat; io.sxp = 3 * v.nbody; io.sxq = 4 * v.nbody; io.ids = c.ids; }
+    return io;
+}
+inline int episode_row_dim(const BatchView &v) { return v.nq + v.nv + v.nsd + v.nu + v.nv; }
+/* place null: cassie_episode_kernel's; else cassie_episode_place_kernel's (the next terrains count only while a bank is set) */
+inline EpisodeIO make_episode_io(const BatchView &v, const EpisodeCfg &e, const PlaceCfg *place, int env0, int n, int restart, const int *pick, const int *force) {
+    EpisodeIO io = zeroed<EpisodeIO>();
+    fill_state(io, v);
+    io.env0 = env0; io.n = n; io.restart = restart ? 1 : 0; io.nrows = e.nrows; io.row_dim = episode_row_dim(v);
+    io.rules = e.rules; io.warn = v.warn;
+    io.done = e.done; io.reason = e.reason; io.steps = e.steps; io.count = e.count; io.terminal = e.terminal;
+    io.bank = e.bank; io.pick = pick; io.force = force;
+    if (place) {
+        fill_surface(io, v);
+        io.model = v.models;
+        io.place_anchor = place->anchor; io.place_npoints = place->npoints; io.place_ground_ref = place->ground_ref; io.place_table = place->table;
+        io.place_offsets = place->offsets; io.place_pose = place->pose; io.place_ground = place->ground;
+        if (v.hfield_nterrain > 0) io.place_next = place->next;
+    }
+    return io;
+}
+inline ResetIO make_reset_io(const BatchView &v, int first, int stride, int count, const double *qpos_row, const double *sens_row) {
+    ResetIO io = zeroed<ResetIO>();
+    fill_state(io, v);
+    io.first = first; io.stride = stride; io.count = count; io.qpos_row = qpos_row; io.sens_row = sens_row;
+    return io;
+}
+inline DeriveIO make_derive_io(const BatchView &v, int nenv, const cm_ext_t *ext, double *derived, double *qM, const int *ids) {
+    DeriveIO io = zeroed<DeriveIO>();
+    io.models = v.models; io.model_stride = v.model_stride; io.nenv = nenv; io.envparams = v.envparams;
+    io.ext = ext; io.xpos = v.xpos; io.xquat = v.xquat; io.derived = derived; io.qM = qM;
+    for (int i = 0; i < 6; ++i) io.ids[i] = ids[i];
+    return io;
+}
+/* mode: a SETCONST_* value */
+inline SetConstIO make_setconst_io(const cm_model_t *model, cm_envparams_t *params, int env0, int n, int mode) {
+    SetConstIO io = zeroed<SetConstIO>();
+    io.model = model; io.params = params; io.env0 = env0; io.nenv = n; io.derive_inertial = mode;
+    return io;
+}
+
+}  // namespace ck
+#endif

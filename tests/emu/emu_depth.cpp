@@ -1,10 +1,11 @@
 /*
- * emu_depth.cpp -- TEST-ONLY: the depth-image kernel (csrc/depth_kernel.h) on the wave emulator.
+ * emu_depth.cpp -- TEST-ONLY: the depth-image kernel (csrc/depth_kernel.h) on the wave emulator, configured, checked and launched as
+ * phys_batch.hip does it (csrc/small_launch.h).
  */
 #include <cmath>
 #include <cstring>
 
-#include "depth_kernel.h"
+#include "small_launch.h"
 #include "emu_runtime.h"
 
 /* phys_batch_depth_image on the emulator: the device's depth kernel on host arrays (indexed by the absolute env; sq / sout = doubles
@@ -16,23 +17,15 @@ extern "C" int emu_depth_image(const cm_model_t *model, const cm_envparams_t *en
                                const double *cam_pos, const double *cam_quat, const double *pose, int width, int height, double fovy,
                                double znear, double zfar, const double *qpos, int sq, double *out, int sout,
                                const float *hfield, unsigned long hfield_stride, const int *hfield_index, int nterrain, int *warn) {
-    if (width < 1 || height < 1 || (long long)width * height > ck::DEPTH_MAXPIXELS || body <= 0 || body >= model->nbody) return -1;
-    if (!(fovy > 0 && fovy < M_PI) || !(znear > 0 && znear < zfar)) return -1;
     static cm_model_t synced;
     synced = *model; cm_model_sync_params(&synced);
-    ck::DepthIO &io = g_depthio;
-    memset(&io, 0, sizeof io);
-    io.models = &synced; io.model_stride = 0; io.envparams = envparams;
-    io.env0 = env0; io.n = n; io.body = body; io.width = width; io.height = height;
-    io.tan_half = tan(0.5 * fovy); io.znear = znear; io.zfar = zfar;
-    for (int k = 0; k < 3; ++k) io.cam_pos[k] = cam_pos[k];
-    for (int k = 0; k < 4; ++k) io.cam_quat[k] = cam_quat[k];
-    io.pose = pose;
-    io.qpos = qpos; io.sq = sq; io.out = out; io.sout = sout;
-    io.hfield = hfield; io.hfield_stride = hfield_stride; io.hfield_index = hfield_index; io.hfield_nterrain = nterrain;
-    io.warn = warn;
-    const int tiles = ((width + ck::DEPTH_TILE - 1) / ck::DEPTH_TILE) * ((height + ck::DEPTH_TILE - 1) / ck::DEPTH_TILE);
-    const long long jobs = (long long)n * tiles;
-    emu::run_grid(body_depth, grid > 0 ? grid : (int)(jobs < ck::DEPTH_GRID ? jobs : ck::DEPTH_GRID));
+    ck::DepthCfg cfg;
+    if (ck::depth_configure(synced, 0, body, cam_pos, cam_quat, width, height, fovy, znear, zfar, cfg)) return -1;
+    cfg.pose = pose;
+    if (ck::depth_scene_kernel(synced, cfg)) return -1;   /* (a fresh configuration is the static kernel's: this entry point's) */
+    ck::BatchView v = {&synced, 0, envparams, hfield, hfield_stride, const_cast<int *>(hfield_index), nterrain};
+    v.qpos = const_cast<double *>(qpos); v.sq = sq; v.warn = warn;
+    g_depthio = ck::make_depth_io(v, cfg, out, sout, env0, n, false);
+    emu::run_grid(body_depth, grid > 0 ? grid : ck::depth_grid(n, width, height));
     return 0;
 }

@@ -1,14 +1,15 @@
 /*
- * emu_kernels.cpp -- TEST-ONLY: the small kernels (csrc/small_kernels.h: set_const, derive, episodes, height scan) on the wave emulator,
- * the wave primitives' checks (tests/device/wave_bodies.h), and the probes of layouts, constants and elementary functions the tests
- * read.  The step kernel is emu_step.cpp's: nothing here instantiates it.
+ * emu_kernels.cpp -- TEST-ONLY: the small kernels (csrc/small_kernels.h: set_const, derive; episode_kernels.h: episodes; surface_kernels.h:
+ * height scan) on the wave emulator, launched as phys_batch.hip launches them (csrc/small_launch.h: the same records, builders, grids and
+ * checks), the probes of those rules, the wave primitives' checks (tests/device/wave_bodies.h), and the probes of layouts, constants
+ * and elementary functions the tests read.  The step kernel is emu_step.cpp's: nothing here instantiates it.
  */
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <vector>
 
-#include "small_kernels.h"
+#include "small_launch.h"
 #include "emu_runtime.h"
 
 extern "C" unsigned long emu_offsetof32(int which) {
@@ -24,7 +25,7 @@ extern "C" unsigned long emu_offsetof32(int which) {
 static ck::SetConstIO g_scio;
 static void body_setconst() { ck::cassie_setconst_kernel(g_scio); }
 extern "C" int emu_set_const(const cm_model_t *model, cm_envparams_t *params, int nenv, int derive_inertial) {
-    g_scio.model = model; g_scio.params = params; g_scio.env0 = 0; g_scio.nenv = nenv; g_scio.derive_inertial = derive_inertial;
+    g_scio = ck::make_setconst_io(model, params, 0, nenv, derive_inertial);
     emu::run_grid(body_setconst, nenv);
     return 0;
 }
@@ -49,9 +50,9 @@ extern "C" int emu_derive(const emu_step_args *args, const int *ids, double *der
     a.hfield_stride = 0; a.hfield_index = nullptr; a.nterrain = 0;
     a.xpos = xpos.data(); a.xquat = xquat.data();
     emu::run_step(a, *result, ext.data());
-    memset(&g_dio, 0, sizeof g_dio);
-    g_dio.models = model; g_dio.nenv = nenv; g_dio.envparams = a.envparams; g_dio.ext = ext.data(); g_dio.xpos = a.xpos; g_dio.xquat = a.xquat; g_dio.derived = derived; g_dio.qM = qM;
-    for (int i = 0; i < 6; ++i) g_dio.ids[i] = ids[i];
+    ck::BatchView v = {model, 0, a.envparams};
+    v.xpos = a.xpos; v.xquat = a.xquat;
+    g_dio = ck::make_derive_io(v, nenv, ext.data(), derived, qM, ids);
     emu::with_settings hooks(a.settings);
     emu::run_grid(body_derive, nenv);
     return 0;
@@ -67,17 +68,13 @@ extern "C" int emu_end_episodes(const cm_model_t *model, const cm_episode_rules_
                                 int *done, int *reason, int *steps, int *count, double *terminal,
                                 const double *bank, int nrows, const int *pick, const int *force) {
     if (restart && (!bank || nrows <= 0)) return -1;
-    ck::EpisodeIO &io = g_epio;
-    memset(&io, 0, sizeof io);
-    io.env0 = env0; io.n = n; io.restart = restart ? 1 : 0; io.nrows = nrows;
-    io.nq = model->nq; io.nv = model->nv; io.nu = model->nu; io.nsd = model->nsensordata; io.sq = sq; io.sqv = sqv; io.ssd = ssd;
-    io.row_dim = model->nq + model->nv + model->nsensordata + model->nu + model->nv;
-    io.rules = *rules;
-    io.qpos = qpos; io.qvel = qvel; io.warm = qacc_warmstart; io.ctrl = ctrl; io.qacc = qacc; io.time = time; io.sens = sensordata;
-    io.actvel = actuator_velocity; io.meas = meas; io.drive = drive; io.warn = warn;
-    io.done = done; io.reason = reason; io.steps = steps; io.count = count; io.terminal = terminal;
-    io.bank = bank; io.pick = pick; io.force = force;
-    emu::run_grid(body_episode, grid > 0 ? grid : (n < ck::EPISODE_GRID ? n : ck::EPISODE_GRID));
+    ck::BatchView v = {};
+    ck::view_sizes(v, *model);
+    v.sq = sq; v.sqv = sqv; v.ssd = ssd;
+    v.qpos = qpos; v.qvel = qvel; v.warm = qacc_warmstart; v.ctrl = ctrl; v.qacc = qacc; v.time = time; v.sens = sensordata;
+    v.actvel = actuator_velocity; v.meas = meas; v.drive = drive; v.warn = warn;
+    g_epio = ck::make_episode_io(v, {*rules, done, reason, steps, count, terminal, bank, nrows}, nullptr, env0, n, restart, pick, force);
+    emu::run_grid(body_episode, grid > 0 ? grid : ck::episode_grid(n));
     return 0;
 }
 extern "C" unsigned long emu_sizeof_episode_rules(void) { return sizeof(cm_episode_rules_t); }
@@ -96,19 +93,40 @@ static void body_scan() { ck::cassie_scan_kernel(g_scanio); }
 extern "C" int emu_height_scan(const cm_model_t *model, const cm_envparams_t *envparams, int env0, int n, int grid, const double *offsets,
                                int npoints, int body, double range, const double *qpos, int sq, double *out, int sout,
                                const float *hfield, unsigned long hfield_stride, const int *hfield_index, int nterrain, int *warn) {
-    if (npoints <= 0 || npoints > ck::SCAN_MAXPOINTS || body <= 0 || body >= model->nbody) return -1;
     static cm_model_t synced;
     synced = *model; cm_model_sync_params(&synced);
-    ck::ScanIO &io = g_scanio;
-    memset(&io, 0, sizeof io);
-    io.models = &synced; io.model_stride = 0; io.envparams = envparams;
-    io.env0 = env0; io.n = n; io.npoints = npoints; io.body = body; io.range = range; io.offsets = offsets;
-    io.qpos = qpos; io.sq = sq; io.out = out; io.sout = sout;
-    io.hfield = hfield; io.hfield_stride = hfield_stride; io.hfield_index = hfield_index; io.hfield_nterrain = nterrain;
-    io.warn = warn;
-    emu::run_grid(body_scan, grid > 0 ? grid : (n < ck::SCAN_GRID ? n : ck::SCAN_GRID));
+    ck::ScanCfg cfg;
+    if (ck::scan_configure(synced, 0, offsets, npoints, body, range, cfg)) return -1;
+    cfg.offsets = offsets;
+    ck::BatchView v = {&synced, 0, envparams, hfield, hfield_stride, const_cast<int *>(hfield_index), nterrain};
+    v.qpos = const_cast<double *>(qpos); v.sq = sq; v.warn = warn;
+    g_scanio = ck::make_scan_io(v, cfg, out, sout, env0, n);
+    emu::run_grid(body_scan, grid > 0 ? grid : ck::scan_grid(n));
     return 0;
 }
+/* the launcher's rules for the small kernels (csrc/small_launch.h) one at a time, for tests/test_small_launch.py.  The grid of kernel
+ * `which` (0 scan, 1 episodes, 2 depth image of width x height, 3 reset, 4 set_const, 5 parameter scatter) over n envs; the depth
+ * kernel (0 static, 1 scene) a mask and bound ids give; the message (null: accepted) of a scan / a depth / a mask configuration */
+extern "C" int emu_small_grid(int which, int n, int width, int height) {
+    return which == 0 ? ck::scan_grid(n) : which == 1 ? ck::episode_grid(n) : which == 2 ? ck::depth_grid(n, width, height)
+         : which == 3 ? ck::reset_grid(n) : which == 4 ? ck::setconst_grid(n) : ck::param_scatter_grid(n);
+}
+extern "C" unsigned emu_depth_geoms(const cm_model_t *model, int all) { return all ? ck::depth_all_geoms(*model) : ck::depth_default_geoms(*model); }
+extern "C" int emu_depth_scene_kernel(const cm_model_t *model, unsigned mask, int ids_bound) {
+    ck::DepthCfg cfg = {};
+    cfg.geoms = mask; cfg.ids = ids_bound ? (int *)model : nullptr;   /* (any address: only compared with null) */
+    return ck::depth_scene_kernel(*model, cfg) ? 1 : 0;
+}
+extern "C" const char *emu_scan_check(const cm_model_t *model, int model_stride, const double *offsets, int npoints, int body, double range) {
+    ck::ScanCfg cfg;
+    return ck::scan_configure(*model, model_stride, offsets, npoints, body, range, cfg);
+}
+extern "C" const char *emu_depth_check(const cm_model_t *model, int model_stride, int body, const double *cam_pos, const double *cam_quat, int width,
+                                       int height, double fovy, double znear, double zfar) {
+    ck::DepthCfg cfg;
+    return ck::depth_configure(*model, model_stride, body, cam_pos, cam_quat, width, height, fovy, znear, zfar, cfg);
+}
+extern "C" const char *emu_depth_geoms_check(const cm_model_t *model, unsigned mask) { return ck::check_depth_geoms(*model, mask); }
 
 extern "C" int emu_warn_bit(int which) { return which == 0 ? ck::WARN_TERRAIN_INDEX : ck::WARN_SCAN_TILTED; }
 /* the layout of emu_api.h's structs, for the ctypes mirror of tests/emu_py.py: which = 0 emu_settings, 1 emu_step_args, 2 emu_step_result;

@@ -1,10 +1,10 @@
 /*
- * emu_placement.cpp -- TEST-ONLY: phys_batch_end_episodes with PLACED restarts (csrc/small_kernels.h: cassie_episode_place_kernel) on the
- * wave emulator.
+ * emu_placement.cpp -- TEST-ONLY: phys_batch_end_episodes with PLACED restarts (csrc/episode_kernels.h: cassie_episode_place_kernel) on the
+ * wave emulator, configured, checked and launched as phys_batch.hip does it (csrc/small_launch.h).
  */
 #include <cstring>
 
-#include "small_kernels.h"
+#include "small_launch.h"
 #include "emu_runtime.h"
 
 /* what a call is handed, by pointer (tests/placement_emu_py.py mirrors it; emu_place_sizeof lets it check the mirror).  The arrays are
@@ -45,30 +45,19 @@ extern "C" int emu_place_end_episodes(const emu_place_args *a, const char **why)
     static const char *none = "";
     if (why) *why = none;
     if (a->restart && (!a->bank || a->nrows <= 0)) return -1;
-    if (a->npoints < 0 || a->npoints > ck::PLACE_MAXPOINTS || (a->npoints > 0 && !a->offsets)) { if (why) *why = "a footprint of 0 .. 1024 points"; return -1; }
     static cm_model_t synced;
     synced = *a->model; cm_model_sync_params(&synced);
-    const cm_model_t *model = &synced;
-    ck::EpisodeIO &io = g_placeio;
-    memset(&io, 0, sizeof io);
     static ck::PlaceTable table;
-    memset(&table, 0, sizeof table);
-    if (const char *bad = ck::place_classify(*model, a->anchor, table)) { if (why) *why = bad; return -1; }
-    io.place_anchor = a->anchor; io.place_table = &table;
-    io.env0 = a->env0; io.n = a->n; io.restart = a->restart ? 1 : 0; io.nrows = a->nrows;
-    io.nq = model->nq; io.nv = model->nv; io.nu = model->nu; io.nsd = model->nsensordata; io.sq = a->sq; io.sqv = a->sqv; io.ssd = a->ssd;
-    io.row_dim = model->nq + model->nv + model->nsensordata + model->nu + model->nv;
-    io.rules = *a->rules;
-    io.qpos = a->qpos; io.qvel = a->qvel; io.warm = a->qacc_warmstart; io.ctrl = a->ctrl; io.qacc = a->qacc; io.time = a->time;
-    io.sens = a->sensordata; io.actvel = a->actuator_velocity; io.meas = a->meas; io.drive = a->drive; io.warn = a->warn;
-    io.done = a->done; io.reason = a->reason; io.steps = a->steps; io.count = a->count; io.terminal = a->terminal;
-    io.bank = a->bank; io.pick = a->pick; io.force = a->force;
-    io.place_npoints = a->npoints; io.place_ground_ref = a->ground_ref;
-    io.place_offsets = a->offsets; io.place_pose = a->pose; io.place_ground = a->ground;
-    io.model = model; io.envparams = a->envparams;
-    io.hfield = a->hfield; io.hfield_stride = a->hfield_stride;
-    if (a->nterrain > 0) { io.hfield_index = a->hfield_index; io.hfield_nterrain = a->nterrain; io.place_next = a->next; }
-    emu::run_grid(body_place, a->grid > 0 ? a->grid : (a->n < ck::EPISODE_GRID ? a->n : ck::EPISODE_GRID));
+    if (const char *bad = ck::place_configure(synced, 0, a->anchor, a->offsets, a->npoints, a->ground_ref, table)) { if (why) *why = bad; return -1; }
+    const ck::PlaceCfg place = {a->anchor, a->npoints, a->ground_ref, &table, a->offsets, a->pose, a->next, a->ground};
+    ck::BatchView v = {&synced, 0, a->envparams, a->hfield, a->hfield_stride, a->hfield_index, a->nterrain};
+    ck::view_sizes(v, synced);
+    v.sq = a->sq; v.sqv = a->sqv; v.ssd = a->ssd;
+    v.qpos = a->qpos; v.qvel = a->qvel; v.warm = a->qacc_warmstart; v.ctrl = a->ctrl; v.qacc = a->qacc; v.time = a->time;
+    v.sens = a->sensordata; v.actvel = a->actuator_velocity; v.meas = a->meas; v.drive = a->drive; v.warn = a->warn;
+    g_placeio = ck::make_episode_io(v, {*a->rules, a->done, a->reason, a->steps, a->count, a->terminal, a->bank, a->nrows}, &place, a->env0, a->n,
+                                    a->restart, a->pick, a->force);
+    emu::run_grid(body_place, a->grid > 0 ? a->grid : ck::episode_grid(a->n));
     return 0;
 }
 extern "C" int emu_place_warn_bit(void) { return ck::WARN_PLACE_MISS; }

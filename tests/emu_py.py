@@ -61,6 +61,12 @@ def lib():
         L.emu_sizeof_episode_rules.restype, L.emu_offsetof_episode_rules.restype = _ul, ctypes.c_long
         L.emu_height_scan.argtypes = [ctypes.POINTER(CmModel), _vp, _ci, _ci, _ci, _vp, _ci, _ci, ctypes.c_double, _vp, _ci, _vp, _ci, _vp, _ul, _vp, _ci, _vp]
         L.emu_core_safety.argtypes, L.emu_core_safety.restype = [_ci] + [_vp] * 7, None
+        L.emu_depth_geoms.argtypes, L.emu_depth_geoms.restype = [ctypes.POINTER(CmModel), _ci], ctypes.c_uint
+        L.emu_depth_scene_kernel.argtypes = [ctypes.POINTER(CmModel), ctypes.c_uint, _ci]
+        L.emu_scan_check.argtypes, L.emu_scan_check.restype = [ctypes.POINTER(CmModel), _ci, _vp, _ci, _ci, ctypes.c_double], ctypes.c_char_p
+        L.emu_depth_check.argtypes = [ctypes.POINTER(CmModel), _ci, _ci, _vp, _vp, _ci, _ci] + [ctypes.c_double] * 3
+        L.emu_depth_check.restype = ctypes.c_char_p
+        L.emu_depth_geoms_check.argtypes, L.emu_depth_geoms_check.restype = [ctypes.POINTER(CmModel), ctypes.c_uint], ctypes.c_char_p
         _lib = L
     return _lib
 
@@ -222,6 +228,45 @@ class RangeTable:
         kept = {(r[0], r[1]): r for r in self.records}             # (a record that survives stays the same list)
         self.records = [kept.get((int(r[0]), int(r[1])), [int(v) for v in r]) for r in rec[: nrec.value]]
         return self.records[at], [tuple(int(v) for v in g) for g in gone[: ngone.value]]
+
+
+SCAN, EPISODES, DEPTH, RESET, SET_CONST, PARAM_SCATTER = range(6)      # emu_small_grid's `which`
+
+
+def small_grid(which, n, width=0, height=0):
+    """The workgroups phys_batch.hip launches kernel `which` with over n envs (csrc/small_launch.h: scan_grid, episode_grid, ...)."""
+    return lib().emu_small_grid(which, n, width, height)
+
+
+def depth_geoms(pod, every=False):
+    """ck::depth_default_geoms / ck::depth_all_geoms."""
+    return lib().emu_depth_geoms(ctypes.byref(pod), int(every))
+
+
+def depth_scene_kernel(pod, mask, ids_bound=False):
+    """ck::depth_scene_kernel: does a depth image of these geoms, with or without a hit-id image bound, take the scene kernel?"""
+    return bool(lib().emu_depth_scene_kernel(ctypes.byref(pod), mask, int(ids_bound)))
+
+
+def _message(m):
+    return None if m is None else m.decode()
+
+
+def scan_check(pod, npoints, body, scan_range, model_stride=0, offsets=True):
+    """ck::scan_configure -> the message of its refusal, None where it accepts."""
+    off = np.zeros((max(npoints, 1), 2)) if offsets else None
+    return _message(lib().emu_scan_check(ctypes.byref(pod), model_stride, _ptr(off), npoints, body, scan_range))
+
+
+def depth_check(pod, body, width, height, fovy, near, far, cam_quat=(1.0, 0.0, 0.0, 0.0), model_stride=0):
+    """ck::depth_configure (fovy in radians) -> the message of its refusal, None where it accepts."""
+    pos, quat = np.zeros(3), np.ascontiguousarray(cam_quat, dtype=np.float64)
+    return _message(lib().emu_depth_check(ctypes.byref(pod), model_stride, body, _ptr(pos), _ptr(quat), width, height, fovy, near, far))
+
+
+def depth_geoms_check(pod, mask):
+    """ck::check_depth_geoms -> the message of its refusal, None where it accepts."""
+    return _message(lib().emu_depth_geoms_check(ctypes.byref(pod), mask))
 
 
 def set_const(pod, blocks, nenv, mode):

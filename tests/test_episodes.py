@@ -1,5 +1,5 @@
 """Episodes that end and restart on the device (phys_batch_end_episodes), on the CPU: the device's episode kernel
-(csrc/small_kernels.h: cassie_episode_kernel) executed by the wave emulator on hand-placed states, byte for byte against the numpy
+(csrc/episode_kernels.h: cassie_episode_kernel) executed by the wave emulator on hand-placed states, byte for byte against the numpy
 restatement of the call in tests/episode_check.py.  The GPU counterpart is tests/test_episodes_gpu.py.
 
 Every rule test asserts on its inputs that NO env lies within 1e-9 of min_height / min_upright (episode_check.

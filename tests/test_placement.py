@@ -1,5 +1,5 @@
 """Placed restarts (phys_batch_place_configure + phys_batch_end_episodes), on the CPU: the device's placed episode kernel
-(csrc/small_kernels.h: cassie_episode_place_kernel) executed by the wave emulator, against the unplaced kernel (the identity placement),
+(csrc/episode_kernels.h: cassie_episode_place_kernel) executed by the wave emulator, against the unplaced kernel (the identity placement),
 against the numpy restatement of the header's definition (tests/placement_check.py), the restatement against the oracle's forward pass,
 and the emulated height scan of the placed envs.  The GPU counterpart is tests/test_placement_gpu.py.
 

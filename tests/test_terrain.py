@@ -1,4 +1,4 @@
-"""Per-env terrains from a bank and the height scan, on the CPU: the device's scan kernel (csrc/small_kernels.h: cassie_scan_kernel)
+"""Per-env terrains from a bank and the height scan, on the CPU: the device's scan kernel (csrc/surface_kernels.h: cassie_scan_kernel)
 and the step kernel's terrain index (PhysIO::hfield_index), executed by the wave emulator, against the numpy restatement of the
 scan's definition in tests/terrain_check.py, hand-computed answers, the oracle's height-field narrow phase, and the step kernel
 handed each env's grid as its own.  The GPU counterpart is tests/test_terrain_gpu.py.
