@@ -164,6 +164,13 @@ def _declare(L):
         L.phys_batch_depth_all_geoms.restype = c.c_uint
         L.phys_batch_depth_bind_ids.argtypes = [vp, vp]
         L.phys_batch_debug_depth_launches.argtypes = [vp, c.POINTER(c.c_longlong), c.POINTER(c.c_longlong)]
+    if hasattr(L, "phys_batch_rays_cast"):   # (likewise)
+        L.phys_batch_rays_configure.argtypes = [vp, vp, c.c_int, c.c_double, c.c_double]
+        L.phys_batch_rays_set_geoms.argtypes = [vp, c.c_uint]
+        L.phys_batch_rays_bind_ids.argtypes = [vp, vp]
+        L.phys_batch_rays_bind_normals.argtypes = [vp, vp]
+        L.phys_batch_rays_cast.argtypes = [vp, c.c_int, c.c_int, vp]
+        L.phys_batch_debug_ray_launches.argtypes = [vp, c.POINTER(c.c_longlong)]
     if hasattr(L, "phys_batch_download_progress"):   # (absent from older variant builds selected with CASSIE_LIB)
         L.phys_batch_download_progress.argtypes = [vp, vp]
     L.phys_batch_set_all_outputs_every_substep.argtypes = [vp, c.c_int]

@@ -15,7 +15,7 @@ from ._lib import CmDriveState, CmEnvParams, CmEpisodeRules, CmModel, MODEL_DIR,
 # field ids (enum in cassie_phys.h)
 (F_QPOS, F_QVEL, F_QACC_WARMSTART, F_TIME, F_CTRL, F_QFRC_APPLIED, F_XFRC_APPLIED, F_QACC, F_SENSORDATA,
  F_ACTUATOR_VELOCITY, F_XPOS, F_XQUAT, F_PD_PTARGET, F_PD_KP, F_PD_KD, F_BODY_CFRC, F_DRIVE_CMD, F_MEAS, F_PD_DTARGET,
- F_PD_TORQUE, F_DERIVED, F_QM, F_HEIGHT_SCAN, F_DEPTH) = range(24)
+ F_PD_TORQUE, F_DERIVED, F_QM, F_HEIGHT_SCAN, F_DEPTH, F_RAYS) = range(25)
 
 # layout of the derived block F_DERIVED (CM_DRV_* in cm_model.h); MAXV = CM_MAXV
 MAXV = 40
@@ -36,6 +36,10 @@ WARN_SCAN_TILTED = 64       # height scan: the env's height-field geom is tilted
 WARN_PLACE_MISS = 128       # placed restart: the footprint met no ground anywhere, the env was put down at ground_ref
 SCAN_MAXPOINTS = 1024
 DEPTH_MAXPIXELS = 16384
+# range sensors on any body: the frames of a ray (PHYS_RAY_* in cassie_phys.h) and the layout of phys_ray_t
+RAY_BODY, RAY_WORLD_DIR, RAY_HEADING = range(3)
+RAYS_MAX = 1024
+RAY_DTYPE = np.dtype([("body", np.int32), ("frame", np.int32), ("origin", np.float64, 3), ("dir", np.float64, 3)])
 
 # per-env physical parameters (CM_P_* in cm_model.h): what Batch.randomize takes
 (P_BODY_MASS, P_BODY_IPOS, P_BODY_INERTIA, P_DOF_DAMPING, P_GEOM_FRICTION,
@@ -169,7 +173,7 @@ class Batch:
         return lib().phys_batch_device_ptr(self._h, field)
 
     def bind(self, field, device_ptr, row_stride=None):
-        """Aliases a field to caller-owned HBM; `row_stride` (doubles, qpos / qvel / sensordata / the height scan / the depth image only) lets the field be a
+        """Aliases a field to caller-owned HBM; `row_stride` (doubles, qpos / qvel / sensordata / the height scan / the depth image / the ray ranges only) lets the field be a
         column block of a wider tensor, e.g. one [nenv][nq + nv + nsensordata] observation block."""
         rc = (lib().phys_batch_bind(self._h, field, device_ptr) if row_stride is None
               else lib().phys_batch_bind_strided(self._h, field, device_ptr, int(row_stride)))
@@ -399,6 +403,60 @@ class Batch:
         n = self.nenv - env0 if n is None else n
         if lib().phys_batch_depth_image(self._h, int(env0), int(n), stream) != 0:
             raise RuntimeError("depth_image failed: " + (lib().phys_last_error() or b"").decode())
+
+    # ---- range sensors on any body (phys_batch_rays_cast) ----
+    def configure_rays(self, rays, rmin, rmax):
+        """The table of rays: a list of (body, frame, origin [3], dir [3]) or a structured array of RAY_DTYPE, 1 .. RAYS_MAX of them; frame
+        is RAY_BODY (origin and direction turn with the body), RAY_WORLD_DIR (the origin turns with the body, the direction is the
+        world's: straight down from a toe) or RAY_HEADING (both turn with the body's yaw only).  Body 0 is the world.  Directions are
+        normalised, so a value is a metric range in [rmin, rmax], 0 <= rmin < rmax.  The bodies' poses are F_XPOS / F_XQUAT as the last
+        step launch or forward pass left them (NOT refreshed by reset_envs, end_episodes or set(F_QPOS)).  Sizes F_RAYS to one double per
+        ray and env (bind a tensor after this call), restores the default geoms and drops bound ids and normals."""
+        if isinstance(rays, np.ndarray) and rays.dtype.names:
+            table = np.ascontiguousarray(rays.astype(RAY_DTYPE, copy=False)).reshape(-1)
+        else:
+            rays = list(rays)
+            table = np.zeros(len(rays), dtype=RAY_DTYPE)
+            for k, (body, frame, origin, direction) in enumerate(rays):
+                table[k] = (int(body), int(frame), np.asarray(origin, dtype=np.float64), np.asarray(direction, dtype=np.float64))
+        assert RAY_DTYPE.itemsize == 56
+        if lib().phys_batch_rays_configure(self._h, table.ctypes.data, int(table.size), float(rmin), float(rmax)) != 0:
+            raise ValueError("configure_rays failed: " + (lib().phys_last_error() or b"").decode())
+
+    def ray_geoms(self, mask=None):
+        """Which geoms the rays see: bit g of `mask` = compiled collision geom g; None: the default (the static planes, boxes and height
+        field).  Whatever the mask, a ray never sees the geoms of its own body.  -> the mask now in force."""
+        mask = self.depth_default_geoms() if mask is None else int(mask)
+        if mask < 0 or mask >> 32:
+            raise ValueError("ray_geoms: the mask is one 32-bit word")
+        if lib().phys_batch_rays_set_geoms(self._h, mask) != 0:
+            raise ValueError("ray_geoms failed: " + (lib().phys_last_error() or b"").decode())
+        return mask
+
+    def bind_ray_ids(self, device_ptr):
+        """The hit ids: int32 [nenv][nrays] in HBM, contiguous: per ray the compiled geom that gave the range, -1 where it is rmax.  None
+        unbinds; configure_rays drops the binding."""
+        if lib().phys_batch_rays_bind_ids(self._h, device_ptr) != 0:
+            raise RuntimeError("bind_ray_ids failed: " + (lib().phys_last_error() or b"").decode())
+
+    def bind_ray_normals(self, device_ptr):
+        """The normals: float64 [nenv][nrays][3] in HBM, contiguous: the world-frame unit normal of the surface at the hit, against the
+        ray; zero on a miss and where the range is rmin from inside a solid.  None unbinds; configure_rays drops the binding."""
+        if lib().phys_batch_rays_bind_normals(self._h, device_ptr) != 0:
+            raise RuntimeError("bind_ray_normals failed: " + (lib().phys_last_error() or b"").decode())
+
+    def cast_rays(self, env0=0, n=None, stream=None):
+        """One launch on `stream` (default: the batch's own), in order with the step launches there: F_RAYS (and the bound ids and
+        normals) of envs [env0, env0 + n)."""
+        n = self.nenv - env0 if n is None else n
+        if lib().phys_batch_rays_cast(self._h, int(env0), int(n), stream) != 0:
+            raise RuntimeError("cast_rays failed: " + (lib().phys_last_error() or b"").decode())
+
+    def ray_launches(self):
+        """Diagnostics: the ray launches so far."""
+        a = ctypes.c_longlong(0)
+        lib().phys_batch_debug_ray_launches(self._h, ctypes.byref(a))
+        return a.value
 
     def set_pd_mode(self, on=True):
         lib().phys_batch_set_pd_mode(self._h, 1 if on else 0)

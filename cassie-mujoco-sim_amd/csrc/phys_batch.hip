@@ -11,6 +11,7 @@
  */
 #include <hip/hip_runtime.h>
 
+#include <cstddef>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -51,6 +52,9 @@ struct phys_batch {
     DevBuf<double> d_scan_offsets;
     ck::DepthCfg depth = {};        /* the depth image (phys_batch_depth_configure, _bind_pose, _set_geoms, _bind_ids: the caller's arrays) */
     long long depth_launches[2] = {0, 0}; /* launches of the static / the scene kernel (phys_batch_debug_depth_launches) */
+    ck::RayCfg rays = {};           /* the range sensors (phys_batch_rays_configure, _set_geoms, _bind_ids, _bind_normals): their table is d_rays */
+    DevBuf<ck::RayDef> d_rays;
+    long long ray_launches = 0;     /* launches of the ray kernel (phys_batch_debug_ray_launches) */
     hipStream_t stream = nullptr;
     hipStream_t recent_streams[4] = {nullptr, nullptr, nullptr, nullptr}; /* streams of the most recent launches (callers may pass
                                        their own, and ranges of one batch may be in flight on several at once) */
@@ -423,7 +427,7 @@ static void note_field_in_use(phys_batch *b, int field) {
 /* rows [env0, env0 + n) of a field between a dense host array and HBM (dense, or strided when the field is a column
  * block of a caller-owned tensor), asynchronously on the batch's stream */
 static bool copy_rows(phys_batch *b, int field, void *host, int env0, int n, bool to_device, const char *what) {
-    if (!b->d_field[field]) { phys_set_last_error("this field is allocated by phys_batch_derive (PHYS_F_HEIGHT_SCAN: phys_batch_scan_configure, PHYS_F_DEPTH: phys_batch_depth_configure); call it first"); return false; }
+    if (!b->d_field[field]) { phys_set_last_error("this field is allocated by phys_batch_derive (PHYS_F_HEIGHT_SCAN: phys_batch_scan_configure, PHYS_F_DEPTH: phys_batch_depth_configure, PHYS_F_RAYS: phys_batch_rays_configure); call it first"); return false; }
     const size_t row = (size_t)b->dim[field], st = (size_t)b->stride[field];
     double *dev = b->d_field[field] + st * env0;
     if (n == 0) return true;
@@ -457,7 +461,7 @@ phys_batch_t *phys_batch_create(const cm_model_t *model, int nenv, int device) {
     const int d[PHYS_F_COUNT] = {model->nq, model->nv, model->nv, 1, model->nu, model->nv, model->nbody * 6,
                                  model->nv, model->nsensordata, model->nu, model->nbody * 3, model->nbody * 4,
                                  model->nu, model->nu, model->nu, model->nbody * 3,
-                                 model->nu + 1, CM_MEAS_DIM, model->nu, model->nu, CM_DRV_DIM, model->nv * model->nv, 0, 0};
+                                 model->nu + 1, CM_MEAS_DIM, model->nu, model->nu, CM_DRV_DIM, model->nv * model->nv, 0, 0, 0};
     const size_t n = (size_t)nenv;
     bool ok = true;
     for (int f = 0; f < PHYS_F_COUNT; ++f) {
@@ -465,6 +469,7 @@ phys_batch_t *phys_batch_create(const cm_model_t *model, int nenv, int device) {
         if (f == PHYS_F_DERIVED || f == PHYS_F_QM) continue; /* large and optional: allocated by the first phys_batch_derive */
         if (f == PHYS_F_HEIGHT_SCAN) continue;              /* sized and allocated by phys_batch_scan_configure */
         if (f == PHYS_F_DEPTH) continue;                    /* ... by phys_batch_depth_configure */
+        if (f == PHYS_F_RAYS) continue;                     /* ... by phys_batch_rays_configure */
         ok = ok && b->d_field[f].alloc(n * (d[f] > 0 ? d[f] : 1), true, "field");
     }
     ok = ok && b->d_models.alloc(1, false, "model");
@@ -660,14 +665,15 @@ int phys_batch_bind(phys_batch_t *b, int field, void *device_ptr) {
 int phys_batch_bind_strided(phys_batch_t *b, int field, void *device_ptr, int row_stride) {
     if (!b || !device_ptr || field < 0 || field >= PHYS_F_COUNT) return -1;
     if (row_stride != b->dim[field]) {
-        const bool may = field == PHYS_F_QPOS || field == PHYS_F_QVEL || field == PHYS_F_SENSORDATA || field == PHYS_F_HEIGHT_SCAN || field == PHYS_F_DEPTH;
+        const bool may = field == PHYS_F_QPOS || field == PHYS_F_QVEL || field == PHYS_F_SENSORDATA || field == PHYS_F_HEIGHT_SCAN || field == PHYS_F_DEPTH || field == PHYS_F_RAYS;
         if (!may || row_stride < b->dim[field]) {
-            phys_set_last_error("phys_batch_bind_strided: only qpos / qvel / sensordata / the height scan / the depth image take a row stride, and it must be >= the field's dim");
+            phys_set_last_error("phys_batch_bind_strided: only qpos / qvel / sensordata / the height scan / the depth image / the ray ranges take a row stride, and it must be >= the field's dim");
             return -1;
         }
     }
     if (field == PHYS_F_HEIGHT_SCAN && b->scan.npoints <= 0) { phys_set_last_error("phys_batch_bind: configure the scan first (phys_batch_scan_configure sizes PHYS_F_HEIGHT_SCAN)"); return -1; }
     if (field == PHYS_F_DEPTH && b->depth.width <= 0) { phys_set_last_error("phys_batch_bind: configure the depth image first (phys_batch_depth_configure sizes PHYS_F_DEPTH)"); return -1; }
+    if (field == PHYS_F_RAYS && b->rays.nrays <= 0) { phys_set_last_error("phys_batch_bind: configure the rays first (phys_batch_rays_configure sizes PHYS_F_RAYS)"); return -1; }
     (void)hipSetDevice(b->device);
     /* no stream synchronisation: launches already queued keep the pointers they were given, and hipFree of the
      * replaced buffer waits for the device by itself */
@@ -1084,6 +1090,68 @@ int phys_batch_depth_image(phys_batch_t *b, int env0, int n, void *stream) {
     if (scene) hipLaunchKernelGGL(ck::cassie_depth_scene_kernel, grid, dim3(WV_WAVE), 0, s, io);
     else hipLaunchKernelGGL(ck::cassie_depth_kernel, grid, dim3(WV_WAVE), 0, s, io);
     return hip_ok(hipGetLastError(), scene ? "cassie_depth_scene_kernel launch" : "cassie_depth_kernel launch") ? 0 : -1;
+}
+
+/* ------------------------------------------------ range sensors ---- */
+static_assert(sizeof(ck::RayDef) == sizeof(phys_ray_t) && offsetof(ck::RayDef, origin) == offsetof(phys_ray_t, origin) &&
+              offsetof(ck::RayDef, dir) == offsetof(phys_ray_t, dir) && offsetof(ck::RayDef, frame) == offsetof(phys_ray_t, frame), "phys_ray_t is the kernel's table entry");
+static_assert(PHYS_RAY_BODY == ck::RAY_BODY && PHYS_RAY_WORLD_DIR == ck::RAY_WORLD_DIR && PHYS_RAY_HEADING == ck::RAY_HEADING, "the frames' numbers");
+int phys_batch_rays_configure(phys_batch_t *b, const phys_ray_t *rays, int nrays, double rmin, double rmax) {
+    if (!b) return refuse("phys_batch_rays_configure", ck::RAYS_SIZE_REFUSAL);
+    ck::RayCfg cfg;
+    std::vector<ck::RayDef> table(nrays >= 1 && nrays <= ck::RAYS_MAX ? (size_t)nrays : 1);
+    if (const char *why = ck::rays_configure(b->host_model, (const ck::RayDef *)rays, nrays, rmin, rmax, table.data(), cfg)) return refuse("phys_batch_rays_configure", why);
+    (void)hipSetDevice(b->device);
+    if (!quiesce(b)) return -1;  /* (launches in flight may be reading the table that goes away) */
+    DevBuf<ck::RayDef> tab;
+    DevBuf<double> out;
+    if (!tab.alloc((size_t)nrays, false, "ray table")) return -1;
+    if (!hip_ok(hipMemcpy(tab, table.data(), sizeof(ck::RayDef) * (size_t)nrays, hipMemcpyHostToDevice), "hipMemcpy(ray table)")) return -1;
+    /* the field takes the table's size: a buffer of the batch's own of the new size (a caller's binding is dropped: bind again) */
+    if (!out.alloc((size_t)nrays * (size_t)b->nenv, true, "ray ranges")) return -1;
+    b->d_rays = std::move(tab);
+    b->d_field[PHYS_F_RAYS] = std::move(out);
+    b->dim[PHYS_F_RAYS] = nrays; b->stride[PHYS_F_RAYS] = nrays;
+    b->rays = cfg;               /* (the default geoms again, no ids and no normals -- their size may have changed: bind them again) */
+    return 0;
+}
+int phys_batch_rays_set_geoms(phys_batch_t *b, unsigned mask) {
+    if (!b) return -1;
+    if (b->rays.nrays <= 0) { phys_set_last_error("phys_batch_rays_set_geoms: call phys_batch_rays_configure first (it restores the default set)"); return -1; }
+    if (const char *why = ck::check_ray_geoms(b->host_model, mask)) return refuse("phys_batch_rays_set_geoms", why);
+    b->rays.geoms = mask;        /* (as phys_batch_bind: launches already queued keep the mask they were given) */
+    return 0;
+}
+int phys_batch_rays_bind_ids(phys_batch_t *b, void *device_ptr) {
+    if (!b) return -1;
+    if (b->rays.nrays <= 0) { phys_set_last_error("phys_batch_rays_bind_ids: call phys_batch_rays_configure first (it sizes the table)"); return -1; }
+    b->rays.ids = (int *)device_ptr;
+    return 0;
+}
+int phys_batch_rays_bind_normals(phys_batch_t *b, void *device_ptr) {
+    if (!b) return -1;
+    if (b->rays.nrays <= 0) { phys_set_last_error("phys_batch_rays_bind_normals: call phys_batch_rays_configure first (it sizes the table)"); return -1; }
+    b->rays.normals = (double *)device_ptr;
+    return 0;
+}
+int phys_batch_debug_ray_launches(const phys_batch_t *b, long long *launches) {
+    if (!b) return -1;
+    if (launches) *launches = b->ray_launches;
+    return 0;
+}
+int phys_batch_rays_cast(phys_batch_t *b, int env0, int n, void *stream) {
+    if (!b) return -1;
+    if (b->rays.nrays <= 0 || !b->d_field[PHYS_F_RAYS] || !b->d_rays) { phys_set_last_error("phys_batch_rays_cast: call phys_batch_rays_configure first"); return -1; }
+    if (!range_ok(b, env0, n)) { phys_set_last_error("phys_batch_rays_cast: env range out of bounds"); return -1; }
+    (void)hipSetDevice(b->device);
+    if (n == 0) return 0;
+    hipStream_t s = launch_stream(b, stream);
+    ck::RayCfg rays = b->rays;
+    rays.rays = b->d_rays;
+    ++b->ray_launches;
+    hipLaunchKernelGGL(ck::cassie_rays_kernel, dim3((unsigned)ck::rays_grid(n, rays.nrays)), dim3(WV_WAVE), 0, s,
+                       ck::make_rays_io(view_of(b), rays, b->d_field[PHYS_F_RAYS], b->stride[PHYS_F_RAYS], env0, n));
+    return hip_ok(hipGetLastError(), "cassie_rays_kernel launch") ? 0 : -1;
 }
 
 int phys_batch_sync(phys_batch_t *b) {

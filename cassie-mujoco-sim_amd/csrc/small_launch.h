@@ -1,12 +1,12 @@
 /*
- * small_launch.h -- how the kernels around the step kernel (small_kernels.h, surface_kernels.h, depth_kernel.h, episode_kernels.h) are
+ * small_launch.h -- how the kernels around the step kernel (small_kernels.h, surface_kernels.h, depth_kernel.h, ray_kernel.h, episode_kernels.h) are
  * launched: the records a kernel's arguments are built from, one builder per kernel that returns its filled argument struct for an env
  * range, the grid of every launch, and the checks of what a caller configures, each returning the message of its refusal (null: fine).
  * Pure host code, no HIP runtime calls, in the spirit of step_policy.h: the launcher (phys_batch.hip) keeps the records in the batch,
  * prefixes a message with its entry point's name and launches what a builder returns on the grid given here; the wave emulator's entry
  * points (tests/emu) fill the same records from their arguments and go through the same builders, grids and checks, so a CPU test of
  * one of these kernels also runs the launcher's refusals, grid and choice of kernel (tests/test_small_launch.py pins them one by one).
- * No field of ScanIO, DepthIO, EpisodeIO, ResetIO, DeriveIO or SetConstIO is assigned anywhere else.
+ * No field of ScanIO, DepthIO, RayIO, EpisodeIO, ResetIO, DeriveIO or SetConstIO is assigned anywhere else.
  */
 #ifndef CASSIE_SMALL_LAUNCH_H
 #define CASSIE_SMALL_LAUNCH_H
@@ -16,6 +16,7 @@
 
 #include "depth_kernel.h"
 #include "episode_kernels.h"
+#include "ray_kernel.h"
 #include "small_kernels.h"
 
 namespace ck {
@@ -46,6 +47,9 @@ struct ScanCfg { int npoints, body; double range; const double *offsets; };
 /* the depth image (phys_batch_depth_configure; width 0: not configured): the camera on its body, tan(fovy / 2), the caller's per-env
  * extrinsics (null: the shared pose), the geoms it renders and the caller's hit-id image (null: none) */
 struct DepthCfg { int width, height, body; double tan_half, znear, zfar, cam_pos[3], cam_quat[4]; const double *pose; unsigned geoms; int *ids; };
+/* the range sensors (phys_batch_rays_configure; nrays 0: not configured): the table [nrays] (where it lies once a kernel reads it, which
+ * the caller names), the range, the geoms they see and the caller's hit ids / normals (null: none) */
+struct RayCfg { int nrays; double rmin, rmax; const RayDef *rays; unsigned geoms; int *ids; double *normals; };
 /* placed restarts (phys_batch_place_configure; anchor 0: off): the footprint [npoints][2], the table of what a placement moves, and the
  * per-env arrays: poses [nenv][4], next terrains [nenv] (null: none bound), ground heights [nenv] */
 struct PlaceCfg { int anchor, npoints; double ground_ref; const PlaceTable *table; const double *offsets, *pose; const int *next; double *ground; };
@@ -93,6 +97,27 @@ inline const char *depth_configure(const cm_model_t &m, int model_stride, int bo
          nullptr, depth_default_geoms(m), nullptr};
     return nullptr;
 }
+/* the geoms a ray may see: the depth image's rule */
+inline const char *check_ray_geoms(const cm_model_t &m, unsigned mask) { return check_depth_geoms(m, mask); }
+/* (what the launcher also answers a call without a batch) */
+constexpr const char *RAYS_SIZE_REFUSAL = "1 .. 1024 rays and 0 <= rmin < rmax";
+/* the range sensors' configuration: checks the caller's rays [nrays] and writes them, the directions normalised, to table [nrays]
+ * (which the caller then hands to the kernel: c.rays stays null); fills c: the default geoms, no ids, no normals */
+inline const char *rays_configure(const cm_model_t &m, const RayDef *rays, int nrays, double rmin, double rmax, RayDef *table, RayCfg &c) {
+    if (!rays || !table || nrays < 1 || nrays > RAYS_MAX || !(rmin >= 0 && rmin < rmax && rmax < INFINITY)) return RAYS_SIZE_REFUSAL;
+    for (int j = 0; j < nrays; ++j) {
+        const RayDef &r = rays[j];
+        if (r.body < 0 || r.body >= m.nbody) return "a ray's body must lie in [0, nbody)";
+        if (r.frame != RAY_BODY && r.frame != RAY_WORLD_DIR && r.frame != RAY_HEADING) return "a ray's frame is PHYS_RAY_BODY, PHYS_RAY_WORLD_DIR or PHYS_RAY_HEADING";
+        const double len = sqrt(r.dir[0] * r.dir[0] + r.dir[1] * r.dir[1] + r.dir[2] * r.dir[2]);
+        const bool finite = std::isfinite(r.origin[0]) && std::isfinite(r.origin[1]) && std::isfinite(r.origin[2]);
+        if (!(len > 0 && len < INFINITY) || !finite) return "a ray needs a finite origin and a finite direction that is not zero";
+        table[j] = r;
+        for (int k = 0; k < 3; ++k) table[j].dir[k] = r.dir[k] / len;
+    }
+    c = {nrays, rmin, rmax, nullptr, depth_default_geoms(m), nullptr, nullptr};
+    return nullptr;
+}
 /* a placement's configuration; fills the table (place_classify, episode_kernels.h) */
 inline const char *place_configure(const cm_model_t &m, int model_stride, int anchor, const double *offsets_xy, int npoints, double ground_ref, PlaceTable &tab) {
     if (npoints < 0 || npoints > PLACE_MAXPOINTS || (npoints > 0 && !offsets_xy) || !(ground_ref == ground_ref)) return "a footprint of 0 .. 1024 points and a ground height";
@@ -113,6 +138,11 @@ inline int depth_grid(int n, int width, int height) {
     const int T = DEPTH_TILE;
     const long long jobs = (long long)n * (((width + T - 1) / T) * ((height + T - 1) / T));
     return (int)(jobs < DEPTH_GRID ? jobs : DEPTH_GRID);
+}
+/* a job is (env, block of 64 rays); a fixed grid walks the job list (a first choice: ray_kernel.h) */
+inline int rays_grid(int n, int nrays) {
+    const long long jobs = (long long)n * ((nrays + WV_WAVE - 1) / WV_WAVE);
+    return (int)(jobs < RAYS_GRID ? jobs : RAYS_GRID);
 }
 /* a few workgroups walk the envs: one workgroup per env made the kernel a 0.5 ms stall of its stream on a saturated GPU (cassie_reset_kernel) */
 inline int reset_grid(int count) { return count < 4 ? count : 4; }
@@ -162,6 +192,15 @@ inline DepthIO make_depth_io(const BatchView &v, const DepthCfg &c, double *out,
     io.pose = c.pose;
     io.qpos = v.qpos; io.sq = v.sq; io.out = out; io.sout = sout; io.warn = v.warn;
     if (scene) { io.geoms = c.geoms; io.xpos = v.xpos; io.xquat = v.xquat; io.sxp = 3 * v.nbody; io.sxq = 4 * v.nbody; io.ids = c.ids; }
+    return io;
+}
+inline RayIO make_rays_io(const BatchView &v, const RayCfg &c, double *out, int sout, int env0, int n) {
+    RayIO io = zeroed<RayIO>();
+    fill_surface(io, v);
+    io.models = v.models; io.model_stride = v.model_stride;
+    io.env0 = env0; io.n = n; io.nrays = c.nrays; io.rmin = c.rmin; io.rmax = c.rmax; io.rays = c.rays; io.geoms = c.geoms;
+    io.xpos = v.xpos; io.xquat = v.xquat; io.sxp = 3 * v.nbody; io.sxq = 4 * v.nbody;
+    io.out = out; io.sout = sout; io.ids = c.ids; io.normals = c.normals; io.warn = v.warn;
     return io;
 }
 inline int episode_row_dim(const BatchView &v) { return v.nq + v.nv + v.nsd + v.nu + v.nv; }

@@ -89,6 +89,7 @@ enum { PHYS_F_QPOS, PHYS_F_QVEL, PHYS_F_QACC_WARMSTART, PHYS_F_TIME, PHYS_F_CTRL
        PHYS_F_HEIGHT_SCAN, /* [npoints]: the height scan of phys_batch_height_scan (sized by phys_batch_scan_configure) */
        PHYS_F_DEPTH,      /* [height * width], row-major, row 0 at the top: the depth image of phys_batch_depth_image (sized by
                              phys_batch_depth_configure) */
+       PHYS_F_RAYS,       /* [nrays]: the ranges of phys_batch_rays_cast (sized by phys_batch_rays_configure) */
        PHYS_F_COUNT };
 
 /* mj_makeData (reference :441-447) for nenv environments on HIP device `device`;
@@ -278,6 +279,65 @@ unsigned phys_batch_depth_default_geoms(const phys_batch_t *b);
 unsigned phys_batch_depth_all_geoms(const phys_batch_t *b);
 int phys_batch_depth_bind_ids(phys_batch_t *b, void *device_ptr);
 int phys_batch_debug_depth_launches(const phys_batch_t *b, long long *static_kernel, long long *scene_kernel);
+/* RANGE SENSORS ON ANY BODY: a table of rays, each attached to a body of its own -- a foot, a shin, the world -- against the env's
+ * collision geometry on the device: the range, the geom hit and the surface normal (foot clearance, the slope under a foothold, a forward
+ * range reading, a fixed lidar fan).  Where the scan and the depth image start from one body whose pose follows from qpos, a ray starts
+ * from ANY body, whose pose is read from PHYS_F_XPOS / PHYS_F_XQUAT.
+ *   phys_batch_rays_configure   rays [nrays] (host memory), 1 <= nrays <= 1024, 0 <= rmin < rmax (finite), every `body` in [0, nbody) -- body 0, the
+ *                               world, is allowed: a sensor fixed in the scene -- every `frame` one of PHYS_RAY_*, `origin` finite, `dir`
+ *                               finite and not zero: the call NORMALISES dir on the host, so a ray's parameter is a metric range.  Sizes
+ *                               PHYS_F_RAYS to nrays doubles per env in a buffer of the batch's own (bind a tensor AFTER configuring;
+ *                               phys_batch_bind_strided takes a row stride for this field).  Uploads the table, waits for the batch's
+ *                               streams, restores the default mask.  Reconfiguring is allowed; it drops the id and normal bindings (their
+ *                               size may change).  -1 + phys_last_error() on failure.
+ *                                 POSES         a ray's body pose is the env's row of PHYS_F_XPOS / PHYS_F_XQUAT USED AS STORED (not
+ *                                               normalised, not recomputed), as for the moving geoms of the depth image: what the STALENESS
+ *                                               paragraph of phys_batch_depth_set_geoms above says holds here word for word -- stepping
+ *                                               launches and forward passes write these rows (and an upload or binding of the two fields);
+ *                                               phys_batch_reset_envs, phys_batch_end_episodes with restart, an upload of qpos and
+ *                                               phys_batch_drive_pass do NOT, and after one of those rays and moving geoms are where the
+ *                                               bodies WERE; a fresh batch holds zeros there: run a forward pass first.
+ *                                 FRAMES        with p = xpos[body], R = R(xquat[body]) and Rz the rotation about world z by the heading of
+ *                                               xquat[body] (the scan's: atan2(2 (w z + x y), 1 - 2 (y y + z z))), the ray o + t u has
+ *                                                 PHYS_RAY_BODY       o = p + R origin,   u = R dir;
+ *                                                 PHYS_RAY_WORLD_DIR  o = p + R origin,   u = dir  (straight down from a toe, say);
+ *                                                 PHYS_RAY_HEADING    o = p + Rz origin,  u = Rz dir.
+ *   phys_batch_rays_cast        one launch on `stream` (NULL: the batch's own), in order with the stepping launches there, for envs
+ *                               [env0, env0 + n).  A ray's VALUE is the smallest t in [rmin, rmax] at which o + t u meets a geom of the
+ *                               mask, rmax where there is none.  Geoms, their poses (static bodies composed; moving bodies from xpos /
+ *                               xquat as stored; CM_P_GEOM_POS / CM_P_GEOM_QUAT the env's own once geometry is randomised), the env's
+ *                               terrain grid and WARN_TERRAIN_INDEX are exactly those of the depth image with a mask (phys_batch_depth_
+ *                               set_geoms above): static planes, boxes, the height field, spheres and capsules; spheres, capsules and
+ *                               boxes on moving bodies.  A convex solid met over [t0, t1] gives t0 if t0 >= rmin, rmin if t0 < rmin <= t1
+ *                               (the origin is inside it), else nothing.  A NaN pose -- the geom's or the ray's body's -- fails every
+ *                               comparison: the geom, or the ray, sees nothing (rmax, id -1, normal 0); nothing indexes memory by such a
+ *                               value.  A batch that never configures rays runs exactly as before.
+ *   phys_batch_rays_set_geoms   which geoms the rays see: bit g = compiled collision geom g, checked as phys_batch_depth_set_geoms checks
+ *                               its mask.  The default, restored by every configure, is phys_batch_depth_default_geoms' set.
+ *                               SELF-EXCLUSION: whatever the mask says, a ray skips every geom whose geom_bodyid equals the ray's `body`
+ *                               (a toe-mounted ray does not read rmin off the toe's own capsule).
+ *   phys_batch_rays_bind_ids    optional HIT IDS: int32 [nenv][nrays] in DEVICE memory, contiguous, indexed by the absolute env: the
+ *                               compiled geom that gave the value, -1 where the value is rmax; ties go to the lower index.  Configure
+ *                               first; NULL unbinds.
+ *   phys_batch_rays_bind_normals optional NORMALS: double [nenv][nrays][3] in DEVICE memory, contiguous: the world-frame unit normal of the
+ *                               surface at the hit, oriented against the ray (n . u <= 0); (0, 0, 0) on a miss and where the value is rmin
+ *                               taken from inside a solid.
+ *                                 plane         plus or minus the geom's z axis;
+ *                                 box           the face of the slab axis that gave t0 (on a tie the lowest axis index);
+ *                                 sphere        from the centre to the hit;
+ *                                 capsule       from the axis point clamp(z, -h, h) to the hit;
+ *                                 height field  the normal of the triangle that gave the hit (v00 v10 v01 or v11 v01 v10), rotated by the
+ *                                               geom's frame; any pose of the geom, as in the depth image.
+ *                               Configure first; NULL unbinds.
+ *   phys_batch_debug_ray_launches  diagnostics: the ray launches so far. */
+typedef struct { int body; int frame; double origin[3]; double dir[3]; } phys_ray_t;
+enum { PHYS_RAY_BODY = 0, PHYS_RAY_WORLD_DIR = 1, PHYS_RAY_HEADING = 2 };
+int phys_batch_rays_configure(phys_batch_t *b, const phys_ray_t *rays, int nrays, double rmin, double rmax);
+int phys_batch_rays_set_geoms(phys_batch_t *b, unsigned mask);
+int phys_batch_rays_bind_ids(phys_batch_t *b, void *device_ptr);      /* int32 [nenv][nrays], NULL unbinds */
+int phys_batch_rays_bind_normals(phys_batch_t *b, void *device_ptr);  /* double [nenv][nrays][3], NULL unbinds */
+int phys_batch_rays_cast(phys_batch_t *b, int env0, int n, void *stream);
+int phys_batch_debug_ray_launches(const phys_batch_t *b, long long *launches);
 /* host <-> HBM copies of whole fields or of a row range [env0, env0 + n) */
 int phys_batch_upload(phys_batch_t *b, int field, const double *host, int env0, int n);
 int phys_batch_download(phys_batch_t *b, int field, double *host, int env0, int n);
@@ -291,7 +351,7 @@ int phys_batch_download_warn(phys_batch_t *b, int *host_warn, int *host_info /* 
 /* raw device pointer of a field (for torch / RCCL interop); bind replaces it with caller-owned HBM */
 void *phys_batch_device_ptr(phys_batch_t *b, int field);
 int phys_batch_bind(phys_batch_t *b, int field, void *device_ptr);
-/* same with a row stride in doubles (>= the field's dim) for PHYS_F_QPOS / QVEL / SENSORDATA / HEIGHT_SCAN / DEPTH, so that they can be
+/* same with a row stride in doubles (>= the field's dim) for PHYS_F_QPOS / QVEL / SENSORDATA / HEIGHT_SCAN / DEPTH / RAYS, so that they can be
  * column blocks of ONE caller-owned [nenv][nq + nv + nsensordata] observation tensor -- the buffer an RCCL all-gather
  * sends as is; uploads / downloads of a strided field are 2-D copies */
 int phys_batch_bind_strided(phys_batch_t *b, int field, void *device_ptr, int row_stride);
