@@ -372,7 +372,7 @@
         }
         if (ncon_found > capc) warn |= WARN_CONTACT_FULL;
         if constexpr (NW == 1) if (io.drive_mode) {
-            if (io.integrate) drive_level_io(io, S, m, env, lane, lastsub); /* mj_forward leaves the drive-level state alone */
+            if (integrates<FEAT>(io)) drive_level_io(io, S, m, env, lane, lastsub); /* mj_forward leaves the drive-level state alone */
             wv::sync();
         }
         if constexpr (NW == 2) { CK_STAMP(33); wv::publish(&S.cmd[4], sub + 1); wv::wait_for(&S.cmd[3], sub + 1); } /* the verdict for wave 1; wave 1's com / cinert / cdof for the stage below */

@@ -204,8 +204,8 @@
                 rt[0] = rR; rt[1] = rtype >= 0 ? -rB * jvel - rK * rimp * (rpos - rmargin) : 0.0; rt[2] = jws;
                 rt[3] = rtype < 0 ? -1.0 : (rtype == CM_CNSTR_EQUALITY ? 0.0 : 1.0);
             }
-            if (io.ext && pass == 0 && rtype == CM_CNSTR_EQUALITY && r_ < CM_MAXEQROW) {
-                cm_ext_t *ex = io.ext + env;
+            if (readout_ext<FEAT>(io) && pass == 0 && rtype == CM_CNSTR_EQUALITY && r_ < CM_MAXEQROW) {
+                cm_ext_t *ex = readout_ext<FEAT>(io) + env;
                 ex->eq_pos[r_] = rpos; ex->eq_id[r_] = rid;
 #pragma unroll
                 for (int k = 0; k < NVP; ++k) if (k < nv) ex->eq_J[r_][k] = ycol[k];
@@ -235,8 +235,8 @@
             for (int i = 0; i < 3; ++i) io.xpos_out[((size_t)env * io.sb + b) * 3 + i] = S.x.s.xpos[b][i];
             if (io.xquat_out) for (int i = 0; i < 4; ++i) io.xquat_out[((size_t)env * io.sb + b) * 4 + i] = S.x.s.xquat[b][i];
         }
-        if (io.ext) {
-            cm_ext_t *ex = io.ext + env;
+        if (readout_ext<FEAT>(io)) {
+            cm_ext_t *ex = readout_ext<FEAT>(io) + env;
             if (isbody) for (int i = 0; i < 6; ++i) ex->cvel[b][i] = S.x.s.cvel[b][i];
             if (isbody) for (int i = 0; i < 3; ++i) { ex->subtree_com[b][i] = S.com[broot > 0 ? broot : 0][i]; ex->xipos[b][i] = S.x.s.xipos[b][i]; }
             if (lane < m->nsite) {
@@ -267,8 +267,8 @@
         }
         /* first constraint row of every contact (lane = contact), for the contact-force read-out */
         int caddr = -1;
-        const bool want_cfrc = io.body_cfrc && (sub == nsub - 1 || !io.integrate); /* read out by the last substep only */
-        if (io.ext || want_cfrc) {
+        const bool want_cfrc = io.body_cfrc && (sub == nsub - 1 || !integrates<FEAT>(io)); /* read out by the last substep only */
+        if (readout_ext<FEAT>(io) || want_cfrc) {
             int acc = nefc_before_contacts;
             for (int c = 0; c < ncon; ++c) {
                 const int dim = S.c_dim[c];

@@ -14,9 +14,9 @@
             if (lane == 0) { fbuf[2 * NROW] = (double)ncon; fbuf[2 * NROW + 1] = (double)nefc; fbuf[2 * NROW + 2] = (double)iters; fbuf[2 * NROW + 3] = (double)nguarded; }
             wv::block_barrier(); /* P */
 #ifdef CK_WIDE_PROFILE
-            if (io.prof && lane < 12) io.prof[(size_t)env * NSTAMP + (lane < 6 ? 16 + lane : 22 + lane)] = (long long)S.x.stepv[lane / 6][lane % 6];   /* slots 16..21: wave 0, 28..33: wave 1 */
+            if constexpr (feat_prof(FEAT)) if (io.prof && lane < 12) io.prof[(size_t)env * NSTAMP + (lane < 6 ? 16 + lane : 22 + lane)] = (long long)S.x.stepv[lane / 6][lane % 6];   /* slots 16..21: wave 0, 28..33: wave 1 */
 #endif
-            if (io.ext || want_cfrc) {
+            if (readout_ext<FEAT>(io) || want_cfrc) {
                 /* decode the pyramid: normal = sum of the edge forces, tangents = mu (f+ - f-); the rows' forces from LDS */
                 const int a0 = caddr >= 0 ? caddr : 0;
                 double fn = 0, ft1 = 0, ft2 = 0;
@@ -25,8 +25,8 @@
                     if (S.c_dim[lane] == 1) fn = f0;
                     else { const double f1 = fbuf[a0 + 1], f2 = fbuf[a0 + 2], f3 = fbuf[a0 + 3], mu = S.c_fri[lane][0]; fn = f0 + f1 + f2 + f3; ft1 = mu * (f0 - f1); ft2 = mu * (f2 - f3); }
                 }
-                if (io.ext) {
-                    cm_ext_t *ex = io.ext + env;
+                if (readout_ext<FEAT>(io)) {
+                    cm_ext_t *ex = readout_ext<FEAT>(io) + env;
                     if (lane < ncon) { ex->con_force[lane][0] = fn; ex->con_force[lane][1] = ft1; ex->con_force[lane][2] = ft2; }
                     if (lane == 0) { ex->ncon = ncon; ex->nefc = nefc; ex->solver_iter = iters; }
                 }
@@ -53,7 +53,7 @@
             wv::block_barrier(); /* E */
             CK_STAMP(37);
             if (wv::opaque(S.cmd[0])) { warn |= WARN_DIVERGED; break; }
-            if (!io.integrate) break;
+            if (!integrates<FEAT>(io)) break;
             time += h;
             continue;
         }
@@ -411,7 +411,7 @@
         }
         if constexpr (NW == 2 && CK_PRIO_W0_PGS != CK_PRIO_W0) wv::set_priority<CK_PRIO_W0>();
         CK_STAMP(11);
-        if (io.ext || want_cfrc) {
+        if (readout_ext<FEAT>(io) || want_cfrc) {
             /* decode the pyramid: normal = sum of the edge forces, tangents = mu (f+ - f-) */
             const int a0 = caddr >= 0 ? caddr : 0;
             const double f0 = wv::shfl(f, a0), f1 = wv::shfl(f, (a0 + 1) & 63), f2 = wv::shfl(f, (a0 + 2) & 63), f3 = wv::shfl(f, (a0 + 3) & 63);
@@ -420,8 +420,8 @@
                 if (S.c_dim[lane] == 1) fn = f0;
                 else { const double mu = S.c_fri[lane][0]; fn = f0 + f1 + f2 + f3; ft1 = mu * (f0 - f1); ft2 = mu * (f2 - f3); }
             }
-            if (io.ext) {
-                cm_ext_t *ex = io.ext + env;
+            if (readout_ext<FEAT>(io)) {
+                cm_ext_t *ex = readout_ext<FEAT>(io) + env;
                 if (lane < ncon) { ex->con_force[lane][0] = fn; ex->con_force[lane][1] = ft1; ex->con_force[lane][2] = ft2; }
                 if (lane == 0) { ex->ncon = ncon; ex->nefc = nefc; ex->solver_iter = iters; }
             }
@@ -461,7 +461,7 @@
             wv::block_barrier(); /* E */
             CK_STAMP(37);
             if (wv::opaque(S.cmd[0])) { warn |= WARN_DIVERGED; break; }
-            if (!io.integrate) break;
+            if (!integrates<FEAT>(io)) break;
             time += h;
             continue;
         }
@@ -503,7 +503,7 @@
 
         /* ---- sensors, part 2 (the accelerometer needs qacc), actuator velocities, the last substep's outputs ---- */
         outputs_after_qacc(io, S, m, env, lane, isdof, k_, nu, qacc, aslot, sb, need_imu, lastsub, pf_agear * S.qvel[pf_adof], ncon, nefc, iters, nguarded);
-        if (!io.integrate) break;
+        if (!integrates<FEAT>(io)) break;
         CK_STAMP(13);
 
         /* ================= P12 semi-implicit Euler with implicit joint damping ================= */

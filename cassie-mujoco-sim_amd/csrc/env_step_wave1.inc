@@ -49,7 +49,7 @@
                 wv::wait_for(&S.cmd[4], sub1 + 1);
                 if (wv::opaque(S.cmd[0])) return -1; /* (the row-capped instantiation hands this substep over) */
                 if (io.drive_mode) {
-                    if (io.integrate) drive_level_io(io, S, m, env, lane, sub1 == nsub - 1);
+                    if (integrates<FEAT>(io)) drive_level_io(io, S, m, env, lane, sub1 == nsub - 1);
                     wv::sync();
                 }
                 CK_STAMP(4);
@@ -59,10 +59,10 @@
                     const double kgear = m->dof_gear[kd], klo = m->dof_ctrl_lo[kd], khi = m->dof_ctrl_hi[kd];
                     const int kq = m->dof_qadr[kd], ka = m->dof_act[kd];
                     wv::wait_for(&S.cmd[1], sub1 + 1); /* wave 0's velocity stage has the body forces (cfrc) in LDS */
-                    bias_forces_and_qfrc_smooth<NVP, (NVP > 32)>(io, S, m, env, ids, kdamp, kstiff, kref, kgear, klo, khi, kq, ka);
+                    bias_forces_and_qfrc_smooth<NVP, FEAT, (NVP > 32)>(io, S, m, env, ids, kdamp, kstiff, kref, kgear, klo, khi, kq, ka);
                 }
                 /* (the sensor stage's constants: requested ahead of the barrier) */
-                const bool lastsub1 = sub1 == nsub - 1 || !io.integrate;
+                const bool lastsub1 = sub1 == nsub - 1 || !integrates<FEAT>(io);
                 const bool need_imu1 = lastsub1 || io.all_outputs_every_substep || (io.drive_mode && sub1 + 2 == nsub);
                 const bool issens1 = lane < m->nsensor && (lastsub1 || io.drive_mode || io.all_outputs_every_substep);
                 const int ls1 = issens1 ? lane : 0;
@@ -184,7 +184,7 @@
                      * behind them and the substep's outputs -- the accelerometers (they read qacc, the partials parked in S.accel and
                      * cdof, none of which wave 0 touches before the next barrier F), the actuator velocities, the last substep's
                      * stores -- run beside wave 0's guard and kinematics stage instead of in front of them */
-                    if (io.integrate) {
+                    if (integrates<FEAT>(io)) {
                         if constexpr (!stage_h_early) stage_factor_h<NVP, TOPO>(S, k_, isdof, nv, lcol, lrowh);
                         euler_step<NVP, TOPO>(S, m, lane, isdof, k_, nv, njnt, h, qacc, lcol, lrowh, dih, pf_kdamp, pf_ejt, pf_eqa, pf_eda);
                     }
@@ -194,7 +194,7 @@
                     outputs_after_qacc(io, S, m, env, lane, isdof, k_, nu, qacc, aslot, sb, need_imu, lastsub, av, ncon, nefc, iters, nguarded);
                     CK_STAMP(14);
                 }
-                if (!io.integrate || ++sub1 >= nsub) return -1;
+                if (!integrates<FEAT>(io) || ++sub1 >= nsub) return -1;
             }
         }
     }

@@ -1,5 +1,7 @@
-/* cassie_hfield.xml, the row-capped fast instantiation in its two-wave form (see kernels_cassie_2w.hip) */
+/* cassie_hfield.xml, the row-capped fast instantiation in its two-wave form (see kernels_cassie_2w.hip)
+ * (a LEAN form, pk_stages.h: neither FEAT_READOUT nor FEAT_PROF -- the launcher never starts it with the read-out block, as a
+ * forward pass or with the stage stamps on, step_policy.h) */
 #include "step_kernels.h"
 namespace ck {
-template void launch_step<32, TopoCassie32, FEAT_HFIELD, FAST_ROWS, 2>(unsigned, hipStream_t, const PhysIO &);
+template void launch_step<32, TopoCassie32, FEAT_HFIELD, FAST_ROWS, 2, false, 2, 0, FEAT_LEAN>(unsigned, hipStream_t, const PhysIO &);
 }  // namespace ck

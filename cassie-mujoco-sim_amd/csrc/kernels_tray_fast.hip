@@ -3,9 +3,10 @@
  * a substep with more rows hands the env over to the full instantiation behind it, which walks the hand-over list -- one
  * wavefront per env as well: a workgroup of it fits wherever a workgroup of the fast kernel has retired (the two-wave form of the
  * pass wants two SIMDs with 256 free registers each on one CU, and waited 4 ms for them behind the other env range's one-wave
- * workgroups) */
+ * workgroups)
+ * (the row-capped instantiation is a LEAN form, pk_stages.h: neither FEAT_READOUT nor FEAT_PROF) */
 #include "step_kernels.h"
 namespace ck {
-template void launch_step<40, TopoCassieTray38, FEAT_WAVEPAIRS, FAST_ROWS_TRAY>(unsigned, hipStream_t, const PhysIO &);
+template void launch_step<40, TopoCassieTray38, FEAT_WAVEPAIRS, FAST_ROWS_TRAY, 1, false, 1, 0, FEAT_LEAN>(unsigned, hipStream_t, const PhysIO &);
 template void launch_step<40, TopoCassieTray38, FEAT_WAVEPAIRS, MID_ROWS, 1, true>(unsigned, hipStream_t, const PhysIO &);
 }  // namespace ck

@@ -224,30 +224,37 @@ static int refuse(const char *entry, const char *why) {
 using ck::launch_step;
 using ck::FAST_ROWS; using ck::FAST_ROWS_TRAY; using ck::MID_ROWS; using ck::WIDE_ROWS;
 using ck::TopoCassie32; using ck::TopoCassieTray38; using ck::TopoRuntime;
-/* plain cassie.xml (FEAT 0) and cassie_hfield.xml (FEAT_HFIELD): all three tiers */
+/* plain cassie.xml (FEAT 0) and cassie_hfield.xml (FEAT_HFIELD): all three tiers.  The fast forms are LEAN (step_plan.h: is_lean_form --
+ * the kernel's trailing SERVE parameter is FEAT_LEAN), their _PROF forms add the stage stamps, every other form carries both FEAT_READOUT
+ * and FEAT_PROF (the default) */
+using ck::FEAT_LEAN; using ck::FEAT_PROF; using ck::FEAT_READOUT; using ck::FEAT_FULL;
 template <int FEAT>
 static const ck::StepLauncher CASSIE_FORMS[ck::FORM_COUNT] = {
-    launch_step<32, TopoCassie32, FEAT>,                                   /* FORM_ALONE (+ the one-wave lookup pass) */
-    launch_step<32, TopoCassie32, FEAT, MID_ROWS, 2, false, 1>,           /* FORM_ALONE_2W: 512 registers a lane */
-    launch_step<32, TopoCassie32, FEAT, WIDE_ROWS, 2, false, 1>,          /* FORM_WIDE */
-    launch_step<32, TopoCassie32, FEAT, FAST_ROWS>,                        /* FORM_FAST */
-    launch_step<32, TopoCassie32, FEAT, FAST_ROWS, 2>,                     /* FORM_FAST_2W */
-    launch_step<32, TopoCassie32, FEAT, FAST_ROWS, 2, false, 2, MID_ROWS>, /* FORM_FAST_INPLACE */
-    nullptr,                                                               /* FORM_MID_WALK */
-    launch_step<32, TopoCassie32, FEAT, MID_ROWS, 2, true>,               /* FORM_MID_WALK_2W */
-    launch_step<32, TopoCassie32, FEAT, WIDE_ROWS, 2, true, 1>,           /* FORM_WIDE_WALK */
+    launch_step<32, TopoCassie32, FEAT>,                                              /* FORM_ALONE (+ the one-wave lookup pass) */
+    launch_step<32, TopoCassie32, FEAT, MID_ROWS, 2, false, 1>,                      /* FORM_ALONE_2W: 512 registers a lane */
+    launch_step<32, TopoCassie32, FEAT, WIDE_ROWS, 2, false, 1>,                     /* FORM_WIDE */
+    launch_step<32, TopoCassie32, FEAT, FAST_ROWS, 1, false, 1, 0, FEAT_LEAN>,        /* FORM_FAST */
+    launch_step<32, TopoCassie32, FEAT, FAST_ROWS, 2, false, 2, 0, FEAT_LEAN>,        /* FORM_FAST_2W */
+    launch_step<32, TopoCassie32, FEAT, FAST_ROWS, 2, false, 2, MID_ROWS, FEAT_LEAN>, /* FORM_FAST_INPLACE */
+    nullptr,                                                                          /* FORM_MID_WALK */
+    launch_step<32, TopoCassie32, FEAT, MID_ROWS, 2, true>,                          /* FORM_MID_WALK_2W */
+    launch_step<32, TopoCassie32, FEAT, WIDE_ROWS, 2, true, 1>,                      /* FORM_WIDE_WALK */
+    launch_step<32, TopoCassie32, FEAT, FAST_ROWS, 1, false, 1, 0, FEAT_PROF>,        /* FORM_FAST_PROF */
+    launch_step<32, TopoCassie32, FEAT, FAST_ROWS, 2, false, 2, 0, FEAT_PROF>,        /* FORM_FAST_2W_PROF */
 };
 /* cassie_tray_box.xml without height-field pairs: fast (47 rows) and 63 rows */
 static const ck::StepLauncher TRAY_FORMS[ck::FORM_COUNT] = {
-    launch_step<40, TopoCassieTray38, ck::FEAT_WAVEPAIRS>,                         /* FORM_ALONE */
-    launch_step<40, TopoCassieTray38, ck::FEAT_WAVEPAIRS, MID_ROWS, 2>,            /* FORM_ALONE_2W */
-    nullptr,                                                                       /* FORM_WIDE */
-    launch_step<40, TopoCassieTray38, ck::FEAT_WAVEPAIRS, FAST_ROWS_TRAY>,         /* FORM_FAST */
-    launch_step<40, TopoCassieTray38, ck::FEAT_WAVEPAIRS, FAST_ROWS_TRAY, 2>,      /* FORM_FAST_2W */
-    nullptr,                                                                       /* FORM_FAST_INPLACE */
-    launch_step<40, TopoCassieTray38, ck::FEAT_WAVEPAIRS, MID_ROWS, 1, true>,      /* FORM_MID_WALK */
-    launch_step<40, TopoCassieTray38, ck::FEAT_WAVEPAIRS, MID_ROWS, 2, true>,      /* FORM_MID_WALK_2W */
-    nullptr,                                                                       /* FORM_WIDE_WALK */
+    launch_step<40, TopoCassieTray38, ck::FEAT_WAVEPAIRS>,                                              /* FORM_ALONE */
+    launch_step<40, TopoCassieTray38, ck::FEAT_WAVEPAIRS, MID_ROWS, 2>,                                 /* FORM_ALONE_2W */
+    nullptr,                                                                                            /* FORM_WIDE */
+    launch_step<40, TopoCassieTray38, ck::FEAT_WAVEPAIRS, FAST_ROWS_TRAY, 1, false, 1, 0, FEAT_LEAN>,    /* FORM_FAST */
+    launch_step<40, TopoCassieTray38, ck::FEAT_WAVEPAIRS, FAST_ROWS_TRAY, 2, false, 2, 0, FEAT_READOUT>, /* FORM_FAST_2W (keeps the read-out code: kernels_tray_2w.hip) */
+    nullptr,                                                                                            /* FORM_FAST_INPLACE */
+    launch_step<40, TopoCassieTray38, ck::FEAT_WAVEPAIRS, MID_ROWS, 1, true>,                           /* FORM_MID_WALK */
+    launch_step<40, TopoCassieTray38, ck::FEAT_WAVEPAIRS, MID_ROWS, 2, true>,                           /* FORM_MID_WALK_2W */
+    nullptr,                                                                                            /* FORM_WIDE_WALK */
+    launch_step<40, TopoCassieTray38, ck::FEAT_WAVEPAIRS, FAST_ROWS_TRAY, 1, false, 1, 0, FEAT_PROF>,    /* FORM_FAST_PROF */
+    launch_step<40, TopoCassieTray38, ck::FEAT_WAVEPAIRS, FAST_ROWS_TRAY, 2, false, 2, 0, FEAT_FULL>,    /* FORM_FAST_2W_PROF */
 };
 /* FORM_ALONE only: the Cassie topology with both height-field and box pairs, the tray model with height-field pairs, any other model */
 static const ck::StepLauncher CASSIE_ALL_FORMS[ck::FORM_COUNT] = {launch_step<32, TopoCassie32, ck::FEAT_ALL>};
@@ -370,8 +377,9 @@ static int launch(phys_batch *b, int nsub, int integrate, hipStream_t s, bool sc
     const ck::StepFamily fam = ck::pick_family(hm, b->generic_kernel);
     const ck::StepLauncher *family = FAMILY_FORMS[fam];
     const bool has_inplace = family[ck::FORM_FAST_INPLACE] != nullptr;
+    const bool prof = io.prof != nullptr;
     auto forms_if = [&](bool inplace) {
-        return ck::launch_forms(fam, has_inplace, hm.maxefc, integrate, io.ext != nullptr, n, nsub, b->fast_rows, b->waves_per_env, b->waves_per_env_tray, inplace);
+        return ck::launch_forms(fam, has_inplace, hm.maxefc, integrate, io.ext != nullptr, n, nsub, b->fast_rows, b->waves_per_env, b->waves_per_env_tray, inplace, prof);
     };
     ck::StepForms forms = forms_if(false);
     const bool fast = ck::is_fast_form(forms.first);
@@ -389,9 +397,10 @@ static int launch(phys_batch *b, int nsub, int integrate, hipStream_t s, bool sc
         if (forms.wide) { hl.list2 = b->d_handover_list2; hl.count2 = b->d_handover_count2 + 2 * (size_t)env0; hl.seen2 = b->handover_seen2.dev() + env0; }
         const int seen = *(volatile int *)(b->handover_seen.host() + env0);
         grids = ck::pass_grids(n, seen, forms.wide ? b->handover_seen2.host()[env0] : 0, forms.wide);
-        if (forms.first == ck::FORM_FAST_2W && has_inplace) {
+        if ((forms.first == ck::FORM_FAST_2W || forms.first == ck::FORM_FAST_2W_PROF) && has_inplace) {
             const bool was = range->inplace;
-            range->inplace = ck::next_inplace(was, seen, b->inplace_mode, io.order != nullptr);
+            /* (a profiled launch takes the plain form -- the stamps are in FORM_FAST_2W_PROF alone -- and the range goes with it) */
+            range->inplace = !prof && ck::next_inplace(was, seen, b->inplace_mode, io.order != nullptr);
             if (was != range->inplace) reset_range_words(b, env0, s);
             ++b->form_launches[range->inplace ? 1 : 0];
             forms = forms_if(range->inplace);
@@ -401,6 +410,11 @@ static int launch(phys_batch *b, int nsub, int integrate, hipStream_t s, bool sc
     for (int i = 0; i < plan.n; ++i) {
         const ck::StepPass &p = plan.pass[i];
         if (!family[p.form]) { (void)hip_ok(hipErrorInvalidDeviceFunction, "cassie_step_kernel launch (no instantiation of this form)"); return -1; }
+        /* (the policy never pairs them; a plan that does is not launched: the code for it is not in the kernel) */
+        if (ck::lean_form_refuses(p.form, p.io.ext != nullptr, p.io.integrate, p.io.prof != nullptr)) {
+            (void)hip_ok(hipErrorInvalidValue, "cassie_step_kernel launch (a lean fast form with the read-out block, a forward pass or the stage stamps)");
+            return -1;
+        }
         family[p.form](p.grid, s, p.io);
         if (!hip_ok(hipGetLastError(), "cassie_step_kernel launch")) return -1;
         if (i == 0 && ev_after) (void)hipEventRecord(ev_after, s);   /* (the first kernel of the launch does the work: per-kernel timing) */

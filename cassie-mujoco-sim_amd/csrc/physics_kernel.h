@@ -46,6 +46,16 @@
  * behind the solve; four workgroup barriers and four LDS flags per substep; bit for bit the one-wave form); the hand-over list
  * and the list-walking pass behind the row-capped fast instantiation.
  *
+ * Round 7: two more FEAT_* bits say what kinds of launch an instantiation can serve (pk_stages.h).  FEAT_READOUT: the read-out block
+ * (PhysIO::ext -- every cm_ext_t store) and forward passes (PhysIO::integrate == 0 -- the exits behind the solve, the integrate tests of
+ * the loop); FEAT_PROF: the stage stamps (CK_STAMP is CK_FRESH() alone without it), the placement and clock words at the env's end,
+ * the wide solve's stepv dump.  Each is tested in one helper (readout_ext<FEAT>, integrates<FEAT>, feat_prof(FEAT): `if constexpr`), so
+ * an instantiation without a bit contains none of that code and one with it exactly what it always did.  The fast forms are LEAN --
+ * neither bit (step_plan.h: is_lean_form) -- because the launcher never starts them with the read-out block, as a forward pass or
+ * with the profile buffer on (step_policy.h: launch_forms; lean_form_refuses is its last check); their _PROF siblings add FEAT_PROF
+ * for profiled launches; every other form carries both (FEAT_FULL).  The kernel takes the two bits as a trailing template parameter of
+ * their own (cassie_step_kernel's SERVE, default FEAT_FULL) and hands env_step FEAT | SERVE.
+ *
  * Numerically this follows the same algorithm as oracle/cassie_oracle.c but with
  * its own operation order (half solves, reciprocal multiplies, wave reductions,
  * chain sums), so parity is to a tolerance, not bitwise.
@@ -71,7 +81,9 @@ namespace ck {
 /* ======================================================== the env step ==== */
 /* FEAT selects the collision code a model needs, so that the instantiation for plain cassie.xml does not carry the
  * register pressure of paths it never takes: FEAT_HFIELD = height-field pairs, FEAT_WAVEPAIRS = plane-box / box-box
- * pairs handled by the whole wave.  The launcher picks the instantiation from the model (phys_batch.hip). */
+ * pairs handled by the whole wave -- and the launches it can serve: FEAT_READOUT = the read-out block and forward passes,
+ * FEAT_PROF = the stage stamps (the header comment; the fast forms have neither).  The launcher picks the instantiation from the
+ * model and the launch (phys_batch.hip, step_policy.h). */
 
 /* (env_step's return value: the substep it ended in front of, with this bit set when it ended there because the substep fits the
  * fast code again -- PhysIO::down_rows -- and not because it needs more than this code holds) */
@@ -201,11 +213,11 @@ WV_DEVICE int env_step(const PhysIO &io, EnvShared<NVP, LPack<TOPO, NVP>::count,
          * are stored only by the LAST substep of a launch: the others' values would be overwritten anyway, and on this
          * hardware vector stores share the loads' completion counter (vmcnt), so a store that is still in flight holds up
          * the next stage's first model read. */
-        const bool lastsub = sub == nsub - 1 || !io.integrate;
+        const bool lastsub = sub == nsub - 1 || !integrates<FEAT>(io);
         /* Body quaternions feed only the IMU frame sensor, the site / body orientation read-outs and xquat_out -- all of
          * them values of the last substep (in a drive mode also of the one before it, see the sensors): the other
          * substeps carry rotation matrices only through the kinematic recursion. */
-        const bool need_quat = lastsub || io.ext != nullptr || io.all_outputs_every_substep || (io.drive_mode && sub + 2 == nsub);
+        const bool need_quat = lastsub || readout_ext<FEAT>(io) != nullptr || io.all_outputs_every_substep || (io.drive_mode && sub + 2 == nsub);
         /* divergence guard (mj_checkPos/mj_checkVel role): sticky flag, state left alone */
         {
             bool badv = false;
@@ -591,7 +603,7 @@ WV_DEVICE int env_step(const PhysIO &io, EnvShared<NVP, LPack<TOPO, NVP>::count,
             /* the body forces are in LDS: wave 1 projects them on the motion axes and forms qfrc_smooth behind its
              * factorisations (bias_forces_and_qfrc_smooth), while this wave goes on to the constraint rows */
             wv::publish(&S.cmd[1], sub + 1);
-        } else bias_forces_and_qfrc_smooth<NVP>(io, S, m, env, ids, kdamp, kstiff, kref, kgear, klo, khi, kq, ka);
+        } else bias_forces_and_qfrc_smooth<NVP, FEAT>(io, S, m, env, ids, kdamp, kstiff, kref, kgear, klo, khi, kq, ka);
         const int pf_eq = lane < 3 * m->neq ? lane / 3 : 0;
         /* (only what the rows' LDS reads hang on: the bodies and their roots; the anchors, masks and solver parameters are read in place,
          * where their trip to memory runs under those LDS reads -- carrying them too pushes launch-long values into scratch) */
@@ -608,7 +620,7 @@ WV_DEVICE int env_step(const PhysIO &io, EnvShared<NVP, LPack<TOPO, NVP>::count,
         io.progress[env] = bailed ? sub : nsub;
         if (bailed && !bailed_down && io.handover_out_list) io.handover_out_list[io.env0 + wv::atomic_add(io.handover_out_count, 1)] = env;
     }
-    if (io.integrate && io.drive_mode) {
+    if (integrates<FEAT>(io) && io.drive_mode) {
         drive_state_store(io, S, env, lane);
         if (lane < nu) io.ctrl[(size_t)env * io.su + lane] = S.ctrl[lane]; /* the applied torque: d->ctrl of the reference */
         if (bailed) {
@@ -622,7 +634,7 @@ WV_DEVICE int env_step(const PhysIO &io, EnvShared<NVP, LPack<TOPO, NVP>::count,
             }
         }
     }
-    if (io.integrate) {
+    if (integrates<FEAT>(io)) {
         if (lane < nq) io.qpos[(size_t)env * io.sq + lane] = S.qpos[lane];
         if (lane < nv) {
             io.qvel[(size_t)env * io.sqv + lane] = S.qvel[lane];
@@ -656,8 +668,12 @@ WV_DEVICE int env_step(const PhysIO &io, EnvShared<NVP, LPack<TOPO, NVP>::count,
  * take ALL its remaining substeps to the pass behind the kernel, one serial chain per env while the range's stream waited (23 % of
  * the stress workload's time for 0.3 % of the env-launches); in place it costs that one substep's longer code path.  Results are
  * the same bit for bit: a substep is computed by the same instructions whichever instantiation holds it. */
-template <int NVP, class TOPO, int FEAT = FEAT_ALL, int MAXR = MID_ROWS, int NW = 1, bool WALK = false, int WPS = NW, int INROWS = 0>
+/* SERVE (round 7): FEAT_READOUT | FEAT_PROF (pk_stages.h), the launches the instantiation can serve -- handed to env_step beside the
+ * collision bits as ONE set, FEAT | SERVE.  A trailing parameter with the full default, so that every instantiation that does not
+ * name it is what it always was; the lean fast forms name FEAT_LEAN (their _PROF forms FEAT_PROF). */
+template <int NVP, class TOPO, int FEAT = FEAT_ALL, int MAXR = MID_ROWS, int NW = 1, bool WALK = false, int WPS = NW, int INROWS = 0, int SERVE = FEAT_FULL>
 WV_GLOBAL void __launch_bounds__(WV_WAVE * NW) WV_OCC WV_WAVES_PER_SIMD(WPS) cassie_step_kernel(PhysIO io) {
+    static_assert((FEAT & FEAT_FULL) == 0 && (SERVE & ~FEAT_FULL) == 0, "FEAT: the collision bits; SERVE: FEAT_READOUT / FEAT_PROF");
     WV_SHARED EnvShared<NVP, LPack<TOPO, NVP>::count, MAXR> S;
     const int slot = wv::env_id();
     if constexpr (WALK) {
@@ -667,7 +683,7 @@ WV_GLOBAL void __launch_bounds__(WV_WAVE * NW) WV_OCC WV_WAVES_PER_SIMD(WPS) cas
         for (int idx = slot; idx < count; idx += wv::grid_size()) {
             const int env = io.handover_list[io.env0 + idx];
             const long long t0 = io.cost ? wv::clock() : 0, t0w = io.cost_wall ? wv::wall_clock() : 0;
-            env_step<NVP, TOPO, FEAT, MAXR, NW>(io, S, env, io.progress[env], io.nsub);
+            env_step<NVP, TOPO, FEAT | SERVE, MAXR, NW>(io, S, env, io.progress[env], io.nsub);
             if (io.cost && wv::lane() == 0 && (NW == 1 || wv::wave_id() == 0)) {
                 io.cost[env] += (unsigned)((wv::clock() - t0) >> 6);
                 if (io.cost_wall) io.cost_wall[env] += (unsigned)(wv::wall_clock() - t0w);
@@ -717,7 +733,7 @@ WV_GLOBAL void __launch_bounds__(WV_WAVE * NW) WV_OCC WV_WAVES_PER_SIMD(WPS) cas
         const bool stay = io.inplace_stay_rows > 0;
         bool did = false;
         for (int s = sub_start;;) {
-            int at = env_step<NVP, TOPO, FEAT, MAXR, NW>(io, S, env, s, sub_end);
+            int at = env_step<NVP, TOPO, FEAT | SERVE, MAXR, NW>(io, S, env, s, sub_end);
             /* (wave 0 knows where the call ended; both waves' stores of the state are out before either loads it again) */
             if (wv::lane() == 0 && wv::wave_id() == 0) S.cmd[5] = at;
             wv::drain_vmem(); wv::block_barrier();
@@ -725,7 +741,7 @@ WV_GLOBAL void __launch_bounds__(WV_WAVE * NW) WV_OCC WV_WAVES_PER_SIMD(WPS) cas
             if (at < 0 || at >= sub_end) break;                 /* done (or the state diverged: flagged, left alone) */
             did = true;
             /* the 63-row code: for this one substep, or (PhysIO::inplace_stay_rows) until a substep fits the fast code again */
-            int at2 = env_step<NVP, TOPO, FEAT, INROWS, NW>(io2, S2, env, at, stay ? sub_end : at + 1);
+            int at2 = env_step<NVP, TOPO, FEAT | SERVE, INROWS, NW>(io2, S2, env, at, stay ? sub_end : at + 1);
             if (wv::lane() == 0 && wv::wave_id() == 0) S.cmd[5] = at2;
             wv::drain_vmem(); wv::block_barrier();
             at2 = wv::opaque(S.cmd[5]);
@@ -737,11 +753,13 @@ WV_GLOBAL void __launch_bounds__(WV_WAVE * NW) WV_OCC WV_WAVES_PER_SIMD(WPS) cas
             s = at2;
         }
         if (did && io.inplace_count && wv::lane() == 0 && wv::wave_id() == 0) wv::atomic_add(io.inplace_count, 1);
-    } else env_step<NVP, TOPO, FEAT, MAXR, NW>(io, S, env, sub_start, sub_end);
+    } else env_step<NVP, TOPO, FEAT | SERVE, MAXR, NW>(io, S, env, sub_start, sub_end);
     if (sub_end < io.nsub) wv::publish_global<NW>(io.chunk_flag + env, io.chunk_seq, chunk + 1);
+    if constexpr (feat_prof(SERVE)) {
     if (io.prof && wv::lane() == 0) io.prof[(size_t)env * NSTAMP + 40 + (NW == 2 ? wv::wave_id() : 0)] = wv::hw_id(); /* (profiling aid: the CU / SIMD of the wave) */
     if (io.prof && wv::lane() == 0 && (NW == 1 || wv::wave_id() == 0)) { /* (profiling aid: the shader clock against the 100 MHz wall clock at the env's end) */
         io.prof[(size_t)env * NSTAMP + 42] = wv::clock(); io.prof[(size_t)env * NSTAMP + 43] = wv::wall_clock();
+    }
     }
     if (io.cost && wv::lane() == 0 && (NW == 1 || wv::wave_id() == 0)) { /* 64-clock units: 32 bits hold minutes */
         const unsigned c = (unsigned)((wv::clock() - t0) >> 6);

@@ -186,8 +186,20 @@ WV_DRIVE_FN void drive_level_io(const PhysIO &io, SH &S, ModelPtr m, int env, in
     }
 }
 
-/* FEAT selects the collision code a model needs (see env_step) */
-enum { FEAT_HFIELD = 1, FEAT_WAVEPAIRS = 2, FEAT_ALL = 3 };
+/* FEAT selects the collision code a model needs, and the launches an instantiation can serve (see env_step):
+ *   FEAT_READOUT  the read-out block (PhysIO::ext) and forward passes (PhysIO::integrate == 0)
+ *   FEAT_PROF     the stage stamps (PhysIO::prof), the placement / clock words at the env's end, the wide solve's stepv dump
+ * FEAT_FULL = both: every instantiation but the lean fast forms (step_plan.h: is_lean_form; FEAT_LEAN = neither), which the launcher
+ * never hands such a launch (step_policy.h: launch_forms, lean_form_refuses).  The kernel takes these two as its trailing SERVE
+ * parameter (default FEAT_FULL) and env_step sees FEAT | SERVE; FEAT_ALL is every collision code */
+enum { FEAT_HFIELD = 1, FEAT_WAVEPAIRS = 2, FEAT_READOUT = 4, FEAT_PROF = 8, FEAT_LEAN = 0, FEAT_FULL = FEAT_READOUT | FEAT_PROF, FEAT_ALL = FEAT_HFIELD | FEAT_WAVEPAIRS };
+
+/* The one place each of the two bits is tested: an instantiation without the bit sees a constant, so nothing behind it is compiled. */
+constexpr bool feat_readout(int feat) { return (feat & FEAT_READOUT) != 0; }
+constexpr bool feat_prof(int feat) { return (feat & FEAT_PROF) != 0; }   /* (CK_STAMP, pk_types.h, and the other profiling aids test this one) */
+/* the read-out block of the launch, and whether it integrates: what an instantiation without FEAT_READOUT is never launched with */
+template <int FEAT> WV_DEVICE cm_ext_t *readout_ext(const PhysIO &io) { if constexpr (feat_readout(FEAT)) return io.ext; else return nullptr; }
+template <int FEAT> WV_DEVICE bool integrates(const PhysIO &io) { if constexpr (feat_readout(FEAT)) return io.integrate != 0; else return true; }
 
 /* what a lane is, as a body and as a dof: model indices read once per launch and handed to the stage functions that both waves of
  * the two-wave form call */
@@ -372,8 +384,8 @@ WV_DEVICE void mass_matrix_columns(const PhysIO &io, SH &S, ModelPtr m, int env,
         }
     }
     }
-    if (io.ext && isdof) {
-        cm_ext_t *ex = io.ext + env;
+    if (readout_ext<FEAT>(io) && isdof) {
+        cm_ext_t *ex = readout_ext<FEAT>(io) + env;
 #pragma unroll
         for (int i = 0; i < NVP; ++i) if (i < nv && i >= k_) { const double v = (i == k_) ? col[i] + m->dof_armature[k_] : col[i]; ex->qM[i][k_] = v; ex->qM[k_][i] = v; }
     }
@@ -383,7 +395,7 @@ WV_DEVICE void mass_matrix_columns(const PhysIO &io, SH &S, ModelPtr m, int env,
 /* ---------------- bias forces projected on the motion axes, passive forces, actuation -> qfrc_smooth (lane = dof).  Reads the
  * cfrc tile the velocity stage left, cdof, qpos / qvel / ctrl; writes S.qfrc_smooth.  One-wave form: in line behind the
  * velocity stage.  Two-wave form: wave 1, behind its factorisations, once wave 0 has published the cfrc tile. ---------------- */
-template <int NVP, bool ROLLED = false, class SH>
+template <int NVP, int FEAT, bool ROLLED = false, class SH>
 WV_DEVICE void bias_forces_and_qfrc_smooth(const PhysIO &io, SH &S, ModelPtr m, int env, const LaneIds &ids, const double kdamp, const double kstiff,
                                            const double kref, const double kgear, const double klo, const double khi, const int kq, const int ka) {
     const int nbody = ids.nbody, nv = ids.nv, kbody = ids.kbody, kbend = ids.kbend;

@@ -18,7 +18,8 @@ constexpr int NSTAMP = 48;   /* 0..15 stage boundaries, 16..32 sub-stage stamps,
                                 40..41 where the hardware placed the env's wave(s), 42..43 shader clock and 100 MHz clock at the env's end,
                                 44..46 the height-field pre-pass, 47 wave 1's sensor stage (tools/stage_profile.py names them) */
 #define CK_TRI(k, i) ((k) * ((k) + 1) / 2 + (i))
-#define CK_STAMP(i) do { if (io.prof && lane == 0) io.prof[(size_t)env * NSTAMP + (i)] = wv::clock(); CK_FRESH(); } while (0)
+/* (FEAT: the enclosing template's; an instantiation without FEAT_PROF -- pk_stages.h: feat_prof -- keeps CK_FRESH() alone) */
+#define CK_STAMP(i) do { if constexpr (feat_prof(FEAT)) { if (io.prof && lane == 0) io.prof[(size_t)env * NSTAMP + (i)] = wv::clock(); } CK_FRESH(); } while (0)
 /* stage boundary: re-derive the lane index and its aliases (see wv::fresh_lane) */
 #define CK_FRESH() do { lane = wv::fresh_lane(); b = lane; k_ = lane; isbody = b < nbody; isdof = k_ < nv; } while (0)
 

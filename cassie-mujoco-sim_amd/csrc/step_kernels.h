@@ -8,9 +8,9 @@
 #include "step_launch.h"
 
 namespace ck {
-template <int NVP, class TOPO, int FEAT, int MAXR, int NW, bool WALK, int WPS, int INROWS>
+template <int NVP, class TOPO, int FEAT, int MAXR, int NW, bool WALK, int WPS, int INROWS, int SERVE>
 void launch_step(unsigned grid, hipStream_t s, const PhysIO &io) {
-    hipLaunchKernelGGL((cassie_step_kernel<NVP, TOPO, FEAT, MAXR, NW, WALK, WPS, INROWS>), dim3(grid), dim3(NW * WV_WAVE), 0, s, io);
+    hipLaunchKernelGGL((cassie_step_kernel<NVP, TOPO, FEAT, MAXR, NW, WALK, WPS, INROWS, SERVE>), dim3(grid), dim3(NW * WV_WAVE), 0, s, io);
 }
 }  // namespace ck
 #endif

@@ -14,7 +14,7 @@
 namespace ck {
 using StepLauncher = void (*)(unsigned grid, hipStream_t s, const PhysIO &io);
 
-template <int NVP, class TOPO, int FEAT = FEAT_ALL, int MAXR = MID_ROWS, int NW = 1, bool WALK = false, int WPS = NW, int INROWS = 0>
+template <int NVP, class TOPO, int FEAT = FEAT_ALL, int MAXR = MID_ROWS, int NW = 1, bool WALK = false, int WPS = NW, int INROWS = 0, int SERVE = FEAT_FULL>
 void launch_step(unsigned grid, hipStream_t s, const PhysIO &io);
 }  // namespace ck
 #endif

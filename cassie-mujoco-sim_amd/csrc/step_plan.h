@@ -29,6 +29,8 @@ enum StepForm {
     FORM_MID_WALK,      /* 63 rows walking the first list, one wave per env */
     FORM_MID_WALK_2W,   /* ... two waves per env */
     FORM_WIDE_WALK,     /* 127 rows walking the second list */
+    FORM_FAST_PROF,     /* FORM_FAST with the stage stamps (FEAT_PROF): what a profiled stepping launch takes */
+    FORM_FAST_2W_PROF,  /* FORM_FAST_2W likewise */
     FORM_COUNT
 };
 
@@ -65,7 +67,7 @@ inline StepFamily pick_family(const cm_model_t &m, bool generic_only) {
 /* the forms a launch takes: `first` is one of the FORM_FAST* forms (the tiers behind it follow) or the form that steps every env alone */
 struct StepForms {
     int first;
-    int mid;            /* behind FORM_FAST / FORM_FAST_2W: FORM_MID_WALK(_2W), or FORM_ALONE (the lookup pass) */
+    int mid;            /* behind FORM_FAST / FORM_FAST_2W (and their _PROF forms): FORM_MID_WALK(_2W), or FORM_ALONE (the lookup pass) */
     bool wide;          /* the model's caps are 127 rows: a FORM_WIDE_WALK pass walks the second list */
     int stay_rows;      /* FORM_FAST_INPLACE: PhysIO::inplace_stay_rows */
 };
@@ -82,7 +84,13 @@ struct StepGrids { unsigned envs, mid, wide; };
 struct StepPass { int form; unsigned grid; PhysIO io; };
 struct StepPlan { int n; StepPass pass[3]; };
 
-inline bool is_fast_form(int form) { return form == FORM_FAST || form == FORM_FAST_2W || form == FORM_FAST_INPLACE; }
+/* The LEAN forms: instantiated with neither FEAT_READOUT nor FEAT_PROF (pk_stages.h), so the read-out stores, the forward-mode exits
+ * and the stage stamps are not in their code at all.  Only stepping launches without the read-out block and without the profile
+ * buffer may take them (step_policy.h: launch_forms never answers otherwise, lean_form_refuses is the launcher's last check). */
+inline bool is_lean_form(int form) { return form == FORM_FAST || form == FORM_FAST_2W || form == FORM_FAST_INPLACE; }
+/* ... and the same code with the stamps (without FEAT_READOUT all the same: stepping launches, no read-out block) */
+inline bool is_prof_form(int form) { return form == FORM_FAST_PROF || form == FORM_FAST_2W_PROF; }
+inline bool is_fast_form(int form) { return is_lean_form(form) || is_prof_form(form); }
 
 /* base: the launch's PhysIO with progress (for a fast first form) and the chunk fields set; the plan clears what the passes do not use */
 inline StepPlan plan_step(const PhysIO &base, const StepForms &f, const HandoverLists &hl, const StepGrids &g) {

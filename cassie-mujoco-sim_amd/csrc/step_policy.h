@@ -25,9 +25,13 @@ constexpr int INPLACE_STAY_ROWS = FAST_ROWS - 4;
 
 /* The forms of the launch of nsub substeps over n envs of a model of family fam (has_inplace: the family has a FORM_FAST_INPLACE
  * instantiation; maxefc: the model's row cap; ext: the read-out block is on; fast_rows, waves_per_env, waves_per_env_tray: the
- * batch's settings; inplace: what the launch's range has decided about the form of its two-wave fast kernel, next_inplace below) */
+ * batch's settings; inplace: what the launch's range has decided about the form of its two-wave fast kernel, next_inplace below;
+ * prof: the batch's profile buffer is on, PhysIO::prof).
+ * The fast forms are LEAN (step_plan.h: is_lean_form): they are chosen only where integrate && !ext -- every branch below that
+ * answers one says so -- and with prof their _PROF forms take their place: the plain form whatever `inplace` says, since the stamps
+ * are in the plain fast kernel alone and a profile is of the code it names. */
 inline StepForms launch_forms(int fam, bool has_inplace, int maxefc, int integrate, bool ext, int n, int nsub, bool fast_rows,
-                              int waves_per_env, int waves_per_env_tray, bool inplace) {
+                              int waves_per_env, int waves_per_env_tray, bool inplace, bool prof = false) {
     StepForms forms = {FORM_ALONE, FORM_ALONE, false, INPLACE_STAY_ROWS};
     if (fam == CASSIE || fam == CASSIE_HFIELD) {
         /* stepping launches go through the row-capped fast instantiation first; the 63-row pass behind it finishes the envs that met
@@ -41,16 +45,28 @@ inline StepForms launch_forms(int fam, bool has_inplace, int maxefc, int integra
              * caps: the one-wave form, whose 421 registers leave room for four envs per CU; the two-wave 512-register form halves that
              * and only pays where the chip is not full anyway, profiles/round6/alone_pass_ab.txt) */
             forms.first = forms.wide ? FORM_WIDE : n > SMALL_BATCH ? FORM_ALONE : FORM_ALONE_2W;
-        else if (waves_per_env == 2) { forms.first = inplace && has_inplace ? FORM_FAST_INPLACE : FORM_FAST_2W; forms.mid = FORM_MID_WALK_2W; }
-        else forms.first = FORM_FAST;     /* (behind it the one-wave 63-row pass looks every env's record up: FORM_ALONE) */
+        else if (waves_per_env == 2) { forms.first = prof ? FORM_FAST_2W_PROF : inplace && has_inplace ? FORM_FAST_INPLACE : FORM_FAST_2W; forms.mid = FORM_MID_WALK_2W; }
+        else forms.first = prof ? FORM_FAST_PROF : FORM_FAST;     /* (behind it the one-wave 63-row pass looks every env's record up: FORM_ALONE) */
     } else if (fam == TRAY) {
         /* the 40-dof model: a fast instantiation of 47 rows (the boxes resting on the tray take it to 32 .. 40 routinely) with the 63-row
          * one behind it walking the list, both in the two-wave form by default (waves_per_env_tray) -- or the 63-row one alone */
         const bool plain = integrate && !ext, two = plain && waves_per_env_tray == 2;
-        if (plain && fast_rows) { forms.first = two ? FORM_FAST_2W : FORM_FAST; forms.mid = two ? FORM_MID_WALK_2W : FORM_MID_WALK; }
+        if (plain && fast_rows) {
+            forms.first = two ? (prof ? FORM_FAST_2W_PROF : FORM_FAST_2W) : (prof ? FORM_FAST_PROF : FORM_FAST);
+            forms.mid = two ? FORM_MID_WALK_2W : FORM_MID_WALK;
+        }
         else forms.first = two ? FORM_ALONE_2W : FORM_ALONE;
     }
     return forms;
+}
+
+/* What the launcher checks in front of every pass, whatever made the plan: a lean form does not hold the code for the read-out block,
+ * a forward pass or the stage stamps -- launched with one of them it would silently do without -- and a profiled form not that for
+ * the first two.  True: the pass must not be launched. */
+inline bool lean_form_refuses(int form, bool ext, int integrate, bool prof) {
+    if (is_lean_form(form)) return ext || !integrate || prof;
+    if (is_prof_form(form)) return ext || !integrate;
+    return false;
 }
 
 /* ---- the chunks of a launch ---- */

@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""Per-stage shader-clock breakdown of the step kernel (profiling aid; needs a GPU)."""
+"""Per-stage shader-clock breakdown of the step kernel (profiling aid; needs a GPU).  A profiled launch of a fast kernel takes its
+_PROF form (csrc/step_plan.h: the fast code + the stage stamps, always the plain form; the fast kernels themselves carry no stamp)."""
 import os, sys
 import numpy as np
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
