@@ -54,9 +54,17 @@ WV_DEVICE void segment_closest(const double *p1, const double *a1, double l1, co
     }
     x1 = t1; x2 = t2;
 }
+/* completes a contact frame from its normal and an optional tangent hint (same rule as oracle/cassie_oracle.c make_frame): a hint
+ * shorter than 0.5 is none, and so is one that is (nearly) parallel to the normal -- a capsule's axis where an end cap meets a face
+ * squarely -- whose remainder after its component along the normal is removed is shorter than FRAME_MIN_HINT: rounding noise of
+ * relative size u / length, or zero, which normalize3 would turn into (1, 0, 0), possibly the normal itself.  The remainder's
+ * squared length is |hint|^2 - (n . hint)^2 for the unit normal n, to 1e-15 (a thousandth of the threshold's square).  Without a
+ * hint the tangent is the y axis (|n_y| < 0.5) or the z axis, less its component along the normal. */
+constexpr double FRAME_MIN_HINT = 1e-6;
 WV_DEVICE void make_frame(double *frame) {
     normalize3(frame);
-    if (sqrt(dot3(frame + 3, frame + 3)) < 0.5) {
+    const double hh = dot3(frame + 3, frame + 3), th = dot3(frame, frame + 3);
+    if (hh < 0.25 || hh - th * th < FRAME_MIN_HINT * FRAME_MIN_HINT) {
         frame[3] = frame[4] = frame[5] = 0;
         if (frame[1] < 0.5 && frame[1] > -0.5) frame[4] = 1; else frame[5] = 1;
     }

@@ -505,8 +505,9 @@ static int plane_box(raw_contact_t *c, const double *pp, const double *mp, const
  * resting and edge-crossing configurations but are not bit-compatible. */
 typedef struct { double u, v, w; int valid; } bb_cand_t;
 #define BB_TIE 1e-10
+/* (which: optional, the candidate number each contact came from -- 0 for the edge contact -- for the test hooks) */
 static int box_box_keep(raw_contact_t *c, int keep, const double *p1, const double *m1, const double *s1, const double *p2, const double *m2, const double *s2,
-                   double margin) {
+                   double margin, int *which) {
     double A[3][3], B[3][3], d[3] = {p2[0] - p1[0], p2[1] - p1[1], p2[2] - p1[2]}, ta[3], tb[3], C[3][3], Q[3][3];
     for (int i = 0; i < 3; ++i) for (int k = 0; k < 3; ++k) { A[i][k] = m1[3 * k + i]; B[i][k] = m2[3 * k + i]; }
     for (int i = 0; i < 3; ++i) { ta[i] = dot3(d, A[i]); tb[i] = dot3(d, B[i]); }
@@ -555,6 +556,7 @@ static int box_box_keep(raw_contact_t *c, int keep, const double *p1, const doub
         c[0].dist = dot3(cd, n);
         if (c[0].dist > margin) return 0;
         for (int x = 0; x < 3; ++x) { c[0].normal[x] = n[x]; c[0].tangent[x] = 0; c[0].pos[x] = 0.5 * (ca[x] + cb[x]); }
+        if (which) which[0] = 0;
         return 1;
     }
 
@@ -639,6 +641,7 @@ static int box_box_keep(raw_contact_t *c, int keep, const double *p1, const doub
     int nc = 0;
     for (int q = 0; q < 24 && nc < bb_keep; ++q) {
         if (cand[q].valid != 1) continue;
+        if (which) which[nc] = q;
         c[nc].dist = cand[q].w;
         for (int x = 0; x < 3; ++x) {
             const double px = cr[x] + cand[q].u * R[a1][x] + cand[q].v * R[a2][x] + cand[q].w * n[x];
@@ -655,13 +658,13 @@ static int box_box_keep(raw_contact_t *c, int keep, const double *p1, const doub
  * out[4][7] = dist, pos, normal */
 int co_test_box_box_keep(int keep, const double *p1, const double *m1, const double *s1, const double *p2, const double *m2, const double *s2, double margin, double *out) {
     raw_contact_t c[8];
-    int n = box_box_keep(c, keep < 1 ? 1 : (keep > 8 ? 8 : keep), p1, m1, s1, p2, m2, s2, margin);
+    int n = box_box_keep(c, keep < 1 ? 1 : (keep > 8 ? 8 : keep), p1, m1, s1, p2, m2, s2, margin, NULL);
     for (int k = 0; k < n; ++k) { out[7 * k] = c[k].dist; for (int i = 0; i < 3; ++i) { out[7 * k + 1 + i] = c[k].pos[i]; out[7 * k + 4 + i] = c[k].normal[i]; } }
     return n;
 }
 int co_test_box_box(const double *p1, const double *m1, const double *s1, const double *p2, const double *m2, const double *s2, double margin, double *out) {
     raw_contact_t c[8];
-    int n = box_box_keep(c, 4, p1, m1, s1, p2, m2, s2, margin);
+    int n = box_box_keep(c, 4, p1, m1, s1, p2, m2, s2, margin, NULL);
     for (int k = 0; k < n; ++k) { out[7 * k] = c[k].dist; for (int i = 0; i < 3; ++i) { out[7 * k + 1 + i] = c[k].pos[i]; out[7 * k + 4 + i] = c[k].normal[i]; } }
     return n;
 }
@@ -973,9 +976,13 @@ int co_test_hfield_capsule(const cm_model_t *m, const double *pc, const double *
 }
 
 /* completes a contact frame from its normal and an optional tangent hint */
+/* a hint (nearly) parallel to the normal -- its remainder after the projection, of squared length |hint|^2 - (n . hint)^2,
+ * shorter than FRAME_MIN_HINT: rounding noise, or zero -- counts as no hint (the kernel's rule and expression, pk_collision.h) */
+#define FRAME_MIN_HINT 1e-6
 static void make_frame(double *frame) {
     normalize3(frame);
-    if (norm3(frame + 3) < 0.5) {
+    const double hh = dot3(frame + 3, frame + 3), th = dot3(frame, frame + 3);
+    if (hh < 0.25 || hh - th * th < FRAME_MIN_HINT * FRAME_MIN_HINT) {
         frame[3] = frame[4] = frame[5] = 0;
         if (frame[1] < 0.5 && frame[1] > -0.5) frame[4] = 1; else frame[5] = 1;
     }
@@ -1036,7 +1043,7 @@ void co_collision(const cm_model_t *m, co_data_t *d) {
         else if (t1 == CM_GEOM_SPHERE && t2 == CM_GEOM_BOX) n = sphere_box(rc, p1, m->geom_size[g1][0], p2, m2, m->geom_size[g2], margin);
         else if (t1 == CM_GEOM_CAPSULE && t2 == CM_GEOM_BOX) n = capsule_box(rc, p1, m1, m->geom_size[g1], p2, m2, m->geom_size[g2], margin);
         else if (t1 == CM_GEOM_PLANE && t2 == CM_GEOM_BOX) n = plane_box(rc, p1, m1, p2, m2, m->geom_size[g2], margin);
-        else if (t1 == CM_GEOM_BOX && t2 == CM_GEOM_BOX) n = box_box_keep(rc, (m->flags & CM_FLAG_BOX8) ? 8 : 4, p1, m1, m->geom_size[g1], p2, m2, m->geom_size[g2], margin);
+        else if (t1 == CM_GEOM_BOX && t2 == CM_GEOM_BOX) n = box_box_keep(rc, (m->flags & CM_FLAG_BOX8) ? 8 : 4, p1, m1, m->geom_size[g1], p2, m2, m->geom_size[g2], margin, NULL);
         else { d->warn_unsupported_pair = 1; continue; }
         for (int k = 0; k < n; ++k) {
             if (d->ncon >= maxcon) { d->warn_contact_full = 1; break; }
@@ -1554,4 +1561,87 @@ void co_step_batch(const cm_model_t *m, co_data_t *d, int n, int nsteps, const d
             if (ptarget) co_pd_ctrl(m, &d[e], ptarget + (size_t)e * m->nu, kp + (size_t)e * m->nu, kd + (size_t)e * m->nu);
             co_step(m, &d[e]);
         }
+}
+
+/* ---- test hooks: the narrow-phase routines one at a time, n trials to a call.  A trial's inputs are the routine's arguments in their
+ * order, vectors and matrices element by element (in[n][nin]); its outputs (out[n][nout]) are laid out as the probe bodies of
+ * tests/device/wave_bodies.h lay theirs out: a contact is dist, pos, normal, tangent, and what the routine does not write is left as
+ * the caller filled it. ---- */
+static void put_contact(double *o, const raw_contact_t *c) {
+    o[0] = c->dist;
+    for (int i = 0; i < 3; ++i) { o[1 + i] = c->pos[i]; o[4 + i] = c->normal[i]; o[7 + i] = c->tangent[i]; }
+}
+void co_test_plane_sphere(int n, const double *in, double *out) {       /* in[17]: ppos, pmat, spos, r, margin; out[11]: count, contact */
+    for (int t = 0; t < n; ++t, in += 17, out += 11) {
+        raw_contact_t c;
+        out[0] = plane_sphere(&c, in, in + 3, in + 12, in[15], in[16]);
+        if (out[0] > 0) put_contact(out + 1, &c);
+    }
+}
+void co_test_sphere_sphere(int n, const double *in, double *out) {      /* in[9]: p1, r1, p2, r2, margin; out[11] */
+    for (int t = 0; t < n; ++t, in += 9, out += 11) {
+        raw_contact_t c;
+        out[0] = sphere_sphere(&c, in, in[3], in + 4, in[7], in[8]);
+        if (out[0] > 0) put_contact(out + 1, &c);
+    }
+}
+void co_test_segment_closest(int n, const double *in, double *out) {    /* in[14]: p1, a1, l1, p2, a2, l2; out[2]: x1, x2 */
+    for (int t = 0; t < n; ++t, in += 14, out += 2) segment_closest(in, in + 3, in[6], in + 7, in + 10, in[13], out, out + 1);
+}
+void co_test_point_box(int n, const double *in, double *out) {          /* in[18]: q, pb, mb, sb; out[4]: dist, nworld */
+    for (int t = 0; t < n; ++t, in += 18, out += 4) out[0] = point_box(in, in + 3, in + 6, in + 15, out + 1);
+}
+void co_test_sphere_box(int n, const double *in, double *out) {         /* in[20]: ps, r, pb, mb, sb, margin; out[11] */
+    for (int t = 0; t < n; ++t, in += 20, out += 11) {
+        raw_contact_t c;
+        out[0] = sphere_box(&c, in, in[3], in + 4, in + 7, in + 16, in[19]);
+        if (out[0] > 0) put_contact(out + 1, &c);
+    }
+}
+void co_test_capsule_box(int n, const double *in, double *out) {        /* in[30]: pc, mc, rad, h, pb, mb, sb, margin; out[21]: count, 2 contacts */
+    for (int t = 0; t < n; ++t, in += 30, out += 21) {
+        raw_contact_t c[2];
+        const double sc[3] = {in[12], in[13], 0};
+        const int k = capsule_box(c, in, in + 3, sc, in + 14, in + 17, in + 26, in[29]);
+        out[0] = k;
+        for (int i = 0; i < k; ++i) put_contact(out + 1 + 10 * i, c + i);
+    }
+}
+void co_test_closest_on_triangle(int n, const double *in, double *out) { /* in[12]: p, a, b, c; out[3] */
+    for (int t = 0; t < n; ++t, in += 12, out += 3) closest_on_triangle(in, in + 3, in + 6, in + 9, out);
+}
+/* in[15]: p, v00, v10, v01, v11 -- the two triangles of a grid cell in hfield_sphere's order and from its start values;
+ * out[4]: best, the normal */
+void co_test_hfield_triangle(int n, const double *in, double *out) {
+    for (int t = 0; t < n; ++t, in += 15, out += 4) {
+        double best = 1e300, bn[3] = {0, 0, 1};
+        hfield_triangle(in, in + 3, in + 6, in + 9, &best, bn);
+        hfield_triangle(in, in + 12, in + 9, in + 6, &best, bn);
+        out[0] = best; out[1] = bn[0]; out[2] = bn[1]; out[3] = bn[2];
+    }
+}
+void co_test_make_frame(int n, const double *in, double *out) {          /* in[6]: normal, tangent hint; out[9] */
+    for (int t = 0; t < n; ++t, in += 6, out += 9) {
+        for (int i = 0; i < 9; ++i) out[i] = i < 6 ? in[i] : 0.0;
+        make_frame(out);
+    }
+}
+void co_test_impedance(int n, const double *in, double *out) {           /* in[7]: solimp, pos, margin; out[1] */
+    for (int t = 0; t < n; ++t, in += 7, out += 1) impedance(in, in[5], in[6], out);
+}
+/* in[31]: p1, m1, s1, p2, m2, s2, margin; out[11][64]: per CANDIDATE (the kernel's lane) whether it is kept, then its contact */
+void co_test_box_box_lanes(int n, int keep, const double *in, double *out) {
+    for (int t = 0; t < n; ++t, in += 31, out += 11 * 64) {
+        raw_contact_t c[8];
+        int which[8];
+        const int k = box_box_keep(c, keep < 1 ? 1 : (keep > 8 ? 8 : keep), in, in + 3, in + 12, in + 15, in + 18, in + 27, in[30], which);
+        for (int l = 0; l < 64; ++l) out[l] = 0;
+        for (int i = 0; i < k; ++i) {
+            const int l = which[i];
+            double o[10];
+            put_contact(o, c + i);
+            out[l] = 1;
+            for (int f = 0; f < 10; ++f) out[(1 + f) * 64 + l] = o[f];
+        }
+    }
 }

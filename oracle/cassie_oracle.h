@@ -96,6 +96,18 @@ int co_test_box_box(const double *p1, const double *m1, const double *s1, const 
 int co_test_hfield_capsule(const cm_model_t *m, const double *pc, const double *mc, double radius, double halflen, double margin, double *out);
 int co_test_hfield_sphere(const cm_model_t *m, const double *ps, double r, double margin, double *out);
 int co_test_hfield_prism(const cm_model_t *m, const double *pc, const double *mc, double radius, double halflen, double margin, int max, double *out);
+/* the narrow-phase routines one at a time, n trials to a call: in[n][nin], out[n][nout] (cassie_oracle.c, at its end) */
+void co_test_plane_sphere(int n, const double *in, double *out);
+void co_test_sphere_sphere(int n, const double *in, double *out);
+void co_test_segment_closest(int n, const double *in, double *out);
+void co_test_point_box(int n, const double *in, double *out);
+void co_test_sphere_box(int n, const double *in, double *out);
+void co_test_capsule_box(int n, const double *in, double *out);
+void co_test_closest_on_triangle(int n, const double *in, double *out);
+void co_test_hfield_triangle(int n, const double *in, double *out);
+void co_test_make_frame(int n, const double *in, double *out);
+void co_test_impedance(int n, const double *in, double *out);
+void co_test_box_box_lanes(int n, int keep, const double *in, double *out);
 /* joint PD -> motor-side ctrl (pd_input motor law + reference motor() speed-torque limit, no delay line) */
 void co_pd_ctrl(const cm_model_t *m, co_data_t *d, const double *ptarget, const double *kp, const double *kd);
 /* OpenMP over independent envs: nsteps of co_step (optionally with the PD law) for each of n envs */

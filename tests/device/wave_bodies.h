@@ -8,7 +8,14 @@
  *     run-time topology, factor_pair_by_height for Cassie-32 and the packed tray model, interleaved and split), the packed rows
  *     read back as the kernel stages them (stage_factor_row / stage_factor_h of pk_stages.h) into solve_forward /
  *     solve_backward, and one sweep of pgs_rows and of pgs_rows_fast at the three row counts the kernel instantiates.
- * Not covered here: wide_solve and the convergence logic around the sweeps (they need the step kernel's shared state).
+ *   - the narrow phase of pk_collision.h.  Lane = trial (64 different trials to a wave, so that the lanes diverge into different
+ *     branches): plane_sphere, sphere_sphere, segment_closest, point_box, sphere_box, capsule_box, closest_on_triangle,
+ *     hfield_triangle folded over the two triangles of a grid cell the way hfield_sphere does, make_frame, impedance.  Wave = trial:
+ *     box_box_lane at keepmax 4 and 8, called by all 64 lanes as in the kernel, every lane storing its keep flag and its contact.
+ * Not covered here: wide_solve and the convergence logic around the sweeps (they need the step kernel's shared state);
+ * hfield_sphere, hfield_spheres_wave, hfield_prism_wave and finish_contacts (they need the model and the shared state:
+ * tests/test_hfield.py holds them to a numpy brute force through the emulator); the pair types env_step_collision.inc assembles
+ * inline (plane-capsule, sphere-capsule, plane-box).
  *
  * The same source is compiled twice: for gfx950 with the product's flags (wave_check.hip: one workgroup of one wave per
  * trial) and into the CPU wave emulator (tests/emu/emu_runtime.cpp: the body runs through the emulator's rendezvous
@@ -49,7 +56,19 @@
     X(pgs_guarded64, 64 + 5, 3)    \
     X(pgs_fast32, 32 + 5, 2)       \
     X(pgs_fast48, 48 + 5, 2)       \
-    X(pgs_fast64, 64 + 5, 2)
+    X(pgs_fast64, 64 + 5, 2)       \
+    X(plane_sphere, 17, 11)        \
+    X(sphere_sphere, 9, 11)        \
+    X(segment_closest, 14, 2)      \
+    X(point_box, 18, 4)            \
+    X(sphere_box, 20, 11)          \
+    X(capsule_box, 30, 21)         \
+    X(closest_on_triangle, 12, 3)  \
+    X(hfield_triangle, 15, 8)      \
+    X(make_frame, 6, 9)            \
+    X(impedance, 7, 1)             \
+    X(box_box4, 31, 11)            \
+    X(box_box8, 31, 11)
 
 #define WAVE_CHECK_AUX_BODIES(X)                                                       \
     X(factor_rt, 2 * 40, (wc::factor_set_rows<40, ck::TopoRuntime>()))                \
@@ -191,6 +210,152 @@ WV_DEVICE void pgs_guarded64(const double *in, double *out) { pgs_guarded<64>(in
 WV_DEVICE void pgs_fast32(const double *in, double *out) { pgs_fast<32>(in, out); }
 WV_DEVICE void pgs_fast48(const double *in, double *out) { pgs_fast<48>(in, out); }
 WV_DEVICE void pgs_fast64(const double *in, double *out) { pgs_fast<64>(in, out); }
+
+/* ---- the narrow phase (pk_collision.h).  Inputs are the routine's arguments in their order, vectors and matrices element by
+ * element (matrices row-major, as the kernel holds them).  A contact is stored as dist, pos, normal, tangent (10 values); a
+ * contact the routine did not write stays NaN. ---- */
+template <int N> WV_DEVICE void take(const double *in, int &row, double (&v)[N]) {
+    const int l = wv::lane();
+#pragma unroll
+    for (int i = 0; i < N; ++i) v[i] = in[(row + i) * 64 + l];
+    row += N;
+}
+WV_DEVICE double take(const double *in, int &row) { return in[(row++) * 64 + wv::lane()]; }
+WV_DEVICE void blank(ck::RawContact &c) {
+    const double nan = __builtin_nan("");
+    c.dist = nan;
+    for (int i = 0; i < 3; ++i) c.pos[i] = c.normal[i] = c.tangent[i] = nan;
+}
+WV_DEVICE void put(double *out, int row, const ck::RawContact &c) {
+    const int l = wv::lane();
+    out[row * 64 + l] = c.dist;
+    for (int i = 0; i < 3; ++i) { out[(row + 1 + i) * 64 + l] = c.pos[i]; out[(row + 4 + i) * 64 + l] = c.normal[i]; out[(row + 7 + i) * 64 + l] = c.tangent[i]; }
+}
+/* lane = trial: the count, then the contact */
+WV_DEVICE void plane_sphere(const double *in, double *out) {
+    int row = 0;
+    double ppos[3], pmat[9], spos[3];
+    take(in, row, ppos); take(in, row, pmat); take(in, row, spos);
+    const double r = take(in, row), margin = take(in, row);
+    ck::RawContact c;
+    blank(c);
+    out[wv::lane()] = (double)ck::plane_sphere(c, ppos, pmat, spos, r, margin);
+    put(out, 1, c);
+}
+WV_DEVICE void sphere_sphere(const double *in, double *out) {
+    int row = 0;
+    double p1[3], p2[3];
+    take(in, row, p1);
+    const double r1 = take(in, row);
+    take(in, row, p2);
+    const double r2 = take(in, row), margin = take(in, row);
+    ck::RawContact c;
+    blank(c);
+    out[wv::lane()] = (double)ck::sphere_sphere(c, p1, r1, p2, r2, margin);
+    put(out, 1, c);
+}
+/* the two parameters */
+WV_DEVICE void segment_closest(const double *in, double *out) {
+    int row = 0;
+    double p1[3], a1[3], p2[3], a2[3];
+    take(in, row, p1); take(in, row, a1);
+    const double l1 = take(in, row);
+    take(in, row, p2); take(in, row, a2);
+    const double l2 = take(in, row);
+    double x1 = __builtin_nan(""), x2 = __builtin_nan("");
+    ck::segment_closest(p1, a1, l1, p2, a2, l2, x1, x2);
+    out[wv::lane()] = x1;
+    out[64 + wv::lane()] = x2;
+}
+/* the signed distance, then the outward normal in world axes */
+WV_DEVICE void point_box(const double *in, double *out) {
+    int row = 0;
+    double q[3], pb[3], mb[9], sb[3], nw[3];
+    take(in, row, q); take(in, row, pb); take(in, row, mb); take(in, row, sb);
+    const int l = wv::lane();
+    out[l] = ck::point_box(q, pb, mb, sb, nw);
+    for (int i = 0; i < 3; ++i) out[(1 + i) * 64 + l] = nw[i];
+}
+WV_DEVICE void sphere_box(const double *in, double *out) {
+    int row = 0;
+    double ps[3], pb[3], mb[9], sb[3];
+    take(in, row, ps);
+    const double r = take(in, row);
+    take(in, row, pb); take(in, row, mb); take(in, row, sb);
+    const double margin = take(in, row);
+    ck::RawContact c;
+    blank(c);
+    out[wv::lane()] = (double)ck::sphere_box(c, ps, r, pb, mb, sb, margin);
+    put(out, 1, c);
+}
+/* the count, then both contacts */
+WV_DEVICE void capsule_box(const double *in, double *out) {
+    int row = 0;
+    double pc[3], mc[9], pb[3], mb[9], sb[3];
+    take(in, row, pc); take(in, row, mc);
+    const double rad = take(in, row), h = take(in, row);
+    take(in, row, pb); take(in, row, mb); take(in, row, sb);
+    const double margin = take(in, row);
+    ck::RawContact c0, c1;
+    blank(c0); blank(c1);
+    out[wv::lane()] = (double)ck::capsule_box(c0, c1, pc, mc, rad, h, pb, mb, sb, margin);
+    put(out, 1, c0);
+    put(out, 11, c1);
+}
+WV_DEVICE void closest_on_triangle(const double *in, double *out) {
+    int row = 0;
+    double p[3], a[3], b[3], c[3], q[3];
+    take(in, row, p); take(in, row, a); take(in, row, b); take(in, row, c);
+    ck::closest_on_triangle(p, a, b, c, q);
+    for (int i = 0; i < 3; ++i) out[i * 64 + wv::lane()] = q[i];
+}
+/* the centre p against the two triangles of the cell with corners v00, v10, v01, v11, from the start values and in the order of
+ * hfield_sphere: best, bv, bdiv, then the normal the caller forms (bdiv ? bv / best : bv) */
+WV_DEVICE void hfield_triangle(const double *in, double *out) {
+    int row = 0;
+    double p[3], v00[3], v10[3], v01[3], v11[3];
+    take(in, row, p); take(in, row, v00); take(in, row, v10); take(in, row, v01); take(in, row, v11);
+    double best = 1e300, bv[3] = {0, 0, 1};
+    bool bdiv = false;
+    ck::hfield_triangle(p, v00, v10, v01, best, bv, bdiv);
+    ck::hfield_triangle(p, v11, v01, v10, best, bv, bdiv);
+    const int l = wv::lane();
+    out[l] = best;
+    for (int i = 0; i < 3; ++i) { out[(1 + i) * 64 + l] = bv[i]; out[(5 + i) * 64 + l] = bdiv ? bv[i] / best : bv[i]; }
+    out[4 * 64 + l] = bdiv ? 1.0 : 0.0;
+}
+/* the normal and the tangent hint in, the three rows of the frame out */
+WV_DEVICE void make_frame(const double *in, double *out) {
+    int row = 0;
+    double six[6], fr[9];
+    take(in, row, six);
+    for (int i = 0; i < 6; ++i) fr[i] = six[i];
+    fr[6] = fr[7] = fr[8] = 0;
+    ck::make_frame(fr);
+    for (int i = 0; i < 9; ++i) out[i * 64 + wv::lane()] = fr[i];
+}
+WV_DEVICE void impedance(const double *in, double *out) {
+    int row = 0;
+    double solimp[5];
+    take(in, row, solimp);
+    const double pos = take(in, row), margin = take(in, row);
+    out[wv::lane()] = ck::impedance(solimp, pos, margin);
+}
+/* wave = trial: every lane holds the same two boxes and the margin, all 64 lanes call (lane = candidate, as in the kernel); each
+ * lane stores whether it keeps a contact, then its contact */
+template <int KEEPMAX> WV_DEVICE void box_box(const double *in, double *out) {
+    int row = 0;
+    double p1[3], m1[9], s1[3], p2[3], m2[9], s2[3];
+    take(in, row, p1); take(in, row, m1); take(in, row, s1); take(in, row, p2); take(in, row, m2); take(in, row, s2);
+    const double margin = take(in, row);
+    ck::RawContact c;
+    blank(c);
+    const bool keep = ck::box_box_lane(c, wv::lane(), p1, m1, s1, p2, m2, s2, margin, KEEPMAX);
+    out[wv::lane()] = keep ? 1.0 : 0.0;
+    put(out, 1, c);
+}
+WV_DEVICE void box_box4(const double *in, double *out) { box_box<4>(in, out); }
+WV_DEVICE void box_box8(const double *in, double *out) { box_box<8>(in, out); }
 
 /* the wave-uniform sum, stored by every lane */
 WV_DEVICE void wave_sum(const double *in, double *out) {
