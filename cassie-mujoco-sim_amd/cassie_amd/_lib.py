@@ -171,6 +171,8 @@ def _declare(L):
         L.phys_batch_rays_bind_normals.argtypes = [vp, vp]
         L.phys_batch_rays_cast.argtypes = [vp, c.c_int, c.c_int, vp]
         L.phys_batch_debug_ray_launches.argtypes = [vp, c.POINTER(c.c_longlong)]
+    if hasattr(L, "phys_batch_step_sums_enable"):   # (likewise)
+        L.phys_batch_step_sums_enable.argtypes = [vp, c.c_int]
     if hasattr(L, "phys_batch_download_progress"):   # (absent from older variant builds selected with CASSIE_LIB)
         L.phys_batch_download_progress.argtypes = [vp, vp]
     L.phys_batch_set_all_outputs_every_substep.argtypes = [vp, c.c_int]

@@ -15,7 +15,19 @@ from ._lib import CmDriveState, CmEnvParams, CmEpisodeRules, CmModel, MODEL_DIR,
 # field ids (enum in cassie_phys.h)
 (F_QPOS, F_QVEL, F_QACC_WARMSTART, F_TIME, F_CTRL, F_QFRC_APPLIED, F_XFRC_APPLIED, F_QACC, F_SENSORDATA,
  F_ACTUATOR_VELOCITY, F_XPOS, F_XQUAT, F_PD_PTARGET, F_PD_KP, F_PD_KD, F_BODY_CFRC, F_DRIVE_CMD, F_MEAS, F_PD_DTARGET,
- F_PD_TORQUE, F_DERIVED, F_QM, F_HEIGHT_SCAN, F_DEPTH, F_RAYS) = range(25)
+ F_PD_TORQUE, F_DERIVED, F_QM, F_HEIGHT_SCAN, F_DEPTH, F_RAYS, F_STEP_SUMS) = range(26)
+
+# layout of the step-sums block F_STEP_SUMS (CM_SUM_* in cm_model.h): what a stepping launch added up over its substeps
+# (Batch.enable_step_sums); MAXBODY = CM_MAXBODY, MAXU = CM_MAXU
+MAXBODY, MAXU = 32, 12
+SUM_COUNT, SUM_BODY_CFRC = 0, 1
+SUM_BODY_TOUCH = SUM_BODY_CFRC + 3 * MAXBODY
+SUM_BODY_CFRC_MAX2 = SUM_BODY_TOUCH + MAXBODY
+SUM_ACT_FORCE = SUM_BODY_CFRC_MAX2 + MAXBODY
+SUM_ACT_FORCE2 = SUM_ACT_FORCE + MAXU
+SUM_ACT_POWER = SUM_ACT_FORCE2 + MAXU
+SUM_ACT_POSPOWER = SUM_ACT_POWER + MAXU
+SUM_DIM = SUM_ACT_POSPOWER + MAXU
 
 # layout of the derived block F_DERIVED (CM_DRV_* in cm_model.h); MAXV = CM_MAXV
 MAXV = 40
@@ -685,6 +697,33 @@ class Batch:
         """Stepping launches of the fast kernels as `chunks` workgroups per env (1 = off); results are bit for bit the same."""
         if lib().phys_batch_set_chunks(self._h, int(chunks)) != 0:
             raise ValueError("chunks per env-launch: 1 .. 7")
+
+    def enable_step_sums(self, on=True):
+        """The step sums: while on, every stepping launch (step, step_range) zeroes the rows of its env range of F_STEP_SUMS on its
+        stream and then adds up, over the substeps it integrates, each body's net contact force (what F_BODY_CFRC holds for the last
+        substep alone), the substeps in which the body touched anything, the largest squared force, and per actuator the applied
+        torque, its square, the mechanical power and its positive part -- sequential sums in substep order, whatever tier or chunk of
+        the launch finished a substep (layout: SUM_*; exact definitions: CM_SUM_* in csrc/cm_model.h).  Forward passes, derive(),
+        end_episodes() and restarts leave the block alone.  Off by default, and off again restores the launches as they were.
+        The block is allocated on first use unless a tensor is bound to the field (bind(F_STEP_SUMS, ptr): [nenv][SUM_DIM] float64)."""
+        if not hasattr(lib(), "phys_batch_step_sums_enable"):
+            raise RuntimeError("this build of the library has no step sums")
+        if lib().phys_batch_step_sums_enable(self._h, 1 if on else 0) != 0:
+            raise RuntimeError("enable_step_sums failed: " + (lib().phys_last_error() or b"").decode())
+
+    def step_sums(self, env0=0, n=None):
+        """The rows [env0, env0 + n) of F_STEP_SUMS as named views of one download: count [n], body_cfrc [n][nbody][3], body_touch
+        [n][nbody], body_cfrc_max2 [n][nbody], act_force / act_force2 / act_power / act_pospower [n][nu], and the rows themselves
+        under "raw".  Means are the caller's: divide by count.  An env whose launch diverged (WARN_DIVERGED): count is the number of
+        substeps it finished, the rest is unspecified."""
+        raw = self.get(F_STEP_SUMS, env0, n)
+        nb, nu = self.pod.nbody, self.pod.nu
+        per_body = lambda at, w=1: raw[:, at:at + w * MAXBODY].reshape(raw.shape[0], MAXBODY, w)[:, :nb]
+        out = dict(raw=raw, count=raw[:, SUM_COUNT], body_cfrc=per_body(SUM_BODY_CFRC, 3), body_touch=per_body(SUM_BODY_TOUCH)[:, :, 0],
+                   body_cfrc_max2=per_body(SUM_BODY_CFRC_MAX2)[:, :, 0])
+        for name, at in (("act_force", SUM_ACT_FORCE), ("act_force2", SUM_ACT_FORCE2), ("act_power", SUM_ACT_POWER), ("act_pospower", SUM_ACT_POSPOWER)):
+            out[name] = raw[:, at:at + nu]
+        return out
 
     def launch_cost(self):
         """Shader clocks every env's last stepping launch took, first to last instruction (diagnostics; batches >= 2048 envs)."""

@@ -368,6 +368,21 @@ enum { CM_DRV_COM_POS = 0, CM_DRV_COM_VEL = 3, CM_DRV_ANGMOM = 6,
        CM_DRV_FOOT_JACP = 52,   /* [2][3][CM_MAXV] translational Jacobians of the foot bodies' origins (cassie_sim_get_jacobian) */
        CM_DRV_FOOT_JACR = 52 + 6 * CM_MAXV, /* [2][3][CM_MAXV] rotational */
        CM_DRV_DIM = 52 + 12 * CM_MAXV };
+/* The step-sums block of an env (phys_batch_step_sums_enable, PHYS_F_STEP_SUMS): what a stepping launch adds up over the substeps it
+ * integrates -- the reference's users average cassie_sim_foot_forces and integrate torque / mechanical power over the 50 - 60
+ * cassie_sim_step_pd calls of a policy step -- as one row of doubles per env.  Every sum is a sequential sum in substep order from
+ * +0.0, every product rounded on its own before it is added; entries past the model's nbody / nu stay 0.  F_u = ctrl_u clamped to
+ * ctrlrange (the motor-side torque the substep applied, MuJoCo's actuator_force), V_u = gear_u * qvel[dof_u] at the start of the
+ * substep (actuator_velocity).  An env whose launch raised WARN_DIVERGED: CM_SUM_COUNT = the substeps it finished, the rest unspecified. */
+enum { CM_SUM_COUNT = 0,                                   /* substeps accumulated */
+       CM_SUM_BODY_CFRC = 1,                               /* [CM_MAXBODY][3] sum of the body's net contact force (PHYS_F_BODY_CFRC of every substep) */
+       CM_SUM_BODY_TOUCH = CM_SUM_BODY_CFRC + 3 * CM_MAXBODY,   /* [CM_MAXBODY] substeps in which the body took part in at least one contact */
+       CM_SUM_BODY_CFRC_MAX2 = CM_SUM_BODY_TOUCH + CM_MAXBODY,  /* [CM_MAXBODY] max over substeps of |net contact force|^2 */
+       CM_SUM_ACT_FORCE = CM_SUM_BODY_CFRC_MAX2 + CM_MAXBODY,   /* [CM_MAXU] sum F_u */
+       CM_SUM_ACT_FORCE2 = CM_SUM_ACT_FORCE + CM_MAXU,     /* [CM_MAXU] sum F_u^2 */
+       CM_SUM_ACT_POWER = CM_SUM_ACT_FORCE2 + CM_MAXU,     /* [CM_MAXU] sum F_u V_u */
+       CM_SUM_ACT_POSPOWER = CM_SUM_ACT_POWER + CM_MAXU,   /* [CM_MAXU] sum max(F_u V_u, 0) */
+       CM_SUM_DIM = CM_SUM_ACT_POSPOWER + CM_MAXU };
 
 /* drive modes of the step kernel */
 enum { CM_DRIVE_OFF = 0,     /* ctrl (or the exact-state PD of phys_batch_set_pd_mode) goes straight to the actuators */

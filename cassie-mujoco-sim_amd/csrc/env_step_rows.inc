@@ -268,7 +268,7 @@
         /* first constraint row of every contact (lane = contact), for the contact-force read-out */
         int caddr = -1;
         const bool want_cfrc = io.body_cfrc && (sub == nsub - 1 || !integrates<FEAT>(io)); /* read out by the last substep only */
-        if (readout_ext<FEAT>(io) || want_cfrc) {
+        if (readout_ext<FEAT>(io) || want_cfrc || sums) { /* (the step sums take every substep's contact forces) */
             int acc = nefc_before_contacts;
             for (int c = 0; c < ncon; ++c) {
                 const int dim = S.c_dim[c];

@@ -8,6 +8,8 @@
             const double f = wide_solve<NVP, TOPO>(S, m, P, 0, nefc, sub, iters, nguarded);
             CK_STAMP(11);
 
+            /* (the step sums' actuator terms: ahead of the barrier P, behind which wave 1's Euler step changes qvel) */
+            if constexpr (feat_sums(FEAT)) { if (sums && lane < nu) step_sums_add_actuator(sums, S, m, lane); }
             static_assert(sizeof(S.c_solimp) >= (2 * NROW + 4) * sizeof(double), "the row forces are handed over through the contacts' solimp slots");
             double *const fbuf = &S.c_solimp[0][0];
             fbuf[lane] = f;
@@ -16,7 +18,7 @@
 #ifdef CK_WIDE_PROFILE
             if constexpr (feat_prof(FEAT)) if (io.prof && lane < 12) io.prof[(size_t)env * NSTAMP + (lane < 6 ? 16 + lane : 22 + lane)] = (long long)S.x.stepv[lane / 6][lane % 6];   /* slots 16..21: wave 0, 28..33: wave 1 */
 #endif
-            if (readout_ext<FEAT>(io) || want_cfrc) {
+            if (readout_ext<FEAT>(io) || want_cfrc || sums) {
                 /* decode the pyramid: normal = sum of the edge forces, tangents = mu (f+ - f-); the rows' forces from LDS */
                 const int a0 = caddr >= 0 ? caddr : 0;
                 double fn = 0, ft1 = 0, ft2 = 0;
@@ -30,7 +32,7 @@
                     if (lane < ncon) { ex->con_force[lane][0] = fn; ex->con_force[lane][1] = ft1; ex->con_force[lane][2] = ft2; }
                     if (lane == 0) { ex->ncon = ncon; ex->nefc = nefc; ex->solver_iter = iters; }
                 }
-                if (want_cfrc) {
+                if (want_cfrc || sums) {
                     if (lane < ncon) {
                         const double *fr = S.c_frame[lane];
                         double fw[3];
@@ -40,12 +42,15 @@
                     wv::sync();
                     if (isbody) {
                         double acc[3] = {0, 0, 0};
+                        bool touched = false;
                         for (int c = 0; c < ncon; ++c) {
                             const int b1 = m->geom_bodyid[S.c_g1[c]], b2 = m->geom_bodyid[S.c_g2[c]];
                             const double sg = (b2 == b ? 1.0 : 0.0) - (b1 == b ? 1.0 : 0.0);
+                            if constexpr (feat_sums(FEAT)) touched |= b1 == b || b2 == b;
                             for (int j = 0; j < 3; ++j) acc[j] += sg * S.c_pos[c][j];
                         }
-                        for (int j = 0; j < 3; ++j) io.body_cfrc[((size_t)env * io.sb + b) * 3 + j] = acc[j];
+                        if (want_cfrc) for (int j = 0; j < 3; ++j) io.body_cfrc[((size_t)env * io.sb + b) * 3 + j] = acc[j];
+                        if constexpr (feat_sums(FEAT)) { if (sums) step_sums_add_body(sums, b, acc, touched); }
                     }
                     wv::sync();
                 }
@@ -411,7 +416,7 @@
         }
         if constexpr (NW == 2 && CK_PRIO_W0_PGS != CK_PRIO_W0) wv::set_priority<CK_PRIO_W0>();
         CK_STAMP(11);
-        if (readout_ext<FEAT>(io) || want_cfrc) {
+        if (readout_ext<FEAT>(io) || want_cfrc || sums) {
             /* decode the pyramid: normal = sum of the edge forces, tangents = mu (f+ - f-) */
             const int a0 = caddr >= 0 ? caddr : 0;
             const double f0 = wv::shfl(f, a0), f1 = wv::shfl(f, (a0 + 1) & 63), f2 = wv::shfl(f, (a0 + 2) & 63), f3 = wv::shfl(f, (a0 + 3) & 63);
@@ -425,7 +430,7 @@
                 if (lane < ncon) { ex->con_force[lane][0] = fn; ex->con_force[lane][1] = ft1; ex->con_force[lane][2] = ft2; }
                 if (lane == 0) { ex->ncon = ncon; ex->nefc = nefc; ex->solver_iter = iters; }
             }
-            if (want_cfrc) {
+            if (want_cfrc || sums) {
                 /* world-frame force of every contact parked over its (no longer needed) position, then lane = body adds
                  * up the contacts it takes part in: + on geom2's body, - on geom1's */
                 if (lane < ncon) {
@@ -437,16 +442,21 @@
                 wv::sync();
                 if (isbody) {
                     double acc[3] = {0, 0, 0};
+                    bool touched = false;
                     for (int c = 0; c < ncon; ++c) {
                         const int b1 = m->geom_bodyid[S.c_g1[c]], b2 = m->geom_bodyid[S.c_g2[c]];
                         const double sg = (b2 == b ? 1.0 : 0.0) - (b1 == b ? 1.0 : 0.0);
+                        if constexpr (feat_sums(FEAT)) touched |= b1 == b || b2 == b;
                         for (int j = 0; j < 3; ++j) acc[j] += sg * S.c_pos[c][j];
                     }
-                    for (int j = 0; j < 3; ++j) io.body_cfrc[((size_t)env * io.sb + b) * 3 + j] = acc[j];
+                    if (want_cfrc) for (int j = 0; j < 3; ++j) io.body_cfrc[((size_t)env * io.sb + b) * 3 + j] = acc[j];
+                    if constexpr (feat_sums(FEAT)) { if (sums) step_sums_add_body(sums, b, acc, touched); }
                 }
                 wv::sync();
             }
         }
+        /* (the step sums' actuator terms: qvel is still the state the substep started from -- the Euler step is below, or wave 1's behind P) */
+        if constexpr (feat_sums(FEAT)) { if (sums && lane < nu) step_sums_add_actuator(sums, S, m, lane); }
 
         if constexpr (NW == 2) {
             /* Two-wave form: the stages behind the solve -- qacc, the accelerometers, the substep's outputs, the Euler step -- are

@@ -75,6 +75,7 @@ struct phys_batch {
     int waves_per_env_tray = DEFAULT_TRAY_WAVES; /* ... of the 40-dof instantiations (CASSIE_TRAY_TWO_WAVES=0/1 overrides the default: A/B aid) */
     int inplace_mode = 2;           /* form of the two-wave fast kernel (phys_batch_set_inplace; ck::next_inplace) */
     long long form_launches[2] = {0, 0};   /* stepping launches of the two-wave fast kernel in the plain / the in-place form (diagnostics) */
+    bool step_sums = false;         /* stepping launches zero and accumulate PHYS_F_STEP_SUMS (phys_batch_step_sums_enable) */
     /* launch-order balancing (see ck::cassie_order_kernel) */
     bool balance = true;
     DevBuf<unsigned> d_cost, d_cost_wall; /* per-env span of the last launch in 64 shader clocks / in 100 MHz ticks */
@@ -265,6 +266,30 @@ static const ck::StepLauncher GENERIC40_FORMS[ck::FORM_COUNT] = {launch_step<40,
 static const ck::StepLauncher *const FAMILY_FORMS[ck::FAMILY_COUNT] = {
     CASSIE_FORMS<0>, CASSIE_FORMS<ck::FEAT_HFIELD>, CASSIE_ALL_FORMS, TRAY_FORMS, TRAY_HFIELD_FORMS, GENERIC32_FORMS, GENERIC40_FORMS,
 };
+/* The second table: the same forms for a launch that accumulates the step-sums block (PhysIO::sums).  The lean fast forms map to their
+ * FEAT_SUMS siblings (kernels_*_sums.hip: the two-wave form alone -- ck::launch_forms answers no other fast form for such a launch; null
+ * otherwise, and for the profiled forms); every other form, FEAT_FULL, is its own entry of the first table (ck::feat_sums: a run-time test
+ * of the pointer).  By family; null: a family of full forms alone. */
+using ck::FEAT_SUMS;
+template <int FEAT>
+static const ck::StepLauncher CASSIE_SUMS_FAST[ck::FORM_COUNT] = {
+    nullptr, nullptr, nullptr, nullptr,
+    launch_step<32, TopoCassie32, FEAT, FAST_ROWS, 2, false, 2, 0, FEAT_SUMS>,        /* FORM_FAST_2W */
+};
+static const ck::StepLauncher TRAY_SUMS_FAST[ck::FORM_COUNT] = {
+    nullptr, nullptr, nullptr, nullptr,
+    launch_step<40, TopoCassieTray38, ck::FEAT_WAVEPAIRS, FAST_ROWS_TRAY, 2, false, 2, 0, FEAT_READOUT | FEAT_SUMS>, /* FORM_FAST_2W */
+};
+static const ck::StepLauncher *const FAMILY_SUMS_FAST[ck::FAMILY_COUNT] = {
+    CASSIE_SUMS_FAST<0>, CASSIE_SUMS_FAST<ck::FEAT_HFIELD>, nullptr, TRAY_SUMS_FAST, nullptr, nullptr, nullptr,
+};
+/* the kernel of a pass: from the second table for an accumulating launch (*sums_inst: it is a FEAT_SUMS instantiation), null where there is none */
+static ck::StepLauncher pass_kernel(ck::StepFamily fam, int form, bool sums, bool *sums_inst) {
+    *sums_inst = false;
+    if (!sums || !ck::is_fast_form(form)) return FAMILY_FORMS[fam][form];
+    *sums_inst = FAMILY_SUMS_FAST[fam] && FAMILY_SUMS_FAST[fam][form];
+    return *sums_inst ? FAMILY_SUMS_FAST[fam][form] : nullptr;
+}
 
 /* A launch in chunks hands an env's state from one workgroup to another through the L2 both share (wave.h: publish_global): the
  * chunks of an env are workgroups a multiple of 8 apart, and workgroup w runs on XCD w % 8.  That assignment is checked here, once
@@ -378,8 +403,15 @@ static int launch(phys_batch *b, int nsub, int integrate, hipStream_t s, bool sc
     const ck::StepLauncher *family = FAMILY_FORMS[fam];
     const bool has_inplace = family[ck::FORM_FAST_INPLACE] != nullptr;
     const bool prof = io.prof != nullptr;
+    /* the step sums (phys_batch_step_sums_enable): a stepping launch zeroes the rows of its range on its stream, ahead of its first
+     * substep, and its passes add to them; forward / read-out passes are not handed the block */
+    const bool sums = integrate && b->step_sums && b->d_field[PHYS_F_STEP_SUMS];
+    if (sums) {
+        io.sums = b->d_field[PHYS_F_STEP_SUMS]; io.sums_stride = b->stride[PHYS_F_STEP_SUMS];
+        if (!hip_ok(hipMemsetAsync(io.sums + (size_t)env0 * CM_SUM_DIM, 0, sizeof(double) * CM_SUM_DIM * (size_t)n, s), "hipMemset(step sums)")) return -1;
+    }
     auto forms_if = [&](bool inplace) {
-        return ck::launch_forms(fam, has_inplace, hm.maxefc, integrate, io.ext != nullptr, n, nsub, b->fast_rows, b->waves_per_env, b->waves_per_env_tray, inplace, prof);
+        return ck::launch_forms(fam, has_inplace, hm.maxefc, integrate, io.ext != nullptr, n, nsub, b->fast_rows, b->waves_per_env, b->waves_per_env_tray, inplace, prof, sums);
     };
     ck::StepForms forms = forms_if(false);
     const bool fast = ck::is_fast_form(forms.first);
@@ -400,22 +432,25 @@ static int launch(phys_batch *b, int nsub, int integrate, hipStream_t s, bool sc
         if ((forms.first == ck::FORM_FAST_2W || forms.first == ck::FORM_FAST_2W_PROF) && has_inplace) {
             const bool was = range->inplace;
             /* (a profiled launch takes the plain form -- the stamps are in FORM_FAST_2W_PROF alone -- and the range goes with it) */
-            range->inplace = !prof && ck::next_inplace(was, seen, b->inplace_mode, io.order != nullptr);
+            /* (... and so does an accumulating launch: its kernel is the plain form's FEAT_SUMS sibling, which the count of the lean forms' launches leaves out) */
+            range->inplace = !prof && !sums && ck::next_inplace(was, seen, b->inplace_mode, io.order != nullptr);
             if (was != range->inplace) reset_range_words(b, env0, s);
-            ++b->form_launches[range->inplace ? 1 : 0];
+            if (!sums) ++b->form_launches[range->inplace ? 1 : 0];
             forms = forms_if(range->inplace);
         }
     }
     const ck::StepPlan plan = ck::plan_step(io, forms, hl, grids);
     for (int i = 0; i < plan.n; ++i) {
         const ck::StepPass &p = plan.pass[i];
-        if (!family[p.form]) { (void)hip_ok(hipErrorInvalidDeviceFunction, "cassie_step_kernel launch (no instantiation of this form)"); return -1; }
+        bool sums_inst = false;
+        const ck::StepLauncher kernel = pass_kernel(fam, p.form, p.io.sums != nullptr, &sums_inst);
+        if (!kernel) { (void)hip_ok(hipErrorInvalidDeviceFunction, "cassie_step_kernel launch (no instantiation of this form)"); return -1; }
         /* (the policy never pairs them; a plan that does is not launched: the code for it is not in the kernel) */
-        if (ck::lean_form_refuses(p.form, p.io.ext != nullptr, p.io.integrate, p.io.prof != nullptr)) {
-            (void)hip_ok(hipErrorInvalidValue, "cassie_step_kernel launch (a lean fast form with the read-out block, a forward pass or the stage stamps)");
+        if (ck::step_sums_refuses(p.form, p.io.ext != nullptr, p.io.integrate, p.io.prof != nullptr, p.io.sums != nullptr, sums_inst)) {
+            (void)hip_ok(hipErrorInvalidValue, "cassie_step_kernel launch (a lean fast form with the read-out block, a forward pass, the stage stamps or the step sums)");
             return -1;
         }
-        family[p.form](p.grid, s, p.io);
+        kernel(p.grid, s, p.io);
         if (!hip_ok(hipGetLastError(), "cassie_step_kernel launch")) return -1;
         if (i == 0 && ev_after) (void)hipEventRecord(ev_after, s);   /* (the first kernel of the launch does the work: per-kernel timing) */
     }
@@ -475,7 +510,7 @@ phys_batch_t *phys_batch_create(const cm_model_t *model, int nenv, int device) {
     const int d[PHYS_F_COUNT] = {model->nq, model->nv, model->nv, 1, model->nu, model->nv, model->nbody * 6,
                                  model->nv, model->nsensordata, model->nu, model->nbody * 3, model->nbody * 4,
                                  model->nu, model->nu, model->nu, model->nbody * 3,
-                                 model->nu + 1, CM_MEAS_DIM, model->nu, model->nu, CM_DRV_DIM, model->nv * model->nv, 0, 0, 0};
+                                 model->nu + 1, CM_MEAS_DIM, model->nu, model->nu, CM_DRV_DIM, model->nv * model->nv, 0, 0, 0, CM_SUM_DIM};
     const size_t n = (size_t)nenv;
     bool ok = true;
     for (int f = 0; f < PHYS_F_COUNT; ++f) {
@@ -484,6 +519,7 @@ phys_batch_t *phys_batch_create(const cm_model_t *model, int nenv, int device) {
         if (f == PHYS_F_HEIGHT_SCAN) continue;              /* sized and allocated by phys_batch_scan_configure */
         if (f == PHYS_F_DEPTH) continue;                    /* ... by phys_batch_depth_configure */
         if (f == PHYS_F_RAYS) continue;                     /* ... by phys_batch_rays_configure */
+        if (f == PHYS_F_STEP_SUMS) continue;                /* allocated by phys_batch_step_sums_enable */
         ok = ok && b->d_field[f].alloc(n * (d[f] > 0 ? d[f] : 1), true, "field");
     }
     ok = ok && b->d_models.alloc(1, false, "model");
@@ -1378,6 +1414,15 @@ int phys_batch_debug_form_launches(const phys_batch_t *b, long long *plain, long
 int phys_batch_set_inplace(phys_batch_t *b, int mode) {
     if (!b || mode < 0 || mode > 2) return -1;
     b->inplace_mode = mode;
+    return 0;
+}
+
+int phys_batch_step_sums_enable(phys_batch_t *b, int on) {
+    if (!b) return -1;
+    (void)hipSetDevice(b->device);
+    /* (first use: the batch's own block, zeroed -- unless a caller's tensor is bound to the field) */
+    if (on && !b->d_field[PHYS_F_STEP_SUMS] && !b->d_field[PHYS_F_STEP_SUMS].alloc((size_t)b->nenv * CM_SUM_DIM, true, "step sums")) return -1;
+    b->step_sums = on != 0;
     return 0;
 }
 

@@ -56,6 +56,10 @@
  * for profiled launches; every other form carries both (FEAT_FULL).  The kernel takes the two bits as a trailing template parameter of
  * their own (cassie_step_kernel's SERVE, default FEAT_FULL) and hands env_step FEAT | SERVE.
  *
+ * Round 8: FEAT_SUMS, a third such bit: the step-sums block (PhysIO::sums, cm_model.h CM_SUM_*) -- contact forces, touches and
+ * actuator work added up over the substeps of a launch, each substep by the pass that finishes it, behind its solve.  The lean fast
+ * forms do not carry it; their siblings for accumulating launches name the bit (kernels_*_sums.hip), every FEAT_FULL form tests the pointer.
+ *
  * Numerically this follows the same algorithm as oracle/cassie_oracle.c but with
  * its own operation order (half solves, reciprocal multiplies, wave reductions,
  * chain sums), so parity is to a tolerance, not bitwise.
@@ -205,6 +209,9 @@ WV_DEVICE int env_step(const PhysIO &io, EnvShared<NVP, LPack<TOPO, NVP>::count,
         env_hfield = terrain_grid(io.hfield, io.hfield_stride, io.hfield_index, io.hfield_nterrain, env, &clamped);
         if (clamped && lane == 0 && wid == 0) wv::atomic_or(io.warn + env, WARN_TERRAIN_INDEX);
     }
+
+    /* the env's row of the step-sums block (PhysIO::sums; a constant null in an instantiation without feat_sums) */
+    double *const sums = sums_row<FEAT>(io, env);
 
     bool bailed = false, bailed_down = false;
     int sub = sub_start;
@@ -614,6 +621,8 @@ WV_DEVICE int env_step(const PhysIO &io, EnvShared<NVP, LPack<TOPO, NVP>::count,
 #include "env_step_solve.inc"
 
     /* ---------------- store state ---------------- */
+    /* (the substeps this call finished: those in front of the one it ended at -- handed over, diverged, or the end of the launch / chunk) */
+    if constexpr (feat_sums(FEAT)) { if (sums && lane == 0 && sub > sub_start) sums[CM_SUM_COUNT] = sums[CM_SUM_COUNT] + (double)(sub - sub_start); }
     if (io.progress && lane == 0 && (!io.resume || bailed)) {
         /* (a pass behind the fast kernel leaves the record of an env it completes; one that hands the env on -- the 63-row pass of a
          * model that may use 127 -- moves it to the substep the next pass starts from) */
@@ -673,7 +682,7 @@ WV_DEVICE int env_step(const PhysIO &io, EnvShared<NVP, LPack<TOPO, NVP>::count,
  * name it is what it always was; the lean fast forms name FEAT_LEAN (their _PROF forms FEAT_PROF). */
 template <int NVP, class TOPO, int FEAT = FEAT_ALL, int MAXR = MID_ROWS, int NW = 1, bool WALK = false, int WPS = NW, int INROWS = 0, int SERVE = FEAT_FULL>
 WV_GLOBAL void __launch_bounds__(WV_WAVE * NW) WV_OCC WV_WAVES_PER_SIMD(WPS) cassie_step_kernel(PhysIO io) {
-    static_assert((FEAT & FEAT_FULL) == 0 && (SERVE & ~FEAT_FULL) == 0, "FEAT: the collision bits; SERVE: FEAT_READOUT / FEAT_PROF");
+    static_assert((FEAT & FEAT_SERVE) == 0 && (SERVE & ~FEAT_SERVE) == 0, "FEAT: the collision bits; SERVE: FEAT_READOUT / FEAT_PROF / FEAT_SUMS");
     WV_SHARED EnvShared<NVP, LPack<TOPO, NVP>::count, MAXR> S;
     const int slot = wv::env_id();
     if constexpr (WALK) {

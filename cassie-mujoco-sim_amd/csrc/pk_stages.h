@@ -192,11 +192,48 @@ WV_DRIVE_FN void drive_level_io(const PhysIO &io, SH &S, ModelPtr m, int env, in
  * FEAT_FULL = both: every instantiation but the lean fast forms (step_plan.h: is_lean_form; FEAT_LEAN = neither), which the launcher
  * never hands such a launch (step_policy.h: launch_forms, lean_form_refuses).  The kernel takes these two as its trailing SERVE
  * parameter (default FEAT_FULL) and env_step sees FEAT | SERVE; FEAT_ALL is every collision code */
-enum { FEAT_HFIELD = 1, FEAT_WAVEPAIRS = 2, FEAT_READOUT = 4, FEAT_PROF = 8, FEAT_LEAN = 0, FEAT_FULL = FEAT_READOUT | FEAT_PROF, FEAT_ALL = FEAT_HFIELD | FEAT_WAVEPAIRS };
+enum { FEAT_HFIELD = 1, FEAT_WAVEPAIRS = 2, FEAT_READOUT = 4, FEAT_PROF = 8, FEAT_LEAN = 0, FEAT_FULL = FEAT_READOUT | FEAT_PROF, FEAT_ALL = FEAT_HFIELD | FEAT_WAVEPAIRS,
+       /*   FEAT_SUMS     the step-sums block (PhysIO::sums): the fast forms' siblings for accumulating launches name it (kernels_*_sums.hip);
+        * every instantiation with FEAT_FULL serves such launches too, by a run-time test of the pointer, as it serves the read-out block */
+       FEAT_SUMS = 16, FEAT_SERVE = FEAT_FULL | FEAT_SUMS };
 
 /* The one place each of the two bits is tested: an instantiation without the bit sees a constant, so nothing behind it is compiled. */
 constexpr bool feat_readout(int feat) { return (feat & FEAT_READOUT) != 0; }
 constexpr bool feat_prof(int feat) { return (feat & FEAT_PROF) != 0; }   /* (CK_STAMP, pk_types.h, and the other profiling aids test this one) */
+/* ... and the step-sums block: the bit itself, or both of the others (the non-lean forms) */
+constexpr bool feat_sums(int feat) { return (feat & FEAT_SUMS) != 0 || (feat & FEAT_FULL) == FEAT_FULL; }
+template <int FEAT> WV_DEVICE double *sums_row(const PhysIO &io, int env) {
+    if constexpr (feat_sums(FEAT)) return io.sums ? io.sums + (size_t)env * io.sums_stride : nullptr; else return nullptr;
+}
+/* One finished substep into the env's row (wave 0, behind the solve).  Plain load-add-store by the lane that owns the entry: the same
+ * lane of the env's wave 0 in every substep, chunk and pass, one after the other, so each sum is the sequential sum in substep order.
+ * Every product is a statement of its own: the device build contracts within a statement (-ffp-contract=on), never across. */
+/* lane = body: acc = the body's net contact force of the substep (the value PHYS_F_BODY_CFRC gets), touched = it took part in a contact */
+WV_DEVICE void step_sums_add_body(double *sums, int b, const double (&acc)[3], bool touched) {
+    for (int j = 0; j < 3; ++j) { double *p = sums + CM_SUM_BODY_CFRC + 3 * b + j; *p = *p + acc[j]; }
+    if (touched) { double *p = sums + CM_SUM_BODY_TOUCH + b; *p = *p + 1.0; }
+    const double m2 = acc[0] * acc[0] + acc[1] * acc[1] + acc[2] * acc[2];
+    double *pm = sums + CM_SUM_BODY_CFRC_MAX2 + b;
+    if (m2 > *pm) *pm = m2;
+}
+/* lane = actuator u: F = the clamped torque the substep applied (what the passive stage fed qfrc_smooth), V = gear * qvel of the state
+ * the substep started from (what actuator_velocity gets: the caller is ahead of the Euler step) */
+template <class SH>
+WV_DEVICE void step_sums_add_actuator(double *sums, const SH &S, ModelPtr m, int u) {
+    const double F = clampd(S.ctrl[u], m->act_ctrlrange[u][0], m->act_ctrlrange[u][1]);
+    const double V = m->act_gear[u] * S.qvel[m->act_dofid[u]];
+    const double F2 = F * F;
+    const double pw = F * V;
+    const double pp = pw > 0.0 ? pw : 0.0;
+    double *p = sums + CM_SUM_ACT_FORCE + u;
+    *p = *p + F;
+    p = sums + CM_SUM_ACT_FORCE2 + u;
+    *p = *p + F2;
+    p = sums + CM_SUM_ACT_POWER + u;
+    *p = *p + pw;
+    p = sums + CM_SUM_ACT_POSPOWER + u;
+    *p = *p + pp;
+}
 /* the read-out block of the launch, and whether it integrates: what an instantiation without FEAT_READOUT is never launched with */
 template <int FEAT> WV_DEVICE cm_ext_t *readout_ext(const PhysIO &io) { if constexpr (feat_readout(FEAT)) return io.ext; else return nullptr; }
 template <int FEAT> WV_DEVICE bool integrates(const PhysIO &io) { if constexpr (feat_readout(FEAT)) return io.integrate != 0; else return true; }

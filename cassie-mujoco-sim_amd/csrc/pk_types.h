@@ -139,6 +139,15 @@ struct PhysIO {
      * wave-uniform read per env and launch (chunk), ahead of the substep loop. */
     const int *hfield_index;
     int hfield_nterrain;
+    /* The step-sums block (cm_model.h: CM_SUM_*; appended: the offsets of everything above stay put).  Null, or [nenv] rows sums_stride
+     * doubles apart, indexed by the absolute env, that the launcher zeroed on this launch's stream: every substep this launch
+     * integrates is added to the env's row by the pass that FINISHES it, behind its solve (env_step_solve.inc: step_sums_add) -- a
+     * substep handed over, from its start, to the pass or the code behind has added nothing.  The row lives in HBM and is updated by
+     * a plain load-add-store of the owning lane of wave 0 (lane = body, lane = actuator), so an env's sums go through its chunks, the
+     * passes behind the fast kernel and the in-place code the way its state does, in substep order.  Only instantiations with
+     * feat_sums (pk_stages.h) hold the code; forward passes are handed null. */
+    double *sums;
+    int sums_stride;
 };
 
 /* The grid env `env` stands on (see PhysIO::hfield_index); *clamped: the env's index lay outside the bank */

@@ -29,10 +29,19 @@ constexpr int INPLACE_STAY_ROWS = FAST_ROWS - 4;
  * prof: the batch's profile buffer is on, PhysIO::prof).
  * The fast forms are LEAN (step_plan.h: is_lean_form): they are chosen only where integrate && !ext -- every branch below that
  * answers one says so -- and with prof their _PROF forms take their place: the plain form whatever `inplace` says, since the stamps
- * are in the plain fast kernel alone and a profile is of the code it names. */
+ * are in the plain fast kernel alone and a profile is of the code it names.
+ * sums: the launch accumulates the step-sums block (PhysIO::sums; stepping launches only).  The fast forms have a sibling with that
+ * code in the two-wave form alone (FEAT_SUMS: phys_batch.hip's second table), so such a launch takes the PLAIN two-wave fast form +
+ * the mid-walk pass whatever `inplace` says, as with prof -- a range whose envs keep leaving the fast tier (the stress workloads) then
+ * pays the list-walking pass again, the 8 - 24 % the in-place form had gained it (profiles/round6/inplace_ab.txt) -- and where the batch
+ * is set to one wave per env, or profiled at the same time, one full form alone, which holds every code. */
 inline StepForms launch_forms(int fam, bool has_inplace, int maxefc, int integrate, bool ext, int n, int nsub, bool fast_rows,
-                              int waves_per_env, int waves_per_env_tray, bool inplace, bool prof = false) {
+                              int waves_per_env, int waves_per_env_tray, bool inplace, bool prof = false, bool sums = false) {
     StepForms forms = {FORM_ALONE, FORM_ALONE, false, INPLACE_STAY_ROWS};
+    if (sums && integrate) {
+        inplace = false;
+        if (prof || (fam == TRAY ? waves_per_env_tray : waves_per_env) != 2) fast_rows = false;
+    }
     if (fam == CASSIE || fam == CASSIE_HFIELD) {
         /* stepping launches go through the row-capped fast instantiation first; the 63-row pass behind it finishes the envs that met
          * a substep with more rows, and -- for a model with the wide caps (CM_FLAG_HFPRISM) -- the 127-row pass behind that one what
@@ -67,6 +76,16 @@ inline bool lean_form_refuses(int form, bool ext, int integrate, bool prof) {
     if (is_lean_form(form)) return ext || !integrate || prof;
     if (is_prof_form(form)) return ext || !integrate;
     return false;
+}
+
+/* ... and the same check of a pass with the step-sums block in view (sums: PhysIO::sums is set; sums_inst: the pass's kernel comes from
+ * the family's FEAT_SUMS table, phys_batch.hip).  A lean or profiled fast instantiation does not hold the accumulation code -- launched
+ * with the block it would leave the zeroed rows as they are -- and a forward pass must neither zero nor add. */
+inline bool step_sums_refuses(int form, bool ext, int integrate, bool prof, bool sums, bool sums_inst) {
+    if (sums_inst ? (!is_lean_form(form) || ext || !integrate || prof) : lean_form_refuses(form, ext, integrate, prof)) return true;
+    if (!sums) return sums_inst;        /* (a FEAT_SUMS instantiation is for accumulating launches alone) */
+    if (!integrate) return true;
+    return is_fast_form(form) && !sums_inst;
 }
 
 /* ---- the chunks of a launch ---- */

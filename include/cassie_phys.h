@@ -90,6 +90,8 @@ enum { PHYS_F_QPOS, PHYS_F_QVEL, PHYS_F_QACC_WARMSTART, PHYS_F_TIME, PHYS_F_CTRL
        PHYS_F_DEPTH,      /* [height * width], row-major, row 0 at the top: the depth image of phys_batch_depth_image (sized by
                              phys_batch_depth_configure) */
        PHYS_F_RAYS,       /* [nrays]: the ranges of phys_batch_rays_cast (sized by phys_batch_rays_configure) */
+       PHYS_F_STEP_SUMS,  /* [CM_SUM_DIM]: what a stepping launch added up over its substeps (layout: CM_SUM_* in cm_model.h; allocated by
+                             phys_batch_step_sums_enable, or a caller's: phys_batch_bind) */
        PHYS_F_COUNT };
 
 /* mj_makeData (reference :441-447) for nenv environments on HIP device `device`;
@@ -591,6 +593,29 @@ int phys_batch_set_waves_per_env(phys_batch_t *b, int waves);
  * end of a launch while the last-started jobs finish.  Same results, bit for bit (a chunk ends and the next begins exactly
  * like two launches). */
 int phys_batch_set_chunks(phys_batch_t *b, int chunks);
+/* THE STEP SUMS: contact forces, touches and actuator work added up over the substeps of a fused launch.
+ * A stepping launch keeps a policy step's 50 substeps on the device, and everything readable afterwards (PHYS_F_BODY_CFRC, ctrl,
+ * actuator_velocity, sensordata) is the LAST substep's.  The reference's users step cassie_sim_step_pd 50 - 60 times per policy step
+ * and, over those calls, average cassie_sim_foot_forces, ask whether a body touched the ground at any time and integrate torque and
+ * mechanical power.  With the step sums on, a launch does that itself, into one row of CM_SUM_DIM doubles per env (PHYS_F_STEP_SUMS;
+ * layout and exact definitions: CM_SUM_* in cm_model.h):
+ *   phys_batch_step_sums_enable(b, on)   on != 0: allocates the block on first use (unless a caller's tensor is bound to the field) and
+ *                                        switches accumulation on; 0: off again -- nothing below happens and every launch is what it
+ *                                        was without this call (the block keeps its last contents).  Off by default.
+ *     ZEROING        every stepping launch (phys_batch_step, phys_batch_step_range) first zeroes the rows of ITS env range, on its own
+ *                    stream, ahead of its first substep; rows outside the range are left alone, so ranges on several streams each
+ *                    own their rows.
+ *     ACCUMULATION   ... then adds every substep it integrates, in substep order (each sum is the sequential sum from +0.0, every
+ *                    product rounded on its own), whatever tier, pass or chunk of the launch finished the substep: a substep the fast
+ *                    kernel hands to the 63-row or 127-row code is counted once, by the code that finishes it.  Means are the
+ *                    caller's: divide by CM_SUM_COUNT.
+ *     LEFT ALONE     forward passes, phys_batch_derive, phys_batch_forward_kinematics, phys_batch_end_episodes and restarts neither
+ *                    zero nor add: the rows read what the last stepping launch over them left.
+ *     DIVERGED ENVS  an env whose launch raised warning bit 8: CM_SUM_COUNT = the substeps it finished, every other entry unspecified.
+ *     FORMS          accumulating launches take the two-wave fast kernel's sibling with the accumulation code (the lean fast kernels
+ *                    hold none) + the list-walking passes, never the in-place form; a batch set to one wave per env, or profiled, the
+ *                    full 63-row / 127-row form alone.  Cost: README, "step sums" (tools/step_sums_rate.py). */
+int phys_batch_step_sums_enable(phys_batch_t *b, int on);
 /* diagnostics: how many substeps of the last stepping launch the fast kernel completed for every env ([nenv] ints; less than
  * the launch's substep count = the env was handed over to the full kernel there).  Meaningful after a launch that ran the fast
  * kernel: not with the read-out enabled, fast rows off, or a batch of at most 512 envs stepping at most 4 substeps per launch

@@ -5,7 +5,7 @@
 # kernel; KEEP=file keeps the ISA of the last one (tools/asm_segments.py, tools/asm_liveness.py read it).
 # FEAT holds the collision bits; the two other bits (pk_stages.h; the kernel's trailing SERVE parameter) are set as the product's tables have them: the row-capped fast
 # forms (MAXR 31 / 47, not a list-walking pass) are LEAN -- neither FEAT_READOUT (4) nor FEAT_PROF (8) -- and every other form carries
-# both -- except that the 40-dof model's two-wave fast form keeps FEAT_READOUT (kernels_tray_2w.hip says why).  PROF=1 compiles the fast form's profiled instantiation (+ FEAT_PROF: FORM_FAST_PROF / FORM_FAST_2W_PROF), FULL=1 / FULL=0
+# both -- except that the 40-dof model's two-wave fast form keeps FEAT_READOUT (kernels_tray_2w.hip says why).  PROF=1 compiles the fast form's profiled instantiation (+ FEAT_PROF: FORM_FAST_PROF / FORM_FAST_2W_PROF), SUMS=1 its sibling for launches that accumulate the step sums (+ FEAT_SUMS, 16: kernels_*_sums.hip), FULL=1 / FULL=0
 # force both bits on / off whatever the form.
 set -e
 cd "$(dirname "$0")/.."
@@ -14,7 +14,7 @@ T=$(mktemp -d)
 LEAN=0; { [ "$MAXR" = 31 ] || [ "$MAXR" = 47 ]; } && [ "${WALK:-false}" = false ] && LEAN=1
 [ -n "$FULL" ] && LEAN=$((1 - FULL))
 KEEP_READOUT=0; [ "${NVP:-32}" = 40 ] && [ "${NW:-1}" = 2 ] && [ -z "$FULL" ] && KEEP_READOUT=4
-SERVE=$(( LEAN ? (${PROF:-0} ? 8 : 0) | KEEP_READOUT : 12 ))
+SERVE=$(( LEAN ? (${PROF:-0} ? 8 : 0) | KEEP_READOUT | (${SUMS:-0} ? 16 : 0) : 12 ))
 cat > $T/one.hip <<EOS
 #include <hip/hip_runtime.h>
 #include "wave.h"
