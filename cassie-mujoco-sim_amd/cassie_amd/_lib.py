@@ -143,6 +143,22 @@ def _declare(L):
         L.phys_batch_place_bind.argtypes = [vp, c.c_int, vp]
         L.phys_batch_place_upload.argtypes = [vp, c.c_int, vp, c.c_int, c.c_int]
         L.phys_batch_place_download.argtypes = [vp, c.c_int, vp]
+    if hasattr(L, "phys_batch_state_save"):   # (absent from older variant builds selected with CASSIE_LIB)
+        L.phys_batch_state_configure.argtypes = [vp, c.c_int, c.c_int]
+        L.phys_batch_state_bind.argtypes = [vp, vp, c.c_int]
+        L.phys_batch_state_ptr.restype = vp
+        L.phys_batch_state_ptr.argtypes = [vp]
+        for f in ("nslots", "groups", "row_dim"):
+            getattr(L, "phys_batch_state_" + f).argtypes = [vp]
+        L.phys_batch_state_layout.argtypes = [vp, ip]
+        L.phys_batch_state_signature.restype = c.c_ulonglong
+        L.phys_batch_state_signature.argtypes = [vp]
+        L.phys_batch_state_save.argtypes = [vp, c.c_int, c.c_int, vp, vp]
+        L.phys_batch_state_restore.argtypes = [vp, c.c_int, c.c_int, vp, vp]
+        L.phys_batch_state_stage_slots.restype = vp
+        L.phys_batch_state_stage_slots.argtypes = [vp, vp, c.c_int]
+        L.phys_batch_state_download.argtypes = [vp, c.c_int, c.c_int, vp]
+        L.phys_batch_state_upload.argtypes = [vp, c.c_int, c.c_int, vp, c.c_ulonglong]
     if hasattr(L, "phys_batch_set_hfield_bank"):   # (absent from older variant builds selected with CASSIE_LIB)
         L.phys_batch_set_hfield_bank.argtypes = [vp, vp, c.c_int, c.c_int, c.c_int]
         L.phys_batch_nterrain.argtypes = [vp]

@@ -67,6 +67,17 @@ EP_DONE, EP_REASON, EP_STEPS, EP_COUNT, EP_TERMINAL = range(5)
 # placed restarts: the per-env arrays (PHYS_PLACE_* in cassie_phys.h)
 PLACE_POSE, PLACE_NEXT_TERRAIN, PLACE_GROUND = range(3)
 PLACE_MAXPOINTS = 1024
+# the bank of full states: the groups of a row (PHYS_STATE_* in cassie_phys.h), the warning bit of a slot outside the bank, and the
+# sections of a row in the order of PHYS_SS_*, each with the dtype its words are read as (int32 sections hold one value, zero-extended
+# to a word; the drive-level state and the parameter block are the bytes of cm_drive_state_t / cm_envparams_t)
+STATE_CORE, STATE_COMMANDS, STATE_EPISODE, STATE_PARAMS = 1, 2, 4, 8
+WARN_STATE_SLOT = 256       # save_states / restore_states: the env's slot lay outside the bank, nothing was copied
+STATE_SECTIONS = (("time", np.float64), ("qpos", np.float64), ("qvel", np.float64), ("qacc_warmstart", np.float64), ("ctrl", np.float64),
+                  ("qacc", np.float64), ("sensordata", np.float64), ("actuator_velocity", np.float64), ("meas", np.float64),
+                  ("drive_state", np.uint8), ("xpos", np.float64), ("xquat", np.float64), ("warn", np.int32),
+                  ("pd_ptarget", np.float64), ("pd_kp", np.float64), ("pd_kd", np.float64), ("pd_dtarget", np.float64), ("pd_torque", np.float64),
+                  ("drive_cmd", np.float64), ("qfrc_applied", np.float64), ("xfrc_applied", np.float64),
+                  ("ep_steps", np.int32), ("ep_count", np.int32), ("terrain", np.int32), ("params", np.uint8))
 
 # joint configuration the reference writes at init (reference src/cassiemujoco.c:1023-1028)
 QPOS_INIT_JOINTS = np.array(
@@ -630,6 +641,95 @@ class Batch:
                 raise RuntimeError("episode download failed: " + (lib().phys_last_error() or b"").decode())
             out.append(a)
         return tuple(out)
+
+    # ---- a bank of full states: save, rewind and fork envs on the device (phys_batch_state_*) ----
+    def _err(self, what):
+        return RuntimeError(what + " failed: " + (lib().phys_last_error() or b"").decode())
+
+    def configure_states(self, nslots, groups=STATE_CORE):
+        """Allocates a bank of `nslots` rows of full env states in HBM (include/cassie_phys.h: "a bank of full states").  STATE_CORE is
+        always in a row: everything a stepping launch leaves for the next one or for a reader -- time, qpos, qvel, warm start, ctrl, qacc,
+        sensordata, actuator_velocity, F_MEAS, the drive-level state, F_XPOS / F_XQUAT and the warning word -- so that a restored env
+        continues byte for byte as the saved one did.  Optional: STATE_COMMANDS (the PD fields, F_DRIVE_CMD, the applied forces: upload or
+        bind those first), STATE_EPISODE (EP_STEPS, EP_COUNT, the terrain index: enable_episodes first), STATE_PARAMS (the env's parameter
+        block: randomize first; without it a restored env keeps its own masses, friction, ...).  Not in a row: per-env terrains and models,
+        outputs (F_BODY_CFRC, info, ext, derived, the step sums).  Waits for the batch's streams; calling it again replaces the bank."""
+        if lib().phys_batch_state_configure(self._h, int(nslots), int(groups)) != 0:
+            raise ValueError("configure_states failed: " + (lib().phys_last_error() or b"").decode())
+
+    def state_row_dim(self):
+        """8-byte words per row of the bank (0 before configure_states)."""
+        return lib().phys_batch_state_row_dim(self._h)
+
+    def state_layout(self):
+        """name -> (offset, count, dtype) of the sections in this bank's rows, offset and count in 8-byte words (STATE_SECTIONS: float64
+        sections hold count values; int32 sections one value in the low half of their word; 'drive_state' and 'params' the bytes of
+        cm_drive_state_t / cm_envparams_t).  Every offset is even: rows and sections start on 16-byte boundaries."""
+        oc = (ctypes.c_int * (2 * len(STATE_SECTIONS)))()
+        if lib().phys_batch_state_layout(self._h, oc) != len(STATE_SECTIONS):
+            raise self._err("state_layout")
+        return {name: (oc[2 * s], oc[2 * s + 1], dt) for s, (name, dt) in enumerate(STATE_SECTIONS) if oc[2 * s] >= 0}
+
+    def state_signature(self):
+        """Hash of the layout version, the groups, the row dim and the batch's compiled model: what rows saved elsewhere must come with."""
+        return int(lib().phys_batch_state_signature(self._h))
+
+    def _state_call(self, fn, what, slots, env0, n, slots_ptr, stream):
+        n = self.nenv - env0 if n is None else int(n)
+        if slots is not None:
+            if slots_ptr is not None:
+                raise ValueError(what + ": give slots (a host array) or slots_ptr (device int32), not both")
+            a = np.ascontiguousarray(slots, dtype=np.int32).reshape(-1)
+            if a.shape[0] != n:
+                raise ValueError("%s: %d slots for %d envs" % (what, a.shape[0], n))
+            if n > 0:
+                slots_ptr = lib().phys_batch_state_stage_slots(self._h, a.ctypes.data, n)   # (waits for the batch's streams)
+                if not slots_ptr:
+                    raise self._err(what)
+        if fn(self._h, int(env0), n, slots_ptr, stream) != 0:
+            raise self._err(what)
+
+    def save_states(self, slots=None, env0=0, n=None, slots_ptr=None, stream=None):
+        """One small launch on `stream` (default: the batch's own), in order with the step launches there, no host read: env env0 + i goes
+        to bank slot slots_ptr[i] (a DEVICE int32 [n], e.g. a torch tensor's data_ptr(); default: slot env0 + i).  A negative slot skips
+        the env, a slot >= nslots skips it and raises WARN_STATE_SLOT.  A host array `slots` is uploaded first, which waits for the
+        batch's streams: a convenience outside the hot loop."""
+        self._state_call(lib().phys_batch_state_save, "save_states", slots, env0, n, slots_ptr, stream)
+
+    def restore_states(self, slots=None, env0=0, n=None, slots_ptr=None, stream=None):
+        """The reverse, same arguments: env env0 + i takes slot slots_ptr[i] and then continues byte for byte as the env saved there did
+        (negative: left alone; out of range: left alone, WARN_STATE_SLOT).  Any number of envs may take one slot: a fork is save_states
+        followed by restore_states on the same stream."""
+        self._state_call(lib().phys_batch_state_restore, "restore_states", slots, env0, n, slots_ptr, stream)
+
+    def states(self, slot0=0, n=None):
+        """(rows, signature): bank rows [slot0, slot0 + n) as an int64 array [n][state_row_dim()] and the signature set_states asks for
+        (numpy.save the pair to keep states across processes); waits for the batch's streams."""
+        nslots = lib().phys_batch_state_nslots(self._h)
+        n = nslots - slot0 if n is None else int(n)
+        out = np.empty((max(n, 0), self.state_row_dim()), dtype=np.int64)
+        if lib().phys_batch_state_download(self._h, int(slot0), n, out.ctypes.data) != 0:
+            raise self._err("states")
+        return out, self.state_signature()
+
+    def set_states(self, rows, slot0=0, signature=None):
+        """Host rows [n][state_row_dim()] (int64, as states() returns them) into bank slots slot0 ...; `signature` is the one the rows
+        came with (default: this batch's own -- rows it saved itself) and must equal state_signature(), else the rows belong to another
+        model, other groups or another layout version and are refused.  Waits for the batch's streams."""
+        a = np.ascontiguousarray(rows, dtype=np.int64).reshape(-1, self.state_row_dim())
+        sig = self.state_signature() if signature is None else int(signature)
+        if lib().phys_batch_state_upload(self._h, int(slot0), a.shape[0], a.ctypes.data, sig) != 0:
+            raise ValueError("set_states failed: " + (lib().phys_last_error() or b"").decode())
+
+    def bind_states(self, ptr, nslots):
+        """Caller-owned HBM [nslots][state_row_dim()] of 8-byte words (a torch int64 tensor's data_ptr(), 16-byte aligned) in the bank's
+        place; configure_states first (it fixes the groups); None un-binds: the batch's own bank again."""
+        if lib().phys_batch_state_bind(self._h, ptr, int(nslots)) != 0:
+            raise ValueError("bind_states failed: " + (lib().phys_last_error() or b"").decode())
+
+    def state_ptr(self):
+        """Device pointer of the bank in use (None before configure_states)."""
+        return lib().phys_batch_state_ptr(self._h)
 
     def get_drive_state(self, env0=0, n=None):
         n = self.nenv - env0 if n is None else n

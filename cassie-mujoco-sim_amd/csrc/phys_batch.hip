@@ -118,6 +118,14 @@ struct phys_batch {
     ck::PlaceCfg place = {};
     DevBuf<ck::PlaceTable> d_place_table;
     DevBuf<double> d_place_offsets, d_place_pose, d_place_ground;
+    /* the bank of full states (phys_batch_state_configure): its groups and the slots of the bank in use (state.nslots 0: not configured;
+     * state.bank is filled in at the launch), the batch's own rows and -- while bound -- a caller's in their place */
+    ck::StateCfg state = {};
+    DevBuf<unsigned long long> d_state;
+    int state_own_slots = 0;
+    unsigned long long *state_bound = nullptr;
+    DevBuf<int> d_state_staged;     /* a host array of slots on its way to a launch (phys_batch_state_stage_slots) */
+    int state_staged_cap = 0;
 };
 
 static bool hip_ok(hipError_t e, const char *what) {
@@ -212,6 +220,13 @@ static ck::BatchView view_of(const phys_batch *b) {
     v.meas = b->d_drive ? b->d_field[PHYS_F_MEAS].get() : nullptr;
     v.drive = b->d_drive; v.warn = b->d_warn;
     v.xpos = b->d_field[PHYS_F_XPOS]; v.xquat = b->d_field[PHYS_F_XQUAT];
+    v.xpos_w = b->d_field[PHYS_F_XPOS]; v.xquat_w = b->d_field[PHYS_F_XQUAT];
+    v.pd_ptarget = b->d_field[PHYS_F_PD_PTARGET]; v.pd_kp = b->d_field[PHYS_F_PD_KP]; v.pd_kd = b->d_field[PHYS_F_PD_KD];
+    v.pd_dtarget = b->d_field[PHYS_F_PD_DTARGET]; v.pd_torque = b->d_field[PHYS_F_PD_TORQUE]; v.drive_cmd = b->d_field[PHYS_F_DRIVE_CMD];
+    v.qfrc_applied = b->use_applied ? b->d_field[PHYS_F_QFRC_APPLIED].get() : nullptr;
+    v.xfrc_applied = b->use_applied ? b->d_field[PHYS_F_XFRC_APPLIED].get() : nullptr;
+    v.ep_steps = b->episodes ? (int *)b->d_ep[PHYS_EP_STEPS].get() : nullptr; v.ep_count = b->episodes ? (int *)b->d_ep[PHYS_EP_COUNT].get() : nullptr;
+    v.params_w = b->d_envparams;
     return v;
 }
 /* the refusal of an entry point: its name in front of a check's message (small_launch.h) */
@@ -928,6 +943,96 @@ int phys_batch_download_episodes(phys_batch_t *b, int which, void *host) {
     return quiesce(b) && hip_ok(hipMemcpy(host, b->d_ep[which], episode_array_bytes(b, which), hipMemcpyDeviceToHost), "episode array download") ? 0 : -1;
 }
 size_t phys_sizeof_episode_rules(void) { return sizeof(cm_episode_rules_t); }
+
+/* ------------------------------------------------ a bank of full states: save, rewind and fork envs on the device ---- */
+static_assert((int)PHYS_SS_COUNT == (int)ck::SS_COUNT && (int)PHYS_SS_PARAMS == (int)ck::SS_PARAMS && (int)PHYS_STATE_PARAMS == (int)ck::STATE_PARAMS, "the header's sections and groups are small_launch.h's");
+static ck::StateLayout state_layout_of(const phys_batch *b) { return ck::state_layout(view_of(b), b->state.groups); }
+int phys_batch_state_configure(phys_batch_t *b, int nslots, int groups) {
+    if (!b) { phys_set_last_error("phys_batch_state_configure: no batch"); return -1; }
+    if (const char *why = ck::state_configure(view_of(b), nslots, groups)) return refuse("phys_batch_state_configure", why);
+    (void)hipSetDevice(b->device);
+    if (!quiesce(b)) return -1; /* (launches in flight may be using the bank that goes away) */
+    const ck::StateLayout L = ck::state_layout(view_of(b), groups);
+    b->state = {}; b->state_bound = nullptr; b->state_own_slots = 0;
+    if (!b->d_state.alloc((size_t)nslots * (size_t)L.row_dim, true, "state bank")) return -1;
+    b->state.nslots = b->state_own_slots = nslots; b->state.groups = L.groups;
+    return 0;
+}
+int phys_batch_state_bind(phys_batch_t *b, void *device_ptr, int nslots) {
+    if (!b) { phys_set_last_error("phys_batch_state_bind: no batch"); return -1; }
+    if (b->state_own_slots < 1) return refuse("phys_batch_state_bind", "configure first (phys_batch_state_configure fixes the groups, and with them the row)");
+    if (device_ptr && nslots < 1) return refuse("phys_batch_state_bind", "a bank of at least one slot");
+    if (((size_t)device_ptr & 15u) != 0) return refuse("phys_batch_state_bind", "the rows must start on a 16-byte boundary");
+    /* (as phys_batch_bind: launches already queued keep the pointer they were given) */
+    b->state_bound = (unsigned long long *)device_ptr;
+    b->state.nslots = device_ptr ? nslots : b->state_own_slots;
+    return 0;
+}
+void *phys_batch_state_ptr(phys_batch_t *b) { return !b || b->state.nslots < 1 ? nullptr : b->state_bound ? (void *)b->state_bound : (void *)b->d_state.get(); }
+int phys_batch_state_nslots(const phys_batch_t *b) { return b ? b->state.nslots : 0; }
+int phys_batch_state_groups(const phys_batch_t *b) { return b ? b->state.groups : 0; }
+int phys_batch_state_row_dim(const phys_batch_t *b) { return b && b->state.nslots > 0 ? state_layout_of(b).row_dim : 0; }
+int phys_batch_state_layout_version(void) { return ck::STATE_LAYOUT_VERSION; }
+int phys_batch_state_layout(const phys_batch_t *b, int *offsets_counts) {
+    if (!b || b->state.nslots < 1) { phys_set_last_error("phys_batch_state_layout: not configured (phys_batch_state_configure first)"); return -1; }
+    const ck::StateLayout L = state_layout_of(b);
+    for (int s = 0; offsets_counts && s < ck::SS_COUNT; ++s) { offsets_counts[2 * s] = L.off[s]; offsets_counts[2 * s + 1] = L.count[s]; }
+    return ck::SS_COUNT;
+}
+unsigned long long phys_batch_state_signature(const phys_batch_t *b) {
+    return b && b->state.nslots > 0 ? ck::state_signature(b->host_model, state_layout_of(b)) : 0ull;
+}
+static int state_launch(phys_batch *b, const char *entry, bool restore, int env0, int n, const int *slots, void *stream) {
+    if (!b) { phys_set_last_error((std::string(entry) + ": no batch").c_str()); return -1; }
+    ck::StateCfg c = b->state;
+    c.bank = (unsigned long long *)phys_batch_state_ptr(b);
+    if (const char *why = ck::check_state_call(c, b->nenv, env0, n)) return refuse(entry, why);
+    const ck::BatchView v = view_of(b);
+    /* (what the groups need may have gone since: a new shared model drops the parameter blocks) */
+    if (const char *why = ck::state_configure(v, c.nslots, c.groups)) return refuse(entry, why);
+    (void)hipSetDevice(b->device);
+    if (n == 0) return 0;
+    const ck::StateIO io = ck::make_state_io(v, c, env0, n, slots);
+    hipStream_t s = launch_stream(b, stream);
+    const dim3 grid((unsigned)ck::state_grid(n));
+    if (restore) hipLaunchKernelGGL(ck::cassie_state_restore_kernel, grid, dim3(WV_WAVE), 0, s, io);
+    else hipLaunchKernelGGL(ck::cassie_state_save_kernel, grid, dim3(WV_WAVE), 0, s, io);
+    return hip_ok(hipGetLastError(), restore ? "cassie_state_restore_kernel launch" : "cassie_state_save_kernel launch") ? 0 : -1;
+}
+int phys_batch_state_save(phys_batch_t *b, int env0, int n, const int *slots, void *stream) {
+    return state_launch(b, "phys_batch_state_save", false, env0, n, slots, stream);
+}
+int phys_batch_state_restore(phys_batch_t *b, int env0, int n, const int *slots, void *stream) {
+    return state_launch(b, "phys_batch_state_restore", true, env0, n, slots, stream);
+}
+void *phys_batch_state_stage_slots(phys_batch_t *b, const int *host_slots, int n) {
+    if (!b || !host_slots || n < 1) { phys_set_last_error("phys_batch_state_stage_slots: bad arguments"); return nullptr; }
+    (void)hipSetDevice(b->device);
+    if (!quiesce(b)) return nullptr; /* (a launch in flight may still be reading the slots staged before) */
+    if (b->state_staged_cap < n) {
+        b->state_staged_cap = 0;
+        if (!b->d_state_staged.alloc((size_t)n, false, "staged slots")) return nullptr;
+        b->state_staged_cap = n;
+    }
+    return hip_ok(hipMemcpy(b->d_state_staged, host_slots, sizeof(int) * (size_t)n, hipMemcpyHostToDevice), "hipMemcpy(staged slots)") ? (void *)b->d_state_staged.get() : nullptr;
+}
+static bool state_slots_ok(const phys_batch *b, int slot0, int n) {
+    return b && b->state.nslots > 0 && slot0 >= 0 && n >= 0 && (long long)slot0 + n <= b->state.nslots;
+}
+int phys_batch_state_download(phys_batch_t *b, int slot0, int n, void *host) {
+    if (!host || !state_slots_ok(b, slot0, n)) { phys_set_last_error("phys_batch_state_download: not configured, or slots outside the bank"); return -1; }
+    (void)hipSetDevice(b->device);
+    const size_t row = sizeof(unsigned long long) * (size_t)state_layout_of(b).row_dim;
+    return quiesce(b) && (n == 0 || hip_ok(hipMemcpy(host, (char *)phys_batch_state_ptr(b) + row * (size_t)slot0, row * (size_t)n, hipMemcpyDeviceToHost), "state download")) ? 0 : -1;
+}
+int phys_batch_state_upload(phys_batch_t *b, int slot0, int n, const void *host, unsigned long long signature) {
+    if (!host || !state_slots_ok(b, slot0, n)) { phys_set_last_error("phys_batch_state_upload: not configured, or slots outside the bank"); return -1; }
+    if (signature != phys_batch_state_signature(b))
+        return refuse("phys_batch_state_upload", "the rows' signature is not this batch's (phys_batch_state_signature): they were saved from another model, with other groups or by another layout version");
+    (void)hipSetDevice(b->device);
+    const size_t row = sizeof(unsigned long long) * (size_t)state_layout_of(b).row_dim;
+    return quiesce(b) && (n == 0 || hip_ok(hipMemcpy((char *)phys_batch_state_ptr(b) + row * (size_t)slot0, host, row * (size_t)n, hipMemcpyHostToDevice), "state upload")) ? 0 : -1;
+}
 
 /* ------------------------------------------------ terrains: a bank shared by the envs, a per-env index ---- */
 static bool ensure_terrain_index(phys_batch *b) {

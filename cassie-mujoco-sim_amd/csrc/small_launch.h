@@ -6,7 +6,7 @@
  * prefixes a message with its entry point's name and launches what a builder returns on the grid given here; the wave emulator's entry
  * points (tests/emu) fill the same records from their arguments and go through the same builders, grids and checks, so a CPU test of
  * one of these kernels also runs the launcher's refusals, grid and choice of kernel (tests/test_small_launch.py pins them one by one).
- * No field of ScanIO, DepthIO, RayIO, EpisodeIO, ResetIO, DeriveIO or SetConstIO is assigned anywhere else.
+ * No field of ScanIO, DepthIO, RayIO, EpisodeIO, ResetIO, DeriveIO, SetConstIO or StateIO is assigned anywhere else.
  */
 #ifndef CASSIE_SMALL_LAUNCH_H
 #define CASSIE_SMALL_LAUNCH_H
@@ -18,6 +18,7 @@
 #include "episode_kernels.h"
 #include "ray_kernel.h"
 #include "small_kernels.h"
+#include "state_kernels.h"
 
 namespace ck {
 
@@ -27,7 +28,10 @@ namespace ck {
  * model's own), the height field(s) and -- while a bank of terrains is set, hfield_nterrain > 0 -- the envs' index into it, which a
  * placed restart WRITES; all as the fields of PhysIO of the same names.  The state rows: the model's sizes, the doubles between the rows
  * of qpos / qvel / sensordata, the arrays a restart writes (meas, drive: null until a drive mode is in use), the sticky warning word, and
- * the body poses the last step launch or forward pass stored (rows of 3 nbody / 4 nbody doubles). */
+ * the body poses the last step launch or forward pass stored (rows of 3 nbody / 4 nbody doubles).  Appended for the bank of full states
+ * (state_layout below), which restores what every other kernel here only reads: the poses again, writable; the command fields (dense rows;
+ * the applied forces null until uploaded or bound, as the step kernel is handed them); the episode counters (null until episodes are
+ * enabled); the parameter blocks, writable. */
 struct BatchView {
     const cm_model_t *models; int model_stride;
     const cm_envparams_t *envparams;
@@ -37,6 +41,10 @@ struct BatchView {
     cm_drive_state_t *drive;
     int *warn;
     const double *xpos, *xquat;
+    double *xpos_w, *xquat_w;
+    double *pd_ptarget, *pd_kp, *pd_kd, *pd_dtarget, *pd_torque, *drive_cmd, *qfrc_applied, *xfrc_applied;
+    int *ep_steps, *ep_count;
+    cm_envparams_t *params_w;
 };
 /* the sizes of a view from the (host's copy of the) shared model, with dense rows */
 inline void view_sizes(BatchView &v, const cm_model_t &m) {
@@ -55,6 +63,58 @@ struct RayCfg { int nrays; double rmin, rmax; const RayDef *rays; unsigned geoms
 struct PlaceCfg { int anchor, npoints; double ground_ref; const PlaceTable *table; const double *offsets, *pose; const int *next; double *ground; };
 /* episodes (phys_batch_episodes_enable): the rules, the per-env arrays and the bank of start states [nrows][episode_row_dim] */
 struct EpisodeCfg { cm_episode_rules_t rules; int *done, *reason, *steps, *count; double *terminal; const double *bank; int nrows; };
+/* the bank of full states (phys_batch_state_configure, _bind; nslots 0: not configured): the groups of its rows (STATE_* below) and the
+ * rows [nslots][state_layout().row_dim] of 8-byte words */
+struct StateCfg { int nslots, groups; unsigned long long *bank; };
+
+/* ---- the row of a full state ---- */
+
+/* The groups of a row (PHYS_STATE_* of include/cassie_phys.h) and its sections, in the order they lie in a row.  CORE is every word one
+ * stepping launch writes and a later launch reads, or that a reader uses as stored: the state proper, what the drive-level pass of the next
+ * substep reads of the last one (sensordata, actuator_velocity, ctrl), qacc, the measurement block, the drive-level state with its message
+ * word, the stored body poses (the depth image, the range sensors and the derived read-out take them as stored) and the sticky warning word.
+ * Per launch only, or cost only, and therefore in no row: PhysIO::progress, the chunk words (tagged with the launch's own number), the
+ * hand-over lists and their counts (zero between launches), the launch order and the per-env cost (they move an env's wave in the grid,
+ * never its result), info, ext, derived, body_cfrc, the step sums (outputs).
+ * A change of the list or of the order of the sections is a new STATE_LAYOUT_VERSION: the signature of rows kept elsewhere then differs. */
+constexpr int STATE_LAYOUT_VERSION = 1;
+enum { STATE_CORE = 1, STATE_COMMANDS = 2, STATE_EPISODE = 4, STATE_PARAMS = 8, STATE_ALL_GROUPS = 15 };
+enum { SS_TIME, SS_QPOS, SS_QVEL, SS_WARM, SS_CTRL, SS_QACC, SS_SENS, SS_ACTVEL, SS_MEAS, SS_DRIVE, SS_XPOS, SS_XQUAT, SS_WARN,
+       SS_PD_PTARGET, SS_PD_KP, SS_PD_KD, SS_PD_DTARGET, SS_PD_TORQUE, SS_DRIVE_CMD, SS_QFRC_APPLIED, SS_XFRC_APPLIED,
+       SS_EP_STEPS, SS_EP_COUNT, SS_TERRAIN, SS_PARAMS, SS_COUNT };
+static_assert(SS_COUNT <= STATE_MAXSECT, "StateIO holds every section");
+static_assert(sizeof(cm_drive_state_t) % 8 == 0 && sizeof(cm_envparams_t) % 8 == 0, "sections are whole 8-byte words");
+/* offsets and counts in 8-byte words (off -1: the section's group is not in the row); every section starts on an even word, the row
+ * dim is the sum of the padded counts */
+struct StateLayout { int version, groups, row_dim, nsect; int off[SS_COUNT], count[SS_COUNT]; };
+inline int state_section_group(int s) { return s <= SS_WARN ? STATE_CORE : s <= SS_XFRC_APPLIED ? STATE_COMMANDS : s <= SS_TERRAIN ? STATE_EPISODE : STATE_PARAMS; }
+inline StateLayout state_layout(int nq, int nv, int nu, int nsd, int nbody, int groups) {
+    const int words[SS_COUNT] = {1, nq, nv, nv, nu, nv, nsd, nu, CM_MEAS_DIM, (int)(sizeof(cm_drive_state_t) / 8), 3 * nbody, 4 * nbody, 1,
+                                 nu, nu, nu, nu, nu, nu + 1, nv, 6 * nbody, 1, 1, 1, (int)(sizeof(cm_envparams_t) / 8)};
+    StateLayout L;
+    L.version = STATE_LAYOUT_VERSION; L.groups = (groups & STATE_ALL_GROUPS) | STATE_CORE; L.row_dim = 0; L.nsect = 0;
+    for (int s = 0; s < SS_COUNT; ++s) {
+        L.off[s] = -1; L.count[s] = 0;
+        if (!(L.groups & state_section_group(s))) continue;
+        L.off[s] = L.row_dim; L.count[s] = words[s]; L.row_dim += (words[s] + 1) & ~1; ++L.nsect;
+    }
+    return L;
+}
+inline StateLayout state_layout(const BatchView &v, int groups) { return state_layout(v.nq, v.nv, v.nu, v.nsd, v.nbody, groups); }
+/* what keeps rows saved from one model (or with other groups) out of another: the layout's version, groups and row dim and the compiled
+ * model's sizes, options, tree, reference pose, masses and geoms, hashed (FNV-1a over the words) */
+inline unsigned long long state_signature(const cm_model_t &m, const StateLayout &L) {
+    unsigned long long h = 1469598103934665603ull;
+    auto mix = [&h](const void *p, size_t bytes) { for (size_t i = 0; i < bytes; ++i) { h ^= ((const unsigned char *)p)[i]; h *= 1099511628211ull; } };
+    const int head[] = {L.version, L.groups, L.row_dim, m.nq, m.nv, m.nu, m.nbody, m.njnt, m.ngeom, m.npair, m.neq, m.nsensordata, (int)m.flags,
+                        m.hfield_geom, m.hfield_nrow, m.hfield_ncol, m.iterations};
+    mix(head, sizeof head);
+    mix(&m.timestep, sizeof m.timestep); mix(m.gravity, sizeof m.gravity); mix(m.hfield_size, sizeof m.hfield_size);
+    mix(m.body_parentid, sizeof(int) * (size_t)m.nbody); mix(m.body_pos, sizeof(double) * 3 * (size_t)m.nbody);
+    mix(m.body_mass, sizeof(double) * (size_t)m.nbody); mix(m.jnt_type, sizeof(int) * (size_t)m.njnt);
+    mix(m.qpos0, sizeof(double) * (size_t)m.nq); mix(m.geom_type, sizeof(int) * (size_t)m.ngeom);
+    return h;
+}
 
 /* ---- the checks ---- */
 
@@ -125,6 +185,22 @@ inline const char *place_configure(const cm_model_t &m, int model_stride, int an
     memset(&tab, 0, sizeof tab);
     return place_classify(m, anchor, tab);
 }
+/* the bank of full states: what phys_batch_state_configure / _bind refuse (the view tells what the batch has), and what a save or a
+ * restore refuses */
+inline const char *state_configure(const BatchView &v, int nslots, int groups) {
+    if (nslots < 1) return "a bank of at least one slot";
+    if (groups & ~STATE_ALL_GROUPS) return "groups is an OR of PHYS_STATE_CORE, PHYS_STATE_COMMANDS, PHYS_STATE_EPISODE and PHYS_STATE_PARAMS";
+    if ((groups & STATE_EPISODE) && !(v.ep_steps && v.ep_count)) return "PHYS_STATE_EPISODE needs the episode arrays (phys_batch_episodes_enable first)";
+    if ((groups & STATE_PARAMS) && !v.params_w) return "PHYS_STATE_PARAMS needs per-env parameter blocks (phys_batch_randomize first); without the group a restored env keeps its own";
+    if ((groups & STATE_COMMANDS) && !(v.qfrc_applied && v.xfrc_applied))
+        return "PHYS_STATE_COMMANDS holds qfrc_applied / xfrc_applied, which this batch has never uploaded or bound: they would be restored into nothing (upload or bind both first)";
+    return nullptr;
+}
+inline const char *check_state_call(const StateCfg &c, int nenv, int env0, int n) {
+    if (c.nslots < 1 || !c.bank) return "not configured (phys_batch_state_configure or phys_batch_state_bind first)";
+    if (env0 < 0 || n < 0 || (long long)env0 + n > nenv) return "env range out of bounds";
+    return nullptr;
+}
 
 /* ---- the grids ---- */
 
@@ -133,6 +209,8 @@ inline int scan_grid(int n) { return n < SCAN_GRID ? n : SCAN_GRID; }
 /* a few workgroups walk the range, with or without placement: the launch runs behind a range's step launch while the other range's step
  * kernel fills the chip, where every workgroup waits for a wave slot to free (cassie_reset_kernel) */
 inline int episode_grid(int n) { return n < EPISODE_GRID ? n : EPISODE_GRID; }
+/* one wave per env up to STATE_GRID workgroups, which then walk the range (state_kernels.h) */
+inline int state_grid(int n) { return n < STATE_GRID ? n : STATE_GRID; }
 /* a job is (env, tile of DEPTH_TILE x DEPTH_TILE pixels); a fixed grid walks the job list (a first choice: depth_kernel.h) */
 inline int depth_grid(int n, int width, int height) {
     const int T = DEPTH_TILE;
@@ -218,6 +296,27 @@ inline EpisodeIO make_episode_io(const BatchView &v, const EpisodeCfg &e, const 
         io.place_anchor = place->anchor; io.place_npoints = place->npoints; io.place_ground_ref = place->ground_ref; io.place_table = place->table;
         io.place_offsets = place->offsets; io.place_pose = place->pose; io.place_ground = place->ground;
         if (v.hfield_nterrain > 0) io.place_next = place->next;
+    }
+    return io;
+}
+/* cassie_state_save_kernel's and cassie_state_restore_kernel's: the sections of the configured groups, each with the view's array (null
+ * where the batch has none: the measurement block and the drive-level state until a drive mode is in use, the terrain index without a
+ * bank of terrains), its stride in bytes and its place in the row */
+inline StateIO make_state_io(const BatchView &v, const StateCfg &c, int env0, int n, const int *slots) {
+    StateIO io = zeroed<StateIO>();
+    const StateLayout L = state_layout(v, c.groups);
+    io.env0 = env0; io.n = n; io.nslots = c.nslots; io.row_dim = L.row_dim; io.bank = c.bank; io.slots = slots; io.warn = v.warn;
+    const size_t D = sizeof(double);
+    void *const env[SS_COUNT] = {v.time, v.qpos, v.qvel, v.warm, v.ctrl, v.qacc, v.sens, v.actvel, v.meas, v.drive, v.xpos_w, v.xquat_w, v.warn,
+                                 v.pd_ptarget, v.pd_kp, v.pd_kd, v.pd_dtarget, v.pd_torque, v.drive_cmd, v.qfrc_applied, v.xfrc_applied,
+                                 v.ep_steps, v.ep_count, v.hfield_nterrain > 0 ? v.hfield_index : nullptr, v.params_w};
+    const size_t stride[SS_COUNT] = {D, D * v.sq, D * v.sqv, D * v.nv, D * v.nu, D * v.nv, D * v.ssd, D * v.nu, D * CM_MEAS_DIM, sizeof(cm_drive_state_t),
+                                     D * 3 * v.nbody, D * 4 * v.nbody, sizeof(int), D * v.nu, D * v.nu, D * v.nu, D * v.nu, D * v.nu, D * (v.nu + 1), D * v.nv,
+                                     D * 6 * v.nbody, sizeof(int), sizeof(int), sizeof(int), sizeof(cm_envparams_t)};
+    for (int s = 0; s < SS_COUNT; ++s) {
+        if (L.off[s] < 0) continue;
+        const bool word32 = s == SS_WARN || s == SS_EP_STEPS || s == SS_EP_COUNT || s == SS_TERRAIN;
+        io.sect[io.nsect++] = {env[s], (unsigned long)stride[s], L.off[s], L.count[s], word32 ? STATE_INT32 : STATE_WORDS, 0};
     }
     return io;
 }

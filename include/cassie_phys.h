@@ -419,6 +419,76 @@ int phys_batch_end_episodes(phys_batch_t *b, int env0, int n, int restart, const
 /* one whole episode array to the host (int32 [nenv], or double [nenv][nq + nv] for PHYS_EP_TERMINAL); waits for the batch's streams */
 int phys_batch_download_episodes(phys_batch_t *b, int which, void *host);
 size_t phys_sizeof_episode_rules(void);
+/* A BANK OF FULL STATES: save, rewind and fork envs without leaving the device -- the batched form of cassie_get_state / cassie_set_state /
+ * cassie_sim_copy / cassie_sim_duplicate (reference src/cassiemujoco.c).  Where phys_batch_end_episodes starts a NEW EPISODE from a row of
+ * poses (time, warm start, ctrl, measurement block, filter histories and delay lines zero), a row of this bank is a STATE: after a
+ * restore the env continues byte for byte as the env that was saved did.  Sampling-based planning fans one env out to K candidates every
+ * policy step, a reset archive holds states the policy itself reached, a study rewinds, changes one thing and steps again.
+ *
+ * A ROW is phys_batch_state_row_dim 8-byte words; it and every section of it start on a 16-byte boundary (an odd section is followed by
+ * one padding word, zero in a saved row).  A section holds the bytes of one per-env array as stored.  phys_batch_state_layout writes
+ * [PHYS_SS_COUNT][2] ints, (offset, count) in words per section in the order of PHYS_SS_* (offset -1: not in this bank's rows) and
+ * returns PHYS_SS_COUNT.  Groups (`groups` is an OR; CORE is always there):
+ *   PHYS_STATE_CORE      every word a stepping launch writes and a later launch reads, or that a reader uses as stored: time, qpos, qvel,
+ *                        qacc_warmstart, ctrl, qacc, sensordata, actuator_velocity (the next substep's drive-level pass reads the last
+ *                        three), PHYS_F_MEAS, the whole cm_drive_state_t (filter histories, delay lines, safety_msg), PHYS_F_XPOS and
+ *                        PHYS_F_XQUAT, the sticky warning word (32 bits, zero-extended).  THE POSES are in the row because the depth
+ *                        image, the range sensors and phys_batch_derive take them AS STORED (the STALENESS paragraph of
+ *                        phys_batch_depth_set_geoms): a restore that left them alone would show the robot where it was before the restore.
+ *                        A section whose array the batch does not have at a save (the measurement block and the drive-level state until a
+ *                        drive mode is selected) is written as zeros, and skipped at a restore while the batch still has none -- zero is what selecting
+ *                        the mode later leaves, and what a restore after that puts there.
+ *   PHYS_STATE_COMMANDS  PD_PTARGET, PD_KP, PD_KD, PD_DTARGET, PD_TORQUE, DRIVE_CMD, QFRC_APPLIED, XFRC_APPLIED.  Refused by the configure
+ *                        call until both applied forces have been uploaded or bound: the step kernel is not handed them before, and a
+ *                        restore would put them into nothing.
+ *   PHYS_STATE_EPISODE   PHYS_EP_STEPS, PHYS_EP_COUNT and the env's terrain index (zero without a bank of terrains, and then not
+ *                        restored).  Needs phys_batch_episodes_enable.
+ *   PHYS_STATE_PARAMS    the env's cm_envparams_t block.  Needs per-env parameter blocks (phys_batch_randomize).  WITHOUT this group a
+ *                        restored env keeps its own physics -- a legitimate use: the same state under other masses or friction.
+ * NOT in a row: per-env height-field grids and per-env models, the outputs PHYS_F_BODY_CFRC / info / ext / PHYS_F_DERIVED / PHYS_F_QM /
+ * the scan, depth and ray fields / PHYS_F_STEP_SUMS, PHYS_EP_DONE / _REASON / _TERMINAL, the placement arrays, and what the launcher
+ * keeps per env for one launch or for speed alone (progress, chunk words, hand-over lists, launch order and cost: none changes a result).
+ *
+ *   phys_batch_state_configure  allocates a bank of nslots >= 1 zeroed rows in HBM; waits for the batch's streams; calling it again
+ *                               replaces the bank (and drops a binding).
+ *   phys_batch_state_bind       caller-owned device memory [nslots][row_dim] of 8-byte words, 16-byte aligned, in the bank's place
+ *                               (a torch int64 tensor); configure first (it fixes the groups); NULL un-binds: the batch's own bank again.
+ *   phys_batch_state_save       over envs [env0, env0 + n): env env0 + i goes to slot slots[i] (`slots`: a DEVICE int32 [n]; NULL: slot
+ *                               env0 + i).  A negative slot skips the env; a slot >= nslots skips it and raises bit 256 of the env's
+ *                               warning word (WARN_STATE_SLOT).  Two envs saving to one slot in one call is a caller error: that slot
+ *                               alone is unspecified.
+ *   phys_batch_state_restore    env env0 + i takes slot slots[i]; negative: the env is left alone; out of range: left alone, bit 256
+ *                               raised; any number of envs may take the same slot.  The warning word is the row's afterwards.
+ *                               Both are one small launch on `stream` (NULL: the batch's own), in order with the stepping launches there,
+ *                               honour strided qpos / qvel / sensordata bindings and never synchronise the host.  A FORK is a save
+ *                               followed by a restore on the same stream.  -1 + phys_last_error(): not configured, range out of bounds,
+ *                               something a group needs gone since the configure call.
+ *   phys_batch_state_download / _upload   rows [slot0, slot0 + n) to / from host memory; both wait for the batch's streams.  An upload
+ *                               names the signature its rows came with and is refused unless it is this batch's:
+ *   phys_batch_state_signature  a hash of the layout version, the groups, the row dim and the batch's compiled shared model (sizes,
+ *                               options, body tree, reference pose, masses, geoms): what keeps rows saved by one process out of another
+ *                               model.  0 while not configured. */
+enum { PHYS_STATE_CORE = 1, PHYS_STATE_COMMANDS = 2, PHYS_STATE_EPISODE = 4, PHYS_STATE_PARAMS = 8 };
+enum { PHYS_SS_TIME, PHYS_SS_QPOS, PHYS_SS_QVEL, PHYS_SS_QACC_WARMSTART, PHYS_SS_CTRL, PHYS_SS_QACC, PHYS_SS_SENSORDATA, PHYS_SS_ACTUATOR_VELOCITY,
+       PHYS_SS_MEAS, PHYS_SS_DRIVE_STATE, PHYS_SS_XPOS, PHYS_SS_XQUAT, PHYS_SS_WARN,
+       PHYS_SS_PD_PTARGET, PHYS_SS_PD_KP, PHYS_SS_PD_KD, PHYS_SS_PD_DTARGET, PHYS_SS_PD_TORQUE, PHYS_SS_DRIVE_CMD, PHYS_SS_QFRC_APPLIED, PHYS_SS_XFRC_APPLIED,
+       PHYS_SS_EP_STEPS, PHYS_SS_EP_COUNT, PHYS_SS_TERRAIN, PHYS_SS_PARAMS, PHYS_SS_COUNT };
+int phys_batch_state_configure(phys_batch_t *b, int nslots, int groups);
+int phys_batch_state_bind(phys_batch_t *b, void *device_ptr, int nslots);
+void *phys_batch_state_ptr(phys_batch_t *b);
+int phys_batch_state_nslots(const phys_batch_t *b);
+int phys_batch_state_groups(const phys_batch_t *b);
+int phys_batch_state_row_dim(const phys_batch_t *b);
+int phys_batch_state_layout_version(void);
+int phys_batch_state_layout(const phys_batch_t *b, int *offsets_counts);
+unsigned long long phys_batch_state_signature(const phys_batch_t *b);
+int phys_batch_state_save(phys_batch_t *b, int env0, int n, const int *slots, void *stream);
+int phys_batch_state_restore(phys_batch_t *b, int env0, int n, const int *slots, void *stream);
+/* a convenience outside the hot loop: copies a HOST int32 [n] of slots into a buffer of the batch's and returns its device pointer, for
+ * the next save or restore (waits for the batch's streams first: the buffer is reused by the next call); NULL on failure */
+void *phys_batch_state_stage_slots(phys_batch_t *b, const int *host_slots, int n);
+int phys_batch_state_download(phys_batch_t *b, int slot0, int n, void *host);
+int phys_batch_state_upload(phys_batch_t *b, int slot0, int n, const void *host, unsigned long long signature);
 /* PLACED RESTARTS: a restarted env is put down at a pose of its own, on the ground it finds there -- a curriculum's envs no longer all
  * restart at the row's spot and heading, a terrain (or a stair box moved under the spawn point) no longer buries or drops the robot,
  * and the env's NEXT terrain is chosen inside the restart, which can therefore see the ground it is about to stand on.  Still one
