@@ -187,6 +187,17 @@ def _declare(L):
         L.phys_batch_rays_bind_normals.argtypes = [vp, vp]
         L.phys_batch_rays_cast.argtypes = [vp, c.c_int, c.c_int, vp]
         L.phys_batch_debug_ray_launches.argtypes = [vp, c.POINTER(c.c_longlong)]
+    if hasattr(L, "phys_batch_probe"):   # (likewise)
+        L.phys_batch_probes_configure.argtypes = [vp, vp, c.c_int, c.c_uint]
+        L.phys_batch_probe_geom_classes.argtypes = [vp, vp]
+        L.phys_batch_probe.argtypes = [vp, c.c_int, c.c_int, vp]
+        L.phys_batch_probe_row_dim.argtypes = [vp]
+        L.phys_batch_probe_layout.argtypes = [vp, vp, vp]
+        L.phys_batch_probe_contacts_ptr.argtypes = [vp]
+        L.phys_batch_probe_contacts_ptr.restype = vp
+        L.phys_batch_probe_bind_contacts.argtypes = [vp, vp]
+        L.phys_batch_probe_download_contacts.argtypes = [vp, vp]
+        L.phys_batch_debug_probe_launches.argtypes = [vp, c.POINTER(c.c_longlong), c.POINTER(c.c_longlong)]
     if hasattr(L, "phys_batch_step_sums_enable"):   # (likewise)
         L.phys_batch_step_sums_enable.argtypes = [vp, c.c_int]
     if hasattr(L, "phys_batch_download_progress"):   # (absent from older variant builds selected with CASSIE_LIB)

@@ -15,7 +15,7 @@ from ._lib import CmDriveState, CmEnvParams, CmEpisodeRules, CmModel, MODEL_DIR,
 # field ids (enum in cassie_phys.h)
 (F_QPOS, F_QVEL, F_QACC_WARMSTART, F_TIME, F_CTRL, F_QFRC_APPLIED, F_XFRC_APPLIED, F_QACC, F_SENSORDATA,
  F_ACTUATOR_VELOCITY, F_XPOS, F_XQUAT, F_PD_PTARGET, F_PD_KP, F_PD_KD, F_BODY_CFRC, F_DRIVE_CMD, F_MEAS, F_PD_DTARGET,
- F_PD_TORQUE, F_DERIVED, F_QM, F_HEIGHT_SCAN, F_DEPTH, F_RAYS, F_STEP_SUMS) = range(26)
+ F_PD_TORQUE, F_DERIVED, F_QM, F_HEIGHT_SCAN, F_DEPTH, F_RAYS, F_STEP_SUMS, F_PROBES) = range(27)
 
 # layout of the step-sums block F_STEP_SUMS (CM_SUM_* in cm_model.h): what a stepping launch added up over its substeps
 # (Batch.enable_step_sums); MAXBODY = CM_MAXBODY, MAXU = CM_MAXU
@@ -52,6 +52,16 @@ DEPTH_MAXPIXELS = 16384
 RAY_BODY, RAY_WORLD_DIR, RAY_HEADING = range(3)
 RAYS_MAX = 1024
 RAY_DTYPE = np.dtype([("body", np.int32), ("frame", np.int32), ("origin", np.float64, 3), ("dir", np.float64, 3)])
+# probes: the kinds (PHYS_PROBE_* in cassie_phys.h), the layout of phys_probe_t, the quantities (PHYS_PQ_*: bits, in the order their
+# blocks lie in a row; PQ_CONTACTS is the per-env word) with their names and shapes per probe (nv stands for the model's), and the
+# bits of the contact word (PHYS_PC_*: PC_GROUP0 << g = a geom of group 1 touches one of group g, g = 0 .. 5)
+PROBE_BODY, PROBE_SITE = range(2)
+PROBES_MAX = 32
+PROBE_DTYPE = np.dtype([("kind", np.int32), ("id", np.int32), ("offset", np.float64, 3)])
+PQ_POS, PQ_QUAT, PQ_VEL, PQ_CVEL, PQ_ACC, PQ_JACP, PQ_JACR, PQ_CFRC, PQ_CONTACTS = (1 << k for k in range(9))
+PQ_ALL = PQ_CONTACTS * 2 - 1
+PQ_ROW = (("pos", (3,)), ("quat", (4,)), ("vel", (6,)), ("cvel", (6,)), ("acc", (6,)), ("jacp", (3, "nv")), ("jacr", (3, "nv")), ("cfrc", (3,)))
+PC_OBSTACLE, PC_SELF, PC_GROUP0 = 1, 2, 256
 
 # per-env physical parameters (CM_P_* in cm_model.h): what Batch.randomize takes
 (P_BODY_MASS, P_BODY_IPOS, P_BODY_INERTIA, P_DOF_DAMPING, P_GEOM_FRICTION,
@@ -480,6 +490,67 @@ class Batch:
         a = ctypes.c_longlong(0)
         lib().phys_batch_debug_ray_launches(self._h, ctypes.byref(a))
         return a.value
+
+    # ---- probes: the reward-side getters for any body or site (phys_batch_probe) ----
+    def configure_probes(self, probes, quantities):
+        """The list of probes: a list of (kind, id, offset [3]) or a structured array of PROBE_DTYPE, 1 .. PROBES_MAX of them (none:
+        release); kind is PROBE_BODY or PROBE_SITE, id the body or site, offset a point in the body's / site's own frame.  quantities: an
+        OR of PQ_*.  Allocates the rows (F_PROBES: bind a tensor after this call), the contact words and the probes' own read-out block
+        (sizeof(cm_ext_t) = 34 KB per env).  PQ_CONTACTS reads the geoms' classes from the batch's Model (a batch made from a compiled model alone has none)."""
+        if isinstance(probes, np.ndarray) and probes.dtype.names:
+            table = np.ascontiguousarray(probes.astype(PROBE_DTYPE, copy=False)).reshape(-1)
+        else:
+            probes = list(probes)
+            table = np.zeros(len(probes), dtype=PROBE_DTYPE)
+            for k, (kind, ident, offset) in enumerate(probes):
+                table[k] = (int(kind), int(ident), np.asarray(offset, dtype=np.float64))
+        assert PROBE_DTYPE.itemsize == 32
+        if table.size and (int(quantities) & PQ_CONTACTS) and isinstance(self.model, Model):
+            if lib().phys_batch_probe_geom_classes(self._h, self.model._h) != 0:
+                raise ValueError("configure_probes failed: " + (lib().phys_last_error() or b"").decode())
+        if lib().phys_batch_probes_configure(self._h, table.ctypes.data if table.size else None, int(table.size), int(quantities)) != 0:
+            raise ValueError("configure_probes failed: " + (lib().phys_last_error() or b"").decode())
+
+    def probe(self, env0=0, n=None, stream=None):
+        """One forward pass of envs [env0, env0 + n) into the probes' own read-out block and the reduction behind it, on `stream`
+        (default: the batch's own), in order with the step launches there: F_PROBES and the contact words of the range.  Nothing else
+        of the batch changes; no host synchronisation."""
+        n = self.nenv - env0 if n is None else n
+        if lib().phys_batch_probe(self._h, int(env0), int(n), stream) != 0:
+            raise RuntimeError("probe failed: " + (lib().phys_last_error() or b"").decode())
+
+    def probe_layout(self):
+        """{name: (offset in the row, (nprobes, *shape))} of the quantities configured, in row order."""
+        off, dims = (ctypes.c_int * len(PQ_ROW))(), (ctypes.c_int * len(PQ_ROW))()
+        nprobes = lib().phys_batch_probe_layout(self._h, off, dims)
+        if nprobes < 0:
+            raise RuntimeError("probe_layout failed: " + (lib().phys_last_error() or b"").decode())
+        nv = self.pod.nv
+        return {name: (off[k], (nprobes,) + tuple(nv if d == "nv" else d for d in shape)) for k, (name, shape) in enumerate(PQ_ROW) if off[k] >= 0}
+
+    def probes(self, env0=0, n=None):
+        """The rows [env0, env0 + n) of F_PROBES as named arrays of one download: pos [n][nprobes][3] ... jacp [n][nprobes][3][nv]."""
+        n = self.nenv - env0 if n is None else n
+        raw = self.get(F_PROBES, env0, n)
+        return {name: raw[:, o: o + int(np.prod(shape))].reshape((n,) + shape) for name, (o, shape) in self.probe_layout().items()}
+
+    def probe_contacts(self):
+        """The contact words [nenv] (int32; PC_* bits), downloaded -- the batch's own, or the bound tensor's."""
+        out = np.empty(self.nenv, dtype=np.int32)
+        if lib().phys_batch_probe_download_contacts(self._h, out.ctypes.data) != 0:
+            raise RuntimeError("probe_contacts failed: " + (lib().phys_last_error() or b"").decode())
+        return out
+
+    def bind_probe_contacts(self, device_ptr):
+        """The contact words in caller-owned HBM: int32 [nenv]; None: the batch's own again.  configure_probes drops the binding."""
+        if lib().phys_batch_probe_bind_contacts(self._h, device_ptr) != 0:
+            raise RuntimeError("bind_probe_contacts failed: " + (lib().phys_last_error() or b"").decode())
+
+    def probe_launches(self):
+        """Diagnostics: (forward passes, reductions) probe() has launched so far."""
+        a, c_ = ctypes.c_longlong(0), ctypes.c_longlong(0)
+        lib().phys_batch_debug_probe_launches(self._h, ctypes.byref(a), ctypes.byref(c_))
+        return a.value, c_.value
 
     def set_pd_mode(self, on=True):
         lib().phys_batch_set_pd_mode(self._h, 1 if on else 0)

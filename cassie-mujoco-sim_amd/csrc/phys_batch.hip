@@ -126,6 +126,17 @@ struct phys_batch {
     unsigned long long *state_bound = nullptr;
     DevBuf<int> d_state_staged;     /* a host array of slots on its way to a launch (phys_batch_state_stage_slots) */
     int state_staged_cap = 0;
+    /* probes (phys_batch_probes_configure): the list and the quantities (probes.nprobes 0: not configured; the pointers are filled in at
+     * the launch, from the buffers), the table and the classes of the full list's geoms in HBM, the read-out block and the scratch
+     * outputs of the probes' OWN forward pass -- no stepping launch is handed either -- and the contact words (the batch's own, or a caller's) */
+    ck::ProbeCfg probes = {};
+    DevBuf<ck::ProbeDef> d_probes;
+    DevBuf<int> d_probe_geoms;
+    int probe_ngeom = 0;
+    DevBuf<cm_ext_t> d_probe_ext;
+    DevBuf<double> d_probe_scratch;  /* [nenv] rows of qacc | sensordata | actuator_velocity | xpos | xquat, one array after the other */
+    DevBuf<int> d_probe_contacts;
+    long long probe_launches[2] = {0, 0}; /* forward passes / reductions of phys_batch_probe (phys_batch_debug_probe_launches) */
 };
 
 static bool hip_ok(hipError_t e, const char *what) {
@@ -397,11 +408,28 @@ static hipEvent_t timing_begin(phys_batch *b, hipStream_t s) {
     return b->ev_pool[b->ev_used++].second;
 }
 
+/* Where a read-out pass of the probes sends everything a forward pass stores (launch()'s `readout`): the read-out block, and arrays
+ * [nenv] with dense rows in place of the caller's qacc, sensordata, actuator_velocity, xpos and xquat */
+struct ReadoutPass { cm_ext_t *ext; double *qacc, *sensordata, *actuator_velocity, *xpos, *xquat; };
+
 /* One launch: the PhysIO, the range's record, the policy's answers (step_policy.h), the plan (step_plan.h), its passes, the report */
-static int launch(phys_batch *b, int nsub, int integrate, hipStream_t s, bool scratch_outputs = false, int env0 = 0, int n = -1) {
+static int launch(phys_batch *b, int nsub, int integrate, hipStream_t s, bool scratch_outputs = false, int env0 = 0, int n = -1, const ReadoutPass *readout = nullptr) {
     ck::PhysIO io = make_io(b, nsub, integrate);
     if (n < 0) n = b->nenv;
     io.env0 = env0; io.nenv = n;
+    if (readout) {
+        /* the probes' forward pass: into ITS read-out block (the batch's own, phys_batch_enable_ext, is not this pass's business, and the
+         * override is this launch's alone: another range's launch may be made from another thread meanwhile), and nothing a caller can
+         * read is stored to -- the step outputs and the body poses go to the probes' scratch, the per-body contact forces and the
+         * solver statistics nowhere */
+        const cm_model_t &m = b->host_model;
+        io.ext = readout->ext;
+        io.qacc = readout->qacc; io.sv = m.nv;
+        io.sensordata = readout->sensordata; io.ssd = m.nsensordata;
+        io.actuator_velocity = readout->actuator_velocity;
+        io.xpos_out = readout->xpos; io.xquat_out = readout->xquat;
+        io.body_cfrc = nullptr; io.info = nullptr;
+    }
     if (!integrate) { io.order = nullptr; io.cost = nullptr; io.cost_wall = nullptr; } /* forward / read-out passes: one substep, nothing to balance (identity order) */
     if (scratch_outputs) {
         /* a read-out pass: the step outputs the caller's fields hold (sensordata and actuator_velocity of the last STEP feed
@@ -491,7 +519,7 @@ static void note_field_in_use(phys_batch *b, int field) {
 /* rows [env0, env0 + n) of a field between a dense host array and HBM (dense, or strided when the field is a column
  * block of a caller-owned tensor), asynchronously on the batch's stream */
 static bool copy_rows(phys_batch *b, int field, void *host, int env0, int n, bool to_device, const char *what) {
-    if (!b->d_field[field]) { phys_set_last_error("this field is allocated by phys_batch_derive (PHYS_F_HEIGHT_SCAN: phys_batch_scan_configure, PHYS_F_DEPTH: phys_batch_depth_configure, PHYS_F_RAYS: phys_batch_rays_configure); call it first"); return false; }
+    if (!b->d_field[field]) { phys_set_last_error("this field is allocated by phys_batch_derive (PHYS_F_HEIGHT_SCAN: phys_batch_scan_configure, PHYS_F_DEPTH: phys_batch_depth_configure, PHYS_F_RAYS: phys_batch_rays_configure, PHYS_F_PROBES: phys_batch_probes_configure); call it first"); return false; }
     const size_t row = (size_t)b->dim[field], st = (size_t)b->stride[field];
     double *dev = b->d_field[field] + st * env0;
     if (n == 0) return true;
@@ -525,7 +553,7 @@ phys_batch_t *phys_batch_create(const cm_model_t *model, int nenv, int device) {
     const int d[PHYS_F_COUNT] = {model->nq, model->nv, model->nv, 1, model->nu, model->nv, model->nbody * 6,
                                  model->nv, model->nsensordata, model->nu, model->nbody * 3, model->nbody * 4,
                                  model->nu, model->nu, model->nu, model->nbody * 3,
-                                 model->nu + 1, CM_MEAS_DIM, model->nu, model->nu, CM_DRV_DIM, model->nv * model->nv, 0, 0, 0, CM_SUM_DIM};
+                                 model->nu + 1, CM_MEAS_DIM, model->nu, model->nu, CM_DRV_DIM, model->nv * model->nv, 0, 0, 0, CM_SUM_DIM, 0};
     const size_t n = (size_t)nenv;
     bool ok = true;
     for (int f = 0; f < PHYS_F_COUNT; ++f) {
@@ -535,6 +563,7 @@ phys_batch_t *phys_batch_create(const cm_model_t *model, int nenv, int device) {
         if (f == PHYS_F_DEPTH) continue;                    /* ... by phys_batch_depth_configure */
         if (f == PHYS_F_RAYS) continue;                     /* ... by phys_batch_rays_configure */
         if (f == PHYS_F_STEP_SUMS) continue;                /* allocated by phys_batch_step_sums_enable */
+        if (f == PHYS_F_PROBES) continue;                   /* sized and allocated by phys_batch_probes_configure */
         ok = ok && b->d_field[f].alloc(n * (d[f] > 0 ? d[f] : 1), true, "field");
     }
     ok = ok && b->d_models.alloc(1, false, "model");
@@ -730,15 +759,16 @@ int phys_batch_bind(phys_batch_t *b, int field, void *device_ptr) {
 int phys_batch_bind_strided(phys_batch_t *b, int field, void *device_ptr, int row_stride) {
     if (!b || !device_ptr || field < 0 || field >= PHYS_F_COUNT) return -1;
     if (row_stride != b->dim[field]) {
-        const bool may = field == PHYS_F_QPOS || field == PHYS_F_QVEL || field == PHYS_F_SENSORDATA || field == PHYS_F_HEIGHT_SCAN || field == PHYS_F_DEPTH || field == PHYS_F_RAYS;
+        const bool may = field == PHYS_F_QPOS || field == PHYS_F_QVEL || field == PHYS_F_SENSORDATA || field == PHYS_F_HEIGHT_SCAN || field == PHYS_F_DEPTH || field == PHYS_F_RAYS || field == PHYS_F_PROBES;
         if (!may || row_stride < b->dim[field]) {
-            phys_set_last_error("phys_batch_bind_strided: only qpos / qvel / sensordata / the height scan / the depth image / the ray ranges take a row stride, and it must be >= the field's dim");
+            phys_set_last_error("phys_batch_bind_strided: only qpos / qvel / sensordata / the height scan / the depth image / the ray ranges / the probes' rows take a row stride, and it must be >= the field's dim");
             return -1;
         }
     }
     if (field == PHYS_F_HEIGHT_SCAN && b->scan.npoints <= 0) { phys_set_last_error("phys_batch_bind: configure the scan first (phys_batch_scan_configure sizes PHYS_F_HEIGHT_SCAN)"); return -1; }
     if (field == PHYS_F_DEPTH && b->depth.width <= 0) { phys_set_last_error("phys_batch_bind: configure the depth image first (phys_batch_depth_configure sizes PHYS_F_DEPTH)"); return -1; }
     if (field == PHYS_F_RAYS && b->rays.nrays <= 0) { phys_set_last_error("phys_batch_bind: configure the rays first (phys_batch_rays_configure sizes PHYS_F_RAYS)"); return -1; }
+    if (field == PHYS_F_PROBES && b->probes.nprobes <= 0) { phys_set_last_error("phys_batch_bind: configure the probes first (phys_batch_probes_configure sizes PHYS_F_PROBES)"); return -1; }
     (void)hipSetDevice(b->device);
     /* no stream synchronisation: launches already queued keep the pointers they were given, and hipFree of the
      * replaced buffer waits for the device by itself */
@@ -1307,6 +1337,134 @@ int phys_batch_rays_cast(phys_batch_t *b, int env0, int n, void *stream) {
     hipLaunchKernelGGL(ck::cassie_rays_kernel, dim3((unsigned)ck::rays_grid(n, rays.nrays)), dim3(WV_WAVE), 0, s,
                        ck::make_rays_io(view_of(b), rays, b->d_field[PHYS_F_RAYS], b->stride[PHYS_F_RAYS], env0, n));
     return hip_ok(hipGetLastError(), "cassie_rays_kernel launch") ? 0 : -1;
+}
+
+/* ------------------------------------------------ probes ---- */
+static_assert(sizeof(ck::ProbeDef) == sizeof(phys_probe_t) && offsetof(ck::ProbeDef, id) == offsetof(phys_probe_t, id) &&
+              offsetof(ck::ProbeDef, offset) == offsetof(phys_probe_t, offset), "phys_probe_t is the kernel's table entry");
+static_assert(PHYS_PROBE_BODY == ck::PROBE_BODY && PHYS_PROBE_SITE == ck::PROBE_SITE && PHYS_PROBES_MAX == ck::PROBES_MAX, "the kinds' numbers");
+static_assert((int)PHYS_PQ_COUNT == (int)ck::PQ_COUNT && PHYS_PQ_CFRC == 1 << ck::PQ_CFRC && PHYS_PQ_CONTACTS == 1 << ck::PQ_CONTACTS &&
+              PHYS_PC_OBSTACLE == ck::PC_OBSTACLE && PHYS_PC_SELF == ck::PC_SELF && PHYS_PC_GROUP0 == ck::PC_GROUP0, "the header's quantities and contact bits are probe_kernels.h's");
+/* doubles per env of the scratch outputs of the probes' forward pass */
+static size_t probe_scratch_row(const cm_model_t &m) { return (size_t)(m.nv + m.nsensordata + m.nu + 7 * m.nbody); }
+/* the record of a launch: what was configured, with the pointers into the batch's buffers */
+static ck::ProbeCfg probe_cfg_of(const phys_batch *b) {
+    ck::ProbeCfg c = b->probes;
+    const cm_model_t &m = b->host_model;
+    const size_t n = (size_t)b->nenv;
+    c.probes = b->d_probes; c.geom_class = b->d_probe_geoms; c.ngeom = b->probe_ngeom; c.ext = b->d_probe_ext;
+    c.qacc = b->d_probe_scratch;
+    c.xpos = b->d_probe_scratch ? b->d_probe_scratch + n * (size_t)(m.nv + m.nsensordata + m.nu) : nullptr;
+    c.xquat = c.xpos ? c.xpos + n * 3 * (size_t)m.nbody : nullptr;
+    c.contacts = b->d_probe_contacts;
+    return c;
+}
+int phys_batch_probe_geom_classes(phys_batch_t *b, const phys_model_t *host_model) {
+    if (!b) { phys_set_last_error("phys_batch_probe_geom_classes: no batch"); return -1; }
+    (void)hipSetDevice(b->device);
+    if (!quiesce(b)) return -1;  /* (launches in flight may be reading the table that goes away) */
+    if (!host_model) { b->d_probe_geoms.reset(); b->probe_ngeom = 0; return 0; }
+    const int ngeom = phys_model_size(host_model, PHYS_NGEOM);
+    /* (the contact list names geoms of the full list through the compiled model's geom_fullid: the table must hold them all) */
+    for (int g = 0; g < b->host_model.ngeom; ++g)
+        if (b->host_model.geom_fullid[g] < 0 || b->host_model.geom_fullid[g] >= ngeom) return refuse("phys_batch_probe_geom_classes", "not the host model the batch's model was compiled from (a geom_fullid lies outside its geom list)");
+    std::vector<int> table((size_t)(ngeom > 0 ? ngeom : 1), 0);
+    ck::probe_classify_geoms(phys_model_array((phys_model_t *)host_model, PHYS_M_GEOM_USER), phys_model_size(host_model, PHYS_NUSER_GEOM),
+                             phys_model_iarray((phys_model_t *)host_model, PHYS_MI_GEOM_GROUP), ngeom, table.data());
+    DevBuf<int> d;
+    if (!d.alloc(table.size(), false, "geom classes")) return -1;
+    if (!hip_ok(hipMemcpy(d, table.data(), sizeof(int) * table.size(), hipMemcpyHostToDevice), "hipMemcpy(geom classes)")) return -1;
+    b->d_probe_geoms = std::move(d);
+    b->probe_ngeom = ngeom;
+    return 0;
+}
+int phys_batch_probes_configure(phys_batch_t *b, const phys_probe_t *probes, int nprobes, unsigned quantities) {
+    if (!b) return refuse("phys_batch_probes_configure", ck::PROBES_SIZE_REFUSAL);
+    ck::ProbeCfg cfg;
+    if (const char *why = ck::probes_configure(b->host_model, (const ck::ProbeDef *)probes, nprobes, quantities, cfg)) return refuse("phys_batch_probes_configure", why);
+    const bool words = nprobes > 0 && (quantities & PHYS_PQ_CONTACTS) != 0;
+    if (words && !b->d_probe_geoms)
+        return refuse("phys_batch_probes_configure", "PHYS_PQ_CONTACTS reads the geoms' classes, which the compiled model does not carry (phys_batch_probe_geom_classes first)");
+    (void)hipSetDevice(b->device);
+    if (!quiesce(b)) return -1;  /* (launches in flight may be reading the table, or writing the rows, that go away) */
+    if (nprobes == 0) {          /* release: everything but the geoms' classes, which are the model's */
+        b->probes = {};
+        b->d_probes.reset(); b->d_probe_ext.reset(); b->d_probe_scratch.reset(); b->d_probe_contacts.reset();
+        b->d_field[PHYS_F_PROBES].reset();
+        b->dim[PHYS_F_PROBES] = 0; b->stride[PHYS_F_PROBES] = 0;
+        return 0;
+    }
+    const cm_model_t &m = b->host_model;
+    const size_t n = (size_t)b->nenv;
+    const int row = ck::probe_layout(nprobes, quantities, m.nv, nullptr, nullptr);
+    DevBuf<ck::ProbeDef> tab;
+    DevBuf<double> out;
+    DevBuf<int> con;
+    if (!tab.alloc((size_t)nprobes, false, "probe table")) return -1;
+    if (!hip_ok(hipMemcpy(tab, probes, sizeof(ck::ProbeDef) * (size_t)nprobes, hipMemcpyHostToDevice), "hipMemcpy(probe table)")) return -1;
+    /* the field takes the row's size: a buffer of the batch's own of the new size (a caller's binding is dropped: bind again); a row
+     * without doubles -- the contact word alone -- keeps one, so that the field exists */
+    if (!out.alloc(n * (size_t)(row > 0 ? row : 1), true, "probe rows")) return -1;
+    if (words && !con.alloc(n, true, "probe contact words")) return -1;
+    if (!b->d_probe_ext && !b->d_probe_ext.alloc(n, true, "probe read-out")) return -1;
+    if (!b->d_probe_scratch && !b->d_probe_scratch.alloc(n * probe_scratch_row(m), true, "probe scratch outputs")) return -1;
+    b->d_probes = std::move(tab);
+    b->d_field[PHYS_F_PROBES] = std::move(out);
+    b->dim[PHYS_F_PROBES] = row; b->stride[PHYS_F_PROBES] = row;
+    b->d_probe_contacts = std::move(con);
+    b->probes = cfg;
+    b->probes.probes = nullptr;  /* (the caller's array: a launch reads the table in HBM) */
+    return 0;
+}
+int phys_batch_probe_row_dim(const phys_batch_t *b) { return b && b->probes.nprobes > 0 ? b->dim[PHYS_F_PROBES] : 0; }
+int phys_batch_probe_layout(const phys_batch_t *b, int *offsets, int *dims) {
+    if (!b || b->probes.nprobes < 1) { phys_set_last_error("phys_batch_probe_layout: not configured (phys_batch_probes_configure first)"); return -1; }
+    (void)ck::probe_layout(b->probes.nprobes, b->probes.quantities, b->host_model.nv, offsets, dims);
+    return b->probes.nprobes;
+}
+void *phys_batch_probe_contacts_ptr(phys_batch_t *b) { return b ? (void *)b->d_probe_contacts.get() : nullptr; }
+int phys_batch_probe_bind_contacts(phys_batch_t *b, void *device_ptr) {
+    if (!b) { phys_set_last_error("phys_batch_probe_bind_contacts: no batch"); return -1; }
+    if (b->probes.nprobes < 1 || !(b->probes.quantities & PHYS_PQ_CONTACTS)) return refuse("phys_batch_probe_bind_contacts", "configure the probes with PHYS_PQ_CONTACTS first");
+    (void)hipSetDevice(b->device);
+    /* (as phys_batch_bind: launches already queued keep the pointer they were given; hipFree waits for the device by itself.  NULL: the
+     * batch's own words again, zeroed) */
+    if (device_ptr) b->d_probe_contacts.borrow((int *)device_ptr);
+    else if (!b->d_probe_contacts.owned() && !b->d_probe_contacts.alloc((size_t)b->nenv, true, "probe contact words")) return -1;
+    return 0;
+}
+int phys_batch_probe_download_contacts(phys_batch_t *b, int *host) {
+    if (!b || !host || !b->d_probe_contacts) { phys_set_last_error("phys_batch_probe_download_contacts: bad arguments, or the probes were not configured with PHYS_PQ_CONTACTS"); return -1; }
+    (void)hipSetDevice(b->device);
+    return quiesce(b) && hip_ok(hipMemcpy(host, b->d_probe_contacts, sizeof(int) * (size_t)b->nenv, hipMemcpyDeviceToHost), "probe contact words download") ? 0 : -1;
+}
+int phys_batch_debug_probe_launches(const phys_batch_t *b, long long *forward, long long *reduce) {
+    if (!b) return -1;
+    if (forward) *forward = b->probe_launches[0];
+    if (reduce) *reduce = b->probe_launches[1];
+    return 0;
+}
+int phys_batch_probe(phys_batch_t *b, int env0, int n, void *stream) {
+    if (!b) { phys_set_last_error("phys_batch_probe: no batch"); return -1; }
+    const ck::ProbeCfg c = probe_cfg_of(b);
+    if (const char *why = ck::check_probe_call(c, b->nenv, env0, n)) return refuse("phys_batch_probe", why);
+    if (!b->d_field[PHYS_F_PROBES] || !b->d_probe_scratch) return refuse("phys_batch_probe", "not configured (phys_batch_probes_configure first)");
+    (void)hipSetDevice(b->device);
+    if (n == 0) return 0;
+    hipStream_t s = launch_stream(b, stream);
+    /* the read-out of the current state of the range: a forward pass that stores to the probes' block and scratch alone */
+    const cm_model_t &m = b->host_model;
+    const size_t N = (size_t)b->nenv;
+    double *const scratch = b->d_probe_scratch;
+    const ReadoutPass pass = {b->d_probe_ext, scratch, scratch + N * (size_t)m.nv, scratch + N * (size_t)(m.nv + m.nsensordata),
+                              const_cast<double *>(c.xpos), const_cast<double *>(c.xquat)};
+    if (launch(b, 1, 0, s, false, env0, n, &pass) != 0) return -1;
+    ++b->probe_launches[0];
+    hipLaunchKernelGGL(ck::cassie_probe_kernel, dim3((unsigned)ck::probe_grid(n)), dim3(WV_WAVE), 0, s,
+                       ck::make_probe_io(view_of(b), c, b->d_field[PHYS_F_PROBES], b->stride[PHYS_F_PROBES], env0, n));
+    if (!hip_ok(hipGetLastError(), "cassie_probe_kernel launch")) return -1;
+    ++b->probe_launches[1];
+    return 0;
 }
 
 int phys_batch_sync(phys_batch_t *b) {

@@ -95,6 +95,15 @@ WV_DEVICE void quat2mat(double *m, const double *q) {
     m[3] = 2 * (q12 + q03);       m[4] = q00 - q11 + q22 - q33; m[5] = 2 * (q23 - q01);
     m[6] = 2 * (q13 - q02);       m[7] = 2 * (q23 + q01);       m[8] = q00 - q11 - q22 + q33;
 }
+/* the quaternion of a rotation matrix: the host routine of csrc/cassiemujoco.c (cassie_sim_site_xquat) restated, branch by branch, with
+ * its sign convention (the largest of the trace and the diagonal entries picks the branch; that component comes out positive) */
+WV_DEVICE void mat2quat(double *q, const double *m) {
+    const double tr = m[0] + m[4] + m[8];
+    if (tr > 0) { const double s = sqrt(tr + 1.0) * 2; q[0] = 0.25 * s; q[1] = (m[7] - m[5]) / s; q[2] = (m[2] - m[6]) / s; q[3] = (m[3] - m[1]) / s; }
+    else if (m[0] > m[4] && m[0] > m[8]) { const double s = sqrt(1.0 + m[0] - m[4] - m[8]) * 2; q[0] = (m[7] - m[5]) / s; q[1] = 0.25 * s; q[2] = (m[1] + m[3]) / s; q[3] = (m[2] + m[6]) / s; }
+    else if (m[4] > m[8]) { const double s = sqrt(1.0 + m[4] - m[0] - m[8]) * 2; q[0] = (m[2] - m[6]) / s; q[1] = (m[1] + m[3]) / s; q[2] = 0.25 * s; q[3] = (m[5] + m[7]) / s; }
+    else { const double s = sqrt(1.0 + m[8] - m[0] - m[4]) * 2; q[0] = (m[3] - m[1]) / s; q[1] = (m[2] + m[6]) / s; q[2] = (m[5] + m[7]) / s; q[3] = 0.25 * s; }
+}
 WV_DEVICE void mulmatvec3(double *r, const double *m, const double *v) {
     double t0 = m[0] * v[0] + m[1] * v[1] + m[2] * v[2];
     double t1 = m[3] * v[0] + m[4] * v[1] + m[5] * v[2];

@@ -1,12 +1,12 @@
 /*
- * small_launch.h -- how the kernels around the step kernel (small_kernels.h, surface_kernels.h, depth_kernel.h, ray_kernel.h, episode_kernels.h) are
+ * small_launch.h -- how the kernels around the step kernel (small_kernels.h, surface_kernels.h, depth_kernel.h, ray_kernel.h, episode_kernels.h, probe_kernels.h) are
  * launched: the records a kernel's arguments are built from, one builder per kernel that returns its filled argument struct for an env
  * range, the grid of every launch, and the checks of what a caller configures, each returning the message of its refusal (null: fine).
  * Pure host code, no HIP runtime calls, in the spirit of step_policy.h: the launcher (phys_batch.hip) keeps the records in the batch,
  * prefixes a message with its entry point's name and launches what a builder returns on the grid given here; the wave emulator's entry
  * points (tests/emu) fill the same records from their arguments and go through the same builders, grids and checks, so a CPU test of
  * one of these kernels also runs the launcher's refusals, grid and choice of kernel (tests/test_small_launch.py pins them one by one).
- * No field of ScanIO, DepthIO, RayIO, EpisodeIO, ResetIO, DeriveIO, SetConstIO or StateIO is assigned anywhere else.
+ * No field of ScanIO, DepthIO, RayIO, EpisodeIO, ResetIO, DeriveIO, SetConstIO, StateIO or ProbeIO is assigned anywhere else.
  */
 #ifndef CASSIE_SMALL_LAUNCH_H
 #define CASSIE_SMALL_LAUNCH_H
@@ -16,6 +16,7 @@
 
 #include "depth_kernel.h"
 #include "episode_kernels.h"
+#include "probe_kernels.h"
 #include "ray_kernel.h"
 #include "small_kernels.h"
 #include "state_kernels.h"
@@ -66,6 +67,14 @@ struct EpisodeCfg { cm_episode_rules_t rules; int *done, *reason, *steps, *count
 /* the bank of full states (phys_batch_state_configure, _bind; nslots 0: not configured): the groups of its rows (STATE_* below) and the
  * rows [nslots][state_layout().row_dim] of 8-byte words */
 struct StateCfg { int nslots, groups; unsigned long long *bank; };
+/* the probes (phys_batch_probes_configure; nprobes 0: not configured): the table [nprobes] and the quantities as configured; then what the
+ * caller names once a kernel reads them: where the table lies, the classes of the geoms of the full list [ngeom] (null: none were given),
+ * what the probes' own forward pass leaves -- its read-out block [nenv], its body poses (dense rows of 3 nbody / 4 nbody doubles) and its
+ * qacc (dense rows of nv) -- and the contact words [nenv] (null: not asked for) */
+struct ProbeCfg {
+    int nprobes; unsigned quantities; const ProbeDef *probes; const int *geom_class; int ngeom;
+    const cm_ext_t *ext; const double *xpos, *xquat, *qacc; int *contacts;
+};
 
 /* ---- the row of a full state ---- */
 
@@ -185,6 +194,55 @@ inline const char *place_configure(const cm_model_t &m, int model_stride, int an
     memset(&tab, 0, sizeof tab);
     return place_classify(m, anchor, tab);
 }
+/* the probes' row: quantity-major, for every quantity of the mask in bit order a block [nprobes][dim] with nothing between the blocks;
+ * offsets[q] = where quantity q's block starts (-1: not in the mask), dims[q] = its doubles per probe (either may be null) -> the row's length */
+constexpr unsigned PROBE_ALL_QUANTITIES = (1u << (PQ_COUNT + 1)) - 1u;
+inline int probe_layout(int nprobes, unsigned quantities, int nv, int *offsets, int *dims) {
+    const int dim[PQ_COUNT] = {3, 4, 6, 6, 6, 3 * nv, 3 * nv, 3};
+    int row = 0;
+    for (int q = 0; q < PQ_COUNT; ++q) {
+        const bool has = (quantities >> q & 1u) != 0;
+        if (offsets) offsets[q] = has ? row : -1;
+        if (dims) dims[q] = dim[q];
+        if (has) row += nprobes * dim[q];
+    }
+    return row;
+}
+/* (what the launcher also answers a call without a batch) */
+constexpr const char *PROBES_SIZE_REFUSAL = "0 .. 32 probes (0 releases them)";
+/* the probes' configuration: checks the caller's probes [nprobes] and fills c (the table and the quantities; everything the caller
+ * names later stays null).  nprobes 0 is accepted and leaves c empty: the launcher releases what it holds */
+inline const char *probes_configure(const cm_model_t &m, const ProbeDef *probes, int nprobes, unsigned quantities, ProbeCfg &c) {
+    if (nprobes < 0 || nprobes > PROBES_MAX || (nprobes > 0 && !probes)) return PROBES_SIZE_REFUSAL;
+    c = {};
+    if (nprobes == 0) return nullptr;
+    const int nsite = m.nsite < CM_MAXSITE ? m.nsite : CM_MAXSITE;
+    for (int j = 0; j < nprobes; ++j) {
+        const ProbeDef &d = probes[j];
+        if (d.kind != PROBE_BODY && d.kind != PROBE_SITE) return "a probe's kind is PHYS_PROBE_BODY or PHYS_PROBE_SITE";
+        if (d.kind == PROBE_BODY && (d.id < 0 || d.id >= m.nbody)) return "a body probe's id must lie in [0, nbody)";
+        if (d.kind == PROBE_SITE && (d.id < 0 || d.id >= nsite)) return "a site probe's id must lie in [0, nsite) and below CM_MAXSITE, the sites of the read-out";
+        if (!(std::isfinite(d.offset[0]) && std::isfinite(d.offset[1]) && std::isfinite(d.offset[2]))) return "a probe needs a finite offset";
+    }
+    if (quantities == 0 || (quantities & ~PROBE_ALL_QUANTITIES)) return "quantities is a non-empty OR of PHYS_PQ_*";
+    c.nprobes = nprobes; c.quantities = quantities; c.probes = probes;
+    return nullptr;
+}
+/* the classes of the geoms of the host model's FULL list, as the contact word's rules read them (csrc/cassiemujoco.c: the three collision
+ * checks): geom_user[0] == 1 an obstacle, == 2 a geom of the robot (geom_user null or nuser_geom < 1: no classes, as there); geom_group as it is */
+inline void probe_classify_geoms(const double *geom_user, int nuser_geom, const int *geom_group, int ngeom, int *table) {
+    for (int g = 0; g < ngeom; ++g) {
+        const double u = geom_user && nuser_geom >= 1 ? geom_user[(size_t)nuser_geom * g] : 0.0;
+        const int grp = geom_group ? geom_group[g] : PROBE_NO_GROUP;
+        table[g] = (u == 1 ? 1 : u == 2 ? 2 : 0) | ((grp >= 0 && grp < PROBE_NO_GROUP ? grp : PROBE_NO_GROUP) << PROBE_GROUP_SHIFT);
+    }
+}
+/* what a probe call refuses */
+inline const char *check_probe_call(const ProbeCfg &c, int nenv, int env0, int n) {
+    if (c.nprobes < 1 || !c.probes || !c.ext) return "not configured (phys_batch_probes_configure first)";
+    if (env0 < 0 || n < 0 || (long long)env0 + n > nenv) return "env range out of bounds";
+    return nullptr;
+}
 /* the bank of full states: what phys_batch_state_configure / _bind refuse (the view tells what the batch has), and what a save or a
  * restore refuses */
 inline const char *state_configure(const BatchView &v, int nslots, int groups) {
@@ -211,6 +269,9 @@ inline int scan_grid(int n) { return n < SCAN_GRID ? n : SCAN_GRID; }
 inline int episode_grid(int n) { return n < EPISODE_GRID ? n : EPISODE_GRID; }
 /* one wave per env up to STATE_GRID workgroups, which then walk the range (state_kernels.h) */
 inline int state_grid(int n) { return n < STATE_GRID ? n : STATE_GRID; }
+/* one wave per env up to PROBE_GRID workgroups, which then walk the range: few, as the episode kernel's -- the launch runs behind a range's
+ * forward pass while the other range's step kernel fills the chip, where every workgroup waits for a wave slot to free (probe_kernels.h) */
+inline int probe_grid(int n) { return n < PROBE_GRID ? n : PROBE_GRID; }
 /* a job is (env, tile of DEPTH_TILE x DEPTH_TILE pixels); a fixed grid walks the job list (a first choice: depth_kernel.h) */
 inline int depth_grid(int n, int width, int height) {
     const int T = DEPTH_TILE;
@@ -279,6 +340,19 @@ inline RayIO make_rays_io(const BatchView &v, const RayCfg &c, double *out, int 
     io.env0 = env0; io.n = n; io.nrays = c.nrays; io.rmin = c.rmin; io.rmax = c.rmax; io.rays = c.rays; io.geoms = c.geoms;
     io.xpos = v.xpos; io.xquat = v.xquat; io.sxp = 3 * v.nbody; io.sxq = 4 * v.nbody;
     io.out = out; io.sout = sout; io.ids = c.ids; io.normals = c.normals; io.warn = v.warn;
+    return io;
+}
+/* cassie_probe_kernel's: the state rows of the view, the forward pass's outputs and the tables of the record, the row's layout; the
+ * contact word only where it was asked for AND the geoms' classes are there */
+inline ProbeIO make_probe_io(const BatchView &v, const ProbeCfg &c, double *out, int sout, int env0, int n) {
+    ProbeIO io = zeroed<ProbeIO>();
+    io.models = v.models; io.model_stride = v.model_stride;
+    io.env0 = env0; io.n = n; io.nprobes = c.nprobes; io.quantities = c.quantities; io.probes = c.probes;
+    io.ext = c.ext; io.xpos = c.xpos; io.xquat = c.xquat; io.sxp = 3 * v.nbody; io.sxq = 4 * v.nbody;
+    io.qpos = v.qpos; io.sq = v.sq; io.qvel = v.qvel; io.sqv = v.sqv; io.qacc = c.qacc; io.sv = v.nv;
+    io.out = out; io.sout = sout;
+    if ((c.quantities >> PQ_CONTACTS & 1u) && c.geom_class) { io.geom_class = c.geom_class; io.ngeom = c.ngeom; io.contacts = c.contacts; }
+    io.row_dim = probe_layout(c.nprobes, c.quantities, v.nv, io.off, nullptr);
     return io;
 }
 inline int episode_row_dim(const BatchView &v) { return v.nq + v.nv + v.nsd + v.nu + v.nv; }

@@ -92,6 +92,8 @@ enum { PHYS_F_QPOS, PHYS_F_QVEL, PHYS_F_QACC_WARMSTART, PHYS_F_TIME, PHYS_F_CTRL
        PHYS_F_RAYS,       /* [nrays]: the ranges of phys_batch_rays_cast (sized by phys_batch_rays_configure) */
        PHYS_F_STEP_SUMS,  /* [CM_SUM_DIM]: what a stepping launch added up over its substeps (layout: CM_SUM_* in cm_model.h; allocated by
                              phys_batch_step_sums_enable, or a caller's: phys_batch_bind) */
+       PHYS_F_PROBES,     /* [phys_batch_probe_row_dim]: the rows of phys_batch_probe (sized by phys_batch_probes_configure; layout:
+                             phys_batch_probe_layout) */
        PHYS_F_COUNT };
 
 /* mj_makeData (reference :441-447) for nenv environments on HIP device `device`;
@@ -353,7 +355,7 @@ int phys_batch_download_warn(phys_batch_t *b, int *host_warn, int *host_info /* 
 /* raw device pointer of a field (for torch / RCCL interop); bind replaces it with caller-owned HBM */
 void *phys_batch_device_ptr(phys_batch_t *b, int field);
 int phys_batch_bind(phys_batch_t *b, int field, void *device_ptr);
-/* same with a row stride in doubles (>= the field's dim) for PHYS_F_QPOS / QVEL / SENSORDATA / HEIGHT_SCAN / DEPTH / RAYS, so that they can be
+/* same with a row stride in doubles (>= the field's dim) for PHYS_F_QPOS / QVEL / SENSORDATA / HEIGHT_SCAN / DEPTH / RAYS / PROBES, so that they can be
  * column blocks of ONE caller-owned [nenv][nq + nv + nsensordata] observation tensor -- the buffer an RCCL all-gather
  * sends as is; uploads / downloads of a strided field are 2-D copies */
 int phys_batch_bind_strided(phys_batch_t *b, int field, void *device_ptr, int row_stride);
@@ -608,6 +610,69 @@ int phys_batch_download_ext_async(phys_batch_t *b, cm_ext_t *host, int env0, int
  * ids = {left foot body, right foot body, left heel site, right heel site, left toe site, right toe site}, -1 = absent.
  * The forces are those of the CURRENT state (like after cassie_sim_forward).  Costs about one physics step. */
 int phys_batch_derive(phys_batch_t *b, const int ids[6], void *stream);
+
+/* PROBES: the reference's reward-side getters for ANY body or site, for an env range, on the caller's stream.  A probe is a point fixed
+ * in the frame of a body (the body's xpos / xquat) or of a site (site_xpos / site_xmat of the read-out; its body is site_bodyid): with x, R
+ * the frame, the probe's point is p = x + R offset.  A configured list of up to PHYS_PROBES_MAX of them is evaluated by phys_batch_probe
+ * into one row of PHYS_F_PROBES per env; all values are in world axes, and each is the arithmetic of the single-simulator getter named:
+ *   PHYS_PQ_POS   3       p (offset 0: cassie_sim_xpos / cassie_sim_site_xpos)
+ *   PHYS_PQ_QUAT  4       body: the body's xquat; site: the quaternion of site_xmat by the routine and sign convention of cassie_sim_site_xquat
+ *   PHYS_PQ_VEL   6       [w; v_p]: w = cvel[body][0:3], v_p = cvel[body][3:6] + w x (p - subtree_com[body_rootid[body]]): the velocity of
+ *                         the point itself
+ *   PHYS_PQ_CVEL  6       cvel[body] as it is (cassie_sim_body_velocities)
+ *   PHYS_PQ_ACC   6       cassie_sim_body_acceleration of the probe's body: sum over the body's dofs of cdof_dot[k] qvel[k] + cdof[k] qacc[k],
+ *                         plus -gravity in the linear part, with the forward pass's qacc
+ *   PHYS_PQ_JACP, _JACR   3 x nv each, row-major [3][nv]: the Jacobians of the point p moving with the body (offset 0 on a body:
+ *                         cassie_sim_get_jacobian_full; on a site: cassie_sim_get_jacobian_full_site); zero for the world body
+ *   PHYS_PQ_CFRC  3       the summed contact force on the probe's body: cassie_sim_body_contact_force(...)[0:3] with its sign
+ * PHYS_PQ_CONTACTS adds one int32 word per ENV (not per probe, not in the row): bit 0 cassie_sim_check_obstacle_collision, bit 1
+ * cassie_sim_check_self_collision, bit 8 + g (g = 0 .. 5) cassie_sim_geom_collision(g).  These read geom_user[0] and geom_group of the
+ * host model's FULL geom list, which the compiled model a batch is created from does not carry: hand the host model over once with
+ * phys_batch_probe_geom_classes, before configuring with PHYS_PQ_CONTACTS (the table it builds lives in device memory; it outlives
+ * reconfigurations).
+ * ROW LAYOUT: quantity-major -- for every quantity of the mask, in bit order, a block [nprobes][doubles per probe], nothing between the
+ * blocks (a tensor view rows[:, off : off + nprobes * dim] reshapes to [n, nprobes, dim]); phys_batch_probe_layout reports the offsets.
+ *   phys_batch_probes_configure  probes [nprobes] (host memory), the quantities (an OR of PHYS_PQ_*, not empty).  Checks every kind, a body
+ *                               id in [0, nbody), a site id in [0, min(nsite, CM_MAXSITE)), finite offsets.  Allocates everything the
+ *                               feature ever needs: the table, the rows (PHYS_F_PROBES takes their size in a buffer of the batch's own:
+ *                               bind a tensor AFTER configuring; phys_batch_bind_strided takes a row stride for this field), the contact
+ *                               words, and a read-out block of the probes' OWN, sizeof(cm_ext_t) * nenv -- 34 104 bytes per env, 140 MB at
+ *                               4096 envs -- with the scratch outputs of the probes' forward pass ((2 nv + nsensordata + nu + 7 nbody) doubles
+ *                               per env).  Stepping launches never see that block: their kernels and rates are what they were, and a
+ *                               caller's phys_batch_enable_ext is neither needed nor disturbed.  Waits for the batch's streams.
+ *                               Reconfiguring is allowed (it drops the bindings of the rows and of the contact words); nprobes 0 releases
+ *                               everything.  -1 + phys_last_error() on failure.
+ *   phys_batch_probe            enqueues, on `stream` (NULL: the batch's own), one forward pass (nothing is integrated) over
+ *                               [env0, env0 + n) that writes the probes' read-out block and scratch outputs ONLY, and behind it
+ *                               cassie_probe_kernel over the same range.  No host synchronisation, no allocation.  Everything else a
+ *                               caller can read stays byte for byte: qpos, qvel, time, qacc, qacc_warmstart, sensordata,
+ *                               actuator_velocity, ctrl, xpos / xquat, body_cfrc, the solver statistics, the drive-level state, the
+ *                               episode words, the step sums -- but for the sticky warning bits a forward pass of the state raises anyway.
+ *                               Works in every drive mode: the forward pass applies the ctrl last applied and does not advance filter
+ *                               histories or delay lines.  Ranges on different streams may be probed concurrently: each touches its own
+ *                               rows.  An env whose state fails the step kernel's divergence test (NaN, or beyond 1e10) gets a row of
+ *                               NaN and a contact word of 0.
+ *   phys_batch_probe_row_dim    doubles in a row (0: not configured).
+ *   phys_batch_probe_layout     offsets [PHYS_PQ_COUNT] (-1: the quantity is absent) and dims [PHYS_PQ_COUNT] (doubles per probe), either
+ *                               may be NULL -> nprobes, -1 when not configured.
+ *   phys_batch_probe_contacts_ptr / _bind_contacts  the contact words, int32 [nenv] in device memory indexed by the absolute env: the
+ *                               batch's own (NULL unless configured with PHYS_PQ_CONTACTS), or a caller's (NULL: the batch's own again).
+ *   phys_batch_debug_probe_launches  diagnostics: the forward passes and the reductions phys_batch_probe has launched. */
+enum { PHYS_PROBE_BODY = 0, PHYS_PROBE_SITE = 1 };
+typedef struct phys_probe { int kind, id; double offset[3]; } phys_probe_t;   /* offset: in the body's / site's own frame */
+#define PHYS_PROBES_MAX 32
+enum { PHYS_PQ_POS = 1, PHYS_PQ_QUAT = 2, PHYS_PQ_VEL = 4, PHYS_PQ_CVEL = 8, PHYS_PQ_ACC = 16, PHYS_PQ_JACP = 32, PHYS_PQ_JACR = 64,
+       PHYS_PQ_CFRC = 128, PHYS_PQ_CONTACTS = 256, PHYS_PQ_COUNT = 8 /* the quantities of a row */ };
+enum { PHYS_PC_OBSTACLE = 1, PHYS_PC_SELF = 2, PHYS_PC_GROUP0 = 256 /* << g, g = 0 .. 5 */ };
+int phys_batch_probes_configure(phys_batch_t *b, const phys_probe_t *probes, int nprobes, unsigned quantities);  /* nprobes 0: release */
+int phys_batch_probe_geom_classes(phys_batch_t *b, const phys_model_t *host_model);   /* for PHYS_PQ_CONTACTS; NULL drops the table */
+int phys_batch_probe(phys_batch_t *b, int env0, int n, void *stream);
+int phys_batch_probe_row_dim(const phys_batch_t *b);
+int phys_batch_probe_layout(const phys_batch_t *b, int *offsets /*[PHYS_PQ_COUNT], -1 = absent*/, int *dims);
+void *phys_batch_probe_contacts_ptr(phys_batch_t *b);
+int phys_batch_probe_bind_contacts(phys_batch_t *b, void *device_ptr);     /* int32 [nenv], NULL unbinds */
+int phys_batch_probe_download_contacts(phys_batch_t *b, int *host);        /* the words [nenv] to the host, after waiting for the batch's streams */
+int phys_batch_debug_probe_launches(const phys_batch_t *b, long long *forward, long long *reduce);
 
 /* measurement aid: on = every substep of a fused launch evaluates every output (IMU sensors, body quaternions), although
  * only the last substep's values can be read; off (default) = those are formed by the substeps whose values are read */
