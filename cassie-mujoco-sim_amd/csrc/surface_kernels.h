@@ -1,9 +1,10 @@
 /*
  * surface_kernels.h -- what the kernels that look at an env's static geometry share, and the first of them: the world pose of a body
- * from qpos alone and of a static geom (static_body_pose, static_geom_pose), the surface under a world point (scan_surface), which model
- * and which geometry block an env reads (env_model, env_geometry), the heading of a quaternion (quat_heading), and the height scan
- * (cassie_scan_kernel).  Included by depth_kernel.h (the depth image) and episode_kernels.h (placed restarts); the step kernel's own
- * translation units (kernels_*.hip) do not need it.  The launch records, grids and checks are small_launch.h's.
+ * from qpos alone and of a static geom (static_body_pose, static_geom_pose), a ray against a box (ray_box), the surface under a world
+ * point (scan_surface), which model and which geometry block an env reads (env_model, env_geometry), the heading of a quaternion
+ * (quat_heading), and the height scan (cassie_scan_kernel).  Included by scene_rays.h (a ray against the scene's geoms: the depth
+ * images and the range sensors build on that) and episode_kernels.h (placed restarts); the step kernel's own translation units
+ * (kernels_*.hip) do not need it.  The launch records, grids and checks are small_launch.h's.
  */
 #ifndef CASSIE_SURFACE_KERNELS_H
 #define CASSIE_SURFACE_KERNELS_H
@@ -67,6 +68,29 @@ WV_DEVICE void static_geom_pose(ModelPtr m, ParamPtr PG, int g, double *gp, doub
     }
 }
 
+/* The slab test: the interval [t0, t1] over which the ray o + t d, given in a box's frame, lies within the box of half-sizes s0, s1, s2,
+ * and the axis whose slab it enters last -- the face of the entry t0 (the first of equals).  False where it misses the box, a ray
+ * parallel to a slab that lies outside it included.  The one slab test of the kernels that look at the scene: the height scan and the
+ * placed restart (scan_surface: the exit t1 of a vertical line), the depth images and the range sensors (scene_rays.h: the entry, and
+ * the face for the normal) */
+WV_DEVICE bool ray_box(const double *o, const double *d, double s0, double s1, double s2, double *t0_out, double *t1_out, int *axis_out) {
+    const double size[3] = {s0, s1, s2};
+    double t0 = -1e300, t1 = 1e300;
+    int axis = 0;
+    bool inside = true;
+    for (int k = 0; k < 3; ++k) {
+        const double s = size[k];
+        if (d[k] != 0.0) {
+            const double ta = (-s - o[k]) / d[k], tb = (s - o[k]) / d[k];
+            const double lo = ta < tb ? ta : tb, hi = ta < tb ? tb : ta;
+            if (lo > t0) { t0 = lo; axis = k; }
+            t1 = hi < t1 ? hi : t1;
+        } else if (fabs(o[k]) > s) inside = false;
+    }
+    *t0_out = t0; *t1_out = t1; *axis_out = axis;
+    return inside && t0 <= t1;
+}
+
 /* The surface S(X, Y) of the height scan and of the placed restart: the highest point at which the vertical line through the world point
  * (X, Y) meets a static collision geom of the env -- planes, boxes, the height field on `grid` (null: no samples, a miss), as the
  * comment of cassie_scan_kernel below lists them.  Returns whether it meets any, the height in *top; a tilted height-field geom is
@@ -88,17 +112,9 @@ WV_DEVICE bool scan_surface(ModelPtr m, ParamPtr PG, const float *grid, double X
         } else if (gt == CM_GEOM_BOX) {
             /* the line (X, Y, t) in the box's frame: origin R^T ((X, Y, 0) - pos), direction R^T e_z = the third row of R */
             const double o[3] = {R[0] * dx + R[3] * dy - R[6] * gp[2], R[1] * dx + R[4] * dy - R[7] * gp[2], R[2] * dx + R[5] * dy - R[8] * gp[2]};
-            double t0 = -1e300, t1 = 1e300;
-            bool inside = true;
-            for (int k = 0; k < 3; ++k) {
-                const double d = R[6 + k], s = m->geom_size[g][k];
-                if (d != 0.0) {
-                    const double ta = (-s - o[k]) / d, tb = (s - o[k]) / d;
-                    const double lo = ta < tb ? ta : tb, hi = ta < tb ? tb : ta;
-                    t0 = lo > t0 ? lo : t0; t1 = hi < t1 ? hi : t1;
-                } else if (fabs(o[k]) > s) inside = false;
-            }
-            if (inside && t0 <= t1) { has = true; z = t1; }
+            double t0, t1;
+            int axis;
+            if (ray_box(o, R + 6, m->geom_size[g][0], m->geom_size[g][1], m->geom_size[g][2], &t0, &t1, &axis)) { has = true; z = t1; }
         } else {
             const bool upright = fabs(R[2]) <= 1e-12 && fabs(R[5]) <= 1e-12 && R[8] > 0.0;
             if (!upright) warn |= WARN_SCAN_TILTED;

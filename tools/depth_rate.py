@@ -10,8 +10,10 @@ schedule (tools/terrain_rate.py's `bank` leg) -- in four settings in one session
                          and capsules drawn where the step launch in front of it left the bodies.
   depth_128x128          the default geoms, 128 x 128.
 
---parent-lib PATH runs the depth_64x48 leg once more in a child process against another build of the library (the parent commit's):
-the static kernel must not have become slower, and the yardstick for that is the parent in the same session, not a file.
+--parent-lib PATH runs the depth_64x48 and depth_64x48_all_geoms legs once more, each in a child process, against another build of the
+library (the parent commit's): neither kernel must have become slower, and the yardstick for that is the parent in the same session,
+not a file -- this build's median within the parent's ten regions, and its launch alone (the median of ten runs) within the parent's
+ten runs.
 
 The camera is the reference's `egocentric` one in spirit: on the pelvis, pitched 45 degrees down, fovy 65.5, near 0.01, far 5.  Also
 times the depth launch alone over the whole batch on an idle device, for every leg, and records both kernels' registers, scratch and
@@ -48,6 +50,8 @@ from terrain_rate import NTERRAIN, terrain  # noqa: E402
 NSUB = bench.HOLD
 SETTINGS = {"no_depth": None, "depth_64x48": (64, 48), "depth_64x48_all_geoms": (64, 48), "depth_128x128": (128, 128)}
 ALL_GEOMS = {"depth_64x48_all_geoms"}
+PARENT_LEGS = ("depth_64x48", "depth_64x48_all_geoms")     # what --parent-lib runs once more
+ALONE_RUNS = 10
 KERNELS = ("cassie_depth_kernel", "cassie_depth_scene_kernel")
 CAM_POS, FOVY, NEAR, FAR, PITCH = (0.1, 0.0, 0.25), 65.5, 0.01, 5.0, 45.0
 
@@ -139,19 +143,23 @@ def regions(model, n, size, launches, warmup, repeats, all_geoms=False):
         info = {"env_steps_per_s_median": float(np.median(out)), "env_steps_per_s_min": float(min(out)), "env_steps_per_s_max": float(max(out)),
                 "regions": out, "envs_with_warnings": int(b.warnings()[0].astype(bool).sum())}
         if size:
-            # the depth launch alone, over the whole batch on an idle device: HIP events round 20 launches
+            # the depth launch alone, over the whole batch on an idle device: HIP events round 20 launches, ten times (the median counts)
             ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             st = streams[0]
             b.depth_image(0, n, stream=st.cuda_stream)
             torch.cuda.synchronize()
-            with torch.cuda.stream(st):
-                ev0.record()
-                for _ in range(20):
-                    b.depth_image(0, n, stream=st.cuda_stream)
-                ev1.record()
-            torch.cuda.synchronize()
-            us = 1000.0 * ev0.elapsed_time(ev1) / 20
+            runs = []
+            for _ in range(ALONE_RUNS):
+                with torch.cuda.stream(st):
+                    ev0.record()
+                    for _ in range(20):
+                        b.depth_image(0, n, stream=st.cuda_stream)
+                    ev1.record()
+                torch.cuda.synchronize()
+                runs.append(1000.0 * ev0.elapsed_time(ev1) / 20)
+            us = float(np.median(runs))
             info["depth_launch_alone_us"] = us
+            info["depth_launch_alone_us_runs"] = runs
             info["rays_per_s_alone"] = n * size[0] * size[1] / (us * 1e-6)
             v = b.get(P.F_DEPTH)
             info["image"] = [size[0], size[1]]
@@ -175,7 +183,7 @@ def main():
     ap.add_argument("--only", choices=list(SETTINGS), default=None, help="one setting only (e.g. under a kernel trace)")
     ap.add_argument("--out", default=None, help="also write the JSON line to this file")
     ap.add_argument("--resources-only", action="store_true", help="the kernels' resources alone: no leg is run (needs hipcc, no GPU)")
-    ap.add_argument("--parent-lib", default=None, help="another build of the library (the parent commit's): its depth_64x48 leg, in a child process")
+    ap.add_argument("--parent-lib", default=None, help="another build of the library (the parent commit's): its two 64 x 48 legs, each in a child process")
     a = ap.parse_args()
     model = None if a.resources_only else Model("cassie_hfield")
     out = {"tool": "depth_rate", "model": "cassie_hfield", "envs": a.envs, "substeps_per_launch": NSUB, "launches_per_region": a.launches,
@@ -185,13 +193,14 @@ def main():
            "camera": {"body": "pelvis", "pos": list(CAM_POS), "pitch_down_deg": PITCH, "fovy_deg": FOVY, "near": NEAR, "far": FAR},
            "yardstick": "no_depth", "kernels": list(KERNELS), "kernel_resources": kernel_resources()}
     if a.parent_lib and not a.resources_only:
-        # (first, in a process of its own: one library per process; this process has not touched the GPU yet)
-        cmd = [sys.executable, os.path.abspath(__file__), "--only", "depth_64x48", "--envs", str(a.envs), "--launches", str(a.launches),
-               "--warmup", str(a.warmup), "--repeats", str(a.repeats)]
-        r = subprocess.run(cmd, env=dict(os.environ, CASSIE_LIB=os.path.abspath(a.parent_lib)), capture_output=True, text=True, timeout=900)
-        if r.returncode != 0:
-            sys.exit("the --parent-lib leg failed:\n" + r.stderr[-2000:])
-        out["parent_depth_64x48"] = json.loads(r.stdout.strip().splitlines()[-1])["depth_64x48"]
+        # (first, each in a process of its own: one library per process; this process has not touched the GPU yet)
+        for leg in PARENT_LEGS:
+            cmd = [sys.executable, os.path.abspath(__file__), "--only", leg, "--envs", str(a.envs), "--launches", str(a.launches),
+                   "--warmup", str(a.warmup), "--repeats", str(a.repeats)]
+            r = subprocess.run(cmd, env=dict(os.environ, CASSIE_LIB=os.path.abspath(a.parent_lib)), capture_output=True, text=True, timeout=900)
+            if r.returncode != 0:
+                sys.exit("the --parent-lib leg %s failed:\n" % leg + r.stderr[-2000:])
+            out["parent_" + leg] = json.loads(r.stdout.strip().splitlines()[-1])[leg]
     for name, size in SETTINGS.items():
         if a.only in (None, name) and not a.resources_only:
             out[name] = regions(model, a.envs, size, a.launches, a.warmup, a.repeats, all_geoms=name in ALL_GEOMS)
@@ -200,10 +209,15 @@ def main():
         for name in SETTINGS:
             if name != "no_depth" and name in out:
                 out[name]["cost_of_the_loop_percent"] = 100.0 * (1.0 - out[name]["env_steps_per_s_median"] / base)
-    if "parent_depth_64x48" in out and "depth_64x48" in out:
-        par, med = out["parent_depth_64x48"], out["depth_64x48"]["env_steps_per_s_median"]
-        out["static_leg_median_within_the_parents_regions"] = bool(par["env_steps_per_s_min"] <= med <= par["env_steps_per_s_max"])
-        out["static_leg_median_over_parent_median"] = med / par["env_steps_per_s_median"]
+    for leg, key in zip(PARENT_LEGS, ("static_leg", "all_geoms_leg")):
+        if "parent_" + leg in out and leg in out:
+            par, this = out["parent_" + leg], out[leg]
+            med = this["env_steps_per_s_median"]
+            out[key + "_median_within_the_parents_regions"] = bool(par["env_steps_per_s_min"] <= med <= par["env_steps_per_s_max"])
+            out[key + "_median_over_parent_median"] = med / par["env_steps_per_s_median"]
+            runs, us = par["depth_launch_alone_us_runs"], this["depth_launch_alone_us"]
+            out[key + "_launch_alone_median_within_the_parents_runs"] = bool(min(runs) <= us <= max(runs))
+            out[key + "_launch_alone_median_over_parent_median"] = us / par["depth_launch_alone_us"]
     line = json.dumps(out)
     print(line)
     if a.out:

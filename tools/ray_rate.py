@@ -8,9 +8,10 @@ schedule (tools/depth_rate.py's loop) -- in two settings in one session, fenced 
               two feet (16 along each toe) and a fan of 32 rays ahead of the pelvis in its heading frame, every geom in the mask, hit
               ids and normals bound.
 
---parent-lib PATH runs the no_rays leg once more in a child process against another build of the library (the parent commit's): a
-batch that never configures rays must run as before, and the yardstick for that is the parent in the same session, not a file -- the
-median of this build's no_rays regions must lie within the spread of the parent's regions.
+--parent-lib PATH runs both legs once more, each in a child process, against another build of the library (the parent commit's): a
+batch that never configures rays must run as before and the cast must not have become slower, and the yardstick for that is the parent
+in the same session, not a file -- the median of this build's regions must lie within the spread of the parent's regions, leg by leg,
+and the cast alone (the median of ten runs) within the parent's ten runs.
 
 Also times the cast alone over the whole batch on an idle device and records the kernel's registers, scratch and LDS as the compiler
 reports them (hipcc -Rpass-analysis=kernel-resource-usage on csrc/ray_kernel.h; null where hipcc is absent).  Prints one JSON line;
@@ -48,6 +49,7 @@ NSUB = bench.HOLD
 SETTINGS = ("no_rays", "rays_64")
 KERNEL = "cassie_rays_kernel"
 RMIN, RMAX = 0.01, 5.0
+ALONE_RUNS = 10
 
 
 def ray_table(pod):
@@ -145,20 +147,23 @@ def regions(model, n, rays, launches, warmup, repeats):
         info = {"env_steps_per_s_median": float(np.median(out)), "env_steps_per_s_min": float(min(out)), "env_steps_per_s_max": float(max(out)),
                 "regions": out, "envs_with_warnings": int(b.warnings()[0].astype(bool).sum())}
         if rays:
-            # the cast alone, over the whole batch on an idle device: HIP events round 20 launches
+            # the cast alone, over the whole batch on an idle device: HIP events round 20 launches, ten times (the median counts)
             ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             st = streams[0]
             b.cast_rays(0, n, stream=st.cuda_stream)
             torch.cuda.synchronize()
-            with torch.cuda.stream(st):
-                ev0.record()
-                for _ in range(20):
-                    b.cast_rays(0, n, stream=st.cuda_stream)
-                ev1.record()
-            torch.cuda.synchronize()
-            us = 1000.0 * ev0.elapsed_time(ev1) / 20
+            runs = []
+            for _ in range(ALONE_RUNS):
+                with torch.cuda.stream(st):
+                    ev0.record()
+                    for _ in range(20):
+                        b.cast_rays(0, n, stream=st.cuda_stream)
+                    ev1.record()
+                torch.cuda.synchronize()
+                runs.append(1000.0 * ev0.elapsed_time(ev1) / 20)
+            us = float(np.median(runs))
             v, hit = b.get(P.F_RAYS), ids.cpu().numpy()
-            info.update({"cast_alone_us": us, "rays_per_s_alone": n * len(table) / (us * 1e-6), "rays_per_env": len(table),
+            info.update({"cast_alone_us": us, "cast_alone_us_runs": runs, "rays_per_s_alone": n * len(table) / (us * 1e-6), "rays_per_env": len(table),
                          "value_range": [float(v.min()), float(v.max())], "fraction_of_rays_that_hit": float((hit >= 0).mean()),
                          "fraction_on_the_height_field": float((hit == pod.hfield_geom).mean()), "ray_launches": b.ray_launches()})
         return info
@@ -175,7 +180,7 @@ def main():
     ap.add_argument("--only", choices=list(SETTINGS), default=None, help="one setting only (e.g. under a kernel trace)")
     ap.add_argument("--out", default=None, help="also write the JSON line to this file")
     ap.add_argument("--resources-only", action="store_true", help="the kernel's resources alone: no leg is run (needs hipcc, no GPU)")
-    ap.add_argument("--parent-lib", default=None, help="another build of the library (the parent commit's): its no_rays leg, in a child process")
+    ap.add_argument("--parent-lib", default=None, help="another build of the library (the parent commit's): both legs, each in a child process")
     a = ap.parse_args()
     model = None if a.resources_only else Model("cassie_hfield")
     out = {"tool": "ray_rate", "model": "cassie_hfield", "envs": a.envs, "substeps_per_launch": NSUB, "launches_per_region": a.launches,
@@ -185,22 +190,28 @@ def main():
            "rays": {"foot_probes": 32, "forward_fan": 32, "rmin": RMIN, "rmax": RMAX, "mask": "every geom", "ids": True, "normals": True},
            "yardstick": "no_rays", "kernel": KERNEL, "kernel_resources": kernel_resources()}
     if a.parent_lib and not a.resources_only:
-        # (first, in a process of its own: one library per process; this process has not touched the GPU yet)
-        cmd = [sys.executable, os.path.abspath(__file__), "--only", "no_rays", "--envs", str(a.envs), "--launches", str(a.launches),
-               "--warmup", str(a.warmup), "--repeats", str(a.repeats)]
-        r = subprocess.run(cmd, env=dict(os.environ, CASSIE_LIB=os.path.abspath(a.parent_lib)), capture_output=True, text=True, timeout=900)
-        if r.returncode != 0:
-            sys.exit("the --parent-lib leg failed:\n" + r.stderr[-2000:])
-        out["parent_no_rays"] = json.loads(r.stdout.strip().splitlines()[-1])["no_rays"]
+        # (first, each in a process of its own: one library per process; this process has not touched the GPU yet)
+        for leg in SETTINGS:
+            cmd = [sys.executable, os.path.abspath(__file__), "--only", leg, "--envs", str(a.envs), "--launches", str(a.launches),
+                   "--warmup", str(a.warmup), "--repeats", str(a.repeats)]
+            r = subprocess.run(cmd, env=dict(os.environ, CASSIE_LIB=os.path.abspath(a.parent_lib)), capture_output=True, text=True, timeout=900)
+            if r.returncode != 0:
+                sys.exit("the --parent-lib leg %s failed:\n" % leg + r.stderr[-2000:])
+            out["parent_" + leg] = json.loads(r.stdout.strip().splitlines()[-1])[leg]
     for name in SETTINGS:
         if a.only in (None, name) and not a.resources_only:
             out[name] = regions(model, a.envs, name != "no_rays", a.launches, a.warmup, a.repeats)
     if "no_rays" in out and "rays_64" in out:
         out["rays_64"]["cost_of_the_loop_percent"] = 100.0 * (1.0 - out["rays_64"]["env_steps_per_s_median"] / out["no_rays"]["env_steps_per_s_median"])
-    if "parent_no_rays" in out and "no_rays" in out:
-        par, med = out["parent_no_rays"], out["no_rays"]["env_steps_per_s_median"]
-        out["unused_path_median_within_the_parents_regions"] = bool(par["env_steps_per_s_min"] <= med <= par["env_steps_per_s_max"])
-        out["unused_path_median_over_parent_median"] = med / par["env_steps_per_s_median"]
+    for leg, key in zip(SETTINGS, ("unused_path", "rays_64")):
+        if "parent_" + leg in out and leg in out:
+            par, med = out["parent_" + leg], out[leg]["env_steps_per_s_median"]
+            out[key + "_median_within_the_parents_regions"] = bool(par["env_steps_per_s_min"] <= med <= par["env_steps_per_s_max"])
+            out[key + "_median_over_parent_median"] = med / par["env_steps_per_s_median"]
+    if "parent_rays_64" in out and "rays_64" in out:
+        runs, us = out["parent_rays_64"]["cast_alone_us_runs"], out["rays_64"]["cast_alone_us"]
+        out["cast_alone_median_within_the_parents_runs"] = bool(min(runs) <= us <= max(runs))
+        out["cast_alone_median_over_parent_median"] = us / out["parent_rays_64"]["cast_alone_us"]
     line = json.dumps(out)
     print(line)
     if a.out:
