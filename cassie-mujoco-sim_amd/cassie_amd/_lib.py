@@ -198,6 +198,17 @@ def _declare(L):
         L.phys_batch_probe_bind_contacts.argtypes = [vp, vp]
         L.phys_batch_probe_download_contacts.argtypes = [vp, vp]
         L.phys_batch_debug_probe_launches.argtypes = [vp, c.POINTER(c.c_longlong), c.POINTER(c.c_longlong)]
+    if hasattr(L, "phys_batch_obs"):   # (likewise)
+        L.phys_batch_obs_configure.argtypes = [vp, vp, c.c_int, c.c_int, c.c_int, c.c_ulonglong, c.c_uint]
+        L.phys_batch_obs_bind.argtypes = [vp, vp, c.c_longlong]
+        L.phys_batch_obs_bind_input.argtypes = [vp, vp, c.c_int, c.c_longlong, c.c_int]
+        L.phys_batch_obs.argtypes = [vp, c.c_int, c.c_int, vp, vp]
+        L.phys_batch_obs_dim.argtypes = [vp, c.POINTER(c.c_int), c.POINTER(c.c_int), c.POINTER(c.c_int)]
+        L.phys_batch_obs_layout.argtypes = [vp, vp]
+        L.phys_batch_obs_download.argtypes = [vp, vp, c.c_int, c.c_int]
+        L.phys_batch_obs_frames.argtypes = [vp, vp]
+        L.phys_batch_obs_set_frames.argtypes = [vp, vp]
+        L.phys_batch_debug_obs_launches.argtypes = [vp, c.POINTER(c.c_longlong)]
     if hasattr(L, "phys_batch_step_sums_enable"):   # (likewise)
         L.phys_batch_step_sums_enable.argtypes = [vp, c.c_int]
     if hasattr(L, "phys_batch_download_progress"):   # (absent from older variant builds selected with CASSIE_LIB)

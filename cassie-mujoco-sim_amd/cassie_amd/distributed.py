@@ -99,6 +99,7 @@ class OverlappedGather:
     (so the copy is ordered behind the launch that wrote them and ahead of the next), a second stream waits for that copy and
     runs the collective, and range i's NEXT snapshot waits for the collective to have read the previous one.  Nothing here
     blocks the host; `result[i]` ([world * count_i, nobs], rank-major) is valid once `done[i]` has completed.
+    `obs` is any [n, nobs] tensor the range's stream writes: an ObservationBlock's, or the rows Batch.bind_obs put Batch.observe's output in.
     `runtime` supplies Stream() / Event() / use(stream) (torch.cuda on a GPU; a stand-in in the CPU tests)."""
 
     def __init__(self, obs, ranges, streams, world, runtime, collective=gather_observations):

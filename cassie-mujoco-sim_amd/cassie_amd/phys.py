@@ -62,6 +62,46 @@ PQ_POS, PQ_QUAT, PQ_VEL, PQ_CVEL, PQ_ACC, PQ_JACP, PQ_JACR, PQ_CFRC, PQ_CONTACTS
 PQ_ALL = PQ_CONTACTS * 2 - 1
 PQ_ROW = (("pos", (3,)), ("quat", (4,)), ("vel", (6,)), ("cvel", (6,)), ("acc", (6,)), ("jacp", (3, "nv")), ("jacr", (3, "nv")), ("cfrc", (3,)))
 PC_OBSTACLE, PC_SELF, PC_GROUP0 = 1, 2, 256
+# observation rows: the kinds of a term (PHYS_OBS_* in cassie_phys.h), the two sources that are no field of the batch, the layout of
+# phys_obs_term_t and the limits
+OBS_COPY, OBS_ROT_INV = range(2)
+OBS_INPUT, OBS_CONST = -1, -2
+OBS_MAXCOLS, OBS_MAXHISTORY, OBS_MAXROW = 2048, 64, 65536
+OBS_TERM_DTYPE = np.dtype([("kind", np.int32), ("field", np.int32), ("index", np.int32), ("count", np.int32), ("qfield", np.int32),
+                           ("qindex", np.int32), ("vec", np.float64, 3), ("offset", np.float64), ("scale", np.float64), ("noise", np.float64),
+                           ("lo", np.float64), ("hi", np.float64)])
+
+
+def obs_copy(field, index, count, offset=0.0, scale=1.0, noise=0.0, lo=-np.inf, hi=np.inf):
+    """An OBS_TERM_DTYPE entry: count columns, field_row[index + j]."""
+    return (OBS_COPY, int(field), int(index), int(count), 0, 0, (0.0, 0.0, 0.0), offset, scale, noise, lo, hi)
+
+
+def obs_rot_inv(field, index, qfield, qindex, vec=(0.0, 0.0, 0.0), offset=0.0, scale=1.0, noise=0.0, lo=-np.inf, hi=np.inf):
+    """An OBS_TERM_DTYPE entry: 3 columns, R(q)^T v with q = qfield_row[qindex : qindex + 4] and v = field_row[index : index + 3], or
+    `vec` where field is OBS_CONST."""
+    return (OBS_ROT_INV, int(field), int(index), 3, int(qfield), int(qindex), tuple(float(x) for x in vec), offset, scale, noise, lo, hi)
+
+
+def obs_terms(terms):
+    """A list of term tuples (obs_copy / obs_rot_inv) or a structured array -> OBS_TERM_DTYPE entries."""
+    if isinstance(terms, np.ndarray) and terms.dtype.names:
+        return np.ascontiguousarray(terms.astype(OBS_TERM_DTYPE, copy=False)).reshape(-1)
+    terms = list(terms)
+    table = np.zeros(len(terms), dtype=OBS_TERM_DTYPE)
+    for k, t in enumerate(terms):
+        table[k] = tuple(t[:6]) + (np.asarray(t[6], dtype=np.float64),) + tuple(t[7:])
+    return table
+
+
+def _obs_dtype(dtype):
+    """numpy / torch float32 or float64 -> the bytes of an element (PHYS_OBS_F32 / PHYS_OBS_F64); anything else -> 0 (refused by the library)."""
+    name = str(dtype).replace("torch.", "")
+    try:
+        name = np.dtype(dtype).name
+    except TypeError:
+        pass
+    return {"float32": 4, "float64": 8}.get(name, 0)
 
 # per-env physical parameters (CM_P_* in cm_model.h): what Batch.randomize takes
 (P_BODY_MASS, P_BODY_IPOS, P_BODY_INERTIA, P_DOF_DAMPING, P_GEOM_FRICTION,
@@ -551,6 +591,86 @@ class Batch:
         a, c_ = ctypes.c_longlong(0), ctypes.c_longlong(0)
         lib().phys_batch_debug_probe_launches(self._h, ctypes.byref(a), ctypes.byref(c_))
         return a.value, c_.value
+
+    # ---- observation rows: gather, offset, noise, scale, clip, cast and history in one launch (phys_batch_obs) ----
+    def _obs_fail(self, what):
+        raise (ValueError if what.startswith("configure") or what.startswith("bind") else RuntimeError)(
+            what + " failed: " + (lib().phys_last_error() or b"").decode())
+
+    def configure_obs(self, terms, history=1, dtype=np.float32, seed=0, env_base=0):
+        """The terms of a frame: a list of obs_copy(...) / obs_rot_inv(...) tuples or a structured array of OBS_TERM_DTYPE (none:
+        release).  history: the frames of an env's row, newest first; dtype: float32 or float64 rows; seed: the noise's key; env_base:
+        what is added to the env index in the noise's counter (a rank that holds envs [k n, (k + 1) n) of a larger run passes k n).
+        Allocates the rows and the frame counts, zeroed; drops the bindings of the rows and of the input."""
+        table = obs_terms(terms)
+        assert OBS_TERM_DTYPE.itemsize == 88
+        if lib().phys_batch_obs_configure(self._h, table.ctypes.data if table.size else None, int(table.size), int(history), _obs_dtype(dtype),
+                                          int(seed) & 0xFFFFFFFFFFFFFFFF, int(env_base) & 0xFFFFFFFF) != 0:
+            self._obs_fail("configure_obs")
+        self._obs_np = np.float64 if _obs_dtype(dtype) == 8 else np.float32
+
+    def bind_obs(self, device_ptr, row_stride=None):
+        """The rows in caller-owned HBM of the configured dtype, `row_stride` elements (default: the row's) between two envs' rows; None:
+        the batch's own again."""
+        if lib().phys_batch_obs_bind(self._h, device_ptr, int(row_stride if row_stride is not None else self.obs_dim()[2]) if device_ptr else 0) != 0:
+            self._obs_fail("bind_obs")
+
+    def bind_obs_input(self, device_ptr, dim=0, row_stride=None, dtype=np.float32):
+        """The caller's per-env array the OBS_INPUT terms read: [nenv] rows of `dim` float32 / float64 elements, `row_stride` elements
+        apart (default: dim).  None un-binds."""
+        if lib().phys_batch_obs_bind_input(self._h, device_ptr, int(dim), int(dim if row_stride is None else row_stride), _obs_dtype(dtype)) != 0:
+            self._obs_fail("bind_obs_input")
+
+    def observe(self, env0=0, n=None, refill_ptr=None, stream=None):
+        """One launch on `stream` (default: the batch's own), in order with the step launches there: the new frame of every env of
+        [env0, env0 + n) and the shift of its history.  refill_ptr: an int32 device array [n] (the range's slice of EP_DONE), non-zero =
+        the env's whole history becomes the new frame.  No host synchronisation."""
+        n = self.nenv - env0 if n is None else n
+        if lib().phys_batch_obs(self._h, int(env0), int(n), refill_ptr, stream) != 0:
+            self._obs_fail("observe")
+
+    def obs_dim(self):
+        """(ncols, history, elements of a row)."""
+        a, h, r = ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int(0)
+        if lib().phys_batch_obs_dim(self._h, ctypes.byref(a), ctypes.byref(h), ctypes.byref(r)) != 0:
+            self._obs_fail("obs_dim")
+        return a.value, h.value, r.value
+
+    def obs_layout(self):
+        """The first column of every term, in the terms' order."""
+        n = lib().phys_batch_obs_layout(self._h, None)
+        if n < 0:
+            self._obs_fail("obs_layout")
+        first = np.zeros(n, dtype=np.int32)
+        lib().phys_batch_obs_layout(self._h, first.ctypes.data)
+        return [int(v) for v in first]
+
+    def obs(self, env0=0, n=None):
+        """The rows [env0, env0 + n) downloaded: [n][history][ncols] in the configured dtype."""
+        n = self.nenv - env0 if n is None else n
+        ncols, history, _ = self.obs_dim()
+        out = np.empty((n, history, ncols), dtype=self._obs_np)
+        if lib().phys_batch_obs_download(self._h, out.ctypes.data, int(env0), int(n)) != 0:
+            self._obs_fail("obs")
+        return out
+
+    def obs_frames(self):
+        """The calls every env's row has seen (uint32 [nenv]): the third word of the noise's counter."""
+        out = np.empty(self.nenv, dtype=np.uint32)
+        if lib().phys_batch_obs_frames(self._h, out.ctypes.data) != 0:
+            self._obs_fail("obs_frames")
+        return out
+
+    def set_obs_frames(self, frames):
+        a = np.ascontiguousarray(frames, dtype=np.uint32).reshape(self.nenv)
+        if lib().phys_batch_obs_set_frames(self._h, a.ctypes.data) != 0:
+            self._obs_fail("set_obs_frames")
+
+    def obs_launches(self):
+        """Diagnostics: the launches observe() has made so far."""
+        a = ctypes.c_longlong(0)
+        lib().phys_batch_debug_obs_launches(self._h, ctypes.byref(a))
+        return a.value
 
     def set_pd_mode(self, on=True):
         lib().phys_batch_set_pd_mode(self._h, 1 if on else 0)

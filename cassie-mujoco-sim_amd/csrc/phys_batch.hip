@@ -137,6 +137,16 @@ struct phys_batch {
     DevBuf<double> d_probe_scratch;  /* [nenv] rows of qacc | sensordata | actuator_velocity | xpos | xquat, one array after the other */
     DevBuf<int> d_probe_contacts;
     long long probe_launches[2] = {0, 0}; /* forward passes / reductions of phys_batch_probe (phys_batch_debug_probe_launches) */
+    /* observation rows (phys_batch_obs_configure): the record (obs.nterms 0: not configured; its pointers are filled in at the launch, from
+     * the buffers), every term's first column, the column table, the rows (the batch's own or a caller's, floats or doubles) with their
+     * stride in elements, the per-env frame counts and the caller's input array.  No stepping launch reads any of it */
+    ck::ObsCfg obs = {};
+    std::vector<int> obs_term_col;
+    DevBuf<ck::ObsCol> d_obs_cols;
+    DevBuf<char> d_obs_rows;
+    long long obs_srow = 0;
+    DevBuf<unsigned> d_obs_frames;
+    long long obs_launches = 0;     /* launches of cassie_obs_kernel (phys_batch_debug_obs_launches) */
 };
 
 static bool hip_ok(hipError_t e, const char *what) {
@@ -1464,6 +1474,123 @@ int phys_batch_probe(phys_batch_t *b, int env0, int n, void *stream) {
                        ck::make_probe_io(view_of(b), c, b->d_field[PHYS_F_PROBES], b->stride[PHYS_F_PROBES], env0, n));
     if (!hip_ok(hipGetLastError(), "cassie_probe_kernel launch")) return -1;
     ++b->probe_launches[1];
+    return 0;
+}
+
+/* ------------------------------------------------ observation rows ---- */
+static_assert(sizeof(ck::ObsTerm) == sizeof(phys_obs_term_t) && offsetof(ck::ObsTerm, qindex) == offsetof(phys_obs_term_t, qindex) &&
+              offsetof(ck::ObsTerm, vec) == offsetof(phys_obs_term_t, vec) && offsetof(ck::ObsTerm, hi) == offsetof(phys_obs_term_t, hi),
+              "phys_obs_term_t is the term obs_configure reads");
+static_assert(PHYS_OBS_COPY == ck::OBS_COPY && PHYS_OBS_ROT_INV == ck::OBS_ROT_INV && PHYS_OBS_INPUT == ck::OBS_INPUT && PHYS_OBS_CONST == ck::OBS_CONST &&
+              PHYS_OBS_F32 == ck::OBS_F32 && PHYS_OBS_F64 == ck::OBS_F64 && PHYS_OBS_MAXCOLS == ck::OBS_MAXCOLS, "the header's numbers are obs_kernels.h's");
+/* what the batch holds of every field now: where a launch would read it */
+static void obs_fields_of(const phys_batch *b, ck::ObsField *f) {
+    for (int k = 0; k < PHYS_F_COUNT; ++k) f[k] = {b->d_field[k].get(), b->d_field[k] ? b->dim[k] : 0, b->stride[k]};
+}
+/* the record of a launch: what was configured, with the pointers into the batch's buffers */
+static ck::ObsCfg obs_cfg_of(const phys_batch *b) {
+    ck::ObsCfg c = b->obs;
+    c.cols = b->d_obs_cols; c.rows = b->d_obs_rows.get(); c.srow = b->obs_srow; c.frames = b->d_obs_frames;
+    return c;
+}
+int phys_batch_obs_configure(phys_batch_t *b, const phys_obs_term_t *terms, int nterms, int history, int dtype, unsigned long long seed, unsigned env_base) {
+    if (!b) return refuse("phys_batch_obs_configure", ck::OBS_SIZE_REFUSAL);
+    int dims[PHYS_F_COUNT];
+    for (int k = 0; k < PHYS_F_COUNT; ++k) dims[k] = b->d_field[k] ? b->dim[k] : 0;
+    std::vector<ck::ObsCol> table((size_t)ck::OBS_MAXCOLS);
+    std::vector<int> term_col((size_t)(nterms > 0 ? nterms : 0));
+    ck::ObsCfg cfg;
+    if (const char *why = ck::obs_configure(dims, PHYS_F_COUNT, PHYS_F_DEPTH, (const ck::ObsTerm *)terms, nterms, history, dtype, seed, env_base,
+                                            table.data(), term_col.data(), cfg)) return refuse("phys_batch_obs_configure", why);
+    (void)hipSetDevice(b->device);
+    if (!quiesce(b)) return -1;  /* (launches in flight may be reading the table, or writing the rows, that go away) */
+    if (nterms == 0) {
+        b->obs = {}; b->obs_term_col.clear(); b->obs_srow = 0;
+        b->d_obs_cols.reset(); b->d_obs_rows.reset(); b->d_obs_frames.reset();
+        return 0;
+    }
+    const size_t n = (size_t)b->nenv, row = (size_t)cfg.ncols * (size_t)cfg.history;
+    DevBuf<ck::ObsCol> cols;
+    DevBuf<char> rows;
+    DevBuf<unsigned> frames;
+    if (!cols.alloc((size_t)cfg.ncols, false, "observation columns")) return -1;
+    if (!hip_ok(hipMemcpy(cols, table.data(), sizeof(ck::ObsCol) * (size_t)cfg.ncols, hipMemcpyHostToDevice), "hipMemcpy(observation columns)")) return -1;
+    if (!rows.alloc(n * row * (size_t)dtype, true, "observation rows")) return -1;
+    if (!frames.alloc(n, true, "observation frame counts")) return -1;
+    b->d_obs_cols = std::move(cols); b->d_obs_rows = std::move(rows); b->d_obs_frames = std::move(frames);
+    b->obs_srow = (long long)row;
+    b->obs_term_col = std::move(term_col);
+    b->obs = cfg;   /* (no input bound, and the rows are the batch's own: the bindings are dropped) */
+    return 0;
+}
+int phys_batch_obs_bind(phys_batch_t *b, void *device_ptr, long long row_stride) {
+    if (!b) { phys_set_last_error("phys_batch_obs_bind: no batch"); return -1; }
+    const long long row = (long long)b->obs.ncols * b->obs.history;
+    if (const char *why = ck::check_obs_bind(b->obs, device_ptr ? row_stride : row)) return refuse("phys_batch_obs_bind", why);
+    (void)hipSetDevice(b->device);
+    /* (as phys_batch_bind: launches already queued keep the pointer they were given; hipFree waits for the device by itself) */
+    if (device_ptr) { b->d_obs_rows.borrow((char *)device_ptr); b->obs_srow = row_stride; }
+    else if (!b->d_obs_rows.owned()) {
+        if (!b->d_obs_rows.alloc((size_t)b->nenv * (size_t)row * (size_t)b->obs.dtype, true, "observation rows")) return -1;
+        b->obs_srow = row;
+    }
+    return 0;
+}
+int phys_batch_obs_bind_input(phys_batch_t *b, const void *device_ptr, int dim, long long row_stride, int dtype) {
+    if (!b) { phys_set_last_error("phys_batch_obs_bind_input: no batch"); return -1; }
+    if (!device_ptr) { b->obs.input = nullptr; b->obs.input_dim = 0; b->obs.input_stride = 0; b->obs.input_dtype = 0; return 0; }
+    if (const char *why = ck::check_obs_input(b->obs, dim, row_stride, dtype)) return refuse("phys_batch_obs_bind_input", why);
+    b->obs.input = device_ptr; b->obs.input_dim = dim; b->obs.input_stride = (int)row_stride; b->obs.input_dtype = dtype;
+    return 0;
+}
+int phys_batch_obs(phys_batch_t *b, int env0, int n, const void *refill_ptr, void *stream) {
+    if (!b) { phys_set_last_error("phys_batch_obs: no batch"); return -1; }
+    const ck::ObsCfg c = obs_cfg_of(b);
+    ck::ObsField fields[PHYS_F_COUNT];
+    obs_fields_of(b, fields);
+    if (const char *why = ck::check_obs_call(c, fields, PHYS_F_COUNT, b->nenv, env0, n)) return refuse("phys_batch_obs", why);
+    (void)hipSetDevice(b->device);
+    if (n == 0) return 0;
+    hipStream_t s = launch_stream(b, stream);
+    hipLaunchKernelGGL(ck::cassie_obs_kernel, dim3((unsigned)ck::obs_grid(n)), dim3(WV_WAVE), 0, s, ck::make_obs_io(c, fields, env0, n, (const int *)refill_ptr));
+    if (!hip_ok(hipGetLastError(), "cassie_obs_kernel launch")) return -1;
+    ++b->obs_launches;
+    return 0;
+}
+int phys_batch_obs_dim(const phys_batch_t *b, int *ncols, int *history, int *row) {
+    if (!b || b->obs.nterms < 1) { phys_set_last_error("phys_batch_obs_dim: not configured (phys_batch_obs_configure first)"); return -1; }
+    if (ncols) *ncols = b->obs.ncols;
+    if (history) *history = b->obs.history;
+    if (row) *row = b->obs.ncols * b->obs.history;
+    return 0;
+}
+int phys_batch_obs_layout(const phys_batch_t *b, int *first_col) {
+    if (!b || b->obs.nterms < 1) { phys_set_last_error("phys_batch_obs_layout: not configured (phys_batch_obs_configure first)"); return -1; }
+    if (first_col) memcpy(first_col, b->obs_term_col.data(), sizeof(int) * b->obs_term_col.size());
+    return b->obs.nterms;
+}
+int phys_batch_obs_download(phys_batch_t *b, void *host, int env0, int n) {
+    if (!b || !host || b->obs.nterms < 1 || !b->d_obs_rows) { phys_set_last_error("phys_batch_obs_download: bad arguments, or not configured (phys_batch_obs_configure first)"); return -1; }
+    if (!range_ok(b, env0, n)) return refuse("phys_batch_obs_download", "env range out of bounds");
+    (void)hipSetDevice(b->device);
+    if (!quiesce(b)) return -1;
+    if (n == 0) return 0;
+    const size_t el = (size_t)b->obs.dtype, row = (size_t)b->obs.ncols * (size_t)b->obs.history, st = (size_t)b->obs_srow;
+    return hip_ok(hipMemcpy2D(host, el * row, b->d_obs_rows.get() + el * st * (size_t)env0, el * st, el * row, (size_t)n, hipMemcpyDeviceToHost), "observation rows download") ? 0 : -1;
+}
+int phys_batch_obs_frames(phys_batch_t *b, unsigned *host) {
+    if (!b || !host || !b->d_obs_frames) { phys_set_last_error("phys_batch_obs_frames: bad arguments, or not configured (phys_batch_obs_configure first)"); return -1; }
+    (void)hipSetDevice(b->device);
+    return quiesce(b) && hip_ok(hipMemcpy(host, b->d_obs_frames, sizeof(unsigned) * (size_t)b->nenv, hipMemcpyDeviceToHost), "observation frame counts download") ? 0 : -1;
+}
+int phys_batch_obs_set_frames(phys_batch_t *b, const unsigned *host) {
+    if (!b || !host || !b->d_obs_frames) { phys_set_last_error("phys_batch_obs_set_frames: bad arguments, or not configured (phys_batch_obs_configure first)"); return -1; }
+    (void)hipSetDevice(b->device);
+    return quiesce(b) && hip_ok(hipMemcpy(b->d_obs_frames, host, sizeof(unsigned) * (size_t)b->nenv, hipMemcpyHostToDevice), "observation frame counts upload") ? 0 : -1;
+}
+int phys_batch_debug_obs_launches(const phys_batch_t *b, long long *launches) {
+    if (!b) return -1;
+    if (launches) *launches = b->obs_launches;
     return 0;
 }
 

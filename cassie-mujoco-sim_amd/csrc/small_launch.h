@@ -1,12 +1,12 @@
 /*
- * small_launch.h -- how the kernels around the step kernel (small_kernels.h, surface_kernels.h, depth_kernel.h, ray_kernel.h, episode_kernels.h, probe_kernels.h) are
+ * small_launch.h -- how the kernels around the step kernel (small_kernels.h, surface_kernels.h, depth_kernel.h, ray_kernel.h, episode_kernels.h, probe_kernels.h, obs_kernels.h) are
  * launched: the records a kernel's arguments are built from, one builder per kernel that returns its filled argument struct for an env
  * range, the grid of every launch, and the checks of what a caller configures, each returning the message of its refusal (null: fine).
  * Pure host code, no HIP runtime calls, in the spirit of step_policy.h: the launcher (phys_batch.hip) keeps the records in the batch,
  * prefixes a message with its entry point's name and launches what a builder returns on the grid given here; the wave emulator's entry
  * points (tests/emu) fill the same records from their arguments and go through the same builders, grids and checks, so a CPU test of
  * one of these kernels also runs the launcher's refusals, grid and choice of kernel (tests/test_small_launch.py pins them one by one).
- * No field of ScanIO, DepthIO, RayIO, EpisodeIO, ResetIO, DeriveIO, SetConstIO, StateIO or ProbeIO is assigned anywhere else.
+ * No field of ScanIO, DepthIO, RayIO, EpisodeIO, ResetIO, DeriveIO, SetConstIO, StateIO, ProbeIO or ObsIO is assigned anywhere else.
  */
 #ifndef CASSIE_SMALL_LAUNCH_H
 #define CASSIE_SMALL_LAUNCH_H
@@ -16,6 +16,7 @@
 
 #include "depth_kernel.h"
 #include "episode_kernels.h"
+#include "obs_kernels.h"
 #include "probe_kernels.h"
 #include "ray_kernel.h"
 #include "small_kernels.h"
@@ -75,6 +76,21 @@ struct ProbeCfg {
     int nprobes; unsigned quantities; const ProbeDef *probes; const int *geom_class; int ngeom;
     const cm_ext_t *ext; const double *xpos, *xquat, *qacc; int *contacts;
 };
+
+/* the observation rows (phys_batch_obs_configure; nterms 0: not configured): the frame's columns, the frames of a row, the rows' type
+ * (OBS_F32 / OBS_F64), the noise's seed and the offset of its env counter; the sources of a call -- slot s is field slot_field[s] (or
+ * OBS_INPUT), whose row held slot_dim[s] elements when the terms were checked against it -- and the elements the input terms need of the
+ * caller's array.  Then what the caller names once a kernel reads them: the column table [ncols], the rows with their stride in elements,
+ * the counts [nenv], and the caller's input array (null: none bound) with its row length, row stride and type */
+struct ObsCfg {
+    int nterms, ncols, history, dtype, nslots, input_need;
+    unsigned long long seed; unsigned env_base;
+    int slot_field[OBS_MAXSLOTS], slot_dim[OBS_MAXSLOTS];
+    const ObsCol *cols; void *rows; long long srow; unsigned *frames;
+    const void *input; int input_dim, input_stride, input_dtype;
+};
+/* what the batch holds of a field: its rows (null: the batch does not hold it yet), their length and the doubles between two of them */
+struct ObsField { const double *base; int dim, stride; };
 
 /* ---- the row of a full state ---- */
 
@@ -243,6 +259,91 @@ inline const char *check_probe_call(const ProbeCfg &c, int nenv, int env0, int n
     if (env0 < 0 || n < 0 || (long long)env0 + n > nenv) return "env range out of bounds";
     return nullptr;
 }
+/* (what the launcher also answers a call without a batch) */
+constexpr const char *OBS_SIZE_REFUSAL = "0 .. 2048 terms (0 releases them), a history of 1 .. 64 frames, rows of PHYS_OBS_F32 or PHYS_OBS_F64";
+/* the observation's configuration: checks the caller's terms [nterms] against the row lengths the batch holds now (field_dim [nfields],
+ * 0: a field it does not hold yet; depth_field: the one field that is never a source), expands them into the column table
+ * (table [OBS_MAXCOLS]) and the first column of every term (term_col [nterms], may be null) and fills c but for what the caller names
+ * later.  nterms 0 is accepted and leaves c empty: the launcher releases what it holds.  The emulator goes through the same expansion */
+inline const char *obs_configure(const int *field_dim, int nfields, int depth_field, const ObsTerm *terms, int nterms, int history, int dtype,
+                                 unsigned long long seed, unsigned env_base, ObsCol *table, int *term_col, ObsCfg &c) {
+    if (nterms < 0 || nterms > OBS_MAXCOLS || (nterms > 0 && (!terms || !table))) return OBS_SIZE_REFUSAL;
+    c = {};
+    if (nterms == 0) return nullptr;
+    if (history < 1 || history > OBS_MAXHISTORY) return "a history of 1 .. 64 frames";
+    if (dtype != OBS_F32 && dtype != OBS_F64) return "the rows' dtype is PHYS_OBS_F32 or PHYS_OBS_F64";
+    int ncols = 0;
+    /* the slot of a source among the call's (-1: a seventeenth) */
+    auto slot_of = [&c](int field, int dim) {
+        for (int s = 0; s < c.nslots; ++s) if (c.slot_field[s] == field) return s;
+        if (c.nslots == OBS_MAXSLOTS) return -1;
+        c.slot_field[c.nslots] = field; c.slot_dim[c.nslots] = dim;
+        return c.nslots++;
+    };
+    /* the row length of a source as a term may index it (-1: no such source; 0: not held yet; the input's is checked at the call) */
+    auto dim_of = [&](int field) { return field == OBS_INPUT ? 0x7fffffff : field >= 0 && field < nfields && field != depth_field ? field_dim[field] : -1; };
+    for (int t = 0; t < nterms; ++t) {
+        const ObsTerm &d = terms[t];
+        if (d.kind != OBS_COPY && d.kind != OBS_ROT_INV) return "a term's kind is PHYS_OBS_COPY or PHYS_OBS_ROT_INV";
+        const bool rot = d.kind == OBS_ROT_INV, constant = d.field == OBS_CONST;
+        if (constant && !rot) return "PHYS_OBS_CONST is the field of a PHYS_OBS_ROT_INV term only (never a COPY's, never a qfield)";
+        if (rot && d.qfield == OBS_CONST) return "PHYS_OBS_CONST is the field of a PHYS_OBS_ROT_INV term only (never a COPY's, never a qfield)";
+        if (d.field == depth_field || (rot && d.qfield == depth_field)) return "PHYS_F_DEPTH is no source of an observation (images are not columns)";
+        const int dim = constant ? 0 : dim_of(d.field), qdim = rot ? dim_of(d.qfield) : 0;
+        if (dim < 0 || qdim < 0) return "a term's field is a PHYS_F_* field of the batch or PHYS_OBS_INPUT (PHYS_OBS_CONST in a ROT_INV's field)";
+        if ((!constant && dim == 0) || (rot && qdim == 0))
+            return "a term reads a field the batch does not hold yet (the scan, the rays, the probes, the step sums, the derived block: configure or enable them first)";
+        const int count = rot ? 3 : d.count;
+        if (!rot && count < 1) return "a COPY term makes at least one column";
+        if (!constant && (d.index < 0 || (long long)d.index + count > dim)) return rot ? "index + 3 lies beyond the field's row" : "index + count lies beyond the field's row";
+        if (rot && (d.qindex < 0 || (long long)d.qindex + 4 > qdim)) return "qindex + 4 lies beyond the field's row";
+        if (!(std::isfinite(d.offset) && std::isfinite(d.scale) && std::isfinite(d.noise))) return "a term needs a finite offset, scale and noise";
+        if (constant && !(std::isfinite(d.vec[0]) && std::isfinite(d.vec[1]) && std::isfinite(d.vec[2]))) return "a constant vector must be finite";
+        if (d.noise < 0) return "noise is an amplitude: >= 0";
+        if (!(d.lo <= d.hi)) return "lo <= hi (either may be infinite, neither NaN)";
+        if ((long long)ncols + count > OBS_MAXCOLS) return "more than PHYS_OBS_MAXCOLS (2048) columns in a frame";
+        const int slot = constant ? -1 : slot_of(d.field, dim == 0x7fffffff ? 0 : dim), qslot = rot ? slot_of(d.qfield, qdim == 0x7fffffff ? 0 : qdim) : -1;
+        if ((!constant && slot < 0) || (rot && qslot < 0)) return "more than 16 distinct source fields";
+        if (d.field == OBS_INPUT && d.index + count > c.input_need) c.input_need = d.index + count;
+        if (rot && d.qfield == OBS_INPUT && d.qindex + 4 > c.input_need) c.input_need = d.qindex + 4;
+        if (term_col) term_col[t] = ncols;
+        for (int j = 0; j < count; ++j) {
+            ObsCol &o = table[ncols++];
+            o.slot = slot; o.elem = rot ? d.index : d.index + j; o.comp = rot ? j : -1; o.qslot = qslot; o.qelem = rot ? d.qindex : 0; o.pad = 0;
+            for (int k = 0; k < 3; ++k) o.vec[k] = constant ? d.vec[k] : 0.0;
+            o.offset = d.offset; o.scale = d.scale; o.noise = d.noise; o.lo = d.lo; o.hi = d.hi;
+        }
+    }
+    if ((long long)ncols * history > OBS_MAXROW) return "a row of more than 65536 elements (history x columns)";
+    c.nterms = nterms; c.ncols = ncols; c.history = history; c.dtype = dtype; c.seed = seed; c.env_base = env_base;
+    return nullptr;
+}
+/* what phys_batch_obs_bind / _bind_input refuse */
+inline const char *check_obs_bind(const ObsCfg &c, long long row_stride) {
+    if (c.nterms < 1) return "not configured (phys_batch_obs_configure first)";
+    if (row_stride < (long long)c.ncols * c.history) return "a row stride of at least the row's elements (history x columns)";
+    return nullptr;
+}
+inline const char *check_obs_input(const ObsCfg &c, int dim, long long row_stride, int dtype) {
+    if (c.nterms < 1) return "not configured (phys_batch_obs_configure first)";
+    if (dim < 1 || row_stride < dim || row_stride > 0x7fffffff) return "an input of at least one element a row and a row stride of at least that";
+    if (dtype != OBS_F32 && dtype != OBS_F64) return "the input's dtype is PHYS_OBS_F32 or PHYS_OBS_F64";
+    return nullptr;
+}
+/* what an observation call refuses; fields [nfields]: what the batch holds NOW */
+inline const char *check_obs_call(const ObsCfg &c, const ObsField *fields, int nfields, int nenv, int env0, int n) {
+    if (c.nterms < 1 || !c.cols || !c.rows || !c.frames) return "not configured (phys_batch_obs_configure first)";
+    if (env0 < 0 || n < 0 || (long long)env0 + n > nenv) return "env range out of bounds";
+    for (int s = 0; s < c.nslots; ++s) {
+        const int f = c.slot_field[s];
+        if (f == OBS_INPUT) {
+            if (!c.input) return "a PHYS_OBS_INPUT term and no input bound (phys_batch_obs_bind_input first)";
+            if (c.input_dim < c.input_need) return "the bound input's rows are shorter than the PHYS_OBS_INPUT terms reach";
+        } else if (f < 0 || f >= nfields || !fields[f].base || fields[f].dim != c.slot_dim[s])
+            return "the row length of a source field has changed since phys_batch_obs_configure (configure again)";
+    }
+    return nullptr;
+}
 /* the bank of full states: what phys_batch_state_configure / _bind refuse (the view tells what the batch has), and what a save or a
  * restore refuses */
 inline const char *state_configure(const BatchView &v, int nslots, int groups) {
@@ -272,6 +373,8 @@ inline int state_grid(int n) { return n < STATE_GRID ? n : STATE_GRID; }
 /* one wave per env up to PROBE_GRID workgroups, which then walk the range: few, as the episode kernel's -- the launch runs behind a range's
  * forward pass while the other range's step kernel fills the chip, where every workgroup waits for a wave slot to free (probe_kernels.h) */
 inline int probe_grid(int n) { return n < PROBE_GRID ? n : PROBE_GRID; }
+/* one wave per env up to OBS_GRID workgroups, which then walk the range: few, as the probes' (obs_kernels.h) */
+inline int obs_grid(int n) { return n < OBS_GRID ? n : OBS_GRID; }
 /* a job is (env, tile of DEPTH_TILE x DEPTH_TILE pixels); a fixed grid walks the job list (a first choice: depth_kernel.h) */
 inline int depth_grid(int n, int width, int height) {
     const int T = DEPTH_TILE;
@@ -353,6 +456,21 @@ inline ProbeIO make_probe_io(const BatchView &v, const ProbeCfg &c, double *out,
     io.out = out; io.sout = sout;
     if ((c.quantities >> PQ_CONTACTS & 1u) && c.geom_class) { io.geom_class = c.geom_class; io.ngeom = c.ngeom; io.contacts = c.contacts; }
     io.row_dim = probe_layout(c.nprobes, c.quantities, v.nv, io.off, nullptr);
+    return io;
+}
+/* cassie_obs_kernel's: the sources of the record's slots where the batch reads them today (fields [nfields]: its own buffers or the
+ * caller's bound tensors, with their row strides; the caller's input array), the column table, the rows, the counts and the key */
+inline ObsIO make_obs_io(const ObsCfg &c, const ObsField *fields, int env0, int n, const int *refill) {
+    ObsIO io = zeroed<ObsIO>();
+    io.env0 = env0; io.n = n; io.ncols = c.ncols; io.history = c.history; io.f32 = c.dtype == OBS_F32;
+    io.env_base = c.env_base; io.key0 = (unsigned)(c.seed & 0xffffffffull); io.key1 = (unsigned)(c.seed >> 32);
+    io.cols = c.cols;
+    for (int s = 0; s < c.nslots; ++s) {
+        const int f = c.slot_field[s];
+        if (f == OBS_INPUT) io.src[s] = {c.input, c.input_stride, c.input_dtype == OBS_F32, 0};
+        else io.src[s] = {fields[f].base, fields[f].stride, 0, 0};
+    }
+    io.rows = c.rows; io.srow = c.srow; io.frames = c.frames; io.refill = refill;
     return io;
 }
 inline int episode_row_dim(const BatchView &v) { return v.nq + v.nv + v.nsd + v.nu + v.nv; }

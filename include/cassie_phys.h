@@ -450,6 +450,8 @@ size_t phys_sizeof_episode_rules(void);
  * NOT in a row: per-env height-field grids and per-env models, the outputs PHYS_F_BODY_CFRC / info / ext / PHYS_F_DERIVED / PHYS_F_QM /
  * the scan, depth and ray fields / PHYS_F_STEP_SUMS, PHYS_EP_DONE / _REASON / _TERMINAL, the placement arrays, and what the launcher
  * keeps per env for one launch or for speed alone (progress, chunk words, hand-over lists, launch order and cost: none changes a result).
+ * Neither are the observation rows and their per-env frame counts (phys_batch_obs below): a caller that rewinds an env keeps or sets
+ * them itself (phys_batch_obs_set_frames; a refill entry refills the env's history from its restored state).
  *
  *   phys_batch_state_configure  allocates a bank of nslots >= 1 zeroed rows in HBM; waits for the batch's streams; calling it again
  *                               replaces the bank (and drops a binding).
@@ -673,6 +675,79 @@ void *phys_batch_probe_contacts_ptr(phys_batch_t *b);
 int phys_batch_probe_bind_contacts(phys_batch_t *b, void *device_ptr);     /* int32 [nenv], NULL unbinds */
 int phys_batch_probe_download_contacts(phys_batch_t *b, int *host);        /* the words [nenv] to the host, after waiting for the batch's streams */
 int phys_batch_debug_probe_launches(const phys_batch_t *b, long long *forward, long long *reduce);
+
+/* OBSERVATION ROWS: the row a policy network reads, made on the device from the batch's fields by ONE launch per env range: gather,
+ * offset, uniform noise, scale, clip, the cast to the rows' type and a per-env history of frames.  A configured list of TERMS makes the
+ * columns of a FRAME, term after term; an env's ROW is [history][ncols] with frame 0 the newest.
+ * TERMS (phys_obs_term_t):
+ *   PHYS_OBS_COPY     count columns; column j's source is x = field_row[index + j].
+ *   PHYS_OBS_ROT_INV  3 columns: x = R(q)^T v, with q the four doubles qfield_row[qindex .. qindex + 3] AS STORED (not normalised) and v
+ *                     the three doubles field_row[index .. index + 2], or the term's vec where field == PHYS_OBS_CONST.  R(q) is the matrix
+ *                     of a quaternion (w, x, y, z) as the step kernel forms it, m = [q00+q11-q22-q33, 2(q12-q03), 2(q13+q02); 2(q12+q03),
+ *                     q00-q11+q22-q33, 2(q23-q01); 2(q13-q02), 2(q23+q01), q00-q11-q22+q33] with qij = q[i] q[j], and x[k] = (m[k] v[0] +
+ *                     m[3 + k] v[1]) + m[6 + k] v[2]; every product and every sum is rounded on its own, left to right as written (no
+ *                     fused multiply-add).  vec = (0, 0, -1) with q = qpos[3:7] is the projected gravity; v = qvel[0:3] the base velocity
+ *                     in the body frame; v from the input a heading-relative command.  count is ignored.
+ *   field / qfield    any PHYS_F_* field but PHYS_F_DEPTH, with the row length the batch holds for it when the terms are configured (a field
+ *                     that is sized later -- the scan, the rays, the probes, the step sums, the derived block -- must have been
+ *                     configured or enabled before), or PHYS_OBS_INPUT: the caller's own per-env array (commands, a clock phase, the
+ *                     previous action), bound with phys_batch_obs_bind_input as floats or doubles; floats are widened exactly.  A field is
+ *                     read where the batch reads it at the call: its own buffer, or the caller's bound tensor with its row stride.
+ * A COLUMN'S VALUE, every step one individually rounded fp64 operation:
+ *       e = x - offset;   if (noise != 0) e = e + noise * xi;   y = e * scale;   y = y < lo ? lo : (y > hi ? hi : y)   (a NaN passes)
+ *   and the element written is y, or (float)y rounded to nearest even where the rows are PHYS_OBS_F32.
+ * NOISE: xi is uniform on (-1, 1), xi = (w + 0.5) 2^-31 - 1 (exact in fp64) with w word 0 of Philox4x32-10 (Salmon et al., SC 2011;
+ *   multipliers 0xD2511F53 / 0xCD9E8D57, key increments 0x9E3779B9 / 0xBB67AE85) on the counter (env_base + env, column, frames[env], 0)
+ *   -- column: the column's index in the frame; env_base + env modulo 2^32 -- with the key (seed & 0xffffffff, seed >> 32).  A draw depends
+ *   on the env, the column and the number of calls the env has seen, never on how the batch is cut into ranges, streams or ranks: a rank
+ *   that holds envs [k n, (k + 1) n) of a larger run and configures env_base = k n draws what one batch would draw for those envs.
+ * HISTORY: a call over an env first forms the new frame.  If frames[env] == 0 or the call's refill entry for the env is non-zero, every
+ *   frame of the row becomes the new frame; otherwise frame h takes frame h - 1 for h = history - 1 .. 1 and frame 0 the new one.  Then
+ *   frames[env] += 1 (uint32, wraps).  refill: an optional int32 DEVICE array [n], entry i for env env0 + i -- the range's slice of
+ *   PHYS_EP_DONE after phys_batch_end_episodes restarts the history of the envs it restarted.
+ * LIMITS: PHYS_OBS_MAXCOLS columns in a frame, 1 .. 64 frames, a row of at most 65536 elements, 16 distinct sources.
+ *   phys_batch_obs_configure    terms [nterms] (host memory), the frames of a row, the rows' type (PHYS_OBS_F32 / PHYS_OBS_F64), the seed
+ *                               and env_base.  Refuses, with a message in phys_last_error(): an unknown kind or field, PHYS_F_DEPTH, a
+ *                               field the batch does not hold yet, index + count / index + 3 / qindex + 4 beyond the field's row,
+ *                               PHYS_OBS_CONST anywhere but in a ROT_INV's field, a non-finite offset, scale, noise or vec, noise < 0,
+ *                               lo > hi (infinities are allowed), too many columns, a history outside 1 .. 64, an unknown dtype.
+ *                               Allocates the column table, the rows and frames (zeroed); drops the bindings of the rows and of the input;
+ *                               waits for the batch's streams.  nterms 0 releases everything.
+ *   phys_batch_obs_bind         the rows in caller-owned HBM, of the configured type, row_stride elements (>= the row's) between two envs'
+ *                               rows: a column block of the tensor an all-gather sends.  NULL: the batch's own rows again, zeroed.
+ *   phys_batch_obs_bind_input   the caller's per-env array [nenv] rows of dim elements, row_stride elements apart, PHYS_OBS_F32 / _F64.
+ *                               NULL un-binds.
+ *   phys_batch_obs              ONE launch of cassie_obs_kernel over [env0, env0 + n) on `stream` (NULL: the batch's own), in order with
+ *                               the launches there.  No host synchronisation, no allocation, no read on the host.  Writes the rows and
+ *                               frames of the range and nothing else.  Refuses: not configured, a range outside the batch, a source field
+ *                               whose row length is no longer what it was at the configure call, a PHYS_OBS_INPUT term with nothing bound
+ *                               or with a bound dim that its terms reach beyond.
+ *   phys_batch_obs_dim          ncols, history and the row's elements (any may be NULL) -> 0, -1 when not configured.
+ *   phys_batch_obs_layout       first_col [nterms]: every term's first column -> nterms, -1 when not configured.
+ *   phys_batch_obs_download     rows [env0, env0 + n) to dense host memory [n][history][ncols] of the rows' type; waits for the streams.
+ *   phys_batch_obs_frames / _set_frames   the counts [nenv] (uint32) to / from the host, so that a resumed run draws what the first would
+ *                               have drawn; both wait for the streams.
+ *   phys_batch_debug_obs_launches  diagnostics: the launches phys_batch_obs has made. */
+enum { PHYS_OBS_COPY = 0, PHYS_OBS_ROT_INV = 1 };
+enum { PHYS_OBS_INPUT = -1, PHYS_OBS_CONST = -2 };   /* a term's field, beside PHYS_F_* */
+enum { PHYS_OBS_F32 = 4, PHYS_OBS_F64 = 8 };         /* a dtype: the bytes of an element */
+#define PHYS_OBS_MAXCOLS 2048
+typedef struct phys_obs_term {
+    int kind, field, index, count, qfield, qindex;
+    double vec[3];
+    double offset, scale, noise, lo, hi;
+} phys_obs_term_t;
+int phys_batch_obs_configure(phys_batch_t *b, const phys_obs_term_t *terms, int nterms, int history, int dtype, unsigned long long seed,
+                             unsigned env_base);   /* nterms 0: release */
+int phys_batch_obs_bind(phys_batch_t *b, void *device_ptr, long long row_stride);   /* NULL un-binds */
+int phys_batch_obs_bind_input(phys_batch_t *b, const void *device_ptr, int dim, long long row_stride, int dtype);   /* NULL un-binds */
+int phys_batch_obs(phys_batch_t *b, int env0, int n, const void *refill_ptr /* int32 [n] or NULL */, void *stream);
+int phys_batch_obs_dim(const phys_batch_t *b, int *ncols, int *history, int *row);
+int phys_batch_obs_layout(const phys_batch_t *b, int *first_col /*[nterms]*/);
+int phys_batch_obs_download(phys_batch_t *b, void *host, int env0, int n);
+int phys_batch_obs_frames(phys_batch_t *b, unsigned *host /*[nenv]*/);
+int phys_batch_obs_set_frames(phys_batch_t *b, const unsigned *host /*[nenv]*/);
+int phys_batch_debug_obs_launches(const phys_batch_t *b, long long *launches);
 
 /* measurement aid: on = every substep of a fused launch evaluates every output (IMU sensors, body quaternions), although
  * only the last substep's values can be read; off (default) = those are formed by the substeps whose values are read */
