@@ -120,7 +120,11 @@ oracle/libcassie_oracle.so: oracle/cassie_oracle.c oracle/cassie_oracle.h $(CSRC
 # -march, no FMA contraction: the emulator's bit-exactness rests on these flags
 # (the emulator's sources live in the test tree too: an older tests/, whose emulator is one chain of .cpp files that include each other
 # from emu_terrain.cpp down, builds as it did -- one translation unit)
-EMU_FLAGS := -O2 -std=c++17 -fPIC -Itests/emu -I$(CSRC) -Itests/device
+# -DCK_SENSORS_BEHIND_J_HFIELD=1: the emulator's 32-dof bodies are all instantiated with FEAT_ALL, height-field code included, and the
+# product keeps wave 1's sensor stage in front of the barrier J in its height-field forms (physics_kernel.h: sensors_behind_j) -- the
+# emulator would never run the order the benchmark's kernel has.  With the switch its 32-dof two-wave forms all take the new order
+# (tests/test_sensor_stage_behind_j.py); the old one stays covered by its 40-dof two-wave form and by the GPU suite.
+EMU_FLAGS := -O2 -std=c++17 -fPIC -Itests/emu -I$(CSRC) -Itests/device -DCK_SENSORS_BEHIND_J_HFIELD=1
 EMU_DEPS  := $(wildcard tests/emu/*.h) $(wildcard tests/device/wave_bodies.h) $(wildcard $(CSRC)/*.h) $(wildcard $(CSRC)/*.inc)
 ifeq ($(wildcard tests/emu/emu_terrain.cpp),)
 EMU_OBJS := $(OBJD)/emu/emu_runtime.o $(OBJD)/emu/emu_step.o $(OBJD)/emu/emu_kernels.o $(OBJD)/emu/emu_depth.o $(OBJD)/emu/emu_depth_scene.o \

@@ -227,7 +227,8 @@
         }
         const double raref = rtype >= 0 ? -rB * jvel - rK * rimp * (rpos - rmargin) : 0.0;
 
-        /* ---- sensors, part 1 (sensors_before_solve; two-wave form: wave 1 runs it behind the barrier J) ---- */
+        /* ---- sensors, part 1 (sensors_before_solve; two-wave form: wave 1 runs it, in front of the barrier J or behind it -- env_step:
+         *      sensors_behind_j) ---- */
         int aslot = -1;
         if constexpr (NW == 1) aslot = sensors_before_solve(io, S, m, env, issens, ls, sens_c, need_imu, lastsub);
         CK_STAMP(29);
@@ -279,6 +280,7 @@
                 acc += nrow;
             }
         }
-        wv::sync(); /* every reader of the body-stage tiles is done: region x becomes the Y staging tile */
+        wv::sync(); /* every reader of the body-stage tiles ON THIS WAVE is done: region x becomes the Y staging tile (once wave 1's sensor
+                     * stage, where it runs behind J, is done with them too: the wait for cmd[6] in front of the staging store) */
         CK_STAMP(8);
 

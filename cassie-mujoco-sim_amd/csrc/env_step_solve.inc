@@ -99,6 +99,16 @@
                 ycol[k] = xk * S.rsd[k];
             }
         }
+        long long t_wait = 0;
+        if constexpr (sensors_behind_j) {
+            /* this wave's first store into the body tiles' region since J (the matrix-core forms' Gram matrix overlays the same region,
+             * behind this store): wave 1's sensor stage, which ran beside the half solve above, is done reading the tiles.  (The
+             * profiled forms record how long the wait took, in clocks: the lower half of slot 15, stored behind the staging store -- a branch here
+             * costs the stage its register allocation, see wave.h) */
+            if constexpr (feat_prof(FEAT)) t_wait = wv::clock();
+            wv::wait_for_straight(&S.cmd[6], sub + 1); /* (no loop the compiler sees: wave.h) */
+            if constexpr (feat_prof(FEAT)) t_wait = wv::clock() - t_wait;
+        }
         if (r_ < MAXR || lastcol) { /* (lanes MAXR .. 62 of a row-capped instantiation hold no row) */
             const int yrow = lastcol ? MAXR : r_;
 #pragma unroll
@@ -107,6 +117,7 @@
         wv::sync();
         if constexpr (NW == 2) wv::publish(&S.cmd[2], sub + 1); /* wave 1 stages its column of Y for the qacc stage while this wave solves */
         CK_STAMP(9);
+        if constexpr (sensors_behind_j && feat_prof(FEAT)) { if (io.prof && lane == 0) ((int *)&io.prof[(size_t)env * NSTAMP + 15])[0] = (int)t_wait; }
 
         /* ================= P9: this lane's row of A = Y^T Y + diag(R), b = Y^T y63 - aref ================= */
         double arow[MAXR];

@@ -66,15 +66,32 @@
                 const bool need_imu1 = lastsub1 || io.all_outputs_every_substep || (io.drive_mode && sub1 + 2 == nsub);
                 const bool issens1 = lane < m->nsensor && (lastsub1 || io.drive_mode || io.all_outputs_every_substep);
                 const int ls1 = issens1 ? lane : 0;
-                const SensorConsts sens_c1 = request_sensor_consts(m, ls1);
-                /* the sensor stage, in the time this wave used to wait at J for wave 0's Jacobian rows: everything it reads is in LDS
-                 * (poses since F, body velocities and bias accelerations since cmd[1]) and its own drive-level pass has read the
-                 * previous substep's sensor words */
-                const int aslot1 = sensors_before_solve(io, S, m, env, issens1, ls1, sens_c1, need_imu1, lastsub1);
+                SensorConsts sens_c1;
+                int aslot1;
+                if constexpr (!sensors_behind_j) {
+                    sens_c1 = request_sensor_consts(m, ls1);
+                    /* the sensor stage, in the time this wave used to wait at J for wave 0's Jacobian rows: everything it reads is in LDS
+                     * (poses since F, body velocities and bias accelerations since cmd[1]) and its own drive-level pass has read the
+                     * previous substep's sensor words */
+                    aslot1 = sensors_before_solve(io, S, m, env, issens1, ls1, sens_c1, need_imu1, lastsub1);
+                }
                 CK_STAMP(47);
-                wv::block_barrier(); /* J: the factor of M and qfrc_smooth are in LDS, the sensor stage is done with the body tiles */
-                wv::set_priority<CK_PRIO_W1_JP>(); /* (J .. P: this wave has the length of wave 0's solve for the factor of M + hB and its staging) */
+                wv::block_barrier(); /* J: the factor of M and qfrc_smooth are in LDS (and, where the sensor stage runs in front: it is done with the body tiles) */
+                if constexpr (!sensors_behind_j) wv::set_priority<CK_PRIO_W1_JP>(); /* (J .. P: this wave has the length of wave 0's solve for the factor of M + hB and its staging) */
                 CK_STAMP(39);
+                if constexpr (sensors_behind_j) {
+                    /* the sensor stage BEHIND J, beside wave 0's half solve: whichever wave reaches J last, the other one waits for it, and
+                     * in front of J the sensor stage made this wave the late one that much more often -- a wait on wave 0's critical path,
+                     * while this wave has the length of wave 0's solve to spare behind J.  Everything the stage reads is still in LDS:
+                     * wave 0's half solve works in registers and first writes into the body tiles' region with its staging store, in front
+                     * of which it waits for cmd[6].  Wave 0 is waiting for this stage soon, so it runs at this wave's F .. J priority. */
+                    sens_c1 = request_sensor_consts(m, ls1);
+                    aslot1 = sensors_before_solve(io, S, m, env, issens1, ls1, sens_c1, need_imu1, lastsub1);
+                    wv::publish(&S.cmd[6], sub1 + 1); /* the body tiles are wave 0's: the staged matrix may overwrite them */
+                    wv::set_priority<CK_PRIO_W1_JP>();
+                    /* (the profiled forms: the stage's length from the stamp behind J, in the upper half of slot 15 -- pk_types.h) */
+                    if constexpr (feat_prof(FEAT)) { if (io.prof && lane == 0) ((int *)&io.prof[(size_t)env * NSTAMP + 15])[1] = (int)(wv::clock() - io.prof[(size_t)env * NSTAMP + 39]); }
+                }
                 if constexpr (WIDE) {
                     /* the 127-row instantiation: this wave's rows 64 .. 126 and the qfrc_smooth column (wide_solve); its row forces
                      * go to LDS for the barrier P like wave 0's */

@@ -106,10 +106,11 @@ WV_DEVICE int env_step(const PhysIO &io, EnvShared<NVP, LPack<TOPO, NVP>::count,
      * of mass, cinert, cdof, composite inertias, M's columns), the drive-level pass, the two factorisations and the bias /
      * passive stage beside wave 0's collision, velocity and constraint-row stages; then qacc, the accelerometers, the substep's
      * outputs and the Euler step behind wave 0's solve, with their operands staged while wave 0 solves.  Four workgroup
-     * barriers per substep (F: poses in LDS; J: the factors and qfrc_smooth; P: the row forces; E: the substep is complete) and four
+     * barriers per substep (F: poses in LDS; J: the factors and qfrc_smooth; P: the row forces; E: the substep is complete) and five
      * one-directional flags: cmd[3] / cmd[4] where a barrier X used to be (com / cinert / cdof for wave 0's velocity stage, the
      * collision verdict for wave 1's drive-level pass: its factorisations in between do not wait for wave 0's collision stage),
-     * cmd[1] (body forces), cmd[2] (the staged matrix).  Every value is computed by the
+     * cmd[1] (body forces), cmd[2] (the staged matrix), cmd[6] (wave 1's sensor stage, which runs behind J, is done with the body
+     * tiles: wave 0's staging store waits for it).  Every value is computed by the
      * same instructions from the same operands as in the one-wave form, so the results are bit for bit the same. */
     const int wid = NW == 2 ? wv::wave_id() : 0;
     /* (wave 0 is on its env's critical path from F to P: above a wave 1 in a stretch nobody waits for, below one in its tail -- env_step_wave1.inc) */
@@ -122,6 +123,14 @@ WV_DEVICE int env_step(const PhysIO &io, EnvShared<NVP, LPack<TOPO, NVP>::count,
     constexpr int MAXC = SH_T::MAXC;
     constexpr bool WIDE = SH_T::WIDE;
     static_assert(!WIDE || (NW == 2 && MAXR == WIDE_ROWS), "the 127-row instantiation spreads its solve over the two wavefronts of an env");
+    /* (round 8) the two-wave forms whose wave 1 runs its sensor stage behind the barrier J, beside wave 0's half solve, and tells wave 0
+     * through cmd[6] when it is done with the body tiles (env_step_wave1.inc).  Not the 127-row form, whose wave 0 parks rows in the
+     * tiles' region in front of J.  By measurement (profiles/round8/sensor_stage_behind_j_ab.txt) not the height-field forms either --
+     * their wave 0 has a pre-pass of 13 k clocks on its way to J, so wave 1 is never the late one there and the stage in front of J
+     * costs nobody anything, behind J it made wave 0 wait: - 0.5 % -- nor the 40-dof forms, whose wave 1 parks the columns of M + hB
+     * in LDS across these stages (- 0.6 %); the two macros are there to measure it again. */
+    constexpr bool sensors_behind_j = NW == 2 && !WIDE && (NVP <= 32 || CK_SENSORS_BEHIND_J_40DOF != 0) &&
+                                      ((FEAT & FEAT_HFIELD) == 0 || CK_SENSORS_BEHIND_J_HFIELD != 0);
     const ModelPtr m_launch = (ModelPtr)(io.models + (size_t)env * io.model_stride);
     ModelPtr m = m_launch;
     /* the env's physical parameters: its own block, or the model's (wave-uniform either way: scalar loads) */
@@ -142,6 +151,7 @@ WV_DEVICE int env_step(const PhysIO &io, EnvShared<NVP, LPack<TOPO, NVP>::count,
     /* ---------------- load state (coalesced, env-major) ---------------- */
     if (NW == 1 || wid == 0) {
     if (lane == 0) { S.cmd[0] = 0; S.cmd[1] = 0; S.cmd[2] = 0; S.cmd[3] = 0; S.cmd[4] = 0; }
+    if constexpr (sensors_behind_j) { if (lane == 0) S.cmd[6] = 0; } /* (only where somebody reads it: the other forms' code stays what it was, to the byte) */
     /* (the 127-row solve's turn words: wave 1 polls turn[1] for an odd value before anybody wrote it -- whatever an earlier env of
      * this workgroup or raw LDS left there must not look like one) */
     if constexpr (WIDE) { if (lane == 0) { S.x.turn[0] = 0; S.x.turn[1] = 0; S.x.turn[2] = 0; S.x.turn[3] = 0; } }

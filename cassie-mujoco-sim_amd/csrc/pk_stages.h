@@ -565,12 +565,14 @@ WV_DEVICE void stage_factor_h(const SH &S, int k_, bool isdof, int nv, double (&
 }
 /* ---- sensors, part 1 (lane = sensor): everything that does not need qacc is final here; the accelerometer parks its partial
  *      results in LDS (S.accel) because the body tiles are about to be recycled.  One-wave form: in line behind the Jacobian rows.
- *      Two-wave form: wave 1, in front of the barrier J -- in the time it used to wait there for wave 0's Jacobian rows (its own
- *      drive-level pass has read the previous substep's sensor words by then; poses, body velocities and bias accelerations are
- *      in LDS since F / cmd[1]); behind J, where wave 0 ran it until round 5, it was 4.7 k clocks of wave 0's critical path.
- *      (Placed behind J on wave 1 -- beside wave 0's half solve, with a flag before the staged matrix overwrites the body tiles --
- *      it sits between the mass matrix's columns, which wave 1 keeps for the factorisation of M + hB, and their use: 850 values
- *      went to scratch.) ---- */
+ *      Two-wave form: wave 1 (its own drive-level pass has read the previous substep's sensor words by then; poses, body velocities
+ *      and bias accelerations are in LDS since F / cmd[1]); on wave 0 behind J, where it ran until round 5, it was 4.7 k clocks of
+ *      wave 0's critical path.  Round 5 put it in front of J on wave 1; since round 8 the 32-dof forms run it BEHIND J on wave 1,
+ *      beside wave 0's half solve, with a flag (cmd[6]) before the staged matrix overwrites the body tiles (env_step:
+ *      sensors_behind_j; env_step_wave1.inc says why).  An earlier attempt at that place lost 850 values to scratch; this time the
+ *      spills (538 with wv::wait_for) turned out to come not from the stage but from the LOOP of wave 0's wait in front of the
+ *      staging store, which splits the half solve's block: the wait is one asm block now (wave.h: wait_for_straight) and the
+ *      allocation is the parent's.  The 40-dof forms keep the stage in front of J. ---- */
 /* Who reads a substep's sensors: the launch's caller (the last substep's), and in a drive mode the next substep's
  * encoder models (the joint / actuator positions) and the measurement block the LAST substep's drive pass writes
  * (the IMU words of the substep before it).  The IMU sensors -- frame quaternion, gyro, magnetometer and the

@@ -5,6 +5,11 @@
 #ifndef CASSIE_PK_TYPES_H
 #define CASSIE_PK_TYPES_H
 
+#ifndef WV_HAS_WAIT_FOR_STRAIGHT
+/* (a wave.h without a straight-line form of the flag wait -- csrc/wave.h: wait_for_straight; the CPU emulator has no registers to lose) */
+namespace wv { inline void wait_for_straight(const int *flag, int value) { wait_for(flag, value); } }
+#endif
+
 namespace ck {
 
 constexpr int NB = CM_MAXBODY;
@@ -16,7 +21,17 @@ constexpr int FAST_ROWS = 31;  /* rows of the row-capped fast instantiation (+ t
 constexpr int FAST_ROWS_TRAY = 47; /* the 40-dof model's fast instantiation: Cassie + tray + cube at rest use 32 .. 40 rows (+ the qfrc_smooth row: three blocks of 16) */
 constexpr int NSTAMP = 48;   /* 0..15 stage boundaries, 16..32 sub-stage stamps, 33..39 the two-wave form's barrier arrivals / departures,
                                 40..41 where the hardware placed the env's wave(s), 42..43 shader clock and 100 MHz clock at the env's end,
-                                44..46 the height-field pre-pass, 47 wave 1's sensor stage (tools/stage_profile.py names them) */
+                                44..46 the height-field pre-pass, 47 wave 1's sensor stage (tools/stage_profile.py names them); 15 holds no
+                                stamp but two lengths in clocks, 32 bits each: low, how long wave 0 waited for wave 1's sensor stage
+                                (cmd[6], env_step_solve.inc); high, that stage's length where it runs behind J (env_step_wave1.inc) */
+/* the 40-dof / the height-field two-wave forms' sensor stage behind the barrier J too (env_step: sensors_behind_j)?  Both measured
+ * slower that way (profiles/round8/sensor_stage_behind_j_ab.txt): off */
+#ifndef CK_SENSORS_BEHIND_J_40DOF
+#define CK_SENSORS_BEHIND_J_40DOF 0
+#endif
+#ifndef CK_SENSORS_BEHIND_J_HFIELD
+#define CK_SENSORS_BEHIND_J_HFIELD 0
+#endif
 #define CK_TRI(k, i) ((k) * ((k) + 1) / 2 + (i))
 /* (FEAT: the enclosing template's; an instantiation without FEAT_PROF -- pk_stages.h: feat_prof -- keeps CK_FRESH() alone) */
 #define CK_STAMP(i) do { if constexpr (feat_prof(FEAT)) { if (io.prof && lane == 0) io.prof[(size_t)env * NSTAMP + (i)] = wv::clock(); } CK_FRESH(); } while (0)
@@ -235,8 +250,11 @@ struct EnvShared {
      * diverged qacc; cmd[1] = the substep (+ 1) whose body forces wave 0's velocity stage has put in LDS, cmd[2] = the substep
      * (+ 1) whose staged matrix Y wave 0 has put in LDS (wave 1 waits for either); cmd[3] = the substep (+ 1) whose mass-matrix group
      * wave 1 has finished (com, cinert, cdof in LDS, the buf tile free again: wave 0's velocity stage waits for it), cmd[4] = the
-     * substep (+ 1) whose collision verdict wave 0 has reached (cmd[0] = 1: handed over; wave 1's drive-level pass waits for it) */
-    int cmd[6];
+     * substep (+ 1) whose collision verdict wave 0 has reached (cmd[0] = 1: handed over; wave 1's drive-level pass waits for it);
+     * cmd[5] = where an env_step call of the in-place form ended (cassie_step_kernel); cmd[6] = the substep (+ 1) whose sensor stage
+     * wave 1 has finished behind the barrier J (it is done with the body tiles: wave 0's staging store of Y waits for it;
+     * env_step: sensors_behind_j).  (Eight words: the block's size is a multiple of eight bytes either way.) */
+    int cmd[8];
 };
 
 }  // namespace ck

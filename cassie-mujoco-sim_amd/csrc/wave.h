@@ -42,6 +42,28 @@ WV_DEVICE void wait_for(const int *flag, int value) {
     while (__builtin_amdgcn_readfirstlane(*(const volatile int *)flag) != value) __builtin_amdgcn_s_sleep(1);
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
 }
+/* wait_for() as ONE block of the instruction stream: the same poll (LDS read, compare, s_sleep 1), but with its loop inside one asm
+ * statement, so that the compiler sees no control flow.  For a wait in the middle of a stage that lives at the register limit: a loop
+ * there splits the stage into basic blocks, and the fast step kernel's allocation does not survive that (the wait in front of the
+ * staging store of Y as wait_for(): 241 -> 256 registers, 0 -> 538 spilled; this form: as without the wait).  A wave.h without this
+ * form (the CPU emulator's) gets wait_for() under this name from pk_types.h. */
+#define WV_HAS_WAIT_FOR_STRAIGHT 1
+WV_DEVICE void wait_for_straight(const int *flag, int value) {
+    const unsigned addr = (unsigned)(__UINTPTR_TYPE__)(const __attribute__((address_space(3))) int *)flag;
+    const int want = __builtin_amdgcn_readfirstlane(value);
+    int seen_v, seen_s;
+    asm volatile("1:\n\t"
+                 "ds_read_b32 %0, %2\n\t"
+                 "s_waitcnt lgkmcnt(0)\n\t"
+                 "v_readfirstlane_b32 %1, %0\n\t"
+                 "s_cmp_eq_u32 %1, %3\n\t"
+                 "s_cbranch_scc1 2f\n\t"
+                 "s_sleep 1\n\t"
+                 "s_branch 1b\n\t"
+                 "2:"
+                 : "=&v"(seen_v), "=&s"(seen_s) : "v"(addr), "s"(want) : "memory", "scc");
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
+}
 /* the same without the s_sleep between two looks: for a wave that has its SIMD to itself (the 127-row instantiation) */
 WV_DEVICE void wait_for_spin(const int *flag, int value) {
     while (__builtin_amdgcn_readfirstlane(*(const volatile int *)flag) != value) {}

@@ -31,7 +31,13 @@ for n in (int(a) for a in (sys.argv[1:] or ["512", "4096"])):
     b.set(P.F_PD_PTARGET, np.array([0.0045, 0, 0.4973, -1.1997, -1.5968] * 2) + rng.uniform(-0.3, 0.3, (n, 10)))
     b.set(P.F_PD_KP, np.tile([70, 70, 100, 100, 50] * 2, (n, 1)))
     b.set(P.F_PD_KD, np.tile([7, 7, 8, 8, 5] * 2, (n, 1)))
-    b.set_pd_mode(True)
+    if os.environ.get("DRIVE"):
+        # DRIVE=2 / 3: the drive-level PD of the benchmark (DRIVE_PD; DRIVE_PD_SAFE = the flagship's mode) instead of the exact-state PD --
+        # wave 1's drive-level pass, with the safety layer, is on its way to the barrier J then
+        b.forward()
+        b.set_drive_mode(int(os.environ["DRIVE"]))
+    else:
+        b.set_pd_mode(True)
     b.step(300); b.sync()
     ms = b.time_steps(NSUB, 50 if NSUB == 1 else 4) / NSUB
     if os.environ.get("TWO_STREAM_LOAD"):
@@ -100,6 +106,12 @@ for n in (int(a) for a in (sys.argv[1:] or ["512", "4096"])):
                          ("w1 WAIT at F", 35, 36), ("w1 com+cinert+cdof", 36, 2), ("w1 crba + M columns", 2, 3), ("w1 WAIT at X", 3, 38),
                          ("w1 drive io + factor", 38, 4), ("w1 wait cfrc + bias proj", 4, 6), ("w1 qfrc_smooth", 6, 7), ("w1 sensors1", 7, 47), ("w1 WAIT at J", 47, 39), ("w1 busy (F..factor done)", 36, 4), ("w0 F -> J (its parallel part)", 1, 8)]:
             print("  %-36s %9.0f cycles  %5.1f%%" % (nm, dur(a, c), 100 * dur(a, c) / tot0))
+        # slot 15 holds two lengths (csrc/pk_types.h): low word, wave 0's wait for cmd[6] in front of the staging store (inside "w0 halfsolve"
+        # above); high word, wave 1's sensor stage where it runs BEHIND J (inside "w1 factor M+hB ..." above; "w1 sensors1" is then empty)
+        w0wait, w1sens = (st[:, 15] & 0xffffffff).astype(float), (st[:, 15] >> 32).astype(float)
+        if w1sens.any():
+            for nm, v in [("w0 WAIT for w1 sensors (cmd[6])", w0wait), ("w1 sensors1 BEHIND J (to the publish)", w1sens)]:
+                print("  %-36s %9.0f cycles  %5.1f%%   (median %.0f, 90 %% %.0f, max %.0f)" % (nm, v.mean(), 100 * v.mean() / tot0, np.median(v), np.percentile(v, 90), v.max()))
         hw0, hw1 = st[:, 40], st[:, 41]
         simd = lambda h: (h >> 4) & 3
         cu = lambda h: ((h >> 32) << 12) | (((h >> 13) & 7) << 5) | (((h >> 12) & 1) << 4) | ((h >> 8) & 15)
