@@ -209,6 +209,19 @@ def _declare(L):
         L.phys_batch_obs_frames.argtypes = [vp, vp]
         L.phys_batch_obs_set_frames.argtypes = [vp, vp]
         L.phys_batch_debug_obs_launches.argtypes = [vp, c.POINTER(c.c_longlong)]
+    if hasattr(L, "phys_batch_reward"):   # (likewise)
+        L.phys_batch_reward_configure.argtypes = [vp, vp, c.c_int, c.c_int, c.c_double, c.c_double]
+        L.phys_batch_reward_bind.argtypes = [vp, vp, c.c_longlong]
+        L.phys_batch_reward_bind_terms.argtypes = [vp, vp, c.c_longlong, c.c_int]
+        L.phys_batch_reward_bind_input.argtypes = [vp, vp, c.c_int, c.c_longlong, c.c_int]
+        L.phys_batch_reward.argtypes = [vp, c.c_int, c.c_int, vp, vp]
+        L.phys_batch_reward_dim.argtypes = [vp, c.POINTER(c.c_int), c.POINTER(c.c_int), c.POINTER(c.c_int)]
+        L.phys_batch_reward_download.argtypes = [vp, vp, c.c_int, c.c_int]
+        L.phys_batch_reward_download_terms.argtypes = [vp, vp, c.c_int, c.c_int]
+        L.phys_batch_reward_returns.argtypes = [vp, vp]
+        L.phys_batch_reward_set_returns.argtypes = [vp, vp]
+        L.phys_batch_reward_final.argtypes = [vp, vp]
+        L.phys_batch_debug_reward_launches.argtypes = [vp, c.POINTER(c.c_longlong)]
     if hasattr(L, "phys_batch_step_sums_enable"):   # (likewise)
         L.phys_batch_step_sums_enable.argtypes = [vp, c.c_int]
     if hasattr(L, "phys_batch_download_progress"):   # (absent from older variant builds selected with CASSIE_LIB)

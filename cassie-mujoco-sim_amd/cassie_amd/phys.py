@@ -103,6 +103,56 @@ def _obs_dtype(dtype):
         pass
     return {"float32": 4, "float64": 8}.get(name, 0)
 
+
+# reward rows: the kinds, norms and shapes of a term (PHYS_REW_* in cassie_phys.h), what is no field of the batch, the layout of
+# phys_reward_term_t and the limits
+REW_VEC, REW_ROT_INV, REW_QUAT = range(3)
+REW_SUMSQ, REW_SUMABS, REW_MAXABS = range(3)
+REW_LINEAR, REW_EXP, REW_RATIONAL = range(3)
+REW_INPUT, REW_CONST, REW_NONE = -1, -2, -3
+REW_MAXTERMS, REW_MAXCOUNT = 64, 64
+REW_TERM_DTYPE = np.dtype([("kind", np.int32), ("field", np.int32), ("index", np.int32), ("count", np.int32), ("qfield", np.int32), ("qindex", np.int32),
+                           ("tfield", np.int32), ("tindex", np.int32), ("gfield", np.int32), ("gindex", np.int32), ("norm", np.int32), ("shape", np.int32),
+                           ("root", np.int32), ("vec", np.float64, 4), ("target", np.float64), ("dead", np.float64), ("k", np.float64), ("weight", np.float64)],
+                          align=True)
+
+
+def _rew(kind, field, index, count, qfield, qindex, tfield, tindex, gate, norm, shape, root, vec, target, dead, k, weight):
+    gfield, gindex = (REW_NONE, 0) if gate is None else gate
+    vec = tuple(float(x) for x in vec) + (0.0,) * (4 - len(vec))
+    return (int(kind), int(field), int(index), int(count), int(qfield), int(qindex), int(tfield), int(tindex), int(gfield), int(gindex), int(norm), int(shape),
+            int(bool(root)), vec, float(target), float(dead), float(k), float(weight))
+
+
+def rew_vec(field, index, count, target=0.0, tfield=REW_CONST, tindex=0, dead=0.0, norm=REW_SUMSQ, root=False, shape=REW_LINEAR, k=0.0, weight=1.0, gate=None):
+    """A REW_TERM_DTYPE entry: the error of field_row[index : index + count] against `target` (or tfield_row[tindex : tindex + count]),
+    through the deadband, the norm, the root and the shape, times weight and the gate (gfield, gindex)."""
+    return _rew(REW_VEC, field, index, count, 0, 0, tfield, tindex, gate, norm, shape, root, (), target, dead, k, weight)
+
+
+def rew_rot_inv(field, index, qfield, qindex, vec=(0.0, 0.0, 0.0), target=0.0, tfield=REW_CONST, tindex=0, dead=0.0, norm=REW_SUMSQ, root=False,
+                shape=REW_LINEAR, k=0.0, weight=1.0, gate=None):
+    """A REW_TERM_DTYPE entry: the three elements R(q)^T v, q = qfield_row[qindex : qindex + 4], v = field_row[index : index + 3] or `vec`
+    where field is REW_CONST, then as rew_vec."""
+    return _rew(REW_ROT_INV, field, index, 3, qfield, qindex, tfield, tindex, gate, norm, shape, root, vec, target, dead, k, weight)
+
+
+def rew_quat(field, index, tfield=REW_CONST, tindex=0, vec=(1.0, 0.0, 0.0, 0.0), shape=REW_LINEAR, k=0.0, weight=1.0, gate=None):
+    """A REW_TERM_DTYPE entry: s = 1 - (q . t)^2 with q = field_row[index : index + 4] and t = tfield_row[tindex : tindex + 4] or `vec`
+    where tfield is REW_CONST, then the shape, the weight and the gate."""
+    return _rew(REW_QUAT, field, index, 4, 0, 0, tfield, tindex, gate, REW_SUMSQ, shape, False, vec, 0.0, 0.0, k, weight)
+
+
+def rew_terms(terms):
+    """A list of term tuples (rew_vec / rew_rot_inv / rew_quat) or a structured array -> REW_TERM_DTYPE entries."""
+    if isinstance(terms, np.ndarray) and terms.dtype.names:
+        return np.ascontiguousarray(terms.astype(REW_TERM_DTYPE, copy=False)).reshape(-1)
+    terms = list(terms)
+    table = np.zeros(len(terms), dtype=REW_TERM_DTYPE)
+    for i, t in enumerate(terms):
+        table[i] = tuple(t[:13]) + (np.asarray(t[13], dtype=np.float64),) + tuple(t[14:])
+    return table
+
 # per-env physical parameters (CM_P_* in cm_model.h): what Batch.randomize takes
 (P_BODY_MASS, P_BODY_IPOS, P_BODY_INERTIA, P_DOF_DAMPING, P_GEOM_FRICTION,
  P_GEOM_POS, P_GEOM_QUAT, P_JNT_STIFFNESS, P_QPOS_SPRING) = range(9)
@@ -670,6 +720,93 @@ class Batch:
         """Diagnostics: the launches observe() has made so far."""
         a = ctypes.c_longlong(0)
         lib().phys_batch_debug_obs_launches(self._h, ctypes.byref(a))
+        return a.value
+
+    # ---- reward rows: errors, norms, shapes, weights, gates, the clip and the episode returns in one launch (phys_batch_reward) ----
+    def configure_rewards(self, terms, dtype=np.float32, lo=-np.inf, hi=np.inf):
+        """The terms of the reward: a list of rew_vec(...) / rew_rot_inv(...) / rew_quat(...) tuples or a structured array of
+        REW_TERM_DTYPE (none: release).  dtype: float32 or float64 rewards and term rows; lo, hi: the clip of the reward.  Allocates the
+        rewards, the returns and the final returns, zeroed; drops the bindings of the rewards, the term rows and the input."""
+        table = rew_terms(terms)
+        assert REW_TERM_DTYPE.itemsize == 120
+        if lib().phys_batch_reward_configure(self._h, table.ctypes.data if table.size else None, int(table.size), _obs_dtype(dtype), float(lo), float(hi)) != 0:
+            self._obs_fail("configure_rewards")
+        self._rew_np = np.float64 if _obs_dtype(dtype) == 8 else np.float32
+
+    def bind_rewards(self, device_ptr, stride=1):
+        """The rewards in caller-owned HBM of the configured dtype, `stride` elements between two envs'; None: the batch's own again."""
+        if lib().phys_batch_reward_bind(self._h, device_ptr, int(stride) if device_ptr else 0) != 0:
+            self._obs_fail("bind_rewards")
+
+    def bind_reward_terms(self, device_ptr=None, row_stride=None, own=False):
+        """Every term's contribution [nenv][nterms]: in caller-owned HBM, `row_stride` elements (default: nterms) between two envs' rows;
+        or, with own=True, in rows of the batch's own; neither: none are written (the state after configure_rewards)."""
+        stride = int(row_stride if row_stride is not None else self.reward_dim()[0]) if device_ptr else 0
+        if lib().phys_batch_reward_bind_terms(self._h, device_ptr, stride, 1 if own else 0) != 0:
+            self._obs_fail("bind_reward_terms")
+
+    def bind_reward_input(self, device_ptr, dim=0, row_stride=None, dtype=np.float32):
+        """The caller's per-env array the REW_INPUT terms read: [nenv] rows of `dim` float32 / float64 elements, `row_stride` elements
+        apart (default: dim); it may be the observation's input.  None un-binds."""
+        if lib().phys_batch_reward_bind_input(self._h, device_ptr, int(dim), int(dim if row_stride is None else row_stride), _obs_dtype(dtype)) != 0:
+            self._obs_fail("bind_reward_input")
+
+    def reward(self, env0=0, n=None, reset_ptr=None, stream=None):
+        """One launch on `stream` (default: the batch's own), in order with the step launches there: the reward, the term rows and the
+        return of every env of [env0, env0 + n).  reset_ptr: an int32 device array [n] (the range's slice of EP_DONE as the previous
+        policy step's end_episodes left it), non-zero = the env's return moves to the final returns and restarts.  Call it in front of
+        end_episodes.  No host synchronisation."""
+        n = self.nenv - env0 if n is None else n
+        if lib().phys_batch_reward(self._h, int(env0), int(n), reset_ptr, stream) != 0:
+            self._obs_fail("reward")
+
+    def reward_dim(self):
+        """(nterms, bytes of an element, whether term rows are written)."""
+        a, d, t = ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int(0)
+        if lib().phys_batch_reward_dim(self._h, ctypes.byref(a), ctypes.byref(d), ctypes.byref(t)) != 0:
+            self._obs_fail("reward_dim")
+        return a.value, d.value, bool(t.value)
+
+    def rewards(self, env0=0, n=None):
+        """The rewards [env0, env0 + n) downloaded, in the configured dtype."""
+        n = self.nenv - env0 if n is None else n
+        self.reward_dim()
+        out = np.empty(n, dtype=self._rew_np)
+        if lib().phys_batch_reward_download(self._h, out.ctypes.data, int(env0), int(n)) != 0:
+            self._obs_fail("rewards")
+        return out
+
+    def reward_terms(self, env0=0, n=None):
+        """The term rows [env0, env0 + n) downloaded: [n][nterms] in the configured dtype."""
+        n = self.nenv - env0 if n is None else n
+        out = np.empty((n, self.reward_dim()[0]), dtype=self._rew_np)
+        if lib().phys_batch_reward_download_terms(self._h, out.ctypes.data, int(env0), int(n)) != 0:
+            self._obs_fail("reward_terms")
+        return out
+
+    def returns(self):
+        """The running return of every env's episode (float64 [nenv])."""
+        out = np.empty(self.nenv, dtype=np.float64)
+        if lib().phys_batch_reward_returns(self._h, out.ctypes.data) != 0:
+            self._obs_fail("returns")
+        return out
+
+    def set_returns(self, returns):
+        a = np.ascontiguousarray(returns, dtype=np.float64).reshape(self.nenv)
+        if lib().phys_batch_reward_set_returns(self._h, a.ctypes.data) != 0:
+            self._obs_fail("set_returns")
+
+    def final_returns(self):
+        """The return of the last episode of every env that ended (float64 [nenv])."""
+        out = np.empty(self.nenv, dtype=np.float64)
+        if lib().phys_batch_reward_final(self._h, out.ctypes.data) != 0:
+            self._obs_fail("final_returns")
+        return out
+
+    def reward_launches(self):
+        """Diagnostics: the launches reward() has made so far."""
+        a = ctypes.c_longlong(0)
+        lib().phys_batch_debug_reward_launches(self._h, ctypes.byref(a))
         return a.value
 
     def set_pd_mode(self, on=True):

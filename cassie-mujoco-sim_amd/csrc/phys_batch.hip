@@ -147,6 +147,16 @@ struct phys_batch {
     long long obs_srow = 0;
     DevBuf<unsigned> d_obs_frames;
     long long obs_launches = 0;     /* launches of cassie_obs_kernel (phys_batch_debug_obs_launches) */
+    /* reward rows (phys_batch_reward_configure): the record (reward.nterms 0: not configured; its pointers are filled in at the launch,
+     * from the buffers), the term table with the fields as slots, the rewards (the batch's own or a caller's, floats or doubles) with their
+     * stride in elements, the term rows (empty: not written) with theirs, the per-env returns and final returns.  No stepping launch reads
+     * any of it */
+    ck::RewardCfg reward = {};
+    DevBuf<ck::RewardTerm> d_reward_terms;
+    DevBuf<char> d_reward, d_reward_trows;
+    long long reward_srew = 0, reward_sterm = 0;
+    DevBuf<double> d_reward_ret, d_reward_final;
+    long long reward_launches = 0;  /* launches of cassie_reward_kernel (phys_batch_debug_reward_launches) */
 };
 
 static bool hip_ok(hipError_t e, const char *what) {
@@ -1591,6 +1601,141 @@ int phys_batch_obs_set_frames(phys_batch_t *b, const unsigned *host) {
 int phys_batch_debug_obs_launches(const phys_batch_t *b, long long *launches) {
     if (!b) return -1;
     if (launches) *launches = b->obs_launches;
+    return 0;
+}
+
+/* ------------------------------------------------ reward rows ---- */
+static_assert(sizeof(ck::RewardTerm) == sizeof(phys_reward_term_t) && offsetof(ck::RewardTerm, root) == offsetof(phys_reward_term_t, root) &&
+              offsetof(ck::RewardTerm, vec) == offsetof(phys_reward_term_t, vec) && offsetof(ck::RewardTerm, weight) == offsetof(phys_reward_term_t, weight),
+              "phys_reward_term_t is the term reward_configure reads");
+static_assert(PHYS_REW_VEC == ck::REW_VEC && PHYS_REW_ROT_INV == ck::REW_ROT_INV && PHYS_REW_QUAT == ck::REW_QUAT && PHYS_REW_SUMSQ == ck::REW_SUMSQ &&
+              PHYS_REW_SUMABS == ck::REW_SUMABS && PHYS_REW_MAXABS == ck::REW_MAXABS && PHYS_REW_LINEAR == ck::REW_LINEAR && PHYS_REW_EXP == ck::REW_EXP &&
+              PHYS_REW_RATIONAL == ck::REW_RATIONAL && PHYS_REW_INPUT == ck::REW_INPUT && PHYS_REW_CONST == ck::REW_CONST && PHYS_REW_NONE == ck::REW_NONE &&
+              PHYS_REW_MAXTERMS == ck::REWARD_MAXTERMS, "the header's numbers are reward_kernels.h's");
+/* the record of a launch: what was configured, with the pointers into the batch's buffers */
+static ck::RewardCfg reward_cfg_of(const phys_batch *b) {
+    ck::RewardCfg c = b->reward;
+    c.terms = b->d_reward_terms; c.rew = b->d_reward.get(); c.srew = b->reward_srew; c.trows = b->d_reward_trows.get(); c.sterm = b->reward_sterm;
+    c.ret = b->d_reward_ret; c.fin = b->d_reward_final;
+    return c;
+}
+int phys_batch_reward_configure(phys_batch_t *b, const phys_reward_term_t *terms, int nterms, int dtype, double lo, double hi) {
+    if (!b) return refuse("phys_batch_reward_configure", ck::REWARD_SIZE_REFUSAL);
+    int dims[PHYS_F_COUNT];
+    for (int k = 0; k < PHYS_F_COUNT; ++k) dims[k] = b->d_field[k] ? b->dim[k] : 0;
+    std::vector<ck::RewardTerm> table((size_t)ck::REWARD_MAXTERMS);
+    ck::RewardCfg cfg;
+    if (const char *why = ck::reward_configure(dims, PHYS_F_COUNT, PHYS_F_DEPTH, (const ck::RewardTerm *)terms, nterms, dtype, lo, hi, table.data(), cfg))
+        return refuse("phys_batch_reward_configure", why);
+    (void)hipSetDevice(b->device);
+    if (!quiesce(b)) return -1;  /* (launches in flight may be reading the table, or writing the rewards, that go away) */
+    if (nterms == 0) {
+        b->reward = {}; b->reward_srew = 0; b->reward_sterm = 0;
+        b->d_reward_terms.reset(); b->d_reward.reset(); b->d_reward_trows.reset(); b->d_reward_ret.reset(); b->d_reward_final.reset();
+        return 0;
+    }
+    const size_t n = (size_t)b->nenv;
+    DevBuf<ck::RewardTerm> tab;
+    DevBuf<char> rew;
+    DevBuf<double> ret, fin;
+    if (!tab.alloc((size_t)nterms, false, "reward terms")) return -1;
+    if (!hip_ok(hipMemcpy(tab, table.data(), sizeof(ck::RewardTerm) * (size_t)nterms, hipMemcpyHostToDevice), "hipMemcpy(reward terms)")) return -1;
+    if (!rew.alloc(n * (size_t)dtype, true, "rewards")) return -1;
+    if (!ret.alloc(n, true, "returns") || !fin.alloc(n, true, "final returns")) return -1;
+    b->d_reward_terms = std::move(tab); b->d_reward = std::move(rew); b->d_reward_ret = std::move(ret); b->d_reward_final = std::move(fin);
+    b->d_reward_trows.reset();
+    b->reward_srew = 1; b->reward_sterm = 0;
+    b->reward = cfg;   /* (no input bound, the rewards are the batch's own and no term rows are written: the bindings are dropped) */
+    return 0;
+}
+int phys_batch_reward_bind(phys_batch_t *b, void *device_ptr, long long stride) {
+    if (!b) { phys_set_last_error("phys_batch_reward_bind: no batch"); return -1; }
+    if (const char *why = ck::check_reward_bind(b->reward, device_ptr ? stride : 1, 1)) return refuse("phys_batch_reward_bind", why);
+    (void)hipSetDevice(b->device);
+    /* (as phys_batch_bind: launches already queued keep the pointer they were given; hipFree waits for the device by itself) */
+    if (device_ptr) { b->d_reward.borrow((char *)device_ptr); b->reward_srew = stride; }
+    else if (!b->d_reward.owned()) {
+        if (!b->d_reward.alloc((size_t)b->nenv * (size_t)b->reward.dtype, true, "rewards")) return -1;
+        b->reward_srew = 1;
+    }
+    return 0;
+}
+int phys_batch_reward_bind_terms(phys_batch_t *b, void *device_ptr, long long row_stride, int own) {
+    if (!b) { phys_set_last_error("phys_batch_reward_bind_terms: no batch"); return -1; }
+    const long long nt = b->reward.nterms;
+    if (const char *why = ck::check_reward_bind(b->reward, device_ptr ? row_stride : nt, nt > 1 ? nt : 1)) return refuse("phys_batch_reward_bind_terms", why);
+    (void)hipSetDevice(b->device);
+    if (device_ptr) { b->d_reward_trows.borrow((char *)device_ptr); b->reward_sterm = row_stride; }
+    else if (own) {
+        if (!b->d_reward_trows.owned() && !b->d_reward_trows.alloc((size_t)b->nenv * (size_t)nt * (size_t)b->reward.dtype, true, "reward term rows")) return -1;
+        b->reward_sterm = nt;
+    } else { b->d_reward_trows.reset(); b->reward_sterm = 0; }
+    return 0;
+}
+int phys_batch_reward_bind_input(phys_batch_t *b, const void *device_ptr, int dim, long long row_stride, int dtype) {
+    if (!b) { phys_set_last_error("phys_batch_reward_bind_input: no batch"); return -1; }
+    if (!device_ptr) { b->reward.input = nullptr; b->reward.input_dim = 0; b->reward.input_stride = 0; b->reward.input_dtype = 0; return 0; }
+    if (const char *why = ck::check_reward_input(b->reward, dim, row_stride, dtype)) return refuse("phys_batch_reward_bind_input", why);
+    b->reward.input = device_ptr; b->reward.input_dim = dim; b->reward.input_stride = (int)row_stride; b->reward.input_dtype = dtype;
+    return 0;
+}
+int phys_batch_reward(phys_batch_t *b, int env0, int n, const void *reset_ptr, void *stream) {
+    if (!b) { phys_set_last_error("phys_batch_reward: no batch"); return -1; }
+    const ck::RewardCfg c = reward_cfg_of(b);
+    ck::ObsField fields[PHYS_F_COUNT];
+    obs_fields_of(b, fields);
+    if (const char *why = ck::check_reward_call(c, fields, PHYS_F_COUNT, b->nenv, env0, n)) return refuse("phys_batch_reward", why);
+    (void)hipSetDevice(b->device);
+    if (n == 0) return 0;
+    hipStream_t s = launch_stream(b, stream);
+    hipLaunchKernelGGL(ck::cassie_reward_kernel, dim3((unsigned)ck::reward_grid(n)), dim3(WV_WAVE), 0, s, ck::make_reward_io(c, fields, env0, n, (const int *)reset_ptr));
+    if (!hip_ok(hipGetLastError(), "cassie_reward_kernel launch")) return -1;
+    ++b->reward_launches;
+    return 0;
+}
+int phys_batch_reward_dim(const phys_batch_t *b, int *nterms, int *dtype, int *term_rows) {
+    if (!b || b->reward.nterms < 1) { phys_set_last_error("phys_batch_reward_dim: not configured (phys_batch_reward_configure first)"); return -1; }
+    if (nterms) *nterms = b->reward.nterms;
+    if (dtype) *dtype = b->reward.dtype;
+    if (term_rows) *term_rows = b->d_reward_trows ? 1 : 0;
+    return 0;
+}
+/* rows of `width` elements, `stride` elements apart on the device, to dense host memory */
+static int reward_rows_down(phys_batch *b, const char *entry, const char *base, size_t width, size_t stride, void *host, int env0, int n) {
+    if (!range_ok(b, env0, n)) return refuse(entry, "env range out of bounds");
+    (void)hipSetDevice(b->device);
+    if (!quiesce(b)) return -1;
+    if (n == 0) return 0;
+    const size_t el = (size_t)b->reward.dtype;
+    return hip_ok(hipMemcpy2D(host, el * width, base + el * stride * (size_t)env0, el * stride, el * width, (size_t)n, hipMemcpyDeviceToHost), entry) ? 0 : -1;
+}
+int phys_batch_reward_download(phys_batch_t *b, void *host, int env0, int n) {
+    if (!b || !host || b->reward.nterms < 1 || !b->d_reward) { phys_set_last_error("phys_batch_reward_download: bad arguments, or not configured (phys_batch_reward_configure first)"); return -1; }
+    return reward_rows_down(b, "phys_batch_reward_download", b->d_reward.get(), 1, (size_t)b->reward_srew, host, env0, n);
+}
+int phys_batch_reward_download_terms(phys_batch_t *b, void *host, int env0, int n) {
+    if (!b || !host || b->reward.nterms < 1) { phys_set_last_error("phys_batch_reward_download_terms: bad arguments, or not configured (phys_batch_reward_configure first)"); return -1; }
+    if (!b->d_reward_trows) return refuse("phys_batch_reward_download_terms", "no term rows (phys_batch_reward_bind_terms first)");
+    return reward_rows_down(b, "phys_batch_reward_download_terms", b->d_reward_trows.get(), (size_t)b->reward.nterms, (size_t)b->reward_sterm, host, env0, n);
+}
+int phys_batch_reward_returns(phys_batch_t *b, double *host) {
+    if (!b || !host || !b->d_reward_ret) { phys_set_last_error("phys_batch_reward_returns: bad arguments, or not configured (phys_batch_reward_configure first)"); return -1; }
+    (void)hipSetDevice(b->device);
+    return quiesce(b) && hip_ok(hipMemcpy(host, b->d_reward_ret, sizeof(double) * (size_t)b->nenv, hipMemcpyDeviceToHost), "returns download") ? 0 : -1;
+}
+int phys_batch_reward_set_returns(phys_batch_t *b, const double *host) {
+    if (!b || !host || !b->d_reward_ret) { phys_set_last_error("phys_batch_reward_set_returns: bad arguments, or not configured (phys_batch_reward_configure first)"); return -1; }
+    (void)hipSetDevice(b->device);
+    return quiesce(b) && hip_ok(hipMemcpy(b->d_reward_ret, host, sizeof(double) * (size_t)b->nenv, hipMemcpyHostToDevice), "returns upload") ? 0 : -1;
+}
+int phys_batch_reward_final(phys_batch_t *b, double *host) {
+    if (!b || !host || !b->d_reward_final) { phys_set_last_error("phys_batch_reward_final: bad arguments, or not configured (phys_batch_reward_configure first)"); return -1; }
+    (void)hipSetDevice(b->device);
+    return quiesce(b) && hip_ok(hipMemcpy(host, b->d_reward_final, sizeof(double) * (size_t)b->nenv, hipMemcpyDeviceToHost), "final returns download") ? 0 : -1;
+}
+int phys_batch_debug_reward_launches(const phys_batch_t *b, long long *launches) {
+    if (!b) return -1;
+    if (launches) *launches = b->reward_launches;
     return 0;
 }
 

@@ -1,12 +1,12 @@
 /*
- * small_launch.h -- how the kernels around the step kernel (small_kernels.h, surface_kernels.h, depth_kernel.h, ray_kernel.h, episode_kernels.h, probe_kernels.h, obs_kernels.h) are
+ * small_launch.h -- how the kernels around the step kernel (small_kernels.h, surface_kernels.h, depth_kernel.h, ray_kernel.h, episode_kernels.h, probe_kernels.h, obs_kernels.h, reward_kernels.h) are
  * launched: the records a kernel's arguments are built from, one builder per kernel that returns its filled argument struct for an env
  * range, the grid of every launch, and the checks of what a caller configures, each returning the message of its refusal (null: fine).
  * Pure host code, no HIP runtime calls, in the spirit of step_policy.h: the launcher (phys_batch.hip) keeps the records in the batch,
  * prefixes a message with its entry point's name and launches what a builder returns on the grid given here; the wave emulator's entry
  * points (tests/emu) fill the same records from their arguments and go through the same builders, grids and checks, so a CPU test of
  * one of these kernels also runs the launcher's refusals, grid and choice of kernel (tests/test_small_launch.py pins them one by one).
- * No field of ScanIO, DepthIO, RayIO, EpisodeIO, ResetIO, DeriveIO, SetConstIO, StateIO, ProbeIO or ObsIO is assigned anywhere else.
+ * No field of ScanIO, DepthIO, RayIO, EpisodeIO, ResetIO, DeriveIO, SetConstIO, StateIO, ProbeIO, ObsIO or RewardIO is assigned anywhere else.
  */
 #ifndef CASSIE_SMALL_LAUNCH_H
 #define CASSIE_SMALL_LAUNCH_H
@@ -19,6 +19,7 @@
 #include "obs_kernels.h"
 #include "probe_kernels.h"
 #include "ray_kernel.h"
+#include "reward_kernels.h"
 #include "small_kernels.h"
 #include "state_kernels.h"
 
@@ -91,6 +92,20 @@ struct ObsCfg {
 };
 /* what the batch holds of a field: its rows (null: the batch does not hold it yet), their length and the doubles between two of them */
 struct ObsField { const double *base; int dim, stride; };
+
+/* the reward rows (phys_batch_reward_configure; nterms 0: not configured): the terms, the type of the rewards and the term rows (OBS_F32 /
+ * OBS_F64), the clip; the sources of a call as the observation's -- slot s is field slot_field[s] (or REW_INPUT), whose row held
+ * slot_dim[s] elements when the terms were checked against it -- and the elements the terms need of the caller's input array.  Then what
+ * the caller names once a kernel reads them: the term table [nterms] with the fields as slots, the rewards with their stride in
+ * elements, the term rows (null: not written) with theirs, the returns and final returns [nenv], and the caller's input array (null:
+ * none bound) with its row length, row stride and type */
+struct RewardCfg {
+    int nterms, dtype, nslots, input_need;
+    double lo, hi;
+    int slot_field[REWARD_MAXSLOTS], slot_dim[REWARD_MAXSLOTS];
+    const RewardTerm *terms; void *rew; long long srew; void *trows; long long sterm; double *ret, *fin;
+    const void *input; int input_dim, input_stride, input_dtype;
+};
 
 /* ---- the row of a full state ---- */
 
@@ -344,6 +359,98 @@ inline const char *check_obs_call(const ObsCfg &c, const ObsField *fields, int n
     }
     return nullptr;
 }
+/* (what the launcher also answers a call without a batch) */
+constexpr const char *REWARD_SIZE_REFUSAL = "0 .. 64 terms (0 releases them), rewards of PHYS_OBS_F32 or PHYS_OBS_F64";
+/* the reward's configuration: checks the caller's terms [nterms] against the row lengths the batch holds now (as obs_configure: field_dim
+ * [nfields], 0: a field it does not hold yet; depth_field: the one field that is never a source), writes the table a launch reads (table
+ * [REWARD_MAXTERMS]: the terms with their fields replaced by slots) and fills c but for what the caller names later.  nterms 0 is
+ * accepted and leaves c empty: the launcher releases what it holds.  The emulator goes through the same */
+inline const char *reward_configure(const int *field_dim, int nfields, int depth_field, const RewardTerm *terms, int nterms, int dtype, double lo, double hi,
+                                    RewardTerm *table, RewardCfg &c) {
+    if (nterms < 0 || nterms > REWARD_MAXTERMS || (nterms > 0 && (!terms || !table))) return REWARD_SIZE_REFUSAL;
+    c = {};
+    if (nterms == 0) return nullptr;
+    if (dtype != OBS_F32 && dtype != OBS_F64) return "the rewards' dtype is PHYS_OBS_F32 or PHYS_OBS_F64";
+    if (!(lo <= hi)) return "lo <= hi (either may be infinite, neither NaN)";
+    auto slot_of = [&c](int field, int dim) {
+        for (int s = 0; s < c.nslots; ++s) if (c.slot_field[s] == field) return s;
+        if (c.nslots == REWARD_MAXSLOTS) return -1;
+        c.slot_field[c.nslots] = field; c.slot_dim[c.nslots] = dim;
+        return c.nslots++;
+    };
+    /* the row length of a source as a term may index it (-1: no such source; 0: not held yet; the input's is checked at the call) */
+    auto dim_of = [&](int field) { return field == REW_INPUT ? 0x7fffffff : field >= 0 && field < nfields && field != depth_field ? field_dim[field] : -1; };
+    const char *why = nullptr;
+    /* a slice [index, index + len) of a source -> its slot (-1 with why set: refused) */
+    auto slice = [&](int field, int index, int len, const char *beyond) {
+        if (field == depth_field) { why = "PHYS_F_DEPTH is no source of a reward (images are not terms)"; return -1; }
+        const int dim = dim_of(field);
+        if (dim < 0) { why = "a term's field, qfield, tfield and gfield are PHYS_F_* fields of the batch or PHYS_REW_INPUT (PHYS_REW_CONST and PHYS_REW_NONE where the definition allows them)"; return -1; }
+        if (dim == 0) { why = "a term reads a field the batch does not hold yet (the scan, the rays, the probes, the step sums, the derived block: configure or enable them first)"; return -1; }
+        if (index < 0 || (long long)index + len > dim) { why = beyond; return -1; }
+        const int s = slot_of(field, dim == 0x7fffffff ? 0 : dim);
+        if (s < 0) { why = "more than 16 distinct source fields"; return -1; }
+        if (field == REW_INPUT && index + len > c.input_need) c.input_need = index + len;
+        return s;
+    };
+    for (int t = 0; t < nterms; ++t) {
+        const RewardTerm &d = terms[t];
+        RewardTerm &o = table[t];
+        o = d;
+        if (d.kind != REW_VEC && d.kind != REW_ROT_INV && d.kind != REW_QUAT) return "a term's kind is PHYS_REW_VEC, PHYS_REW_ROT_INV or PHYS_REW_QUAT";
+        if (d.shape != REW_LINEAR && d.shape != REW_EXP && d.shape != REW_RATIONAL) return "a term's shape is PHYS_REW_LINEAR, PHYS_REW_EXP or PHYS_REW_RATIONAL";
+        const bool rot = d.kind == REW_ROT_INV, quat = d.kind == REW_QUAT;
+        if (!quat && d.norm != REW_SUMSQ && d.norm != REW_SUMABS && d.norm != REW_MAXABS) return "a term's norm is PHYS_REW_SUMSQ, PHYS_REW_SUMABS or PHYS_REW_MAXABS";
+        if ((d.field == REW_CONST && !rot) || (rot && d.qfield == REW_CONST) || d.gfield == REW_CONST)
+            return "PHYS_REW_CONST is a tfield, or the field of a PHYS_REW_ROT_INV term (never a VEC's or a QUAT's field, never a qfield or a gfield)";
+        if (d.field == REW_NONE || (rot && d.qfield == REW_NONE) || d.tfield == REW_NONE) return "PHYS_REW_NONE is a gfield only (no gate)";
+        if (d.kind == REW_VEC && (d.count < 1 || d.count > REWARD_MAXCOUNT)) return "a VEC term takes 1 .. 64 elements";
+        const int count = rot ? 3 : quat ? 4 : d.count;
+        if (!(std::isfinite(d.dead) && std::isfinite(d.k) && std::isfinite(d.weight))) return "a term needs a finite dead, k and weight";
+        if (!quat && d.tfield == REW_CONST && !std::isfinite(d.target)) return "a constant target must be finite";
+        const int nvec = rot && d.field == REW_CONST ? 3 : quat && d.tfield == REW_CONST ? 4 : 0;
+        for (int k = 0; k < nvec; ++k) if (!std::isfinite(d.vec[k])) return "a constant vector must be finite";
+        if (d.dead < 0) return "dead is a half width: >= 0";
+        if (d.k < 0) return "k >= 0 (the shapes fall with the error)";
+        if (d.field != REW_CONST) {
+            o.field = slice(d.field, d.index, count, rot ? "index + 3 lies beyond the field's row" : quat ? "index + 4 lies beyond the field's row" : "index + count lies beyond the field's row");
+            if (o.field < 0) return why;
+        }
+        if (rot) { o.qfield = slice(d.qfield, d.qindex, 4, "qindex + 4 lies beyond the field's row"); if (o.qfield < 0) return why; }
+        else { o.qfield = 0; o.qindex = 0; }
+        if (d.tfield != REW_CONST) { o.tfield = slice(d.tfield, d.tindex, count, "tindex + the term's elements lies beyond the target's row"); if (o.tfield < 0) return why; }
+        if (d.gfield != REW_NONE) { o.gfield = slice(d.gfield, d.gindex, 1, "gindex lies beyond the gate's row"); if (o.gfield < 0) return why; }
+        o.count = count;
+    }
+    c.nterms = nterms; c.dtype = dtype; c.lo = lo; c.hi = hi;
+    return nullptr;
+}
+/* what phys_batch_reward_bind / _bind_terms / _bind_input refuse.  min_stride: 1 for the rewards, nterms for the term rows */
+inline const char *check_reward_bind(const RewardCfg &c, long long stride, long long min_stride) {
+    if (c.nterms < 1) return "not configured (phys_batch_reward_configure first)";
+    if (stride < min_stride) return min_stride > 1 ? "a row stride of at least the terms" : "an element stride of at least 1";
+    return nullptr;
+}
+inline const char *check_reward_input(const RewardCfg &c, int dim, long long row_stride, int dtype) {
+    if (c.nterms < 1) return "not configured (phys_batch_reward_configure first)";
+    if (dim < 1 || row_stride < dim || row_stride > 0x7fffffff) return "an input of at least one element a row and a row stride of at least that";
+    if (dtype != OBS_F32 && dtype != OBS_F64) return "the input's dtype is PHYS_OBS_F32 or PHYS_OBS_F64";
+    return nullptr;
+}
+/* what a reward call refuses; fields [nfields]: what the batch holds NOW */
+inline const char *check_reward_call(const RewardCfg &c, const ObsField *fields, int nfields, int nenv, int env0, int n) {
+    if (c.nterms < 1 || !c.terms || !c.rew || !c.ret || !c.fin) return "not configured (phys_batch_reward_configure first)";
+    if (env0 < 0 || n < 0 || (long long)env0 + n > nenv) return "env range out of bounds";
+    for (int s = 0; s < c.nslots; ++s) {
+        const int f = c.slot_field[s];
+        if (f == REW_INPUT) {
+            if (!c.input) return "a PHYS_REW_INPUT term and no input bound (phys_batch_reward_bind_input first)";
+            if (c.input_dim < c.input_need) return "the bound input's rows are shorter than the PHYS_REW_INPUT terms reach";
+        } else if (f < 0 || f >= nfields || !fields[f].base || fields[f].dim != c.slot_dim[s])
+            return "the row length of a source field has changed since phys_batch_reward_configure (configure again)";
+    }
+    return nullptr;
+}
 /* the bank of full states: what phys_batch_state_configure / _bind refuse (the view tells what the batch has), and what a save or a
  * restore refuses */
 inline const char *state_configure(const BatchView &v, int nslots, int groups) {
@@ -375,6 +482,8 @@ inline int state_grid(int n) { return n < STATE_GRID ? n : STATE_GRID; }
 inline int probe_grid(int n) { return n < PROBE_GRID ? n : PROBE_GRID; }
 /* one wave per env up to OBS_GRID workgroups, which then walk the range: few, as the probes' (obs_kernels.h) */
 inline int obs_grid(int n) { return n < OBS_GRID ? n : OBS_GRID; }
+/* one wave per 64 envs (a lane takes an env) up to REWARD_GRID workgroups, which then walk the range (reward_kernels.h) */
+inline int reward_grid(int n) { const long long w = ((long long)n + WV_WAVE - 1) / WV_WAVE; return w < REWARD_GRID ? (int)w : REWARD_GRID; }
 /* a job is (env, tile of DEPTH_TILE x DEPTH_TILE pixels); a fixed grid walks the job list (a first choice: depth_kernel.h) */
 inline int depth_grid(int n, int width, int height) {
     const int T = DEPTH_TILE;
@@ -471,6 +580,21 @@ inline ObsIO make_obs_io(const ObsCfg &c, const ObsField *fields, int env0, int 
         else io.src[s] = {fields[f].base, fields[f].stride, 0, 0};
     }
     io.rows = c.rows; io.srow = c.srow; io.frames = c.frames; io.refill = refill;
+    return io;
+}
+/* cassie_reward_kernel's: the sources of the record's slots where the batch reads them today (as make_obs_io), the term table, the
+ * rewards, the term rows, the returns and the clip */
+inline RewardIO make_reward_io(const RewardCfg &c, const ObsField *fields, int env0, int n, const int *reset) {
+    RewardIO io = zeroed<RewardIO>();
+    io.env0 = env0; io.n = n; io.nterms = c.nterms; io.f32 = c.dtype == OBS_F32;
+    io.lo = c.lo; io.hi = c.hi;
+    io.terms = c.terms;
+    for (int s = 0; s < c.nslots; ++s) {
+        const int f = c.slot_field[s];
+        if (f == REW_INPUT) io.src[s] = {c.input, c.input_stride, c.input_dtype == OBS_F32, 0};
+        else io.src[s] = {fields[f].base, fields[f].stride, 0, 0};
+    }
+    io.rew = c.rew; io.srew = c.srew; io.trows = c.trows; io.sterm = c.sterm; io.ret = c.ret; io.fin = c.fin; io.reset = reset;
     return io;
 }
 inline int episode_row_dim(const BatchView &v) { return v.nq + v.nv + v.nsd + v.nu + v.nv; }

@@ -451,7 +451,8 @@ size_t phys_sizeof_episode_rules(void);
  * the scan, depth and ray fields / PHYS_F_STEP_SUMS, PHYS_EP_DONE / _REASON / _TERMINAL, the placement arrays, and what the launcher
  * keeps per env for one launch or for speed alone (progress, chunk words, hand-over lists, launch order and cost: none changes a result).
  * Neither are the observation rows and their per-env frame counts (phys_batch_obs below): a caller that rewinds an env keeps or sets
- * them itself (phys_batch_obs_set_frames; a refill entry refills the env's history from its restored state).
+ * them itself (phys_batch_obs_set_frames; a refill entry refills the env's history from its restored state).  Nor are the running and
+ * final returns of the reward rows (phys_batch_reward below: phys_batch_reward_returns / _set_returns).
  *
  *   phys_batch_state_configure  allocates a bank of nslots >= 1 zeroed rows in HBM; waits for the batch's streams; calling it again
  *                               replaces the bank (and drops a binding).
@@ -748,6 +749,105 @@ int phys_batch_obs_download(phys_batch_t *b, void *host, int env0, int n);
 int phys_batch_obs_frames(phys_batch_t *b, unsigned *host /*[nenv]*/);
 int phys_batch_obs_set_frames(phys_batch_t *b, const unsigned *host /*[nenv]*/);
 int phys_batch_debug_obs_launches(const phys_batch_t *b, long long *launches);
+
+/* REWARD ROWS: the scalar a training loop hands its policy for a step, made on the device by ONE launch per env range from a configured
+ * table of at most PHYS_REW_MAXTERMS TERMS: per env the reward, optionally every term's contribution, and the running return of the
+ * env's episode.  Every arithmetic step below is one individually rounded fp64 operation (multiply, add, subtract, divide, square root
+ * to nearest even; no fused multiply-add, no reassociation), and every sum is sequential from +0.0 in index order: the device, the wave
+ * emulator and a numpy restatement agree on every bit, so a reward can be replayed, rewound with the state bank and compared across ranks.
+ * SOURCES are the observation's: field / qfield / tfield / gfield name any PHYS_F_* field but PHYS_F_DEPTH, with the row length the batch
+ *   holds for it when the terms are configured (a field that is sized later must have been configured or enabled before), read where the
+ *   batch reads it at the call (its own buffer, or the caller's bound tensor with its row stride); or PHYS_REW_INPUT, the caller's own
+ *   per-env array bound with phys_batch_reward_bind_input as floats or doubles, floats widened exactly: commands, a reference pose for
+ *   this step, clock coefficients, the previous and current action.  It may be the tensor bound as the observation's input.  At most 16
+ *   distinct sources.
+ * A TERM (phys_reward_term_t) makes ELEMENTS x[j] by its kind:
+ *   PHYS_REW_VEC      x[j] = field_row[index + j], j < count, 1 <= count <= 64.
+ *   PHYS_REW_ROT_INV  three elements, x = R(q)^T v exactly as PHYS_OBS_ROT_INV forms it above: q the four values qfield_row[qindex ..
+ *                     qindex + 3] as stored, v = field_row[index .. index + 2], or vec[0 .. 2] where field == PHYS_REW_CONST (the base
+ *                     velocity in the body frame against a commanded one).  count is ignored.
+ *   PHYS_REW_QUAT     four values q = field_row[index .. index + 3] and four t = tfield_row[tindex .. tindex + 3], or vec[0 .. 3] where
+ *                     tfield == PHYS_REW_CONST, both as stored: d = ((q0 t0 + q1 t1) + q2 t2) + q3 t3 and s = 1 - d d.  This kind skips
+ *                     the errors, the norm and the root below (count, target, dead, norm and root are ignored).
+ *   ERRORS (VEC, ROT_INV)  e[j] = x[j] - t[j], with t[j] = target where tfield == PHYS_REW_CONST, else tfield_row[tindex + j].  Where
+ *                     dead > 0: m = |e[j]| - dead; e[j] = m < 0 ? 0 : m (a compare and a select: a NaN passes).
+ *   NORM              PHYS_REW_SUMSQ: s = sum_j e[j] e[j];  PHYS_REW_SUMABS: s = sum_j |e[j]|;  PHYS_REW_MAXABS: s = +0.0, then for every j
+ *                     in order  if (|e[j]| > s) s = |e[j]|  (a NaN element is passed over).  Where root != 0: s = sqrt(s).
+ *   SHAPE             PHYS_REW_LINEAR: v = s;  PHYS_REW_EXP: v = expn(k s);  PHYS_REW_RATIONAL: v = 1 / (1 + k s).
+ *   CONTRIBUTION      c = weight v; where gfield != PHYS_REW_NONE: c = c gfield_row[gindex] (a clock coefficient of the input, a touch
+ *                     count of the step sums).
+ * THE REWARD: r = sum_t c_t in term order; then r = r < lo ? lo : (r > hi ? hi : r) with the configured bounds (infinities are allowed; a
+ *   NaN passes).  The element written is r, or (float)r rounded to nearest even where the rewards are PHYS_OBS_F32; the optional TERM ROWS
+ *   [nenv][nterms] take c_t with the same cast.
+ * RETURNS, always fp64: the call takes an optional int32 DEVICE array reset[n], entry i for env env0 + i.  An env whose entry is non-zero
+ *   first does  final[env] = ret[env]; ret[env] = +0.0;  then every env of the range does  ret[env] = ret[env] + r  (the clipped r,
+ *   before the cast).
+ * ORDER IN A POLICY STEP: the step launch; the launches that make sources (probe, rays, scan); phys_batch_reward;
+ *   phys_batch_end_episodes; phys_batch_obs.  The reward must see the state that ENDED an episode, not the restarted one, so it runs in
+ *   front of phys_batch_end_episodes, and `reset` is the range's slice of PHYS_EP_DONE as the PREVIOUS policy step's
+ *   phys_batch_end_episodes left it (the words hold until the next one on that stream): the reward of an episode's last step is added to
+ *   its return, and the next call moves that return to `final`.  A termination bonus is the caller's one statement on r and the done
+ *   words.  ret and final are not in a state-bank row: as with the observation's frame counts, a caller that rewinds an env keeps or sets
+ *   them itself (phys_batch_reward_returns / _set_returns).
+ * NaN AND DIVERGED ENVS: values flow through to the env's own reward, term row and return; nothing indexes memory by a value.
+ * expn(a) ~ exp(-a), a = k s, k >= 0 finite:
+ *   1. a NaN gives NaN.
+ *   2. a > 708 gives +0.0 (the smallest result of the branch below is normal: no result depends on the denormal mode); a < -708 -- only a
+ *      QUAT term of quaternions far from unit length gets there -- gives +inf.
+ *   3. n = rint(a * 1.44269504088896338700e+00), to nearest even.
+ *   4. rho = (a - n * 6.93147180369123816490e-01) - n * 1.90821492927058770002e-10   (the first product is exact).
+ *   5. p = the degree-13 polynomial in x = -rho whose coefficient i is the double nearest 1/i!, by Horner from coefficient 13 down: p = c13;
+ *      p = p x + c_i for i = 12 .. 0, one multiply and one add each.
+ *   6. v = p 2^-n, exact.
+ *   Against exp(-a) to 60 digits on 60 001 points over [0, 708] and 600 small arguments down to 1e-12 the largest error is 1.06 ulp of
+ *   the exact value; expn(0) = 1, and sorted arguments never produce an increase (tests/test_rewards.py).
+ *   phys_batch_reward_configure   terms [nterms] (host memory), the type of the rewards and term rows (PHYS_OBS_F32 / PHYS_OBS_F64) and the
+ *                               clip.  Refuses, with a message in phys_last_error(): an unknown kind, norm or shape, an unknown field,
+ *                               PHYS_F_DEPTH, a field the batch does not hold yet, a slice beyond a row, a count outside 1 .. 64,
+ *                               PHYS_REW_CONST anywhere but in a tfield or a ROT_INV's field, PHYS_REW_NONE anywhere but in a gfield, a
+ *                               non-finite target, vec, dead, k or weight, dead < 0, k < 0, lo > hi, more than PHYS_REW_MAXTERMS terms, an
+ *                               unknown dtype, more than 16 sources.  Allocates the table, the rewards, ret and final (zeroed); drops the
+ *                               bindings of the rewards, the term rows and the input; waits for the batch's streams.  nterms 0 releases.
+ *   phys_batch_reward_bind        the rewards in caller-owned HBM of the configured type, `stride` elements (>= 1) between two envs': a
+ *                               column of a wider tensor.  NULL: the batch's own again, zeroed.
+ *   phys_batch_reward_bind_terms  the term rows: caller-owned HBM with row_stride (>= nterms) elements between two envs' rows; or NULL with
+ *                               own != 0: rows of the batch's own, zeroed; or NULL with own == 0: none are written (the state after
+ *                               a configure call).
+ *   phys_batch_reward_bind_input  the caller's per-env array [nenv] rows of dim elements, row_stride elements apart, PHYS_OBS_F32 / _F64.
+ *                               NULL un-binds.
+ *   phys_batch_reward             ONE launch of cassie_reward_kernel over [env0, env0 + n) on `stream` (NULL: the batch's own), in order
+ *                               with the launches there.  No host synchronisation, no allocation, no read on the host.  Writes the
+ *                               rewards, term rows, ret and (where reset says so) final of the range and nothing else.  Refuses: not
+ *                               configured, a range outside the batch, a source field whose row length is no longer what it was at the
+ *                               configure call, a PHYS_REW_INPUT term with nothing bound or with a bound dim its terms reach beyond.
+ *   phys_batch_reward_dim         nterms, the dtype and whether term rows are written (any may be NULL) -> 0, -1 when not configured.
+ *   phys_batch_reward_download / _download_terms   rewards [env0, env0 + n) / their term rows to dense host memory [n] / [n][nterms] of the
+ *                               configured type; wait for the streams.
+ *   phys_batch_reward_returns / _set_returns / _final   ret [nenv] to and from the host, final [nenv] to the host (doubles); wait for the
+ *                               streams.
+ *   phys_batch_debug_reward_launches  diagnostics: the launches phys_batch_reward has made. */
+enum { PHYS_REW_VEC = 0, PHYS_REW_ROT_INV = 1, PHYS_REW_QUAT = 2 };        /* a term's kind */
+enum { PHYS_REW_SUMSQ = 0, PHYS_REW_SUMABS = 1, PHYS_REW_MAXABS = 2 };     /* its norm */
+enum { PHYS_REW_LINEAR = 0, PHYS_REW_EXP = 1, PHYS_REW_RATIONAL = 2 };     /* its shape */
+enum { PHYS_REW_INPUT = -1, PHYS_REW_CONST = -2, PHYS_REW_NONE = -3 };     /* a term's field / tfield / gfield, beside PHYS_F_* */
+#define PHYS_REW_MAXTERMS 64
+typedef struct phys_reward_term {
+    int kind, field, index, count, qfield, qindex, tfield, tindex, gfield, gindex, norm, shape, root;
+    double vec[4];
+    double target, dead, k, weight;
+} phys_reward_term_t;
+int phys_batch_reward_configure(phys_batch_t *b, const phys_reward_term_t *terms, int nterms, int dtype, double lo, double hi);   /* nterms 0: release */
+int phys_batch_reward_bind(phys_batch_t *b, void *device_ptr, long long stride);   /* NULL un-binds */
+int phys_batch_reward_bind_terms(phys_batch_t *b, void *device_ptr, long long row_stride, int own);
+int phys_batch_reward_bind_input(phys_batch_t *b, const void *device_ptr, int dim, long long row_stride, int dtype);   /* NULL un-binds */
+int phys_batch_reward(phys_batch_t *b, int env0, int n, const void *reset_ptr /* int32 [n] or NULL */, void *stream);
+int phys_batch_reward_dim(const phys_batch_t *b, int *nterms, int *dtype, int *term_rows);
+int phys_batch_reward_download(phys_batch_t *b, void *host, int env0, int n);
+int phys_batch_reward_download_terms(phys_batch_t *b, void *host, int env0, int n);
+int phys_batch_reward_returns(phys_batch_t *b, double *host /*[nenv]*/);
+int phys_batch_reward_set_returns(phys_batch_t *b, const double *host /*[nenv]*/);
+int phys_batch_reward_final(phys_batch_t *b, double *host /*[nenv]*/);
+int phys_batch_debug_reward_launches(const phys_batch_t *b, long long *launches);
 
 /* measurement aid: on = every substep of a fused launch evaluates every output (IMU sensors, body quaternions), although
  * only the last substep's values can be read; off (default) = those are formed by the substeps whose values are read */

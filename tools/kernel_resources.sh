@@ -7,8 +7,19 @@
 # forms (MAXR 31 / 47, not a list-walking pass) are LEAN -- neither FEAT_READOUT (4) nor FEAT_PROF (8) -- and every other form carries
 # both -- except that the 40-dof model's two-wave fast form keeps FEAT_READOUT (kernels_tray_2w.hip says why).  PROF=1 compiles the fast form's profiled instantiation (+ FEAT_PROF: FORM_FAST_PROF / FORM_FAST_2W_PROF), SUMS=1 its sibling for launches that accumulate the step sums (+ FEAT_SUMS, 16: kernels_*_sums.hip), FULL=1 / FULL=0
 # force both bits on / off whatever the form.
+# SMALL=reward (or obs, probe, ...): instead, the kernels of csrc/<SMALL>_kernels.h, which are no templates, with the product's flags.
 set -e
 cd "$(dirname "$0")/.."
+if [ -n "$SMALL" ]; then
+T=$(mktemp -d)
+printf '#include <hip/hip_runtime.h>\n#include "wave.h"\n#include "%s_kernels.h"\n' "$SMALL" > $T/one.hip
+/opt/rocm/bin/hipcc -O3 -std=c++17 --offload-arch=gfx950 --offload-device-only -Iinclude -Icassie-mujoco-sim_amd/csrc \
+  -ffp-contract=on ${SCHED--mllvm -amdgpu-sched-strategy=iterative-ilp} ${LICM--mllvm -disable-machine-licm} $EXTRA -Rpass-analysis=kernel-resource-usage ${KEEP:+-save-temps=obj} -c $T/one.hip -o $T/one.o 2>&1 |
+  grep -E "Function Name|VGPRs:|AGPRs|Spill|ScratchSize|Occupancy|LDS Size|SGPRs:" | sed 's/.*remark: *//; s/ \[-Rpass.*//; s/^ \+/    /'
+[ -n "$KEEP" ] && cp $T/one-hip-amdgcn-amd-amdhsa-gfx950.s "$KEEP" || true
+rm -rf $T
+exit 0
+fi
 for MAXR in ${MAXRS:-31 63}; do
 T=$(mktemp -d)
 LEAN=0; { [ "$MAXR" = 31 ] || [ "$MAXR" = 47 ]; } && [ "${WALK:-false}" = false ] && LEAN=1
