@@ -222,6 +222,18 @@ def _declare(L):
         L.phys_batch_reward_set_returns.argtypes = [vp, vp]
         L.phys_batch_reward_final.argtypes = [vp, vp]
         L.phys_batch_debug_reward_launches.argtypes = [vp, c.POINTER(c.c_longlong)]
+    if hasattr(L, "phys_batch_act"):   # (likewise)
+        L.phys_batch_act_configure.argtypes = [vp, vp, c.c_int, c.c_int, c.c_int, c.c_ulonglong, c.c_uint]
+        L.phys_batch_act_bind_actions.argtypes = [vp, vp, c.c_longlong, c.c_int]
+        L.phys_batch_act_bind_rows.argtypes = [vp, vp, c.c_longlong]
+        L.phys_batch_act_bind_input.argtypes = [vp, vp, c.c_int, c.c_longlong, c.c_int]
+        L.phys_batch_act_bind_delay.argtypes = [vp, vp]
+        L.phys_batch_act.argtypes = [vp, c.c_int, c.c_int, vp, vp]
+        L.phys_batch_act_dim.argtypes = [vp, c.POINTER(c.c_int), c.POINTER(c.c_int), c.POINTER(c.c_int), c.POINTER(c.c_int)]
+        L.phys_batch_act_download.argtypes = [vp, vp, c.c_int, c.c_int]
+        L.phys_batch_act_state.argtypes = [vp, vp, vp]
+        L.phys_batch_act_set_state.argtypes = [vp, vp, vp]
+        L.phys_batch_debug_act_launches.argtypes = [vp, c.POINTER(c.c_longlong)]
     if hasattr(L, "phys_batch_step_sums_enable"):   # (likewise)
         L.phys_batch_step_sums_enable.argtypes = [vp, c.c_int]
     if hasattr(L, "phys_batch_download_progress"):   # (absent from older variant builds selected with CASSIE_LIB)

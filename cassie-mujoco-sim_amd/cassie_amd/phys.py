@@ -153,6 +153,35 @@ def rew_terms(terms):
         table[i] = tuple(t[:13]) + (np.asarray(t[13], dtype=np.float64),) + tuple(t[14:])
     return table
 
+
+# action rows: what is no field of the batch in a column's bfield / dfield (PHYS_ACT_* in cassie_phys.h), the frames of an action row, the
+# layout of phys_act_col_t, the limits and the fields a column may write
+ACT_INPUT, ACT_CONST, ACT_NONE = -1, -2, -3
+ACT_NOW, ACT_PREV, ACT_APPLIED = range(3)
+ACT_MAXCOLS, ACT_MAXDELAY = 256, 8
+ACT_COL_DTYPE = np.dtype([("bfield", np.int32), ("bindex", np.int32), ("dfield", np.int32), ("dindex", np.int32), ("lo", np.float64), ("hi", np.float64),
+                          ("noise", np.float64), ("smooth", np.float64), ("offset", np.float64), ("scale", np.float64), ("out_lo", np.float64),
+                          ("out_hi", np.float64)])
+ACT_CMD_FIELDS = (F_PD_PTARGET, F_PD_DTARGET, F_PD_KP, F_PD_KD, F_PD_TORQUE, F_DRIVE_CMD, F_CTRL, F_QFRC_APPLIED, F_XFRC_APPLIED)
+
+
+def act_col(dfield=ACT_NONE, dindex=0, lo=-np.inf, hi=np.inf, noise=0.0, smooth=1.0, bfield=ACT_CONST, bindex=0, offset=0.0, scale=1.0,
+            out_lo=-np.inf, out_hi=np.inf):
+    """An ACT_COL_DTYPE entry: the action clipped to [lo, hi], noisy, delayed and low-passed (y), then offset (+ bfield_row[bindex]) +
+    scale * y clipped to [out_lo, out_hi] into dfield_row[dindex] (ACT_NONE: a column that is only tracked)."""
+    return (int(bfield), int(bindex), int(dfield), int(dindex), lo, hi, noise, smooth, offset, scale, out_lo, out_hi)
+
+
+def act_cols(cols):
+    """A list of column tuples (act_col) or a structured array -> ACT_COL_DTYPE entries."""
+    if isinstance(cols, np.ndarray) and cols.dtype.names:
+        return np.ascontiguousarray(cols.astype(ACT_COL_DTYPE, copy=False)).reshape(-1)
+    cols = list(cols)
+    table = np.zeros(len(cols), dtype=ACT_COL_DTYPE)
+    for k, t in enumerate(cols):
+        table[k] = tuple(t)
+    return table
+
 # per-env physical parameters (CM_P_* in cm_model.h): what Batch.randomize takes
 (P_BODY_MASS, P_BODY_IPOS, P_BODY_INERTIA, P_DOF_DAMPING, P_GEOM_FRICTION,
  P_GEOM_POS, P_GEOM_QUAT, P_JNT_STIFFNESS, P_QPOS_SPRING) = range(9)
@@ -807,6 +836,91 @@ class Batch:
         """Diagnostics: the launches reward() has made so far."""
         a = ctypes.c_longlong(0)
         lib().phys_batch_debug_reward_launches(self._h, ctypes.byref(a))
+        return a.value
+
+    # ---- action rows: clip, noise, latency, low-pass, the map onto a pose and the store into the command fields in one launch (phys_batch_act) ----
+    def configure_actions(self, cols, delay_max=0, dtype=np.float32, seed=0, env_base=0):
+        """The columns of an action: a list of act_col(...) tuples or a structured array of ACT_COL_DTYPE (none: release).  delay_max:
+        the depth of the per-env delay line in calls (0 .. ACT_MAXDELAY); dtype: float32 or float64 action rows; seed, env_base: the
+        noise's key and the offset of its env counter, as configure_obs takes them.  Allocates the rows, the state and the call counts,
+        zeroed; drops the bindings of the actions, the rows, the input and the delays."""
+        table = act_cols(cols)
+        assert ACT_COL_DTYPE.itemsize == 80
+        if lib().phys_batch_act_configure(self._h, table.ctypes.data if table.size else None, int(table.size), int(delay_max), _obs_dtype(dtype),
+                                          int(seed) & 0xFFFFFFFFFFFFFFFF, int(env_base) & 0xFFFFFFFF) != 0:
+            self._obs_fail("configure_actions")
+        self._act_np = np.float64 if _obs_dtype(dtype) == 8 else np.float32
+
+    def bind_actions(self, device_ptr, row_stride=None, dtype=np.float32):
+        """The policy's output in device memory: [nenv] rows of ncols float32 / float64 elements, `row_stride` elements (default: ncols)
+        apart.  None un-binds."""
+        stride = int(row_stride if row_stride is not None else self.action_dim()[0]) if device_ptr else 0
+        if lib().phys_batch_act_bind_actions(self._h, device_ptr, stride, _obs_dtype(dtype)) != 0:
+            self._obs_fail("bind_actions")
+
+    def bind_action_rows(self, device_ptr, row_stride=None):
+        """The action rows [3][ncols] (ACT_NOW | ACT_PREV | ACT_APPLIED) in caller-owned HBM of the configured dtype, `row_stride`
+        elements (default: 3 ncols) between two envs' rows -- a column block of the tensor bound as the observation's and the reward's
+        input; None: the batch's own again."""
+        if lib().phys_batch_act_bind_rows(self._h, device_ptr, int(row_stride if row_stride is not None else self.action_dim()[2]) if device_ptr else 0) != 0:
+            self._obs_fail("bind_action_rows")
+
+    def bind_action_input(self, device_ptr, dim=0, row_stride=None, dtype=np.float32):
+        """The caller's per-env array the ACT_INPUT columns read (a reference pose for this step): [nenv] rows of `dim` float32 / float64
+        elements, `row_stride` elements apart (default: dim); it may be the observation's input.  None un-binds."""
+        if lib().phys_batch_act_bind_input(self._h, device_ptr, int(dim), int(dim if row_stride is None else row_stride), _obs_dtype(dtype)) != 0:
+            self._obs_fail("bind_action_input")
+
+    def bind_action_delay(self, device_ptr):
+        """The per-env latency in calls: an int32 device array [nenv], clamped to [0, delay_max] without a word.  None: no delay."""
+        if lib().phys_batch_act_bind_delay(self._h, device_ptr) != 0:
+            self._obs_fail("bind_action_delay")
+
+    def act(self, env0=0, n=None, reset_ptr=None, stream=None):
+        """One launch on `stream` (default: the batch's own), in front of the range's step launch: the command fields, the action rows
+        and the delay-line and filter state of every env of [env0, env0 + n) from the bound action tensor.  reset_ptr: an int32 device
+        array [n] (the range's slice of EP_DONE as the previous policy step's end_episodes left it), non-zero = the env starts afresh.
+        No host synchronisation."""
+        n = self.nenv - env0 if n is None else n
+        if lib().phys_batch_act(self._h, int(env0), int(n), reset_ptr, stream) != 0:
+            self._obs_fail("act")
+
+    def action_dim(self):
+        """(ncols, delay_max, elements of a row = 3 ncols, doubles of an env's state = (delay_max + 3) ncols)."""
+        a, d, r, s = ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int(0)
+        if lib().phys_batch_act_dim(self._h, ctypes.byref(a), ctypes.byref(d), ctypes.byref(r), ctypes.byref(s)) != 0:
+            self._obs_fail("action_dim")
+        return a.value, d.value, r.value, s.value
+
+    def action_rows(self, env0=0, n=None):
+        """The rows [env0, env0 + n) downloaded: [n][3][ncols] in the configured dtype."""
+        n = self.nenv - env0 if n is None else n
+        ncols = self.action_dim()[0]
+        out = np.empty((n, 3, ncols), dtype=self._act_np)
+        if lib().phys_batch_act_download(self._h, out.ctypes.data, int(env0), int(n)) != 0:
+            self._obs_fail("action_rows")
+        return out
+
+    def action_state(self):
+        """(state float64 [nenv][delay_max + 3][ncols]: the delay line's slots, newest first | the filter state | the previous clipped
+        action; counts uint32 [nenv]: the calls every env has seen, the third word of the noise's counter)."""
+        ncols, D, _, _ = self.action_dim()
+        state, counts = np.empty((self.nenv, D + 3, ncols), dtype=np.float64), np.empty(self.nenv, dtype=np.uint32)
+        if lib().phys_batch_act_state(self._h, state.ctypes.data, counts.ctypes.data) != 0:
+            self._obs_fail("action_state")
+        return state, counts
+
+    def set_action_state(self, state, counts):
+        ncols, D, _, _ = self.action_dim()
+        s = np.ascontiguousarray(state, dtype=np.float64).reshape(self.nenv, D + 3, ncols)
+        k = np.ascontiguousarray(counts, dtype=np.uint32).reshape(self.nenv)
+        if lib().phys_batch_act_set_state(self._h, s.ctypes.data, k.ctypes.data) != 0:
+            self._obs_fail("set_action_state")
+
+    def action_launches(self):
+        """Diagnostics: the launches act() has made so far."""
+        a = ctypes.c_longlong(0)
+        lib().phys_batch_debug_act_launches(self._h, ctypes.byref(a))
         return a.value
 
     def set_pd_mode(self, on=True):

@@ -157,6 +157,17 @@ struct phys_batch {
     long long reward_srew = 0, reward_sterm = 0;
     DevBuf<double> d_reward_ret, d_reward_final;
     long long reward_launches = 0;  /* launches of cassie_reward_kernel (phys_batch_debug_reward_launches) */
+    /* action rows (phys_batch_act_configure): the record (act.ncols 0: not configured; its pointers are filled in at the launch, from the
+     * buffers; the actions, the input and the delays are the caller's arrays), the column table, the rows (the batch's own or a caller's,
+     * floats or doubles) with their stride in elements, the per-env state [delay_max + 3][ncols] and call counts.  No stepping launch
+     * reads any of it: a step reads the command fields the call wrote */
+    ck::ActCfg act = {};
+    DevBuf<ck::ActCol> d_act_cols;
+    DevBuf<char> d_act_rows;
+    long long act_srow = 0;
+    DevBuf<double> d_act_state;
+    DevBuf<unsigned> d_act_counts;
+    long long act_launches = 0;     /* launches of cassie_act_kernel (phys_batch_debug_act_launches) */
 };
 
 static bool hip_ok(hipError_t e, const char *what) {
@@ -1736,6 +1747,139 @@ int phys_batch_reward_final(phys_batch_t *b, double *host) {
 int phys_batch_debug_reward_launches(const phys_batch_t *b, long long *launches) {
     if (!b) return -1;
     if (launches) *launches = b->reward_launches;
+    return 0;
+}
+
+/* ------------------------------------------------ action rows ---- */
+static_assert(sizeof(ck::ActColDef) == sizeof(phys_act_col_t) && offsetof(ck::ActColDef, dindex) == offsetof(phys_act_col_t, dindex) &&
+              offsetof(ck::ActColDef, lo) == offsetof(phys_act_col_t, lo) && offsetof(ck::ActColDef, smooth) == offsetof(phys_act_col_t, smooth) &&
+              offsetof(ck::ActColDef, out_hi) == offsetof(phys_act_col_t, out_hi), "phys_act_col_t is the column act_configure reads");
+static_assert(PHYS_ACT_INPUT == ck::ACT_INPUT && PHYS_ACT_CONST == ck::ACT_CONST && PHYS_ACT_NONE == ck::ACT_NONE && PHYS_ACT_NOW == ck::ACT_NOW &&
+              PHYS_ACT_PREV == ck::ACT_PREV && PHYS_ACT_APPLIED == ck::ACT_APPLIED && PHYS_ACT_MAXCOLS == ck::ACT_MAXCOLS && PHYS_ACT_MAXDELAY == ck::ACT_MAXDELAY,
+              "the header's numbers are act_kernels.h's");
+/* the fields a column may write: what a stepping launch reads as its commands */
+static const int ACT_CMD_FIELDS[ck::ACT_MAXDST] = {PHYS_F_PD_PTARGET, PHYS_F_PD_DTARGET, PHYS_F_PD_KP, PHYS_F_PD_KD, PHYS_F_PD_TORQUE, PHYS_F_DRIVE_CMD,
+                                                   PHYS_F_CTRL, PHYS_F_QFRC_APPLIED, PHYS_F_XFRC_APPLIED};
+/* the record of a launch: what was configured, with the pointers into the batch's buffers */
+static ck::ActCfg act_cfg_of(const phys_batch *b) {
+    ck::ActCfg c = b->act;
+    c.cols = b->d_act_cols; c.rows = b->d_act_rows.get(); c.srow = b->act_srow; c.state = b->d_act_state; c.counts = b->d_act_counts;
+    return c;
+}
+int phys_batch_act_configure(phys_batch_t *b, const phys_act_col_t *cols, int ncols, int delay_max, int dtype, unsigned long long seed, unsigned env_base) {
+    if (!b) return refuse("phys_batch_act_configure", ck::ACT_SIZE_REFUSAL);
+    int dims[PHYS_F_COUNT];
+    for (int k = 0; k < PHYS_F_COUNT; ++k) dims[k] = b->d_field[k] ? b->dim[k] : 0;
+    std::vector<ck::ActCol> table((size_t)ck::ACT_MAXCOLS);
+    ck::ActCfg cfg;
+    if (const char *why = ck::act_configure(dims, PHYS_F_COUNT, PHYS_F_DEPTH, ACT_CMD_FIELDS, ck::ACT_MAXDST, (const ck::ActColDef *)cols, ncols, delay_max, dtype,
+                                            seed, env_base, table.data(), cfg)) return refuse("phys_batch_act_configure", why);
+    (void)hipSetDevice(b->device);
+    if (!quiesce(b)) return -1;  /* (launches in flight may be reading the table, or writing the rows, that go away) */
+    if (ncols == 0) {
+        b->act = {}; b->act_srow = 0;
+        b->d_act_cols.reset(); b->d_act_rows.reset(); b->d_act_state.reset(); b->d_act_counts.reset();
+        return 0;
+    }
+    const size_t n = (size_t)b->nenv, row = (size_t)ck::ACT_FRAMES * (size_t)ncols;
+    DevBuf<ck::ActCol> tab;
+    DevBuf<char> rows;
+    DevBuf<double> state;
+    DevBuf<unsigned> counts;
+    if (!tab.alloc((size_t)ncols, false, "action columns")) return -1;
+    if (!hip_ok(hipMemcpy(tab, table.data(), sizeof(ck::ActCol) * (size_t)ncols, hipMemcpyHostToDevice), "hipMemcpy(action columns)")) return -1;
+    if (!rows.alloc(n * row * (size_t)dtype, true, "action rows")) return -1;
+    if (!state.alloc(n * (size_t)ck::act_state_dim(cfg), true, "action state")) return -1;
+    if (!counts.alloc(n, true, "action call counts")) return -1;
+    b->d_act_cols = std::move(tab); b->d_act_rows = std::move(rows); b->d_act_state = std::move(state); b->d_act_counts = std::move(counts);
+    b->act_srow = (long long)row;
+    b->act = cfg;   /* (no actions, input or delays bound, and the rows are the batch's own: the bindings are dropped) */
+    /* (a destination the step kernel is handed only once somebody writes it -- the applied forces, the PD's velocity targets and
+     * feed-forward torques -- is in use from here on, as after an upload or a binding: the buffers are zeroed until the first call) */
+    for (int s = 0; s < cfg.ndst; ++s) note_field_in_use(b, cfg.dst_field[s]);
+    return 0;
+}
+int phys_batch_act_bind_actions(phys_batch_t *b, const void *device_ptr, long long row_stride, int dtype) {
+    if (!b) { phys_set_last_error("phys_batch_act_bind_actions: no batch"); return -1; }
+    if (!device_ptr) { b->act.actions = nullptr; b->act.act_stride = 0; b->act.act_dtype = 0; return 0; }
+    if (const char *why = ck::check_act_bind_actions(b->act, row_stride, dtype)) return refuse("phys_batch_act_bind_actions", why);
+    b->act.actions = device_ptr; b->act.act_stride = row_stride; b->act.act_dtype = dtype;
+    return 0;
+}
+int phys_batch_act_bind_rows(phys_batch_t *b, void *device_ptr, long long row_stride) {
+    if (!b) { phys_set_last_error("phys_batch_act_bind_rows: no batch"); return -1; }
+    const long long row = (long long)ck::ACT_FRAMES * b->act.ncols;
+    if (const char *why = ck::check_act_bind_rows(b->act, device_ptr ? row_stride : row)) return refuse("phys_batch_act_bind_rows", why);
+    (void)hipSetDevice(b->device);
+    /* (as phys_batch_bind: launches already queued keep the pointer they were given; hipFree waits for the device by itself) */
+    if (device_ptr) { b->d_act_rows.borrow((char *)device_ptr); b->act_srow = row_stride; }
+    else if (!b->d_act_rows.owned()) {
+        if (!b->d_act_rows.alloc((size_t)b->nenv * (size_t)row * (size_t)b->act.dtype, true, "action rows")) return -1;
+        b->act_srow = row;
+    }
+    return 0;
+}
+int phys_batch_act_bind_input(phys_batch_t *b, const void *device_ptr, int dim, long long row_stride, int dtype) {
+    if (!b) { phys_set_last_error("phys_batch_act_bind_input: no batch"); return -1; }
+    if (!device_ptr) { b->act.input = nullptr; b->act.input_dim = 0; b->act.input_stride = 0; b->act.input_dtype = 0; return 0; }
+    if (const char *why = ck::check_act_bind_input(b->act, dim, row_stride, dtype)) return refuse("phys_batch_act_bind_input", why);
+    b->act.input = device_ptr; b->act.input_dim = dim; b->act.input_stride = (int)row_stride; b->act.input_dtype = dtype;
+    return 0;
+}
+int phys_batch_act_bind_delay(phys_batch_t *b, const void *device_ptr) {
+    if (!b) { phys_set_last_error("phys_batch_act_bind_delay: no batch"); return -1; }
+    if (device_ptr && b->act.ncols < 1) return refuse("phys_batch_act_bind_delay", "not configured (phys_batch_act_configure first)");
+    b->act.delay = (const int *)device_ptr;
+    return 0;
+}
+int phys_batch_act(phys_batch_t *b, int env0, int n, const void *reset_ptr, void *stream) {
+    if (!b) { phys_set_last_error("phys_batch_act: no batch"); return -1; }
+    const ck::ActCfg c = act_cfg_of(b);
+    ck::ObsField fields[PHYS_F_COUNT];
+    obs_fields_of(b, fields);
+    if (const char *why = ck::check_act_call(c, fields, PHYS_F_COUNT, b->nenv, env0, n)) return refuse("phys_batch_act", why);
+    (void)hipSetDevice(b->device);
+    if (n == 0) return 0;
+    hipStream_t s = launch_stream(b, stream);
+    hipLaunchKernelGGL(ck::cassie_act_kernel, dim3((unsigned)ck::act_grid(n)), dim3(WV_WAVE), 0, s, ck::make_act_io(c, fields, env0, n, (const int *)reset_ptr));
+    if (!hip_ok(hipGetLastError(), "cassie_act_kernel launch")) return -1;
+    ++b->act_launches;
+    return 0;
+}
+int phys_batch_act_dim(const phys_batch_t *b, int *ncols, int *delay_max, int *row, int *state) {
+    if (!b || b->act.ncols < 1) { phys_set_last_error("phys_batch_act_dim: not configured (phys_batch_act_configure first)"); return -1; }
+    if (ncols) *ncols = b->act.ncols;
+    if (delay_max) *delay_max = b->act.delay_max;
+    if (row) *row = ck::ACT_FRAMES * b->act.ncols;
+    if (state) *state = (int)ck::act_state_dim(b->act);
+    return 0;
+}
+int phys_batch_act_download(phys_batch_t *b, void *host, int env0, int n) {
+    if (!b || !host || b->act.ncols < 1 || !b->d_act_rows) { phys_set_last_error("phys_batch_act_download: bad arguments, or not configured (phys_batch_act_configure first)"); return -1; }
+    if (!range_ok(b, env0, n)) return refuse("phys_batch_act_download", "env range out of bounds");
+    (void)hipSetDevice(b->device);
+    if (!quiesce(b)) return -1;
+    if (n == 0) return 0;
+    const size_t el = (size_t)b->act.dtype, row = (size_t)ck::ACT_FRAMES * (size_t)b->act.ncols, st = (size_t)b->act_srow;
+    return hip_ok(hipMemcpy2D(host, el * row, b->d_act_rows.get() + el * st * (size_t)env0, el * st, el * row, (size_t)n, hipMemcpyDeviceToHost), "action rows download") ? 0 : -1;
+}
+int phys_batch_act_state(phys_batch_t *b, double *state_host, unsigned *counts_host) {
+    if (!b || !state_host || !counts_host || !b->d_act_state || !b->d_act_counts) { phys_set_last_error("phys_batch_act_state: bad arguments, or not configured (phys_batch_act_configure first)"); return -1; }
+    (void)hipSetDevice(b->device);
+    const size_t n = (size_t)b->nenv;
+    return quiesce(b) && hip_ok(hipMemcpy(state_host, b->d_act_state, sizeof(double) * n * (size_t)ck::act_state_dim(b->act), hipMemcpyDeviceToHost), "action state download") &&
+                   hip_ok(hipMemcpy(counts_host, b->d_act_counts, sizeof(unsigned) * n, hipMemcpyDeviceToHost), "action call counts download") ? 0 : -1;
+}
+int phys_batch_act_set_state(phys_batch_t *b, const double *state_host, const unsigned *counts_host) {
+    if (!b || !state_host || !counts_host || !b->d_act_state || !b->d_act_counts) { phys_set_last_error("phys_batch_act_set_state: bad arguments, or not configured (phys_batch_act_configure first)"); return -1; }
+    (void)hipSetDevice(b->device);
+    const size_t n = (size_t)b->nenv;
+    return quiesce(b) && hip_ok(hipMemcpy(b->d_act_state, state_host, sizeof(double) * n * (size_t)ck::act_state_dim(b->act), hipMemcpyHostToDevice), "action state upload") &&
+                   hip_ok(hipMemcpy(b->d_act_counts, counts_host, sizeof(unsigned) * n, hipMemcpyHostToDevice), "action call counts upload") ? 0 : -1;
+}
+int phys_batch_debug_act_launches(const phys_batch_t *b, long long *launches) {
+    if (!b) return -1;
+    if (launches) *launches = b->act_launches;
     return 0;
 }
 

@@ -1,12 +1,12 @@
 /*
- * small_launch.h -- how the kernels around the step kernel (small_kernels.h, surface_kernels.h, depth_kernel.h, ray_kernel.h, episode_kernels.h, probe_kernels.h, obs_kernels.h, reward_kernels.h) are
+ * small_launch.h -- how the kernels around the step kernel (small_kernels.h, surface_kernels.h, depth_kernel.h, ray_kernel.h, episode_kernels.h, probe_kernels.h, obs_kernels.h, reward_kernels.h, act_kernels.h) are
  * launched: the records a kernel's arguments are built from, one builder per kernel that returns its filled argument struct for an env
  * range, the grid of every launch, and the checks of what a caller configures, each returning the message of its refusal (null: fine).
  * Pure host code, no HIP runtime calls, in the spirit of step_policy.h: the launcher (phys_batch.hip) keeps the records in the batch,
  * prefixes a message with its entry point's name and launches what a builder returns on the grid given here; the wave emulator's entry
  * points (tests/emu) fill the same records from their arguments and go through the same builders, grids and checks, so a CPU test of
  * one of these kernels also runs the launcher's refusals, grid and choice of kernel (tests/test_small_launch.py pins them one by one).
- * No field of ScanIO, DepthIO, RayIO, EpisodeIO, ResetIO, DeriveIO, SetConstIO, StateIO, ProbeIO, ObsIO or RewardIO is assigned anywhere else.
+ * No field of ScanIO, DepthIO, RayIO, EpisodeIO, ResetIO, DeriveIO, SetConstIO, StateIO, ProbeIO, ObsIO, RewardIO or ActIO is assigned anywhere else.
  */
 #ifndef CASSIE_SMALL_LAUNCH_H
 #define CASSIE_SMALL_LAUNCH_H
@@ -14,6 +14,7 @@
 #include <cmath>
 #include <cstring>
 
+#include "act_kernels.h"
 #include "depth_kernel.h"
 #include "episode_kernels.h"
 #include "obs_kernels.h"
@@ -105,6 +106,24 @@ struct RewardCfg {
     int slot_field[REWARD_MAXSLOTS], slot_dim[REWARD_MAXSLOTS];
     const RewardTerm *terms; void *rew; long long srew; void *trows; long long sterm; double *ret, *fin;
     const void *input; int input_dim, input_stride, input_dtype;
+};
+
+/* the action rows (phys_batch_act_configure; ncols 0: not configured): the columns, the depth of the delay line, the rows' type (OBS_F32 /
+ * OBS_F64), the noise's seed and the offset of its env counter; the sources of a call as the observation's -- slot s is field
+ * slot_field[s] (or ACT_INPUT), whose row held slot_dim[s] elements when the columns were checked against it -- the destinations of a
+ * call -- slot s is the command field dst_field[s], whose row held dst_dim[s] -- and the elements the INPUT columns need of the caller's
+ * array.  Then what the caller names once a kernel reads them: the column table [ncols], the rows with their stride in elements, the
+ * state [nenv][delay_max + 3][ncols], the counts [nenv], the policy's actions (null: none bound) with their row stride and type, the
+ * caller's input array (null: none bound) with its row length, row stride and type, and the per-env delays (null: 0) */
+struct ActCfg {
+    int ncols, delay_max, dtype, nslots, ndst, input_need;
+    unsigned long long seed; unsigned env_base;
+    int slot_field[ACT_MAXSLOTS], slot_dim[ACT_MAXSLOTS];
+    int dst_field[ACT_MAXDST], dst_dim[ACT_MAXDST];
+    const ActCol *cols; void *rows; long long srow; double *state; unsigned *counts;
+    const void *actions; long long act_stride; int act_dtype;
+    const void *input; int input_dim, input_stride, input_dtype;
+    const int *delay;
 };
 
 /* ---- the row of a full state ---- */
@@ -451,6 +470,109 @@ inline const char *check_reward_call(const RewardCfg &c, const ObsField *fields,
     }
     return nullptr;
 }
+/* (what the launcher also answers a call without a batch) */
+constexpr const char *ACT_SIZE_REFUSAL = "0 .. 256 columns (0 releases them), a delay depth of 0 .. 8, rows of PHYS_OBS_F32 or PHYS_OBS_F64";
+/* the actions' configuration: checks the caller's columns [ncols] against the row lengths the batch holds now (as obs_configure: field_dim
+ * [nfields], 0: a field it does not hold yet; depth_field: the one field that is never a source; cmd_fields [ncmd]: the fields a column
+ * may write), writes the table a launch reads (table [ACT_MAXCOLS]: the fields replaced by slots) and fills c but for what the caller
+ * names later.  ncols 0 is accepted and leaves c empty: the launcher releases what it holds.  The emulator goes through the same */
+inline const char *act_configure(const int *field_dim, int nfields, int depth_field, const int *cmd_fields, int ncmd, const ActColDef *cols, int ncols,
+                                 int delay_max, int dtype, unsigned long long seed, unsigned env_base, ActCol *table, ActCfg &c) {
+    if (ncols < 0 || ncols > ACT_MAXCOLS || (ncols > 0 && (!cols || !table))) return ACT_SIZE_REFUSAL;
+    c = {};
+    if (ncols == 0) return nullptr;
+    if (delay_max < 0 || delay_max > ACT_MAXDELAY) return "a delay depth of 0 .. 8 calls";
+    if (dtype != OBS_F32 && dtype != OBS_F64) return "the rows' dtype is PHYS_OBS_F32 or PHYS_OBS_F64";
+    for (int k = 0; k < ncols; ++k) {
+        const ActColDef &d = cols[k];
+        ActCol &o = table[k];
+        if (!(d.lo <= d.hi) || !(d.out_lo <= d.out_hi)) return "lo <= hi and out_lo <= out_hi (either may be infinite, neither NaN)";
+        if (!(d.noise >= 0) || !std::isfinite(d.noise)) return "noise is an amplitude: finite and >= 0";
+        if (!(d.smooth > 0 && d.smooth <= 1)) return "smooth lies in (0, 1] (1: no filter)";
+        if (!(std::isfinite(d.offset) && std::isfinite(d.scale))) return "a column needs a finite offset and scale";
+        /* the base: the offset alone, or a slice of one element of a source */
+        o.slot = -1; o.elem = 0;
+        if (d.bfield != ACT_CONST) {
+            if (d.bfield == depth_field) return "PHYS_F_DEPTH is no source of an action (images are not columns)";
+            const bool input = d.bfield == ACT_INPUT;
+            if (!input && (d.bfield < 0 || d.bfield >= nfields)) return "a column's bfield is PHYS_ACT_CONST, PHYS_ACT_INPUT or a PHYS_F_* field of the batch";
+            const int dim = input ? 0x7fffffff : field_dim[d.bfield];
+            if (dim == 0) return "a column reads a field the batch does not hold yet (the scan, the rays, the probes, the step sums, the derived block: configure or enable them first)";
+            if (d.bindex < 0 || d.bindex >= dim) return "bindex lies beyond the field's row";
+            int s = 0;
+            while (s < c.nslots && c.slot_field[s] != d.bfield) ++s;
+            if (s == c.nslots) {
+                if (c.nslots == ACT_MAXSLOTS) return "more than 16 distinct source fields";
+                c.slot_field[s] = d.bfield; c.slot_dim[s] = input ? 0 : dim; ++c.nslots;
+            }
+            if (input && d.bindex + 1 > c.input_need) c.input_need = d.bindex + 1;
+            o.slot = s; o.elem = d.bindex;
+        }
+        /* the destination: none, or one element of a command field that no other column writes */
+        o.dslot = -1; o.delem = 0;
+        if (d.dfield != ACT_NONE) {
+            bool cmd = false;
+            for (int j = 0; j < ncmd; ++j) cmd = cmd || cmd_fields[j] == d.dfield;
+            if (!cmd || d.dfield < 0 || d.dfield >= nfields)
+                return "a column's dfield is PHYS_ACT_NONE or a command field (PHYS_F_PD_PTARGET, _PD_DTARGET, _PD_KP, _PD_KD, _PD_TORQUE, PHYS_F_DRIVE_CMD, PHYS_F_CTRL, PHYS_F_QFRC_APPLIED, PHYS_F_XFRC_APPLIED)";
+            const int dim = field_dim[d.dfield];
+            if (dim == 0) return "a column writes a field the batch does not hold";
+            if (d.dindex < 0 || d.dindex >= dim) return "dindex lies beyond the field's row";
+            for (int j = 0; j < k; ++j)
+                if (cols[j].dfield == d.dfield && cols[j].dindex == d.dindex) return "two columns write the same destination element";
+            int s = 0;
+            while (s < c.ndst && c.dst_field[s] != d.dfield) ++s;
+            if (s == c.ndst) {
+                if (c.ndst == ACT_MAXDST) return "more destination fields than there are command fields";
+                c.dst_field[s] = d.dfield; c.dst_dim[s] = dim; ++c.ndst;
+            }
+            o.dslot = s; o.delem = d.dindex;
+        }
+        o.lo = d.lo; o.hi = d.hi; o.noise = d.noise; o.smooth = d.smooth; o.offset = d.offset; o.scale = d.scale; o.out_lo = d.out_lo; o.out_hi = d.out_hi;
+    }
+    c.ncols = ncols; c.delay_max = delay_max; c.dtype = dtype; c.seed = seed; c.env_base = env_base;
+    return nullptr;
+}
+/* the doubles of an env's state: the line's delay_max + 1 slots, the filter state, the previous clipped action */
+inline long long act_state_dim(const ActCfg &c) { return (long long)(c.delay_max + 3) * c.ncols; }
+/* what phys_batch_act_bind_actions / _bind_rows / _bind_input refuse */
+inline const char *check_act_bind_actions(const ActCfg &c, long long row_stride, int dtype) {
+    if (c.ncols < 1) return "not configured (phys_batch_act_configure first)";
+    if (row_stride < c.ncols) return "a row stride of at least the columns";
+    if (dtype != OBS_F32 && dtype != OBS_F64) return "the actions' dtype is PHYS_OBS_F32 or PHYS_OBS_F64";
+    return nullptr;
+}
+inline const char *check_act_bind_rows(const ActCfg &c, long long row_stride) {
+    if (c.ncols < 1) return "not configured (phys_batch_act_configure first)";
+    if (row_stride < (long long)ACT_FRAMES * c.ncols) return "a row stride of at least the row's elements (3 x columns)";
+    return nullptr;
+}
+inline const char *check_act_bind_input(const ActCfg &c, int dim, long long row_stride, int dtype) {
+    if (c.ncols < 1) return "not configured (phys_batch_act_configure first)";
+    if (dim < 1 || row_stride < dim || row_stride > 0x7fffffff) return "an input of at least one element a row and a row stride of at least that";
+    if (dtype != OBS_F32 && dtype != OBS_F64) return "the input's dtype is PHYS_OBS_F32 or PHYS_OBS_F64";
+    return nullptr;
+}
+/* what an action call refuses; fields [nfields]: what the batch holds NOW */
+inline const char *check_act_call(const ActCfg &c, const ObsField *fields, int nfields, int nenv, int env0, int n) {
+    if (c.ncols < 1 || !c.cols || !c.rows || !c.state || !c.counts) return "not configured (phys_batch_act_configure first)";
+    if (!c.actions) return "no actions bound (phys_batch_act_bind_actions first)";
+    if (env0 < 0 || n < 0 || (long long)env0 + n > nenv) return "env range out of bounds";
+    for (int s = 0; s < c.nslots; ++s) {
+        const int f = c.slot_field[s];
+        if (f == ACT_INPUT) {
+            if (!c.input) return "a PHYS_ACT_INPUT column and no input bound (phys_batch_act_bind_input first)";
+            if (c.input_dim < c.input_need) return "the bound input's rows are shorter than the PHYS_ACT_INPUT columns reach";
+        } else if (f < 0 || f >= nfields || !fields[f].base || fields[f].dim != c.slot_dim[s])
+            return "the row length of a source field has changed since phys_batch_act_configure (configure again)";
+    }
+    for (int s = 0; s < c.ndst; ++s) {
+        const int f = c.dst_field[s];
+        if (f < 0 || f >= nfields || !fields[f].base || fields[f].dim != c.dst_dim[s])
+            return "the row length of a destination field has changed since phys_batch_act_configure (configure again)";
+    }
+    return nullptr;
+}
 /* the bank of full states: what phys_batch_state_configure / _bind refuse (the view tells what the batch has), and what a save or a
  * restore refuses */
 inline const char *state_configure(const BatchView &v, int nslots, int groups) {
@@ -484,6 +606,8 @@ inline int probe_grid(int n) { return n < PROBE_GRID ? n : PROBE_GRID; }
 inline int obs_grid(int n) { return n < OBS_GRID ? n : OBS_GRID; }
 /* one wave per 64 envs (a lane takes an env) up to REWARD_GRID workgroups, which then walk the range (reward_kernels.h) */
 inline int reward_grid(int n) { const long long w = ((long long)n + WV_WAVE - 1) / WV_WAVE; return w < REWARD_GRID ? (int)w : REWARD_GRID; }
+/* one wave per env up to ACT_GRID workgroups, which then walk the range: few, as the observation's (act_kernels.h) */
+inline int act_grid(int n) { return n < ACT_GRID ? n : ACT_GRID; }
 /* a job is (env, tile of DEPTH_TILE x DEPTH_TILE pixels); a fixed grid walks the job list (a first choice: depth_kernel.h) */
 inline int depth_grid(int n, int width, int height) {
     const int T = DEPTH_TILE;
@@ -595,6 +719,24 @@ inline RewardIO make_reward_io(const RewardCfg &c, const ObsField *fields, int e
         else io.src[s] = {fields[f].base, fields[f].stride, 0, 0};
     }
     io.rew = c.rew; io.srew = c.srew; io.trows = c.trows; io.sterm = c.sterm; io.ret = c.ret; io.fin = c.fin; io.reset = reset;
+    return io;
+}
+/* cassie_act_kernel's: the sources and the destinations of the record's slots where the batch reads them today (fields [nfields]: its own
+ * buffers or the caller's bound tensors, with their row strides; the caller's input array), the column table, the actions, the rows, the
+ * state, the counts, the delays and the key */
+inline ActIO make_act_io(const ActCfg &c, const ObsField *fields, int env0, int n, const int *reset) {
+    ActIO io = zeroed<ActIO>();
+    io.env0 = env0; io.n = n; io.ncols = c.ncols; io.delay_max = c.delay_max; io.f32 = c.dtype == OBS_F32; io.act_f32 = c.act_dtype == OBS_F32;
+    io.env_base = c.env_base; io.key0 = (unsigned)(c.seed & 0xffffffffull); io.key1 = (unsigned)(c.seed >> 32);
+    io.cols = c.cols;
+    for (int s = 0; s < c.nslots; ++s) {
+        const int f = c.slot_field[s];
+        if (f == ACT_INPUT) io.src[s] = {c.input, c.input_stride, c.input_dtype == OBS_F32, 0};
+        else io.src[s] = {fields[f].base, fields[f].stride, 0, 0};
+    }
+    for (int s = 0; s < c.ndst; ++s) io.dst[s] = {const_cast<double *>(fields[c.dst_field[s]].base), fields[c.dst_field[s]].stride};
+    io.actions = c.actions; io.sact = c.act_stride;
+    io.rows = c.rows; io.srow = c.srow; io.state = c.state; io.counts = c.counts; io.delay = c.delay; io.reset = reset;
     return io;
 }
 inline int episode_row_dim(const BatchView &v) { return v.nq + v.nv + v.nsd + v.nu + v.nv; }

@@ -849,6 +849,105 @@ int phys_batch_reward_set_returns(phys_batch_t *b, const double *host /*[nenv]*/
 int phys_batch_reward_final(phys_batch_t *b, double *host /*[nenv]*/);
 int phys_batch_debug_reward_launches(const phys_batch_t *b, long long *launches);
 
+/* ACTION ROWS: what a policy step WRITES, made on the device by ONE launch per env range from the tensor the policy network put out: the
+ * clip of the raw action, uniform actuation noise, a latency of a few policy steps that differs per env, a low-pass, the map onto a
+ * reference pose, the clip of the result and the store into the command fields the step kernel reads; and per env a small ACTION ROW the
+ * observation and the reward take as their input, so that "the previous action" and "the action rate" are the library's, not each user's
+ * bookkeeping.  A configured table of ncols COLUMNS (1 .. PHYS_ACT_MAXCOLS), column c for element c of an env's action.
+ * A COLUMN (phys_act_col_t):
+ *   lo, hi            the clip of the raw action (infinities are allowed; a NaN passes).
+ *   noise             >= 0, the amplitude of the uniform actuation noise.
+ *   smooth            in (0, 1], the coefficient of the low-pass; 1: no filter.
+ *   bfield, bindex    the base the scaled action is added to: PHYS_ACT_CONST (the offset alone), element bindex of the env's row of any
+ *                     PHYS_F_* field an observation may read (every field but PHYS_F_DEPTH, with the row length the batch holds for it when
+ *                     the columns are configured, read where the batch reads it at the call), or PHYS_ACT_INPUT: the caller's own per-env
+ *                     array bound with phys_batch_act_bind_input as floats or doubles, floats widened exactly -- a reference pose for
+ *                     this step.  It may be the tensor bound as the observation's and the reward's input.  At most 16 distinct sources.
+ *   offset, scale     finite.
+ *   out_lo, out_hi    the clip of what is written.
+ *   dfield, dindex    the destination: element dindex of the env's row of a command field -- PHYS_F_PD_PTARGET, PHYS_F_PD_DTARGET,
+ *                     PHYS_F_PD_KP, PHYS_F_PD_KD, PHYS_F_PD_TORQUE, PHYS_F_DRIVE_CMD, PHYS_F_CTRL, PHYS_F_QFRC_APPLIED, PHYS_F_XFRC_APPLIED --
+ *                     written where the batch reads the field at the call: its own buffer, or the tensor bound with phys_batch_bind /
+ *                     _bind_strided with its row stride.  PHYS_ACT_NONE: a column that is only tracked (its row entries and state).  No two
+ *                     columns name the same element.  Fields a stepping launch is handed only once somebody wrote them (the applied forces,
+ *                     PHYS_F_PD_DTARGET, PHYS_F_PD_TORQUE) count as written from the configure call on, as after an upload.
+ * PER ENV AND COLUMN c, PER CALL, every arithmetic step one individually rounded fp64 operation (multiply, add, subtract to nearest even;
+ *   no fused multiply-add).  k = counts[env] before the call; a = the env's element c of the bound action tensor (floats widened exactly);
+ *   d = delay[env] clamped to [0, D], D the configured delay depth (0 .. PHYS_ACT_MAXDELAY), delay an int32 DEVICE array [nenv] bound by the
+ *   caller, or unbound for 0 -- the clamp is silent; fresh = (k == 0 or the call's reset entry for the env is non-zero).
+ *     1. u = a < lo ? lo : (a > hi ? hi : a).
+ *     2. v = u, or where noise != 0: v = u + noise * xi, with xi = (w + 0.5) 2^-31 - 1 as the observation's and w word 0 of Philox4x32-10
+ *        on the counter (env_base + env, c, k, 1) with the key (seed & 0xffffffff, seed >> 32).  The fourth word is 1 where the
+ *        observation's is 0: the same seed gives the two their own streams.
+ *     3. THE DELAY LINE, D + 1 slots per column, newest first.  fresh: every slot becomes v.  Otherwise slot h takes slot h - 1 for
+ *        h = D .. 1 and slot 0 becomes v.  z = slot[d].
+ *     4. THE FILTER STATE f.  fresh or smooth == 1: y = z (a skip, not the formula: an unfiltered column reproduces z exactly).  Otherwise
+ *        y = f + smooth * (z - f).  Then f = y.
+ *     5. base = offset for PHYS_ACT_CONST, else offset + source_row[bindex];  t = base + scale * y;  t = t < out_lo ? out_lo : (t > out_hi ?
+ *        out_hi : t).
+ *     6. Where there is a destination: dfield_row[dindex] = t.
+ *     7. THE ACTION ROW [3][ncols] of the configured type (PHYS_OBS_F32 / PHYS_OBS_F64; the cast rounds to nearest even): frame
+ *        PHYS_ACT_NOW = u; frame PHYS_ACT_PREV = the u of the env's previous call, or this u when fresh; frame PHYS_ACT_APPLIED = y.
+ *     8. The previous u is kept in the fp64 state, never read back from the row.
+ *   Then counts[env] += 1 (uint32, wraps).
+ * STATE: per env [D + 3][ncols] doubles -- the line's slots | f | the previous u -- and the count; the batch owns both.  Neither is in a
+ *   state-bank row: as with the observation's frame counts, a caller that rewinds or resumes moves them itself (phys_batch_act_state /
+ *   _set_state).
+ * ORDER IN A POLICY STEP: phys_batch_act; the step launch; the launches that make sources; phys_batch_reward; phys_batch_end_episodes;
+ *   phys_batch_obs -- five launches per range that nothing on the host has to touch.  `reset` is an optional int32 DEVICE array [n], entry i
+ *   for env env0 + i: the range's slice of PHYS_EP_DONE as the PREVIOUS policy step's phys_batch_end_episodes left it, exactly what
+ *   phys_batch_reward is handed -- the first action of a restarted env fills its delay line, and its previous action is that action.
+ * NaN, DIVERGED ENVS AND THE DELAY: values flow through to the env's own destinations, row and state; nothing but the clamped d picks among
+ *   memory by a value, and it picks among the env's own D + 1 slots.
+ *   phys_batch_act_configure    cols [ncols] (host memory), the delay depth, the rows' type, the seed and env_base (as the observation's).
+ *                               Refuses, with a message in phys_last_error(): ncols outside 0 .. PHYS_ACT_MAXCOLS, a depth outside 0 ..
+ *                               PHYS_ACT_MAXDELAY, an unknown dtype, a non-finite offset or scale, noise < 0 or not finite, smooth outside
+ *                               (0, 1], lo > hi or out_lo > out_hi, a destination that is no command field, that the batch does not hold, whose
+ *                               dindex lies beyond its row or that an earlier column names, a source the batch does not hold yet,
+ *                               PHYS_F_DEPTH, bindex beyond the source's row, more than 16 sources.  Allocates the table, the rows, the
+ *                               state and the counts (zeroed); drops the bindings of the actions, the rows, the input and the delays; waits
+ *                               for the batch's streams.  ncols 0 releases everything.
+ *   phys_batch_act_bind_actions the policy's output in device memory: [nenv] rows of ncols elements, row_stride elements (>= ncols) apart,
+ *                               PHYS_OBS_F32 / _F64.  NULL un-binds.
+ *   phys_batch_act_bind_rows    the action rows in caller-owned HBM of the configured type, row_stride elements (>= 3 ncols) between two
+ *                               envs' rows: a column block of the tensor bound as the observation's and the reward's input.  NULL: the
+ *                               batch's own rows again, zeroed.
+ *   phys_batch_act_bind_input   the caller's per-env array [nenv] rows of dim elements, row_stride elements apart, PHYS_OBS_F32 / _F64.
+ *                               NULL un-binds.
+ *   phys_batch_act_bind_delay   the per-env delays, int32 [nenv] in device memory indexed by the absolute env.  NULL: no delay.
+ *   phys_batch_act              ONE launch of cassie_act_kernel over [env0, env0 + n) on `stream` (NULL: the batch's own), in order with
+ *                               the launches there.  No host synchronisation, no allocation, no read on the host.  Writes the destination
+ *                               elements, the action rows, the state and the counts of the range and nothing else.  Refuses: not
+ *                               configured, no actions bound, a PHYS_ACT_INPUT column with nothing bound or with a bound dim its columns
+ *                               reach beyond, a source or destination field whose row length is no longer what it was at the configure
+ *                               call, a range outside the batch.
+ *   phys_batch_act_dim          ncols, the delay depth, the row's elements (3 ncols) and the doubles of an env's state ((D + 3) ncols); any
+ *                               may be NULL -> 0, -1 when not configured.
+ *   phys_batch_act_download     rows [env0, env0 + n) to dense host memory [n][3][ncols] of the rows' type; waits for the streams.
+ *   phys_batch_act_state / _set_state   the state [nenv][D + 3][ncols] (doubles) and the counts [nenv] (uint32) to / from the host, so that
+ *                               a resumed or rewound run makes what the first would have made; both wait for the streams.
+ *   phys_batch_debug_act_launches  diagnostics: the launches phys_batch_act has made. */
+enum { PHYS_ACT_INPUT = -1, PHYS_ACT_CONST = -2, PHYS_ACT_NONE = -3 };     /* a column's bfield / dfield, beside PHYS_F_* */
+enum { PHYS_ACT_NOW = 0, PHYS_ACT_PREV = 1, PHYS_ACT_APPLIED = 2 };        /* the frames of an action row */
+#define PHYS_ACT_MAXCOLS 256
+#define PHYS_ACT_MAXDELAY 8
+typedef struct phys_act_col {
+    int bfield, bindex, dfield, dindex;
+    double lo, hi, noise, smooth, offset, scale, out_lo, out_hi;
+} phys_act_col_t;
+int phys_batch_act_configure(phys_batch_t *b, const phys_act_col_t *cols, int ncols, int delay_max, int dtype, unsigned long long seed,
+                             unsigned env_base);   /* ncols 0: release */
+int phys_batch_act_bind_actions(phys_batch_t *b, const void *device_ptr, long long row_stride, int dtype);   /* NULL un-binds */
+int phys_batch_act_bind_rows(phys_batch_t *b, void *device_ptr, long long row_stride);   /* NULL un-binds */
+int phys_batch_act_bind_input(phys_batch_t *b, const void *device_ptr, int dim, long long row_stride, int dtype);   /* NULL un-binds */
+int phys_batch_act_bind_delay(phys_batch_t *b, const void *device_ptr /* int32 [nenv] or NULL */);
+int phys_batch_act(phys_batch_t *b, int env0, int n, const void *reset_ptr /* int32 [n] or NULL */, void *stream);
+int phys_batch_act_dim(const phys_batch_t *b, int *ncols, int *delay_max, int *row, int *state);
+int phys_batch_act_download(phys_batch_t *b, void *host, int env0, int n);
+int phys_batch_act_state(phys_batch_t *b, double *state_host /*[nenv][D + 3][ncols]*/, unsigned *counts_host /*[nenv]*/);
+int phys_batch_act_set_state(phys_batch_t *b, const double *state_host, const unsigned *counts_host);
+int phys_batch_debug_act_launches(const phys_batch_t *b, long long *launches);
+
 /* measurement aid: on = every substep of a fused launch evaluates every output (IMU sensors, body quaternions), although
  * only the last substep's values can be read; off (default) = those are formed by the substeps whose values are read */
 int phys_batch_set_all_outputs_every_substep(phys_batch_t *b, int on);
