@@ -234,6 +234,16 @@ def _declare(L):
         L.phys_batch_act_state.argtypes = [vp, vp, vp]
         L.phys_batch_act_set_state.argtypes = [vp, vp, vp]
         L.phys_batch_debug_act_launches.argtypes = [vp, c.POINTER(c.c_longlong)]
+    if hasattr(L, "phys_batch_task"):   # (likewise)
+        L.phys_batch_task_configure.argtypes = [vp, vp, c.c_int, c.c_int, c.c_ulonglong, c.c_uint]
+        L.phys_batch_task_set_table.argtypes = [vp, vp, c.c_int, c.c_int]
+        L.phys_batch_task_bind_rows.argtypes = [vp, vp, c.c_longlong]
+        L.phys_batch_task.argtypes = [vp, c.c_int, c.c_int, vp, vp]
+        L.phys_batch_task_dim.argtypes = [vp, c.POINTER(c.c_int), c.POINTER(c.c_int)]
+        L.phys_batch_task_download.argtypes = [vp, vp, c.c_int, c.c_int]
+        L.phys_batch_task_state.argtypes = [vp, vp, vp, vp]
+        L.phys_batch_task_set_state.argtypes = [vp, vp, vp, vp]
+        L.phys_batch_debug_task_launches.argtypes = [vp, c.POINTER(c.c_longlong)]
     if hasattr(L, "phys_batch_step_sums_enable"):   # (likewise)
         L.phys_batch_step_sums_enable.argtypes = [vp, c.c_int]
     if hasattr(L, "phys_batch_download_progress"):   # (absent from older variant builds selected with CASSIE_LIB)

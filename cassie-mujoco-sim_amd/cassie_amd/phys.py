@@ -182,6 +182,60 @@ def act_cols(cols):
         table[k] = tuple(t)
     return table
 
+
+# task rows: the kinds of a column and the forms of a WAVE (PHYS_TASK_* in cassie_phys.h), what is no destination, the layout of
+# phys_task_col_t and the limits
+TASK_SAMPLE, TASK_PHASE, TASK_WAVE, TASK_TABLE = range(4)
+TASK_SAW, TASK_SIN, TASK_COS, TASK_TRAPEZOID = range(4)
+TASK_NONE = ACT_NONE
+TASK_MAXCOLS, TASK_MAXFRAMES, TASK_MAXTCOLS, TASK_MAXPERIOD = 64, 4096, 64, 1 << 30
+TASK_COL_DTYPE = np.dtype([(k, np.int32) for k in ("kind", "form", "group", "rate_col", "phase_col", "src", "tcol", "dfield", "dindex")] +
+                          [(k, np.uint32) for k in ("period_lo", "period_hi", "hold")] +
+                          [(k, np.float64) for k in ("center", "half", "rest", "p_rest", "rate", "rate_scale", "phase0", "shift", "duty", "ramp", "offset", "scale")])
+
+
+def _task_col(kind, **kw):
+    col = dict(kind=kind, form=0, group=-1, rate_col=-1, phase_col=-1, src=-1, tcol=0, dfield=TASK_NONE, dindex=0, period_lo=1, period_hi=1, hold=0,
+               center=0.0, half=0.0, rest=0.0, p_rest=0.0, rate=0.0, rate_scale=0.0, phase0=0.0, shift=0.0, duty=0.0, ramp=0.0, offset=0.0, scale=1.0)
+    col.update(kw)
+    return tuple(col[k] for k in TASK_COL_DTYPE.names)
+
+
+def task_sample(center=0.0, half=0.0, period_lo=1, period_hi=None, rest=0.0, p_rest=0.0, hold=0, group=-1, dfield=TASK_NONE, dindex=0):
+    """A TASK_COL_DTYPE entry: a value center + half * uniform(-1, 1), or `rest` with probability p_rest, held for period_lo ..
+    period_hi calls (shown for the first `hold` of them, then `rest`; 0: all).  group: the SAMPLE column whose schedule it shares
+    (-1: its own).  dfield, dindex: a command-field element that gets the value too (TASK_NONE: none)."""
+    return _task_col(TASK_SAMPLE, center=center, half=half, period_lo=period_lo, period_hi=period_lo if period_hi is None else period_hi, rest=rest,
+                     p_rest=p_rest, hold=hold, group=group, dfield=dfield, dindex=dindex)
+
+
+def task_phase(rate=0.0, rate_col=-1, rate_scale=1.0, phase0=0.0, phase_col=-1, dfield=TASK_NONE, dindex=0):
+    """A clock in [0, 1): advanced by rate (+ rate_scale * the SAMPLE column rate_col) cycles per call, started at phase0 or at the SAMPLE
+    column phase_col."""
+    return _task_col(TASK_PHASE, rate=rate, rate_col=rate_col, rate_scale=rate_scale, phase0=phase0, phase_col=phase_col, dfield=dfield, dindex=dindex)
+
+
+def task_wave(src, form=TASK_SIN, shift=0.0, offset=0.0, scale=1.0, duty=0.0, ramp=0.0, dfield=TASK_NONE, dindex=0):
+    """offset + scale * g(wrap(phase of the PHASE column src + shift)), g the form: TASK_SAW, TASK_SIN, TASK_COS (of 2 pi theta) or
+    TASK_TRAPEZOID (0 at 0, 1 on [ramp, duty], 0 from duty + ramp on)."""
+    return _task_col(TASK_WAVE, src=src, form=form, shift=shift, offset=offset, scale=scale, duty=duty, ramp=ramp, dfield=dfield, dindex=dindex)
+
+
+def task_table(src, tcol, shift=0.0, offset=0.0, scale=1.0, dfield=TASK_NONE, dindex=0):
+    """offset + scale * column tcol of the periodic table (Batch.set_task_table), linearly interpolated at wrap(phase of src + shift)."""
+    return _task_col(TASK_TABLE, src=src, tcol=tcol, shift=shift, offset=offset, scale=scale, dfield=dfield, dindex=dindex)
+
+
+def task_cols(cols):
+    """A list of column tuples (task_sample, task_phase, task_wave, task_table) or a structured array -> TASK_COL_DTYPE entries."""
+    if isinstance(cols, np.ndarray) and cols.dtype.names:
+        return np.ascontiguousarray(cols.astype(TASK_COL_DTYPE, copy=False)).reshape(-1)
+    cols = list(cols)
+    table = np.zeros(len(cols), dtype=TASK_COL_DTYPE)
+    for k, t in enumerate(cols):
+        table[k] = tuple(t)
+    return table
+
 # per-env physical parameters (CM_P_* in cm_model.h): what Batch.randomize takes
 (P_BODY_MASS, P_BODY_IPOS, P_BODY_INERTIA, P_DOF_DAMPING, P_GEOM_FRICTION,
  P_GEOM_POS, P_GEOM_QUAT, P_JNT_STIFFNESS, P_QPOS_SPRING) = range(9)
@@ -921,6 +975,79 @@ class Batch:
         """Diagnostics: the launches act() has made so far."""
         a = ctypes.c_longlong(0)
         lib().phys_batch_debug_act_launches(self._h, ctypes.byref(a))
+        return a.value
+
+    # ---- task rows: commands, gait clocks, waveforms, a reference trajectory and pushes in one launch (phys_batch_task) ----
+    def configure_task(self, cols, dtype=np.float32, seed=0, env_base=0):
+        """The columns of a task row: a list of task_sample / task_phase / task_wave / task_table tuples or a structured array of
+        TASK_COL_DTYPE (1 .. TASK_MAXCOLS).  dtype: float32 or float64 rows; seed, env_base: the key of the draws and the offset of
+        their env counter, as configure_obs takes them.  A table the TABLE columns read is set first (set_task_table).  Allocates the
+        rows, the state and the call counts, zeroed; drops the binding of the rows."""
+        table = task_cols(cols)
+        assert TASK_COL_DTYPE.itemsize == 144
+        if lib().phys_batch_task_configure(self._h, table.ctypes.data if table.size else None, int(table.size), _obs_dtype(dtype),
+                                           int(seed) & 0xFFFFFFFFFFFFFFFF, int(env_base) & 0xFFFFFFFF) != 0:
+            self._obs_fail("configure_task")
+        self._task_np = np.float64 if _obs_dtype(dtype) == 8 else np.float32
+
+    def set_task_table(self, table):
+        """The periodic reference trajectory the TABLE columns interpolate: float64 [nframes][tcols] (<= 4096 x 64), uploaded once."""
+        t = np.ascontiguousarray(table, dtype=np.float64)
+        if t.ndim != 2:
+            raise ValueError("set_task_table: a table is [nframes][tcols]")
+        if lib().phys_batch_task_set_table(self._h, t.ctypes.data if t.size else None, int(t.shape[0]), int(t.shape[1])) != 0:
+            self._obs_fail("set_task_table")
+
+    def bind_task_rows(self, device_ptr, row_stride=None):
+        """The task rows [ncols] in caller-owned HBM of the configured dtype, `row_stride` elements (default: ncols) between two envs' rows
+        -- a column block of the tensor bound as the observation's, the reward's and the action's input; None: the batch's own again."""
+        if lib().phys_batch_task_bind_rows(self._h, device_ptr, int(row_stride if row_stride is not None else self.task_dim()) if device_ptr else 0) != 0:
+            self._obs_fail("bind_task_rows")
+
+    def task(self, env0=0, n=None, reset_ptr=None, stream=None):
+        """One launch on `stream` (default: the batch's own), between the range's end_episodes and its observation: the task rows, the
+        state and the destination elements of every env of [env0, env0 + n).  reset_ptr: an int32 device array [n] (the range's slice
+        of EP_DONE as this policy step's end_episodes left it), non-zero = the env starts afresh.  No host synchronisation."""
+        n = self.nenv - env0 if n is None else n
+        if lib().phys_batch_task(self._h, int(env0), int(n), reset_ptr, stream) != 0:
+            self._obs_fail("task")
+
+    def task_dim(self):
+        """The columns of a task row."""
+        a = ctypes.c_int(0)
+        if lib().phys_batch_task_dim(self._h, ctypes.byref(a), None) != 0:
+            self._obs_fail("task_dim")
+        return a.value
+
+    def task_rows(self, env0=0, n=None):
+        """The rows [env0, env0 + n) downloaded: [n][ncols] in the configured dtype."""
+        n = self.nenv - env0 if n is None else n
+        out = np.empty((n, self.task_dim()), dtype=self._task_np)
+        if lib().phys_batch_task_download(self._h, out.ctypes.data, int(env0), int(n)) != 0:
+            self._obs_fail("task_rows")
+        return out
+
+    def task_state(self):
+        """(state float64 [nenv][ncols]: a SAMPLE's held value, a PHASE's phase; words uint32 [nenv][3][ncols]: a SAMPLE's left | age |
+        epoch; counts uint32 [nenv]: the calls every env has seen)."""
+        ncols = self.task_dim()
+        state, words, counts = np.empty((self.nenv, ncols), dtype=np.float64), np.empty((self.nenv, 3, ncols), dtype=np.uint32), np.empty(self.nenv, dtype=np.uint32)
+        if lib().phys_batch_task_state(self._h, state.ctypes.data, words.ctypes.data, counts.ctypes.data) != 0:
+            self._obs_fail("task_state")
+        return state, words, counts
+
+    def set_task_state(self, state, words, counts):
+        ncols = self.task_dim()
+        s = np.ascontiguousarray(state, dtype=np.float64).reshape(self.nenv, ncols)
+        w = np.ascontiguousarray(words, dtype=np.uint32).reshape(self.nenv, 3, ncols)
+        k = np.ascontiguousarray(counts, dtype=np.uint32).reshape(self.nenv)
+        if lib().phys_batch_task_set_state(self._h, s.ctypes.data, w.ctypes.data, k.ctypes.data) != 0:
+            self._obs_fail("set_task_state")
+
+    def task_launches(self):
+        """Diagnostics: the launches task() has made so far."""
+        a = ctypes.c_longlong(0)
+        lib().phys_batch_debug_task_launches(self._h, ctypes.byref(a))
         return a.value
 
     def set_pd_mode(self, on=True):

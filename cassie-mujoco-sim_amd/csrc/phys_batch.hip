@@ -168,6 +168,19 @@ struct phys_batch {
     DevBuf<double> d_act_state;
     DevBuf<unsigned> d_act_counts;
     long long act_launches = 0;     /* launches of cassie_act_kernel (phys_batch_debug_act_launches) */
+    /* task rows (phys_batch_task_configure): the record (task.ncols 0: not configured; its pointers are filled in at the launch, from the
+     * buffers), the column table, the reference table [task_nframes][task_tcols] (phys_batch_task_set_table), the rows (the batch's own
+     * or a caller's, floats or doubles) with their stride in elements, the per-env state [ncols], words [3][ncols] and call counts.  No
+     * stepping launch reads any of it: a step reads the command fields the call wrote */
+    ck::TaskCfg task = {};
+    DevBuf<ck::TaskCol> d_task_cols;
+    DevBuf<double> d_task_table;
+    int task_nframes = 0, task_tcols = 0;
+    DevBuf<char> d_task_rows;
+    long long task_srow = 0;
+    DevBuf<double> d_task_state;
+    DevBuf<unsigned> d_task_words, d_task_counts;
+    long long task_launches = 0;    /* launches of cassie_task_kernel (phys_batch_debug_task_launches) */
 };
 
 static bool hip_ok(hipError_t e, const char *what) {
@@ -1880,6 +1893,132 @@ int phys_batch_act_set_state(phys_batch_t *b, const double *state_host, const un
 int phys_batch_debug_act_launches(const phys_batch_t *b, long long *launches) {
     if (!b) return -1;
     if (launches) *launches = b->act_launches;
+    return 0;
+}
+
+/* ------------------------------------------------ task rows ---- */
+static_assert(sizeof(ck::TaskColDef) == sizeof(phys_task_col_t) && offsetof(ck::TaskColDef, dindex) == offsetof(phys_task_col_t, dindex) &&
+              offsetof(ck::TaskColDef, hold) == offsetof(phys_task_col_t, hold) && offsetof(ck::TaskColDef, p_rest) == offsetof(phys_task_col_t, p_rest) &&
+              offsetof(ck::TaskColDef, phase0) == offsetof(phys_task_col_t, phase0) && offsetof(ck::TaskColDef, scale) == offsetof(phys_task_col_t, scale),
+              "phys_task_col_t is the column task_configure reads");
+static_assert(PHYS_TASK_SAMPLE == ck::TASK_SAMPLE && PHYS_TASK_PHASE == ck::TASK_PHASE && PHYS_TASK_WAVE == ck::TASK_WAVE && PHYS_TASK_TABLE == ck::TASK_TABLE &&
+              PHYS_TASK_SAW == ck::TASK_SAW && PHYS_TASK_SIN == ck::TASK_SIN && PHYS_TASK_COS == ck::TASK_COS && PHYS_TASK_TRAPEZOID == ck::TASK_TRAPEZOID &&
+              PHYS_TASK_NONE == ck::TASK_NONE && PHYS_TASK_NONE == PHYS_ACT_NONE && PHYS_TASK_MAXCOLS == ck::TASK_MAXCOLS &&
+              PHYS_TASK_MAXFRAMES == ck::TASK_MAXFRAMES && PHYS_TASK_MAXTCOLS == ck::TASK_MAXTCOLS, "the header's numbers are task_kernels.h's");
+/* the record of a launch: what was configured, with the pointers into the batch's buffers */
+static ck::TaskCfg task_cfg_of(const phys_batch *b) {
+    ck::TaskCfg c = b->task;
+    c.cols = b->d_task_cols; c.rows = b->d_task_rows.get(); c.srow = b->task_srow; c.state = b->d_task_state; c.words = b->d_task_words; c.counts = b->d_task_counts;
+    c.table = b->d_task_table; c.nframes = b->task_nframes; c.tcols = b->task_tcols;
+    return c;
+}
+int phys_batch_task_set_table(phys_batch_t *b, const double *host, int nframes, int tcols) {
+    if (!b) return refuse("phys_batch_task_set_table", ck::TASK_TABLE_REFUSAL);
+    if (const char *why = ck::check_task_table(b->task, host, nframes, tcols)) return refuse("phys_batch_task_set_table", why);
+    (void)hipSetDevice(b->device);
+    if (!quiesce(b)) return -1;  /* (launches in flight may be reading the table that goes away) */
+    const size_t count = (size_t)nframes * (size_t)tcols;
+    DevBuf<double> tab;
+    if (!tab.alloc(count, false, "task table")) return -1;
+    if (!hip_ok(hipMemcpy(tab, host, sizeof(double) * count, hipMemcpyHostToDevice), "hipMemcpy(task table)")) return -1;
+    b->d_task_table = std::move(tab); b->task_nframes = nframes; b->task_tcols = tcols;
+    return 0;
+}
+int phys_batch_task_configure(phys_batch_t *b, const phys_task_col_t *cols, int ncols, int dtype, unsigned long long seed, unsigned env_base) {
+    if (!b) return refuse("phys_batch_task_configure", ck::TASK_SIZE_REFUSAL);
+    int dims[PHYS_F_COUNT];
+    for (int k = 0; k < PHYS_F_COUNT; ++k) dims[k] = b->d_field[k] ? b->dim[k] : 0;
+    std::vector<ck::TaskCol> table((size_t)ck::TASK_MAXCOLS);
+    ck::TaskCfg cfg;
+    if (const char *why = ck::task_configure(dims, PHYS_F_COUNT, ACT_CMD_FIELDS, ck::ACT_MAXDST, (const ck::TaskColDef *)cols, ncols, dtype, seed, env_base,
+                                             b->d_task_table ? b->task_nframes : 0, b->d_task_table ? b->task_tcols : 0, table.data(), cfg))
+        return refuse("phys_batch_task_configure", why);
+    (void)hipSetDevice(b->device);
+    if (!quiesce(b)) return -1;  /* (launches in flight may be reading the table, or writing the rows, that go away) */
+    const size_t n = (size_t)b->nenv;
+    DevBuf<ck::TaskCol> tab;
+    DevBuf<char> rows;
+    DevBuf<double> state;
+    DevBuf<unsigned> words, counts;
+    if (!tab.alloc((size_t)ncols, false, "task columns")) return -1;
+    if (!hip_ok(hipMemcpy(tab, table.data(), sizeof(ck::TaskCol) * (size_t)ncols, hipMemcpyHostToDevice), "hipMemcpy(task columns)")) return -1;
+    if (!rows.alloc(n * (size_t)ncols * (size_t)dtype, true, "task rows")) return -1;
+    if (!state.alloc(n * (size_t)ncols, true, "task state")) return -1;
+    if (!words.alloc(n * (size_t)ck::TASK_WORDS * (size_t)ncols, true, "task words")) return -1;
+    if (!counts.alloc(n, true, "task call counts")) return -1;
+    b->d_task_cols = std::move(tab); b->d_task_rows = std::move(rows); b->d_task_state = std::move(state); b->d_task_words = std::move(words);
+    b->d_task_counts = std::move(counts);
+    b->task_srow = (long long)ncols;
+    b->task = cfg;   /* (the rows are the batch's own: the binding is dropped) */
+    /* (as phys_batch_act_configure: a destination the step kernel is handed only once somebody writes it is in use from here on) */
+    for (int s = 0; s < cfg.ndst; ++s) note_field_in_use(b, cfg.dst_field[s]);
+    return 0;
+}
+int phys_batch_task_bind_rows(phys_batch_t *b, void *device_ptr, long long row_stride) {
+    if (!b) { phys_set_last_error("phys_batch_task_bind_rows: no batch"); return -1; }
+    const long long row = b->task.ncols;
+    if (const char *why = ck::check_task_bind_rows(b->task, device_ptr ? row_stride : row)) return refuse("phys_batch_task_bind_rows", why);
+    (void)hipSetDevice(b->device);
+    /* (as phys_batch_bind: launches already queued keep the pointer they were given; hipFree waits for the device by itself) */
+    if (device_ptr) { b->d_task_rows.borrow((char *)device_ptr); b->task_srow = row_stride; }
+    else if (!b->d_task_rows.owned()) {
+        if (!b->d_task_rows.alloc((size_t)b->nenv * (size_t)row * (size_t)b->task.dtype, true, "task rows")) return -1;
+        b->task_srow = row;
+    }
+    return 0;
+}
+int phys_batch_task(phys_batch_t *b, int env0, int n, const void *reset_ptr, void *stream) {
+    if (!b) { phys_set_last_error("phys_batch_task: no batch"); return -1; }
+    const ck::TaskCfg c = task_cfg_of(b);
+    ck::ObsField fields[PHYS_F_COUNT];
+    obs_fields_of(b, fields);
+    if (const char *why = ck::check_task_call(c, fields, PHYS_F_COUNT, b->nenv, env0, n)) return refuse("phys_batch_task", why);
+    (void)hipSetDevice(b->device);
+    if (n == 0) return 0;
+    hipStream_t s = launch_stream(b, stream);
+    hipLaunchKernelGGL(ck::cassie_task_kernel, dim3((unsigned)ck::task_grid(n)), dim3(WV_WAVE), 0, s, ck::make_task_io(c, fields, env0, n, (const int *)reset_ptr));
+    if (!hip_ok(hipGetLastError(), "cassie_task_kernel launch")) return -1;
+    ++b->task_launches;
+    return 0;
+}
+int phys_batch_task_dim(const phys_batch_t *b, int *ncols, int *dtype) {
+    if (!b || b->task.ncols < 1) { phys_set_last_error("phys_batch_task_dim: not configured (phys_batch_task_configure first)"); return -1; }
+    if (ncols) *ncols = b->task.ncols;
+    if (dtype) *dtype = b->task.dtype;
+    return 0;
+}
+int phys_batch_task_download(phys_batch_t *b, void *host, int env0, int n) {
+    if (!b || !host || b->task.ncols < 1 || !b->d_task_rows) { phys_set_last_error("phys_batch_task_download: bad arguments, or not configured (phys_batch_task_configure first)"); return -1; }
+    if (!range_ok(b, env0, n)) return refuse("phys_batch_task_download", "env range out of bounds");
+    (void)hipSetDevice(b->device);
+    if (!quiesce(b)) return -1;
+    if (n == 0) return 0;
+    const size_t el = (size_t)b->task.dtype, row = (size_t)b->task.ncols, st = (size_t)b->task_srow;
+    return hip_ok(hipMemcpy2D(host, el * row, b->d_task_rows.get() + el * st * (size_t)env0, el * st, el * row, (size_t)n, hipMemcpyDeviceToHost), "task rows download") ? 0 : -1;
+}
+int phys_batch_task_state(phys_batch_t *b, double *state_host, unsigned *words_host, unsigned *counts_host) {
+    if (!b || !state_host || !words_host || !counts_host || !b->d_task_state || !b->d_task_words || !b->d_task_counts) {
+        phys_set_last_error("phys_batch_task_state: bad arguments, or not configured (phys_batch_task_configure first)"); return -1;
+    }
+    (void)hipSetDevice(b->device);
+    const size_t n = (size_t)b->nenv, nc = (size_t)b->task.ncols;
+    return quiesce(b) && hip_ok(hipMemcpy(state_host, b->d_task_state, sizeof(double) * n * nc, hipMemcpyDeviceToHost), "task state download") &&
+                   hip_ok(hipMemcpy(words_host, b->d_task_words, sizeof(unsigned) * n * ck::TASK_WORDS * nc, hipMemcpyDeviceToHost), "task words download") &&
+                   hip_ok(hipMemcpy(counts_host, b->d_task_counts, sizeof(unsigned) * n, hipMemcpyDeviceToHost), "task call counts download") ? 0 : -1;
+}
+int phys_batch_task_set_state(phys_batch_t *b, const double *state_host, const unsigned *words_host, const unsigned *counts_host) {
+    if (!b || !state_host || !words_host || !counts_host || !b->d_task_state || !b->d_task_words || !b->d_task_counts) {
+        phys_set_last_error("phys_batch_task_set_state: bad arguments, or not configured (phys_batch_task_configure first)"); return -1;
+    }
+    (void)hipSetDevice(b->device);
+    const size_t n = (size_t)b->nenv, nc = (size_t)b->task.ncols;
+    return quiesce(b) && hip_ok(hipMemcpy(b->d_task_state, state_host, sizeof(double) * n * nc, hipMemcpyHostToDevice), "task state upload") &&
+                   hip_ok(hipMemcpy(b->d_task_words, words_host, sizeof(unsigned) * n * ck::TASK_WORDS * nc, hipMemcpyHostToDevice), "task words upload") &&
+                   hip_ok(hipMemcpy(b->d_task_counts, counts_host, sizeof(unsigned) * n, hipMemcpyHostToDevice), "task call counts upload") ? 0 : -1;
+}
+int phys_batch_debug_task_launches(const phys_batch_t *b, long long *launches) {
+    if (!b) return -1;
+    if (launches) *launches = b->task_launches;
     return 0;
 }
 

@@ -1,12 +1,12 @@
 /*
- * small_launch.h -- how the kernels around the step kernel (small_kernels.h, surface_kernels.h, depth_kernel.h, ray_kernel.h, episode_kernels.h, probe_kernels.h, obs_kernels.h, reward_kernels.h, act_kernels.h) are
+ * small_launch.h -- how the kernels around the step kernel (small_kernels.h, surface_kernels.h, depth_kernel.h, ray_kernel.h, episode_kernels.h, probe_kernels.h, obs_kernels.h, reward_kernels.h, act_kernels.h, task_kernels.h) are
  * launched: the records a kernel's arguments are built from, one builder per kernel that returns its filled argument struct for an env
  * range, the grid of every launch, and the checks of what a caller configures, each returning the message of its refusal (null: fine).
  * Pure host code, no HIP runtime calls, in the spirit of step_policy.h: the launcher (phys_batch.hip) keeps the records in the batch,
  * prefixes a message with its entry point's name and launches what a builder returns on the grid given here; the wave emulator's entry
  * points (tests/emu) fill the same records from their arguments and go through the same builders, grids and checks, so a CPU test of
  * one of these kernels also runs the launcher's refusals, grid and choice of kernel (tests/test_small_launch.py pins them one by one).
- * No field of ScanIO, DepthIO, RayIO, EpisodeIO, ResetIO, DeriveIO, SetConstIO, StateIO, ProbeIO, ObsIO, RewardIO or ActIO is assigned anywhere else.
+ * No field of ScanIO, DepthIO, RayIO, EpisodeIO, ResetIO, DeriveIO, SetConstIO, StateIO, ProbeIO, ObsIO, RewardIO, ActIO or TaskIO is assigned anywhere else.
  */
 #ifndef CASSIE_SMALL_LAUNCH_H
 #define CASSIE_SMALL_LAUNCH_H
@@ -23,6 +23,7 @@
 #include "reward_kernels.h"
 #include "small_kernels.h"
 #include "state_kernels.h"
+#include "task_kernels.h"
 
 namespace ck {
 
@@ -124,6 +125,19 @@ struct ActCfg {
     const void *actions; long long act_stride; int act_dtype;
     const void *input; int input_dim, input_stride, input_dtype;
     const int *delay;
+};
+
+/* the task rows (phys_batch_task_configure; ncols 0: not configured): the columns, the rows' type (OBS_F32 / OBS_F64), the seed of the draws
+ * and the offset of their env counter; the destinations of a call as the action's -- slot s is the command field dst_field[s], whose row
+ * held dst_dim[s] -- and the columns of the table the TABLE columns reach (0: none).  Then what the caller names once a kernel reads them:
+ * the column table [ncols], the rows with their stride in elements, the state [nenv][ncols], the words [nenv][TASK_WORDS][ncols], the
+ * counts [nenv], and the reference table [nframes][tcols] (null: none set) */
+struct TaskCfg {
+    int ncols, dtype, ndst, tcol_need;
+    unsigned long long seed; unsigned env_base;
+    int dst_field[ACT_MAXDST], dst_dim[ACT_MAXDST];
+    const TaskCol *cols; void *rows; long long srow; double *state; unsigned *words; unsigned *counts;
+    const double *table; int nframes, tcols;
 };
 
 /* ---- the row of a full state ---- */
@@ -470,6 +484,46 @@ inline const char *check_reward_call(const RewardCfg &c, const ObsField *fields,
     }
     return nullptr;
 }
+/* the destination of column k of cols [..] (any column type with a dfield and a dindex; ACT_NONE: none), shared by the stages that write
+ * command fields (the action rows, the task rows): one element of a command field (cmd_fields [ncmd]) the batch holds, inside its row,
+ * that no earlier column names -> its slot among the call's destinations (ndst, dst_field, dst_dim [ACT_MAXDST]: extended by a new
+ * field) and its element; dslot -1 for none */
+template <class ColDef>
+inline const char *claim_destination(const int *field_dim, int nfields, const int *cmd_fields, int ncmd, const ColDef *cols, int k,
+                                     int &ndst, int *dst_field, int *dst_dim, int &dslot, int &delem) {
+    const ColDef &d = cols[k];
+    dslot = -1; delem = 0;
+    if (d.dfield == ACT_NONE) return nullptr;
+    bool cmd = false;
+    for (int j = 0; j < ncmd; ++j) cmd = cmd || cmd_fields[j] == d.dfield;
+    if (!cmd || d.dfield < 0 || d.dfield >= nfields)
+        return "a column's dfield is PHYS_ACT_NONE or a command field (PHYS_F_PD_PTARGET, _PD_DTARGET, _PD_KP, _PD_KD, _PD_TORQUE, PHYS_F_DRIVE_CMD, PHYS_F_CTRL, PHYS_F_QFRC_APPLIED, PHYS_F_XFRC_APPLIED)";
+    const int dim = field_dim[d.dfield];
+    if (dim == 0) return "a column writes a field the batch does not hold";
+    if (d.dindex < 0 || d.dindex >= dim) return "dindex lies beyond the field's row";
+    for (int j = 0; j < k; ++j)
+        if (cols[j].dfield == d.dfield && cols[j].dindex == d.dindex) return "two columns write the same destination element";
+    int s = 0;
+    while (s < ndst && dst_field[s] != d.dfield) ++s;
+    if (s == ndst) {
+        if (ndst == ACT_MAXDST) return "more destination fields than there are command fields";
+        dst_field[s] = d.dfield; dst_dim[s] = dim; ++ndst;
+    }
+    dslot = s; delem = d.dindex;
+    return nullptr;
+}
+/* whether every destination field of a call is held NOW with the row length it had at the configure call (fields [nfields]) */
+inline bool destinations_unchanged(int ndst, const int *dst_field, const int *dst_dim, const ObsField *fields, int nfields) {
+    for (int s = 0; s < ndst; ++s) {
+        const int f = dst_field[s];
+        if (f < 0 || f >= nfields || !fields[f].base || fields[f].dim != dst_dim[s]) return false;
+    }
+    return true;
+}
+/* the destinations of a launch where the batch reads them today */
+inline void fill_destinations(ActDst *dst, int ndst, const int *dst_field, const ObsField *fields) {
+    for (int s = 0; s < ndst; ++s) dst[s] = {const_cast<double *>(fields[dst_field[s]].base), fields[dst_field[s]].stride};
+}
 /* (what the launcher also answers a call without a batch) */
 constexpr const char *ACT_SIZE_REFUSAL = "0 .. 256 columns (0 releases them), a delay depth of 0 .. 8, rows of PHYS_OBS_F32 or PHYS_OBS_F64";
 /* the actions' configuration: checks the caller's columns [ncols] against the row lengths the batch holds now (as obs_configure: field_dim
@@ -509,25 +563,7 @@ inline const char *act_configure(const int *field_dim, int nfields, int depth_fi
             o.slot = s; o.elem = d.bindex;
         }
         /* the destination: none, or one element of a command field that no other column writes */
-        o.dslot = -1; o.delem = 0;
-        if (d.dfield != ACT_NONE) {
-            bool cmd = false;
-            for (int j = 0; j < ncmd; ++j) cmd = cmd || cmd_fields[j] == d.dfield;
-            if (!cmd || d.dfield < 0 || d.dfield >= nfields)
-                return "a column's dfield is PHYS_ACT_NONE or a command field (PHYS_F_PD_PTARGET, _PD_DTARGET, _PD_KP, _PD_KD, _PD_TORQUE, PHYS_F_DRIVE_CMD, PHYS_F_CTRL, PHYS_F_QFRC_APPLIED, PHYS_F_XFRC_APPLIED)";
-            const int dim = field_dim[d.dfield];
-            if (dim == 0) return "a column writes a field the batch does not hold";
-            if (d.dindex < 0 || d.dindex >= dim) return "dindex lies beyond the field's row";
-            for (int j = 0; j < k; ++j)
-                if (cols[j].dfield == d.dfield && cols[j].dindex == d.dindex) return "two columns write the same destination element";
-            int s = 0;
-            while (s < c.ndst && c.dst_field[s] != d.dfield) ++s;
-            if (s == c.ndst) {
-                if (c.ndst == ACT_MAXDST) return "more destination fields than there are command fields";
-                c.dst_field[s] = d.dfield; c.dst_dim[s] = dim; ++c.ndst;
-            }
-            o.dslot = s; o.delem = d.dindex;
-        }
+        if (const char *why = claim_destination(field_dim, nfields, cmd_fields, ncmd, cols, k, c.ndst, c.dst_field, c.dst_dim, o.dslot, o.delem)) return why;
         o.lo = d.lo; o.hi = d.hi; o.noise = d.noise; o.smooth = d.smooth; o.offset = d.offset; o.scale = d.scale; o.out_lo = d.out_lo; o.out_hi = d.out_hi;
     }
     c.ncols = ncols; c.delay_max = delay_max; c.dtype = dtype; c.seed = seed; c.env_base = env_base;
@@ -566,11 +602,90 @@ inline const char *check_act_call(const ActCfg &c, const ObsField *fields, int n
         } else if (f < 0 || f >= nfields || !fields[f].base || fields[f].dim != c.slot_dim[s])
             return "the row length of a source field has changed since phys_batch_act_configure (configure again)";
     }
-    for (int s = 0; s < c.ndst; ++s) {
-        const int f = c.dst_field[s];
-        if (f < 0 || f >= nfields || !fields[f].base || fields[f].dim != c.dst_dim[s])
-            return "the row length of a destination field has changed since phys_batch_act_configure (configure again)";
+    if (!destinations_unchanged(c.ndst, c.dst_field, c.dst_dim, fields, nfields))
+        return "the row length of a destination field has changed since phys_batch_act_configure (configure again)";
+    return nullptr;
+}
+/* (what the launcher also answers a call without a batch) */
+constexpr const char *TASK_SIZE_REFUSAL = "1 .. 64 columns (a lane makes a column), rows of PHYS_OBS_F32 or PHYS_OBS_F64";
+constexpr const char *TASK_TABLE_REFUSAL = "a table of 1 .. 4096 frames of 1 .. 64 finite columns";
+/* the reference table of the TABLE columns (phys_batch_task_set_table): host [nframes][tcols] */
+inline const char *check_task_table(const TaskCfg &c, const double *host, int nframes, int tcols) {
+    if (!host || nframes < 1 || nframes > TASK_MAXFRAMES || tcols < 1 || tcols > TASK_MAXTCOLS) return TASK_TABLE_REFUSAL;
+    for (long long k = 0; k < (long long)nframes * tcols; ++k) if (!std::isfinite(host[k])) return TASK_TABLE_REFUSAL;
+    if (c.ncols > 0 && tcols < c.tcol_need) return "the configured TABLE columns reach beyond the new table's columns (configure again)";
+    return nullptr;
+}
+/* the task rows' configuration: checks the caller's columns [ncols] against the row lengths the batch holds now (field_dim [nfields], 0: a
+ * field it does not hold; cmd_fields [ncmd]: the fields a column may write) and against the table that is set (nframes x tcols, 0: none),
+ * writes the table a launch reads (table [TASK_MAXCOLS]: the defaults resolved to lanes, the periods as a span, the resting threshold)
+ * and fills c but for what the caller names later.  The emulator goes through the same */
+inline const char *task_configure(const int *field_dim, int nfields, const int *cmd_fields, int ncmd, const TaskColDef *cols, int ncols, int dtype,
+                                  unsigned long long seed, unsigned env_base, int nframes, int tcols, TaskCol *table, TaskCfg &c) {
+    if (ncols < 1 || ncols > TASK_MAXCOLS || !cols || !table) return TASK_SIZE_REFUSAL;
+    c = {};
+    if (dtype != OBS_F32 && dtype != OBS_F64) return "the rows' dtype is PHYS_OBS_F32 or PHYS_OBS_F64";
+    auto is_kind = [&](int col, int kind) { return col >= 0 && col < ncols && cols[col].kind == kind; };
+    for (int k = 0; k < ncols; ++k) {
+        const TaskColDef &d = cols[k];
+        TaskCol &o = table[k];
+        memset(&o, 0, sizeof o);
+        o.kind = d.kind; o.group = k; o.rate_col = -1; o.phase_col = -1; o.src = -1;
+        if (d.kind == TASK_SAMPLE) {
+            if (!(std::isfinite(d.center) && std::isfinite(d.half) && std::isfinite(d.rest) && std::isfinite(d.p_rest))) return "a SAMPLE column needs a finite center, half, rest and p_rest";
+            if (d.half < 0) return "half is a half width: >= 0";
+            if (!(d.p_rest >= 0 && d.p_rest <= 1)) return "p_rest is a probability: in [0, 1]";
+            if (d.period_lo < 1u || d.period_lo > d.period_hi || d.period_hi > TASK_MAXPERIOD) return "1 <= period_lo <= period_hi <= 2^30 calls";
+            const int g = d.group < 0 ? k : d.group;
+            if (!is_kind(g, TASK_SAMPLE) || (cols[g].group >= 0 && cols[g].group != g)) return "group names a SAMPLE column that is its own group (-1: the column itself)";
+            const TaskColDef &l = cols[g];
+            if (l.period_lo != d.period_lo || l.period_hi != d.period_hi || l.hold != d.hold || l.p_rest != d.p_rest)
+                return "the members of a group share period_lo, period_hi, hold and p_rest with the column the group names";
+            o.group = g; o.period_lo = d.period_lo; o.span = d.period_hi - d.period_lo + 1u; o.hold = d.hold;
+            o.thr = (unsigned long long)llrint(d.p_rest * 4294967296.0);
+            o.center = d.center; o.half = d.half; o.rest = d.rest;
+        } else if (d.kind == TASK_PHASE) {
+            if (!(std::isfinite(d.rate) && std::isfinite(d.rate_scale) && std::isfinite(d.phase0))) return "a PHASE column needs a finite rate, rate_scale and phase0";
+            if (d.rate_col >= 0 && !is_kind(d.rate_col, TASK_SAMPLE)) return "rate_col is -1 or a SAMPLE column";
+            if (d.phase_col >= 0 && !is_kind(d.phase_col, TASK_SAMPLE)) return "phase_col is -1 or a SAMPLE column";
+            o.rate_col = d.rate_col < 0 ? -1 : d.rate_col; o.phase_col = d.phase_col < 0 ? -1 : d.phase_col;
+            o.rate = d.rate; o.rate_scale = d.rate_scale; o.phase0 = d.phase0;
+        } else if (d.kind == TASK_WAVE || d.kind == TASK_TABLE) {
+            if (!is_kind(d.src, TASK_PHASE)) return "src is a PHASE column";
+            if (!(std::isfinite(d.shift) && std::isfinite(d.offset) && std::isfinite(d.scale))) return "a WAVE or TABLE column needs a finite shift, offset and scale";
+            if (d.kind == TASK_WAVE) {
+                if (d.form != TASK_SAW && d.form != TASK_SIN && d.form != TASK_COS && d.form != TASK_TRAPEZOID) return "a WAVE's form is PHYS_TASK_SAW, _SIN, _COS or _TRAPEZOID";
+                if (d.form == TASK_TRAPEZOID) {
+                    if (!(std::isfinite(d.duty) && std::isfinite(d.ramp)) || !(d.ramp > 0) || d.duty < 0 || d.duty + d.ramp > 1) return "a TRAPEZOID needs ramp > 0, duty >= 0 and duty + ramp <= 1";
+                    o.duty = d.duty; o.ramp = d.ramp;
+                }
+                o.form = d.form;
+            } else {
+                if (nframes < 1 || tcols < 1) return "a TABLE column and no table (phys_batch_task_set_table first)";
+                if (d.tcol < 0 || d.tcol >= tcols) return "tcol lies beyond the table's columns";
+                o.tcol = d.tcol;
+                if (d.tcol + 1 > c.tcol_need) c.tcol_need = d.tcol + 1;
+            }
+            o.src = d.src; o.shift = d.shift; o.offset = d.offset; o.scale = d.scale;
+        } else return "a column's kind is PHYS_TASK_SAMPLE, _PHASE, _WAVE or _TABLE";
+        if (const char *why = claim_destination(field_dim, nfields, cmd_fields, ncmd, cols, k, c.ndst, c.dst_field, c.dst_dim, o.dslot, o.delem)) return why;
     }
+    c.ncols = ncols; c.dtype = dtype; c.seed = seed; c.env_base = env_base;
+    return nullptr;
+}
+/* what phys_batch_task_bind_rows refuses */
+inline const char *check_task_bind_rows(const TaskCfg &c, long long row_stride) {
+    if (c.ncols < 1) return "not configured (phys_batch_task_configure first)";
+    if (row_stride < c.ncols) return "a row stride of at least the columns";
+    return nullptr;
+}
+/* what a task call refuses; fields [nfields]: what the batch holds NOW */
+inline const char *check_task_call(const TaskCfg &c, const ObsField *fields, int nfields, int nenv, int env0, int n) {
+    if (c.ncols < 1 || !c.cols || !c.rows || !c.state || !c.words || !c.counts) return "not configured (phys_batch_task_configure first)";
+    if (env0 < 0 || n < 0 || (long long)env0 + n > nenv) return "env range out of bounds";
+    if (c.tcol_need > 0 && (!c.table || c.nframes < 1 || c.tcols < c.tcol_need)) return "a TABLE column and no table that holds its column (phys_batch_task_set_table)";
+    if (!destinations_unchanged(c.ndst, c.dst_field, c.dst_dim, fields, nfields))
+        return "the row length of a destination field has changed since phys_batch_task_configure (configure again)";
     return nullptr;
 }
 /* the bank of full states: what phys_batch_state_configure / _bind refuse (the view tells what the batch has), and what a save or a
@@ -608,6 +723,8 @@ inline int obs_grid(int n) { return n < OBS_GRID ? n : OBS_GRID; }
 inline int reward_grid(int n) { const long long w = ((long long)n + WV_WAVE - 1) / WV_WAVE; return w < REWARD_GRID ? (int)w : REWARD_GRID; }
 /* one wave per env up to ACT_GRID workgroups, which then walk the range: few, as the observation's (act_kernels.h) */
 inline int act_grid(int n) { return n < ACT_GRID ? n : ACT_GRID; }
+/* one wave per env up to TASK_GRID workgroups, which then walk the range: few, as the action's (task_kernels.h) */
+inline int task_grid(int n) { return n < TASK_GRID ? n : TASK_GRID; }
 /* a job is (env, tile of DEPTH_TILE x DEPTH_TILE pixels); a fixed grid walks the job list (a first choice: depth_kernel.h) */
 inline int depth_grid(int n, int width, int height) {
     const int T = DEPTH_TILE;
@@ -734,9 +851,21 @@ inline ActIO make_act_io(const ActCfg &c, const ObsField *fields, int env0, int 
         if (f == ACT_INPUT) io.src[s] = {c.input, c.input_stride, c.input_dtype == OBS_F32, 0};
         else io.src[s] = {fields[f].base, fields[f].stride, 0, 0};
     }
-    for (int s = 0; s < c.ndst; ++s) io.dst[s] = {const_cast<double *>(fields[c.dst_field[s]].base), fields[c.dst_field[s]].stride};
+    fill_destinations(io.dst, c.ndst, c.dst_field, fields);
     io.actions = c.actions; io.sact = c.act_stride;
     io.rows = c.rows; io.srow = c.srow; io.state = c.state; io.counts = c.counts; io.delay = c.delay; io.reset = reset;
+    return io;
+}
+/* cassie_task_kernel's: the destinations of the record's slots where the batch reads them today (as make_act_io), the column table, the
+ * reference table, the rows, the state, the words, the counts and the key */
+inline TaskIO make_task_io(const TaskCfg &c, const ObsField *fields, int env0, int n, const int *reset) {
+    TaskIO io = zeroed<TaskIO>();
+    io.env0 = env0; io.n = n; io.ncols = c.ncols; io.f32 = c.dtype == OBS_F32;
+    io.env_base = c.env_base; io.key0 = (unsigned)(c.seed & 0xffffffffull); io.key1 = (unsigned)(c.seed >> 32);
+    io.cols = c.cols;
+    if (c.tcol_need > 0) { io.table = c.table; io.nframes = c.nframes; io.tcols = c.tcols; }
+    fill_destinations(io.dst, c.ndst, c.dst_field, fields);
+    io.rows = c.rows; io.srow = c.srow; io.state = c.state; io.words = c.words; io.counts = c.counts; io.reset = reset;
     return io;
 }
 inline int episode_row_dim(const BatchView &v) { return v.nq + v.nv + v.nsd + v.nu + v.nv; }

@@ -948,6 +948,127 @@ int phys_batch_act_state(phys_batch_t *b, double *state_host /*[nenv][D + 3][nco
 int phys_batch_act_set_state(phys_batch_t *b, const double *state_host, const unsigned *counts_host);
 int phys_batch_debug_act_launches(const phys_batch_t *b, long long *launches);
 
+/* TASK ROWS: what a policy step is ASKED, made on the device by ONE launch per env range: the velocity command with its resampling timer
+ * and its "stand still", a per-env gait frequency, the gait clock and its sin / cos, the swing / stance gates, the interpolated row of a
+ * periodic reference trajectory, and random pushes into PHYS_F_XFRC_APPLIED -- everything the observation, the reward and the action
+ * stages took as "the caller's input", so that nothing a policy step reads or writes but the network itself is made on the host, and all
+ * of it reproduces whatever the cut of the batch into ranges and ranks.  A configured table of ncols COLUMNS (1 .. PHYS_TASK_MAXCOLS =
+ * 64: a lane of the wave makes a column), column c for element c of an env's TASK ROW [ncols] of the configured type (PHYS_OBS_F32 /
+ * PHYS_OBS_F64; the cast rounds to nearest even).  The row is the batch's own, or the caller's tensor bound with a row stride -- typically a
+ * column block of the tensor phys_batch_obs, _reward and _act bind as their input.
+ * A COLUMN (phys_task_col_t) has a kind and, whatever the kind,
+ *   dfield, dindex    a destination for its fp64 value besides the row, exactly as an action column's: element dindex of the env's row of
+ *                     a command field (the same nine: PHYS_F_PD_PTARGET, _PD_DTARGET, _PD_KP, _PD_KD, _PD_TORQUE, PHYS_F_DRIVE_CMD,
+ *                     PHYS_F_CTRL, PHYS_F_QFRC_APPLIED, PHYS_F_XFRC_APPLIED), written where the batch reads the field at the call;
+ *                     PHYS_TASK_NONE (= PHYS_ACT_NONE): none.  No two columns name the same element.  A field a stepping launch is handed
+ *                     only once somebody wrote it counts as written from the configure call on.
+ * PER ENV AND CALL, every arithmetic step one individually rounded fp64 operation (multiply, add, subtract, divide to nearest even; no fused
+ *   multiply-add; floor and rint are exact).  count = counts[env] before the call; fresh = (count == 0 or the call's reset entry for the
+ *   env is non-zero).  The kinds are evaluated in this order, and a kind only reads kinds above it.  out[c] is column c's value.
+ *   wrap(p): f = p - floor(p); f >= 1 ? 0 : f  (a p just below an integer rounds to 1; NaN and the infinities give NaN).
+ *   xi(w) = (w + 0.5) 2^-31 - 1, the observation's uniform.  Philox is Philox4x32-10 with the key (seed & 0xffffffff, seed >> 32); the
+ *   fourth counter words 2 and 3 are this stage's (the observation uses 0, the action 1).
+ * 1. PHYS_TASK_SAMPLE -- a value held for a random number of calls: a command, a gait frequency, an initial phase, a push.
+ *      constants: center, half (>= 0), rest, p_rest in [0, 1], period_lo <= period_hi (1 .. 2^30 calls), hold (0: the whole period),
+ *      group (-1: the column itself; else a SAMPLE column that is its own group, with which the column must share period_lo, period_hi,
+ *      hold and p_rest).  State per (env, column): x (double); left, age, epoch (uint32).
+ *      A DRAW happens when fresh or left == 0:
+ *        epoch = count == 0 ? 0 : epoch + 1
+ *        s = Philox(env_base + env, group, epoch, 2)
+ *        L = period_lo + (uint32)(((uint64)s[0] * (uint64)(period_hi - period_lo + 1)) >> 32)
+ *        resting = (uint64)s[1] < thr, thr the uint64 nearest p_rest 2^32 (computed once by the configure call)
+ *        v = Philox(env_base + env, c, epoch, 3)
+ *        x = resting ? rest : center + half * xi(v[0]);   left = L;   age = 0
+ *      EVERY call: out = (hold == 0 or age < hold) ? x : rest;  then left -= 1, age += 1.
+ *      The schedule is keyed by the group, the value by the column: the columns of a group resample and rest in the same calls while
+ *      each draws its own value.  A command (vx, vy, yaw) is a group of three; a push is a group of PHYS_F_XFRC_APPLIED columns with a hold
+ *      of a few calls and rest = 0.
+ * 2. PHYS_TASK_PHASE -- a clock.  constants: rate (cycles per call), rate_scale, rate_col (-1 or a SAMPLE column), phase0, phase_col (-1
+ *      or a SAMPLE column).  State: phi.
+ *        fresh:      phi = wrap(phase_col < 0 ? phase0 : out[phase_col])
+ *        otherwise:  phi = wrap(phi + inc),  inc = rate_col < 0 ? rate : rate + rate_scale * out[rate_col]
+ *      out = phi.  (A restarted env gets a new initial phase because its SAMPLE column drew on the reset.)
+ * 3. PHYS_TASK_WAVE -- a waveform of a clock.  constants: src (a PHASE column), shift, form, offset, scale (TRAPEZOID: duty, ramp).
+ *        theta = wrap(out[src] + shift)
+ *        PHYS_TASK_SAW:        g = theta
+ *        PHYS_TASK_SIN, _COS:  g = sin2pi(theta), cos2pi(theta), below
+ *        PHYS_TASK_TRAPEZOID:  up = clamp(theta / ramp, 0, 1);  down = clamp((theta - duty) / ramp, 0, 1);  g = up - down
+ *                              (ramp > 0, duty >= 0, duty + ramp <= 1: 0 at theta = 0, 1 on [ramp, duty], 0 from duty + ramp on -- the
+ *                              swing / stance gate of a clock-gated reward term; clamp(x, lo, hi) = x < lo ? lo : (x > hi ? hi : x))
+ *        out = offset + scale * g
+ * 4. PHYS_TASK_TABLE -- one column of a periodic reference trajectory T [nframes][tcols] (doubles; phys_batch_task_set_table; nframes <=
+ *      4096, tcols <= 64).  constants: src, shift, tcol, offset, scale.
+ *        theta as for a WAVE;  s = theta * (double)nframes;  i = s >= 0 ? (int)floor(s) : 0  (a NaN gives 0);  i = min(i, nframes - 1)
+ *        fr = s - (double)i;  j = i + 1 == nframes ? 0 : i + 1;  g = T[i][tcol] + fr * (T[j][tcol] - T[i][tcol])
+ *        out = offset + scale * g
+ *      The clamped i is the only value that picks among memory, and it picks inside the table.
+ * sin2pi / cos2pi, for theta in [0, 1) (a library's sin does not reproduce between a device and a host):
+ *        a NaN gives NaN.  q = rint(4 theta) (exact);  r = theta - 0.25 q (exact, |r| <= 1/8);  x = r * 6.283185307179586 (the double
+ *        nearest 2 pi; ONE rounding);  z = x * x
+ *        p = -1/19!;  p = k + z * p for k = 1/17!, -1/15!, 1/13!, -1/11!, 1/9!, -1/7!, 1/5!, -1/3!;  S = x + ((x * z) * p)
+ *        c = 1/20!;   c = k + z * c for k = -1/18!, 1/16!, -1/14!, 1/12!, -1/10!, 1/8!, -1/6!, 1/4!, -1/2!;  C = 1 + z * c
+ *        (every 1/k! the double nearest it; every product and every sum rounded on its own)
+ *        (sin2pi, cos2pi) = (S, C), (C, -S), (-S, -C), (-C, S) for q & 3 = 0, 1, 2, 3.
+ *      At theta = 0, 1/4, 1/2, 3/4 the results compare equal to 0 and +-1.  Elsewhere the error against the exact sin(2 pi theta) /
+ *      cos(2 pi theta) is measured by tests/test_task.py (DESIGN.md 4.3 has the figure).
+ * Then the stores: out[c] into the row (cast), into the destination element where there is one; counts[env] += 1 (uint32, wraps: a count
+ *   that comes round to 0 starts the env afresh at epoch 0).
+ * STATE: per env [ncols] doubles (a SAMPLE's x, a PHASE's phi, 0 for the other kinds), [3][ncols] uint32 words (left | age | epoch, 0 for
+ *   other kinds than SAMPLE) and the count; the batch owns them.  None is in a state-bank row: as with the action state, a caller that
+ *   rewinds or resumes moves them itself (phys_batch_task_state / _set_state) and then draws on as the first run would have.
+ * ORDER IN A POLICY STEP: phys_batch_act; the step launch; the launches that make sources; phys_batch_reward; phys_batch_end_episodes;
+ *   phys_batch_task; phys_batch_obs.  `reset` is an optional int32 DEVICE array [n], entry i for env env0 + i: the range's slice of
+ *   PHYS_EP_DONE as THIS step's phys_batch_end_episodes left it, the same words phys_batch_obs takes as `refill`.  The reward therefore
+ *   judges a step against the row the policy saw before it; the observation shows the command, clock and reference of the coming step;
+ *   and phys_batch_act adds onto that reference pose.
+ * NaN AND DIVERGED ENVS: nothing of the state of the simulation is read; a NaN can only come from the caller's constants, which the
+ *   configure call refuses, or from an uploaded state.
+ *   phys_batch_task_configure   cols [ncols] (host memory), the rows' type, the seed and env_base (as the observation's).  Refuses, with a
+ *                               message in phys_last_error(): ncols outside 1 .. PHYS_TASK_MAXCOLS, an unknown kind, form or dtype, a
+ *                               constant of the column's kind that is not finite, half < 0, p_rest outside [0, 1], a period outside
+ *                               1 <= period_lo <= period_hi <= 2^30, a group, rate_col or phase_col that is no SAMPLE column, a group that
+ *                               is not its own group or whose member disagrees with it, a src that is no PHASE column, a TRAPEZOID with
+ *                               ramp <= 0, duty < 0 or duty + ramp > 1, a TABLE column with no table set or with tcol beyond it, and
+ *                               what phys_batch_act_configure refuses of a destination.  Allocates the table, the rows, the state and the
+ *                               counts (zeroed); drops the binding of the rows; waits for the batch's streams.
+ *   phys_batch_task_set_table   the reference trajectory, host [nframes][tcols] doubles (1 .. 4096 frames, 1 .. 64 columns, finite), uploaded
+ *                               once and owned by the batch; set it before the configure call that names it.  Refuses a table narrower
+ *                               than the configured TABLE columns reach.  Waits for the batch's streams.
+ *   phys_batch_task_bind_rows   the task rows in caller-owned HBM of the configured type, row_stride elements (>= ncols) between two envs'
+ *                               rows.  NULL: the batch's own rows again, zeroed.
+ *   phys_batch_task             ONE launch of cassie_task_kernel over [env0, env0 + n) on `stream` (NULL: the batch's own), in order with
+ *                               the launches there.  No host synchronisation, no allocation, no read on the host.  Writes the rows, the
+ *                               state, the counts and the destination elements of the range and nothing else.  Refuses: not configured,
+ *                               a range outside the batch, a destination field whose row length is no longer what it was at the
+ *                               configure call.
+ *   phys_batch_task_dim         ncols and the rows' type; either may be NULL -> 0, -1 when not configured.
+ *   phys_batch_task_download    rows [env0, env0 + n) to dense host memory [n][ncols] of the rows' type; waits for the streams.
+ *   phys_batch_task_state / _set_state   the state [nenv][ncols] (doubles), the words [nenv][3][ncols] (uint32) and the counts [nenv]
+ *                               (uint32) to / from the host; both wait for the streams.
+ *   phys_batch_debug_task_launches  diagnostics: the launches phys_batch_task has made. */
+enum { PHYS_TASK_SAMPLE = 0, PHYS_TASK_PHASE = 1, PHYS_TASK_WAVE = 2, PHYS_TASK_TABLE = 3 };         /* a column's kind */
+enum { PHYS_TASK_SAW = 0, PHYS_TASK_SIN = 1, PHYS_TASK_COS = 2, PHYS_TASK_TRAPEZOID = 3 };           /* a WAVE column's form */
+enum { PHYS_TASK_NONE = -3 };                                                                        /* no destination (= PHYS_ACT_NONE) */
+#define PHYS_TASK_MAXCOLS 64
+#define PHYS_TASK_MAXFRAMES 4096
+#define PHYS_TASK_MAXTCOLS 64
+typedef struct phys_task_col {
+    int kind, form, group, rate_col, phase_col, src, tcol, dfield, dindex;
+    unsigned period_lo, period_hi, hold;
+    double center, half, rest, p_rest;        /* SAMPLE */
+    double rate, rate_scale, phase0;          /* PHASE */
+    double shift, duty, ramp, offset, scale;  /* WAVE, TABLE */
+} phys_task_col_t;
+int phys_batch_task_configure(phys_batch_t *b, const phys_task_col_t *cols, int ncols, int dtype, unsigned long long seed, unsigned env_base);
+int phys_batch_task_set_table(phys_batch_t *b, const double *host /*[nframes][tcols]*/, int nframes, int tcols);
+int phys_batch_task_bind_rows(phys_batch_t *b, void *device_ptr, long long row_stride);   /* NULL un-binds */
+int phys_batch_task(phys_batch_t *b, int env0, int n, const void *reset_ptr /* int32 [n] or NULL */, void *stream);
+int phys_batch_task_dim(const phys_batch_t *b, int *ncols, int *dtype);
+int phys_batch_task_download(phys_batch_t *b, void *host, int env0, int n);
+int phys_batch_task_state(phys_batch_t *b, double *state_host /*[nenv][ncols]*/, unsigned *words_host /*[nenv][3][ncols]*/, unsigned *counts_host /*[nenv]*/);
+int phys_batch_task_set_state(phys_batch_t *b, const double *state_host, const unsigned *words_host, const unsigned *counts_host);
+int phys_batch_debug_task_launches(const phys_batch_t *b, long long *launches);
+
 /* measurement aid: on = every substep of a fused launch evaluates every output (IMU sensors, body quaternions), although
  * only the last substep's values can be read; off (default) = those are formed by the substeps whose values are read */
 int phys_batch_set_all_outputs_every_substep(phys_batch_t *b, int on);
