@@ -1003,6 +1003,16 @@ bool HostModel::compile(cm_model_t *o, std::string *err) const {
         return fail("model exceeds the compiled capacity limits (cm_model.h)");
     o->nq = nq; o->nv = nv; o->nu = nu; o->nbody = nbody; o->njnt = njnt; o->neq = neq; o->nsite = nsite;
     o->nsensor = nsensor; o->nsensordata = nsensordata;
+    /* A free joint IS its body's frame in the world: the kinematics of oracle and kernel read the pose of such a body straight from
+     * qpos, which holds only for a child of the world that has no other joint (MuJoCo refuses both cases too).  On a nested free body
+     * the two disagreed about where it is, beside a hinge they disagreed about the contacts. */
+    for (int j = 0; j < njnt; ++j) {
+        if (jnt_type[j] != CM_JNT_FREE) continue;
+        const int b = jnt_bodyid[j];
+        const std::string nm = j < (int)jnt_name.size() && !jnt_name[j].empty() ? jnt_name[j] : "#" + std::to_string(j);
+        if (body_parentid[b] != 0) return fail("free joint " + nm + " sits on a body whose parent is not the world");
+        if (body_jntnum[b] != 1) return fail("free joint " + nm + " shares its body with other joints");
+    }
     /* (the 127-row solve's cross-wave turn word counts two per sweep in 12 bits, pk_wide_solve.h) */
     if (iterations > 2000) return fail("option iterations > 2000 is not supported (the in-scope models ask for 50)");
     o->iterations = iterations; o->flags = flags;
