@@ -244,6 +244,20 @@ def _declare(L):
         L.phys_batch_task_state.argtypes = [vp, vp, vp, vp]
         L.phys_batch_task_set_state.argtypes = [vp, vp, vp, vp]
         L.phys_batch_debug_task_launches.argtypes = [vp, c.POINTER(c.c_longlong)]
+    if hasattr(L, "phys_batch_events"):   # (likewise)
+        L.phys_batch_events_configure.argtypes = [vp, vp, c.c_int, c.c_int, c.c_ulonglong]
+        L.phys_batch_events_bind_rows.argtypes = [vp, vp, c.c_longlong]
+        L.phys_batch_events_bind_input.argtypes = [vp, vp, c.c_int, c.c_longlong, c.c_int]
+        L.phys_batch_events_bind_flags.argtypes = [vp, vp]
+        L.phys_batch_events_flags_ptr.argtypes = [vp]
+        L.phys_batch_events_flags_ptr.restype = vp
+        L.phys_batch_events.argtypes = [vp, c.c_int, c.c_int, vp, vp]
+        L.phys_batch_events_dim.argtypes = [vp, c.POINTER(c.c_int), c.POINTER(c.c_int), c.POINTER(c.c_ulonglong)]
+        L.phys_batch_events_download.argtypes = [vp, vp, c.c_int, c.c_int]
+        L.phys_batch_events_download_flags.argtypes = [vp, vp]
+        L.phys_batch_events_state.argtypes = [vp, vp, vp, vp]
+        L.phys_batch_events_set_state.argtypes = [vp, vp, vp, vp]
+        L.phys_batch_debug_events_launches.argtypes = [vp, c.POINTER(c.c_longlong)]
     if hasattr(L, "phys_batch_step_sums_enable"):   # (likewise)
         L.phys_batch_step_sums_enable.argtypes = [vp, c.c_int]
     if hasattr(L, "phys_batch_download_progress"):   # (absent from older variant builds selected with CASSIE_LIB)

@@ -236,6 +236,76 @@ def task_cols(cols):
         table[k] = tuple(t)
     return table
 
+
+# event rows: the kinds of a column, a MEASURE's norms and the ops of an EDGE, an ACCUM and a LOGIC (PHYS_EV_* in cassie_phys.h), what is
+# no field of the batch, the layout of phys_event_col_t and the limits
+EV_MEASURE, EV_LEVEL, EV_TIMER, EV_EDGE, EV_LATCH, EV_ACCUM, EV_LOGIC = range(7)
+EV_SIGNED, EV_SUMABS, EV_SUMSQ, EV_MAXABS = range(4)
+EV_RISING, EV_FALLING, EV_EITHER = range(3)
+EV_MAX, EV_MIN, EV_SUM = range(3)
+EV_ANY, EV_ALL, EV_NONE, EV_COUNT = range(4)
+EV_INPUT = -1
+EV_MAXCOLS, EV_MAXCOUNT = 64, 8
+EV_COL_DTYPE = np.dtype([(k, np.int32) for k in ("kind", "field", "index", "count", "norm", "root", "src", "trig", "clear", "gate", "op", "sense", "polarity",
+                                                 "lag", "keep", "pad")] + [("mask", np.uint64)] +
+                        [(k, np.float64) for k in ("target", "on_thr", "off_thr", "dt", "offset", "scale", "init")])
+
+
+def _ev_col(kind, **kw):
+    col = dict(kind=kind, field=0, index=0, count=1, norm=0, root=0, src=-1, trig=-1, clear=-1, gate=-1, op=0, sense=1, polarity=1, lag=0, keep=0, pad=0,
+               mask=0, target=0.0, on_thr=0.0, off_thr=0.0, dt=0.0, offset=0.0, scale=1.0, init=0.0)
+    col.update(kw)
+    return tuple(col[k] for k in EV_COL_DTYPE.names)
+
+
+def ev_measure(field, index, count=1, target=0.0, norm=EV_SIGNED, root=False):
+    """An EV_COL_DTYPE entry: a number from field_row[index : index + count] (count 1 .. 8) minus `target`, through the norm EV_SIGNED
+    (count 1), EV_SUMABS, EV_SUMSQ (root: its square root) or EV_MAXABS.  field: an F_* field or EV_INPUT (Batch.bind_event_input)."""
+    return _ev_col(EV_MEASURE, field=int(field), index=int(index), count=int(count), target=float(target), norm=int(norm), root=int(bool(root)))
+
+
+def ev_level(src, on_thr, off_thr=None, sense=1):
+    """A Schmitt trigger on column src: on from sense * value >= on_thr until it is no longer > off_thr (default: on_thr)."""
+    return _ev_col(EV_LEVEL, src=int(src), on_thr=float(on_thr), off_thr=float(on_thr if off_thr is None else off_thr), sense=int(sense))
+
+
+def ev_timer(src, dt, polarity=1):
+    """dt times the consecutive calls column src has been on (polarity 0: off)."""
+    return _ev_col(EV_TIMER, src=int(src), dt=float(dt), polarity=int(polarity))
+
+
+def ev_edge(src, which=EV_RISING):
+    """1 on the call on which column src switched on (EV_RISING), off (EV_FALLING) or either way (EV_EITHER)."""
+    return _ev_col(EV_EDGE, src=int(src), op=int(which))
+
+
+def ev_latch(src, trig, lag=0, keep=0, offset=0.0, scale=1.0):
+    """offset + scale * column src (lag 1: its value on the call before), taken when column trig is on; shown on that call alone, or
+    with keep=1 until the next one."""
+    return _ev_col(EV_LATCH, src=int(src), trig=int(trig), lag=int(lag), keep=int(keep), offset=float(offset), scale=float(scale))
+
+
+def ev_accum(src, op=EV_MAX, clear=-1, gate=-1, init=0.0):
+    """The running EV_MAX, EV_MIN or EV_SUM of column src from `init`, restarted when column clear is on, fed while column gate is on."""
+    return _ev_col(EV_ACCUM, src=int(src), op=int(op), clear=int(clear), gate=int(gate), init=float(init))
+
+
+def ev_logic(cols, op=EV_ANY):
+    """EV_ANY, EV_ALL, EV_NONE or EV_COUNT of the lower columns `cols` (a list of indices, or a uint64 mask) that are on."""
+    mask = int(cols) if isinstance(cols, (int, np.integer)) else sum(1 << int(k) for k in set(cols))
+    return _ev_col(EV_LOGIC, mask=mask, op=int(op))
+
+
+def ev_cols(cols):
+    """A list of column tuples (ev_measure ... ev_logic) or a structured array -> EV_COL_DTYPE entries."""
+    if isinstance(cols, np.ndarray) and cols.dtype.names:
+        return np.ascontiguousarray(cols.astype(EV_COL_DTYPE, copy=False)).reshape(-1)
+    cols = list(cols)
+    table = np.zeros(len(cols), dtype=EV_COL_DTYPE)
+    for k, t in enumerate(cols):
+        table[k] = tuple(t)
+    return table
+
 # per-env physical parameters (CM_P_* in cm_model.h): what Batch.randomize takes
 (P_BODY_MASS, P_BODY_IPOS, P_BODY_INERTIA, P_DOF_DAMPING, P_GEOM_FRICTION,
  P_GEOM_POS, P_GEOM_QUAT, P_JNT_STIFFNESS, P_QPOS_SPRING) = range(9)
@@ -1048,6 +1118,97 @@ class Batch:
         """Diagnostics: the launches task() has made so far."""
         a = ctypes.c_longlong(0)
         lib().phys_batch_debug_task_launches(self._h, ctypes.byref(a))
+        return a.value
+
+    # ---- event rows: contact flags, timers, edges, latches, running extremes and done words in one launch (phys_batch_events) ----
+    def configure_events(self, cols, dtype=np.float32, done_mask=0):
+        """The columns of an event row: a list of ev_measure / ev_level / ev_timer / ev_edge / ev_latch / ev_accum / ev_logic tuples or a
+        structured array of EV_COL_DTYPE (1 .. EV_MAXCOLS; none: release), evaluated in index order; a column names lower columns only.
+        dtype: float32 or float64 rows; done_mask: a uint64 (or a list of columns) whose on columns set the env's done word.  Allocates
+        the rows, the done words, the state and the call counts, zeroed; drops the bindings of the rows, the input and the done words."""
+        table = ev_cols(cols)
+        assert EV_COL_DTYPE.itemsize == 128
+        mask = int(done_mask) if isinstance(done_mask, (int, np.integer)) else sum(1 << int(k) for k in set(done_mask))
+        if lib().phys_batch_events_configure(self._h, table.ctypes.data if table.size else None, int(table.size), _obs_dtype(dtype), mask & 0xFFFFFFFFFFFFFFFF) != 0:
+            self._obs_fail("configure_events")
+        self._ev_np = np.float64 if _obs_dtype(dtype) == 8 else np.float32
+
+    def bind_event_rows(self, device_ptr, row_stride=None):
+        """The event rows [ncols] in caller-owned HBM of the configured dtype, `row_stride` elements (default: ncols) between two envs' rows
+        -- a column block of the tensor bound as the observation's, the reward's and the action's input; None: the batch's own again."""
+        if lib().phys_batch_events_bind_rows(self._h, device_ptr, int(row_stride if row_stride is not None else self.event_dim()) if device_ptr else 0) != 0:
+            self._obs_fail("bind_event_rows")
+
+    def bind_event_input(self, device_ptr, dim=0, row_stride=None, dtype=np.float32):
+        """The caller's per-env array the EV_INPUT columns read: [nenv] rows of `dim` float32 / float64 elements, `row_stride` elements
+        apart (default: dim).  None un-binds."""
+        if lib().phys_batch_events_bind_input(self._h, device_ptr, int(dim), int(dim if row_stride is None else row_stride), _obs_dtype(dtype)) != 0:
+            self._obs_fail("bind_event_input")
+
+    def bind_event_flags(self, device_ptr):
+        """The done words in caller-owned HBM: int32 [nenv], dense (a torch tensor the loop reads); None: the batch's own again."""
+        if lib().phys_batch_events_bind_flags(self._h, device_ptr) != 0:
+            self._obs_fail("bind_event_flags")
+
+    def event_flags_ptr(self, env0=0):
+        """The device address of env env0's done word: what end_episodes takes as force_ptr for a range that starts there."""
+        p = lib().phys_batch_events_flags_ptr(self._h)
+        if not p:
+            raise RuntimeError("event_flags_ptr: not configured (configure_events first)")
+        return p + 4 * int(env0)
+
+    def events(self, env0=0, n=None, reset_ptr=None, stream=None):
+        """One launch on `stream` (default: the batch's own), behind the step launch and the launches that make sources, in front of
+        reward and end_episodes: the event rows, the done words and the state of every env of [env0, env0 + n).  reset_ptr: an int32
+        device array [n] (the range's slice of EP_DONE as the previous policy step's end_episodes left it), non-zero = the env's columns
+        start afresh.  No host synchronisation."""
+        n = self.nenv - env0 if n is None else n
+        if lib().phys_batch_events(self._h, int(env0), int(n), reset_ptr, stream) != 0:
+            self._obs_fail("events")
+
+    def event_dim(self):
+        """The columns of an event row."""
+        a = ctypes.c_int(0)
+        if lib().phys_batch_events_dim(self._h, ctypes.byref(a), None, None) != 0:
+            self._obs_fail("event_dim")
+        return a.value
+
+    def event_rows(self, env0=0, n=None):
+        """The rows [env0, env0 + n) downloaded: [n][ncols] in the configured dtype."""
+        n = self.nenv - env0 if n is None else n
+        out = np.empty((n, self.event_dim()), dtype=self._ev_np)
+        if lib().phys_batch_events_download(self._h, out.ctypes.data, int(env0), int(n)) != 0:
+            self._obs_fail("event_rows")
+        return out
+
+    def event_flags(self):
+        """The done words downloaded: int32 [nenv]."""
+        out = np.empty(self.nenv, dtype=np.int32)
+        if lib().phys_batch_events_download_flags(self._h, out.ctypes.data) != 0:
+            self._obs_fail("event_flags")
+        return out
+
+    def event_state(self):
+        """(state float64 [nenv][2][ncols]: slot 0 a LATCH's h and an ACCUM's m, slot 1 a LATCH's q; words uint32 [nenv][ncols]: a LEVEL's
+        s, a TIMER's t, an EDGE's p; counts uint32 [nenv]: the calls every env has seen)."""
+        ncols = self.event_dim()
+        state, words, counts = np.empty((self.nenv, 2, ncols), dtype=np.float64), np.empty((self.nenv, ncols), dtype=np.uint32), np.empty(self.nenv, dtype=np.uint32)
+        if lib().phys_batch_events_state(self._h, state.ctypes.data, words.ctypes.data, counts.ctypes.data) != 0:
+            self._obs_fail("event_state")
+        return state, words, counts
+
+    def set_event_state(self, state, words, counts):
+        ncols = self.event_dim()
+        s = np.ascontiguousarray(state, dtype=np.float64).reshape(self.nenv, 2, ncols)
+        w = np.ascontiguousarray(words, dtype=np.uint32).reshape(self.nenv, ncols)
+        k = np.ascontiguousarray(counts, dtype=np.uint32).reshape(self.nenv)
+        if lib().phys_batch_events_set_state(self._h, s.ctypes.data, w.ctypes.data, k.ctypes.data) != 0:
+            self._obs_fail("set_event_state")
+
+    def event_launches(self):
+        """Diagnostics: the launches events() has made so far."""
+        a = ctypes.c_longlong(0)
+        lib().phys_batch_debug_events_launches(self._h, ctypes.byref(a))
         return a.value
 
     def set_pd_mode(self, on=True):

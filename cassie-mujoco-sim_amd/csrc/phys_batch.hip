@@ -181,6 +181,18 @@ struct phys_batch {
     DevBuf<double> d_task_state;
     DevBuf<unsigned> d_task_words, d_task_counts;
     long long task_launches = 0;    /* launches of cassie_task_kernel (phys_batch_debug_task_launches) */
+    /* event rows (phys_batch_events_configure): the record (events.ncols 0: not configured; its pointers are filled in at the launch, from
+     * the buffers), the column table, the rows (the batch's own or a caller's, floats or doubles) with their stride in elements, the done
+     * words (the batch's own or a caller's), the per-env state [2][ncols][nenv], words [ncols][nenv] and call counts.  No stepping launch
+     * reads any of it */
+    ck::EventCfg events = {};
+    DevBuf<ck::EventCol> d_event_cols;
+    DevBuf<char> d_event_rows;
+    long long event_srow = 0;
+    DevBuf<int> d_event_flags;
+    DevBuf<double> d_event_state;
+    DevBuf<unsigned> d_event_words, d_event_counts;
+    long long event_launches = 0;   /* launches of cassie_event_kernel (phys_batch_debug_events_launches) */
 };
 
 static bool hip_ok(hipError_t e, const char *what) {
@@ -2019,6 +2031,165 @@ int phys_batch_task_set_state(phys_batch_t *b, const double *state_host, const u
 int phys_batch_debug_task_launches(const phys_batch_t *b, long long *launches) {
     if (!b) return -1;
     if (launches) *launches = b->task_launches;
+    return 0;
+}
+
+/* ------------------------------------------------ event rows ---- */
+static_assert(sizeof(ck::EventCol) == sizeof(phys_event_col_t) && offsetof(ck::EventCol, root) == offsetof(phys_event_col_t, root) &&
+              offsetof(ck::EventCol, gate) == offsetof(phys_event_col_t, gate) && offsetof(ck::EventCol, keep) == offsetof(phys_event_col_t, keep) &&
+              offsetof(ck::EventCol, mask) == offsetof(phys_event_col_t, mask) && offsetof(ck::EventCol, init) == offsetof(phys_event_col_t, init),
+              "phys_event_col_t is the column events_configure reads");
+static_assert(PHYS_EV_MEASURE == ck::EV_MEASURE && PHYS_EV_LEVEL == ck::EV_LEVEL && PHYS_EV_TIMER == ck::EV_TIMER && PHYS_EV_EDGE == ck::EV_EDGE &&
+              PHYS_EV_LATCH == ck::EV_LATCH && PHYS_EV_ACCUM == ck::EV_ACCUM && PHYS_EV_LOGIC == ck::EV_LOGIC && PHYS_EV_SIGNED == ck::EV_SIGNED &&
+              PHYS_EV_SUMABS == ck::EV_SUMABS && PHYS_EV_SUMSQ == ck::EV_SUMSQ && PHYS_EV_MAXABS == ck::EV_MAXABS && PHYS_EV_RISING == ck::EV_RISING &&
+              PHYS_EV_FALLING == ck::EV_FALLING && PHYS_EV_EITHER == ck::EV_EITHER && PHYS_EV_MAX == ck::EV_MAX && PHYS_EV_MIN == ck::EV_MIN &&
+              PHYS_EV_SUM == ck::EV_SUM && PHYS_EV_ANY == ck::EV_ANY && PHYS_EV_ALL == ck::EV_ALL && PHYS_EV_NONE == ck::EV_NONE &&
+              PHYS_EV_COUNT == ck::EV_COUNT && PHYS_EV_INPUT == ck::EV_INPUT && PHYS_EV_MAXCOLS == ck::EVENT_MAXCOLS && PHYS_EV_MAXCOUNT == ck::EVENT_MAXCOUNT,
+              "the header's numbers are event_kernels.h's");
+/* the record of a launch: what was configured, with the pointers into the batch's buffers */
+static ck::EventCfg events_cfg_of(const phys_batch *b) {
+    ck::EventCfg c = b->events;
+    c.cols = b->d_event_cols; c.rows = b->d_event_rows.get(); c.srow = b->event_srow; c.flags = b->d_event_flags; c.state = b->d_event_state;
+    c.words = b->d_event_words; c.counts = b->d_event_counts;
+    return c;
+}
+int phys_batch_events_configure(phys_batch_t *b, const phys_event_col_t *cols, int ncols, int dtype, unsigned long long done_mask) {
+    if (!b) return refuse("phys_batch_events_configure", ck::EVENT_SIZE_REFUSAL);
+    int dims[PHYS_F_COUNT];
+    for (int k = 0; k < PHYS_F_COUNT; ++k) dims[k] = b->d_field[k] ? b->dim[k] : 0;
+    std::vector<ck::EventCol> table((size_t)ck::EVENT_MAXCOLS);
+    ck::EventCfg cfg;
+    if (const char *why = ck::events_configure(dims, PHYS_F_COUNT, PHYS_F_DEPTH, (const ck::EventCol *)cols, ncols, dtype, done_mask, table.data(), cfg))
+        return refuse("phys_batch_events_configure", why);
+    (void)hipSetDevice(b->device);
+    if (!quiesce(b)) return -1;  /* (launches in flight may be reading the table, or writing the rows, that go away) */
+    if (ncols == 0) {
+        b->events = {}; b->event_srow = 0;
+        b->d_event_cols.reset(); b->d_event_rows.reset(); b->d_event_flags.reset(); b->d_event_state.reset(); b->d_event_words.reset(); b->d_event_counts.reset();
+        return 0;
+    }
+    const size_t n = (size_t)b->nenv;
+    DevBuf<ck::EventCol> tab;
+    DevBuf<char> rows;
+    DevBuf<int> flags;
+    DevBuf<double> state;
+    DevBuf<unsigned> words, counts;
+    if (!tab.alloc((size_t)ncols, false, "event columns")) return -1;
+    if (!hip_ok(hipMemcpy(tab, table.data(), sizeof(ck::EventCol) * (size_t)ncols, hipMemcpyHostToDevice), "hipMemcpy(event columns)")) return -1;
+    if (!rows.alloc(n * (size_t)ncols * (size_t)dtype, true, "event rows")) return -1;
+    if (!flags.alloc(n, true, "event done words")) return -1;
+    if (!state.alloc(2 * n * (size_t)ncols, true, "event state")) return -1;
+    if (!words.alloc(n * (size_t)ncols, true, "event words")) return -1;
+    if (!counts.alloc(n, true, "event call counts")) return -1;
+    b->d_event_cols = std::move(tab); b->d_event_rows = std::move(rows); b->d_event_flags = std::move(flags); b->d_event_state = std::move(state);
+    b->d_event_words = std::move(words); b->d_event_counts = std::move(counts);
+    b->event_srow = (long long)ncols;
+    b->events = cfg;   /* (no input bound, the rows and the done words are the batch's own: the bindings are dropped) */
+    return 0;
+}
+int phys_batch_events_bind_rows(phys_batch_t *b, void *device_ptr, long long row_stride) {
+    if (!b) { phys_set_last_error("phys_batch_events_bind_rows: no batch"); return -1; }
+    const long long row = b->events.ncols;
+    if (const char *why = ck::check_events_bind_rows(b->events, device_ptr ? row_stride : row)) return refuse("phys_batch_events_bind_rows", why);
+    (void)hipSetDevice(b->device);
+    /* (as phys_batch_bind: launches already queued keep the pointer they were given; hipFree waits for the device by itself) */
+    if (device_ptr) { b->d_event_rows.borrow((char *)device_ptr); b->event_srow = row_stride; }
+    else if (!b->d_event_rows.owned()) {
+        if (!b->d_event_rows.alloc((size_t)b->nenv * (size_t)row * (size_t)b->events.dtype, true, "event rows")) return -1;
+        b->event_srow = row;
+    }
+    return 0;
+}
+int phys_batch_events_bind_input(phys_batch_t *b, const void *device_ptr, int dim, long long row_stride, int dtype) {
+    if (!b) { phys_set_last_error("phys_batch_events_bind_input: no batch"); return -1; }
+    if (!device_ptr) { b->events.input = nullptr; b->events.input_dim = 0; b->events.input_stride = 0; b->events.input_dtype = 0; return 0; }
+    if (const char *why = ck::check_events_input(b->events, dim, row_stride, dtype)) return refuse("phys_batch_events_bind_input", why);
+    b->events.input = device_ptr; b->events.input_dim = dim; b->events.input_stride = (int)row_stride; b->events.input_dtype = dtype;
+    return 0;
+}
+int phys_batch_events_bind_flags(phys_batch_t *b, void *device_ptr) {
+    if (!b) { phys_set_last_error("phys_batch_events_bind_flags: no batch"); return -1; }
+    if (const char *why = ck::check_events_bind_flags(b->events)) return refuse("phys_batch_events_bind_flags", why);
+    (void)hipSetDevice(b->device);
+    if (device_ptr) b->d_event_flags.borrow((int *)device_ptr);
+    else if (!b->d_event_flags.owned() && !b->d_event_flags.alloc((size_t)b->nenv, true, "event done words")) return -1;
+    return 0;
+}
+void *phys_batch_events_flags_ptr(phys_batch_t *b) { return b && b->events.ncols > 0 ? (void *)b->d_event_flags.get() : nullptr; }
+int phys_batch_events(phys_batch_t *b, int env0, int n, const void *reset_ptr, void *stream) {
+    if (!b) { phys_set_last_error("phys_batch_events: no batch"); return -1; }
+    const ck::EventCfg c = events_cfg_of(b);
+    ck::ObsField fields[PHYS_F_COUNT];
+    obs_fields_of(b, fields);
+    if (const char *why = ck::check_events_call(c, fields, PHYS_F_COUNT, b->nenv, env0, n)) return refuse("phys_batch_events", why);
+    (void)hipSetDevice(b->device);
+    if (n == 0) return 0;
+    hipStream_t s = launch_stream(b, stream);
+    hipLaunchKernelGGL(ck::cassie_event_kernel, dim3((unsigned)ck::events_grid(n)), dim3(WV_WAVE), 0, s, ck::make_events_io(c, fields, b->nenv, env0, n, (const int *)reset_ptr));
+    if (!hip_ok(hipGetLastError(), "cassie_event_kernel launch")) return -1;
+    ++b->event_launches;
+    return 0;
+}
+int phys_batch_events_dim(const phys_batch_t *b, int *ncols, int *dtype, unsigned long long *done_mask) {
+    if (!b || b->events.ncols < 1) { phys_set_last_error("phys_batch_events_dim: not configured (phys_batch_events_configure first)"); return -1; }
+    if (ncols) *ncols = b->events.ncols;
+    if (dtype) *dtype = b->events.dtype;
+    if (done_mask) *done_mask = b->events.done_mask;
+    return 0;
+}
+int phys_batch_events_download(phys_batch_t *b, void *host, int env0, int n) {
+    if (!b || !host || b->events.ncols < 1 || !b->d_event_rows) { phys_set_last_error("phys_batch_events_download: bad arguments, or not configured (phys_batch_events_configure first)"); return -1; }
+    if (!range_ok(b, env0, n)) return refuse("phys_batch_events_download", "env range out of bounds");
+    (void)hipSetDevice(b->device);
+    if (!quiesce(b)) return -1;
+    if (n == 0) return 0;
+    const size_t el = (size_t)b->events.dtype, row = (size_t)b->events.ncols, st = (size_t)b->event_srow;
+    return hip_ok(hipMemcpy2D(host, el * row, b->d_event_rows.get() + el * st * (size_t)env0, el * st, el * row, (size_t)n, hipMemcpyDeviceToHost), "event rows download") ? 0 : -1;
+}
+int phys_batch_events_download_flags(phys_batch_t *b, int *host) {
+    if (!b || !host || b->events.ncols < 1 || !b->d_event_flags) { phys_set_last_error("phys_batch_events_download_flags: bad arguments, or not configured (phys_batch_events_configure first)"); return -1; }
+    (void)hipSetDevice(b->device);
+    return quiesce(b) && hip_ok(hipMemcpy(host, b->d_event_flags, sizeof(int) * (size_t)b->nenv, hipMemcpyDeviceToHost), "event done words download") ? 0 : -1;
+}
+/* the host's shape is [nenv][2][ncols] and [nenv][ncols]; the device's [2][ncols][nenv] and [ncols][nenv] (event_kernels.h) */
+int phys_batch_events_state(phys_batch_t *b, double *state_host, unsigned *words_host, unsigned *counts_host) {
+    if (!b || !state_host || !words_host || !counts_host || !b->d_event_state || !b->d_event_words || !b->d_event_counts) {
+        phys_set_last_error("phys_batch_events_state: bad arguments, or not configured (phys_batch_events_configure first)"); return -1;
+    }
+    (void)hipSetDevice(b->device);
+    const size_t n = (size_t)b->nenv, nc = (size_t)b->events.ncols;
+    std::vector<double> st(2 * nc * n);
+    std::vector<unsigned> wd(nc * n);
+    if (!(quiesce(b) && hip_ok(hipMemcpy(st.data(), b->d_event_state, sizeof(double) * st.size(), hipMemcpyDeviceToHost), "event state download") &&
+          hip_ok(hipMemcpy(wd.data(), b->d_event_words, sizeof(unsigned) * wd.size(), hipMemcpyDeviceToHost), "event words download") &&
+          hip_ok(hipMemcpy(counts_host, b->d_event_counts, sizeof(unsigned) * n, hipMemcpyDeviceToHost), "event call counts download"))) return -1;
+    for (size_t e = 0; e < n; ++e)
+        for (size_t c = 0; c < nc; ++c) {
+            for (size_t s = 0; s < 2; ++s) state_host[(e * 2 + s) * nc + c] = st[(s * nc + c) * n + e];
+            words_host[e * nc + c] = wd[c * n + e];
+        }
+    return 0;
+}
+int phys_batch_events_set_state(phys_batch_t *b, const double *state_host, const unsigned *words_host, const unsigned *counts_host) {
+    if (!b || !state_host || !words_host || !counts_host || !b->d_event_state || !b->d_event_words || !b->d_event_counts) {
+        phys_set_last_error("phys_batch_events_set_state: bad arguments, or not configured (phys_batch_events_configure first)"); return -1;
+    }
+    (void)hipSetDevice(b->device);
+    const size_t n = (size_t)b->nenv, nc = (size_t)b->events.ncols;
+    std::vector<double> st(2 * nc * n);
+    std::vector<unsigned> wd(nc * n);
+    for (size_t e = 0; e < n; ++e)
+        for (size_t c = 0; c < nc; ++c) {
+            for (size_t s = 0; s < 2; ++s) st[(s * nc + c) * n + e] = state_host[(e * 2 + s) * nc + c];
+            wd[c * n + e] = words_host[e * nc + c];
+        }
+    return quiesce(b) && hip_ok(hipMemcpy(b->d_event_state, st.data(), sizeof(double) * st.size(), hipMemcpyHostToDevice), "event state upload") &&
+                   hip_ok(hipMemcpy(b->d_event_words, wd.data(), sizeof(unsigned) * wd.size(), hipMemcpyHostToDevice), "event words upload") &&
+                   hip_ok(hipMemcpy(b->d_event_counts, counts_host, sizeof(unsigned) * n, hipMemcpyHostToDevice), "event call counts upload") ? 0 : -1;
+}
+int phys_batch_debug_events_launches(const phys_batch_t *b, long long *launches) {
+    if (!b) return -1;
+    if (launches) *launches = b->event_launches;
     return 0;
 }
 

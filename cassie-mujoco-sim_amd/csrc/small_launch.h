@@ -1,12 +1,12 @@
 /*
- * small_launch.h -- how the kernels around the step kernel (small_kernels.h, surface_kernels.h, depth_kernel.h, ray_kernel.h, episode_kernels.h, probe_kernels.h, obs_kernels.h, reward_kernels.h, act_kernels.h, task_kernels.h) are
+ * small_launch.h -- how the kernels around the step kernel (small_kernels.h, surface_kernels.h, depth_kernel.h, ray_kernel.h, episode_kernels.h, probe_kernels.h, obs_kernels.h, reward_kernels.h, act_kernels.h, task_kernels.h, event_kernels.h) are
  * launched: the records a kernel's arguments are built from, one builder per kernel that returns its filled argument struct for an env
  * range, the grid of every launch, and the checks of what a caller configures, each returning the message of its refusal (null: fine).
  * Pure host code, no HIP runtime calls, in the spirit of step_policy.h: the launcher (phys_batch.hip) keeps the records in the batch,
  * prefixes a message with its entry point's name and launches what a builder returns on the grid given here; the wave emulator's entry
  * points (tests/emu) fill the same records from their arguments and go through the same builders, grids and checks, so a CPU test of
  * one of these kernels also runs the launcher's refusals, grid and choice of kernel (tests/test_small_launch.py pins them one by one).
- * No field of ScanIO, DepthIO, RayIO, EpisodeIO, ResetIO, DeriveIO, SetConstIO, StateIO, ProbeIO, ObsIO, RewardIO, ActIO or TaskIO is assigned anywhere else.
+ * No field of ScanIO, DepthIO, RayIO, EpisodeIO, ResetIO, DeriveIO, SetConstIO, StateIO, ProbeIO, ObsIO, RewardIO, ActIO, TaskIO or EventIO is assigned anywhere else.
  */
 #ifndef CASSIE_SMALL_LAUNCH_H
 #define CASSIE_SMALL_LAUNCH_H
@@ -17,6 +17,7 @@
 #include "act_kernels.h"
 #include "depth_kernel.h"
 #include "episode_kernels.h"
+#include "event_kernels.h"
 #include "obs_kernels.h"
 #include "probe_kernels.h"
 #include "ray_kernel.h"
@@ -138,6 +139,20 @@ struct TaskCfg {
     int dst_field[ACT_MAXDST], dst_dim[ACT_MAXDST];
     const TaskCol *cols; void *rows; long long srow; double *state; unsigned *words; unsigned *counts;
     const double *table; int nframes, tcols;
+};
+
+/* the event rows (phys_batch_events_configure; ncols 0: not configured): the columns, the rows' type (OBS_F32 / OBS_F64), the done mask;
+ * the sources of a call as the observation's -- slot s is field slot_field[s] (or EV_INPUT), whose row held slot_dim[s] elements when the
+ * columns were checked against it -- and the elements the columns need of the caller's input array.  Then what the caller names once a
+ * kernel reads them: the column table [ncols] with the fields as slots, the rows with their stride in elements, the done words [nenv],
+ * the state [2][ncols][nenv], the words [ncols][nenv], the counts [nenv], and the caller's input array (null: none bound) with its row
+ * length, row stride and type */
+struct EventCfg {
+    int ncols, dtype, nslots, input_need;
+    unsigned long long done_mask;
+    int slot_field[EVENT_MAXSLOTS], slot_dim[EVENT_MAXSLOTS];
+    const EventCol *cols; void *rows; long long srow; int *flags; double *state; unsigned *words; unsigned *counts;
+    const void *input; int input_dim, input_stride, input_dtype;
 };
 
 /* ---- the row of a full state ---- */
@@ -688,6 +703,110 @@ inline const char *check_task_call(const TaskCfg &c, const ObsField *fields, int
         return "the row length of a destination field has changed since phys_batch_task_configure (configure again)";
     return nullptr;
 }
+/* (what the launcher also answers a call without a batch) */
+constexpr const char *EVENT_SIZE_REFUSAL = "1 .. 64 columns (0 releases them), rows of PHYS_OBS_F32 or PHYS_OBS_F64";
+/* the event rows' configuration: checks the caller's columns [ncols] against the row lengths the batch holds now (as reward_configure:
+ * field_dim [nfields], 0: a field it does not hold; depth_field: the one field that is never a source), writes the table a launch reads
+ * (table [EVENT_MAXCOLS]: the columns with a MEASURE's field replaced by its slot and the fields its kind does not name cleared) and
+ * fills c but for what the caller names later.  ncols 0 is accepted and leaves c empty: the launcher releases what it holds.  The
+ * emulator goes through the same */
+inline const char *events_configure(const int *field_dim, int nfields, int depth_field, const EventCol *cols, int ncols, int dtype,
+                                    unsigned long long done_mask, EventCol *table, EventCfg &c) {
+    if (ncols < 0 || ncols > EVENT_MAXCOLS || (ncols > 0 && (!cols || !table))) return EVENT_SIZE_REFUSAL;
+    c = {};
+    if (ncols == 0) return nullptr;
+    if (dtype != OBS_F32 && dtype != OBS_F64) return "the rows' dtype is PHYS_OBS_F32 or PHYS_OBS_F64";
+    if (ncols < 64 && (done_mask >> ncols) != 0ull) return "done_mask has a bit at or above ncols";
+    const char *const lower = "a column's src, trig, clear and gate name columns with a lower index (clear and gate may be -1)";
+    for (int k = 0; k < ncols; ++k) {
+        const EventCol &d = cols[k];
+        EventCol &o = table[k];
+        o = EventCol();
+        o.kind = d.kind; o.src = o.trig = o.clear = o.gate = -1;
+        auto is_lower = [k](int j) { return j >= 0 && j < k; };
+        if (d.kind == EV_MEASURE) {
+            if (d.norm != EV_SIGNED && d.norm != EV_SUMABS && d.norm != EV_SUMSQ && d.norm != EV_MAXABS) return "a MEASURE's norm is PHYS_EV_SIGNED, _SUMABS, _SUMSQ or _MAXABS";
+            if (d.count < 1 || d.count > EVENT_MAXCOUNT) return "a MEASURE takes 1 .. 8 elements";
+            if (d.norm == EV_SIGNED && d.count != 1) return "a SIGNED MEASURE takes one element";
+            if (!std::isfinite(d.target)) return "a column's constants must be finite";
+            if (d.field == depth_field) return "PHYS_F_DEPTH is no source of an event (images are not columns)";
+            const int dim = d.field == EV_INPUT ? 0x7fffffff : d.field >= 0 && d.field < nfields ? field_dim[d.field] : -1;
+            if (dim < 0) return "a MEASURE's field is a PHYS_F_* field of the batch or PHYS_EV_INPUT";
+            if (dim == 0) return "a column reads a field the batch does not hold yet (the scan, the rays, the probes, the step sums, the derived block: configure or enable them first)";
+            if (d.index < 0 || (long long)d.index + d.count > dim) return "index + count lies beyond the field's row";
+            int s = 0;
+            while (s < c.nslots && c.slot_field[s] != d.field) ++s;
+            if (s == c.nslots) {
+                if (c.nslots == EVENT_MAXSLOTS) return "more than 16 distinct source fields";
+                c.slot_field[s] = d.field; c.slot_dim[s] = d.field == EV_INPUT ? 0 : dim; ++c.nslots;
+            }
+            if (d.field == EV_INPUT && d.index + d.count > c.input_need) c.input_need = d.index + d.count;
+            o.field = s; o.index = d.index; o.count = d.count; o.norm = d.norm; o.root = d.norm == EV_SUMSQ && d.root != 0; o.target = d.target;
+        } else if (d.kind == EV_LEVEL) {
+            if (!is_lower(d.src)) return lower;
+            if (!(std::isfinite(d.on_thr) && std::isfinite(d.off_thr))) return "a column's constants must be finite";
+            if (d.off_thr > d.on_thr) return "off_thr <= on_thr";
+            if (d.sense != 1 && d.sense != -1) return "a LEVEL's sense is +1 or -1";
+            o.src = d.src; o.on_thr = d.on_thr; o.off_thr = d.off_thr; o.sense = d.sense;
+        } else if (d.kind == EV_TIMER) {
+            if (!is_lower(d.src)) return lower;
+            if (!std::isfinite(d.dt)) return "a column's constants must be finite";
+            o.src = d.src; o.dt = d.dt; o.polarity = d.polarity != 0;
+        } else if (d.kind == EV_EDGE) {
+            if (!is_lower(d.src)) return lower;
+            if (d.op != EV_RISING && d.op != EV_FALLING && d.op != EV_EITHER) return "an EDGE's op is PHYS_EV_RISING, _FALLING or _EITHER";
+            o.src = d.src; o.op = d.op;
+        } else if (d.kind == EV_LATCH) {
+            if (!is_lower(d.src) || !is_lower(d.trig)) return lower;
+            if (!(std::isfinite(d.offset) && std::isfinite(d.scale))) return "a column's constants must be finite";
+            if ((d.lag != 0 && d.lag != 1) || (d.keep != 0 && d.keep != 1)) return "a LATCH's lag and keep are 0 or 1";
+            o.src = d.src; o.trig = d.trig; o.lag = d.lag; o.keep = d.keep; o.offset = d.offset; o.scale = d.scale;
+        } else if (d.kind == EV_ACCUM) {
+            if (!is_lower(d.src) || (d.clear != -1 && !is_lower(d.clear)) || (d.gate != -1 && !is_lower(d.gate))) return lower;
+            if (d.op != EV_MAX && d.op != EV_MIN && d.op != EV_SUM) return "an ACCUM's op is PHYS_EV_MAX, _MIN or _SUM";
+            if (!std::isfinite(d.init)) return "a column's constants must be finite";
+            o.src = d.src; o.clear = d.clear; o.gate = d.gate; o.op = d.op; o.init = d.init;
+        } else if (d.kind == EV_LOGIC) {
+            if (d.op != EV_ANY && d.op != EV_ALL && d.op != EV_NONE && d.op != EV_COUNT) return "a LOGIC's op is PHYS_EV_ANY, _ALL, _NONE or _COUNT";
+            if (d.mask == 0ull) return "a LOGIC's mask names at least one column";
+            if (ncols < 64 && (d.mask >> ncols) != 0ull) return "a LOGIC's mask has a bit at or above ncols";
+            if ((d.mask >> k) != 0ull) return "a LOGIC's mask names columns with a lower index";
+            o.op = d.op; o.mask = d.mask;
+        } else return "a column's kind is PHYS_EV_MEASURE, _LEVEL, _TIMER, _EDGE, _LATCH, _ACCUM or _LOGIC";
+    }
+    c.ncols = ncols; c.dtype = dtype; c.done_mask = done_mask;
+    return nullptr;
+}
+/* what phys_batch_events_bind_rows / _bind_input / _bind_flags refuse */
+inline const char *check_events_bind_rows(const EventCfg &c, long long row_stride) {
+    if (c.ncols < 1) return "not configured (phys_batch_events_configure first)";
+    if (row_stride < c.ncols) return "a row stride of at least the columns";
+    return nullptr;
+}
+inline const char *check_events_input(const EventCfg &c, int dim, long long row_stride, int dtype) {
+    if (c.ncols < 1) return "not configured (phys_batch_events_configure first)";
+    if (dim < 1 || row_stride < dim || row_stride > 0x7fffffff) return "an input of at least one element a row and a row stride of at least that";
+    if (dtype != OBS_F32 && dtype != OBS_F64) return "the input's dtype is PHYS_OBS_F32 or PHYS_OBS_F64";
+    return nullptr;
+}
+inline const char *check_events_bind_flags(const EventCfg &c) {
+    if (c.ncols < 1) return "not configured (phys_batch_events_configure first)";
+    return nullptr;
+}
+/* what an events call refuses; fields [nfields]: what the batch holds NOW */
+inline const char *check_events_call(const EventCfg &c, const ObsField *fields, int nfields, int nenv, int env0, int n) {
+    if (c.ncols < 1 || !c.cols || !c.rows || !c.flags || !c.state || !c.words || !c.counts) return "not configured (phys_batch_events_configure first)";
+    if (env0 < 0 || n < 0 || (long long)env0 + n > nenv) return "env range out of bounds";
+    for (int s = 0; s < c.nslots; ++s) {
+        const int f = c.slot_field[s];
+        if (f == EV_INPUT) {
+            if (!c.input) return "a PHYS_EV_INPUT column and no input bound (phys_batch_events_bind_input first)";
+            if (c.input_dim < c.input_need) return "the bound input's rows are shorter than the PHYS_EV_INPUT columns reach";
+        } else if (f < 0 || f >= nfields || !fields[f].base || fields[f].dim != c.slot_dim[s])
+            return "the row length of a source field has changed since phys_batch_events_configure (configure again)";
+    }
+    return nullptr;
+}
 /* the bank of full states: what phys_batch_state_configure / _bind refuse (the view tells what the batch has), and what a save or a
  * restore refuses */
 inline const char *state_configure(const BatchView &v, int nslots, int groups) {
@@ -725,6 +844,8 @@ inline int reward_grid(int n) { const long long w = ((long long)n + WV_WAVE - 1)
 inline int act_grid(int n) { return n < ACT_GRID ? n : ACT_GRID; }
 /* one wave per env up to TASK_GRID workgroups, which then walk the range: few, as the action's (task_kernels.h) */
 inline int task_grid(int n) { return n < TASK_GRID ? n : TASK_GRID; }
+/* one wave per 64 envs (a lane takes an env) up to EVENT_GRID workgroups, which then walk the range (event_kernels.h) */
+inline int events_grid(int n) { const long long w = ((long long)n + WV_WAVE - 1) / WV_WAVE; return w < EVENT_GRID ? (int)w : EVENT_GRID; }
 /* a job is (env, tile of DEPTH_TILE x DEPTH_TILE pixels); a fixed grid walks the job list (a first choice: depth_kernel.h) */
 inline int depth_grid(int n, int width, int height) {
     const int T = DEPTH_TILE;
@@ -866,6 +987,20 @@ inline TaskIO make_task_io(const TaskCfg &c, const ObsField *fields, int env0, i
     if (c.tcol_need > 0) { io.table = c.table; io.nframes = c.nframes; io.tcols = c.tcols; }
     fill_destinations(io.dst, c.ndst, c.dst_field, fields);
     io.rows = c.rows; io.srow = c.srow; io.state = c.state; io.words = c.words; io.counts = c.counts; io.reset = reset;
+    return io;
+}
+/* cassie_event_kernel's: the sources of the record's slots where the batch reads them today (as make_reward_io), the column table, the
+ * rows, the done words, the state, the words and the counts; nenv: the envs of the batch (the stride of the state's columns) */
+inline EventIO make_events_io(const EventCfg &c, const ObsField *fields, int nenv, int env0, int n, const int *reset) {
+    EventIO io = zeroed<EventIO>();
+    io.env0 = env0; io.n = n; io.ncols = c.ncols; io.f32 = c.dtype == OBS_F32; io.nenv = nenv; io.done_mask = c.done_mask;
+    io.cols = c.cols;
+    for (int s = 0; s < c.nslots; ++s) {
+        const int f = c.slot_field[s];
+        if (f == EV_INPUT) io.src[s] = {c.input, c.input_stride, c.input_dtype == OBS_F32, 0};
+        else io.src[s] = {fields[f].base, fields[f].stride, 0, 0};
+    }
+    io.rows = c.rows; io.srow = c.srow; io.flags = c.flags; io.state = c.state; io.words = c.words; io.counts = c.counts; io.reset = reset;
     return io;
 }
 inline int episode_row_dim(const BatchView &v) { return v.nq + v.nv + v.nsd + v.nu + v.nv; }

@@ -452,7 +452,8 @@ size_t phys_sizeof_episode_rules(void);
  * keeps per env for one launch or for speed alone (progress, chunk words, hand-over lists, launch order and cost: none changes a result).
  * Neither are the observation rows and their per-env frame counts (phys_batch_obs below): a caller that rewinds an env keeps or sets
  * them itself (phys_batch_obs_set_frames; a refill entry refills the env's history from its restored state).  Nor are the running and
- * final returns of the reward rows (phys_batch_reward below: phys_batch_reward_returns / _set_returns).
+ * final returns of the reward rows (phys_batch_reward below: phys_batch_reward_returns / _set_returns), nor the state of the event rows
+ * (phys_batch_events below: phys_batch_events_state / _set_state).
  *
  *   phys_batch_state_configure  allocates a bank of nslots >= 1 zeroed rows in HBM; waits for the batch's streams; calling it again
  *                               replaces the bank (and drops a binding).
@@ -1068,6 +1069,115 @@ int phys_batch_task_download(phys_batch_t *b, void *host, int env0, int n);
 int phys_batch_task_state(phys_batch_t *b, double *state_host /*[nenv][ncols]*/, unsigned *words_host /*[nenv][3][ncols]*/, unsigned *counts_host /*[nenv]*/);
 int phys_batch_task_set_state(phys_batch_t *b, const double *state_host, const unsigned *words_host, const unsigned *counts_host);
 int phys_batch_debug_task_launches(const phys_batch_t *b, long long *launches);
+
+/* EVENT ROWS: what a policy step remembers of the steps before it -- contact flags with hysteresis, the time a foot has been in the air,
+ * the call on which it touched down, the peak force of a stance, and terminations the fixed rules of phys_batch_episodes_enable cannot
+ * state -- made on the device by ONE launch per env range.  A configured table of ncols COLUMNS (1 .. PHYS_EV_MAXCOLS = 64) is evaluated
+ * IN INDEX ORDER; a column names only columns with a LOWER index (the configure call refuses anything else), so no value ever picks
+ * among memory.  Per env the call writes the EVENT ROW [ncols] (floats or doubles; the batch's own rows or a caller's tensor bound with
+ * a row stride -- typically a column block of the tensor phys_batch_obs, _reward, _act and _task bind as their input) and one int32 DONE
+ * WORD, 1 or 0 (the batch's own array, phys_batch_events_flags_ptr, or a bound one), which phys_batch_end_episodes takes as `force`.
+ * COMMON RULES, per env and call:
+ *   count = counts[env] before the call;  fresh = (count == 0 or the call's reset entry is non-zero);
+ *   out[k] is column k's fp64 value of THIS call; on(k) means out[k] > 0.0, so a NaN is off.
+ *   Every arithmetic step is one individually rounded fp64 operation (multiply, add, subtract, square root to nearest even; no fused
+ *   multiply-add, no reassociation); every sum is sequential from +0.0 in index order; every comparison is written so that a NaN takes
+ *   the branch stated.  The device, the wave emulator and a numpy restatement agree on every bit, whatever the cut into ranges.
+ * A COLUMN (phys_event_col_t) by its kind; the fields a kind does not name are ignored:
+ *   PHYS_EV_MEASURE  a number from a source.  field: any PHYS_F_* field but PHYS_F_DEPTH, with the row length the batch holds for it at
+ *                    the configure call, read where the batch reads it at the call; or PHYS_EV_INPUT, the caller's per-env array bound
+ *                    with phys_batch_events_bind_input (floats widened exactly).  At most 16 distinct sources.  index, count (1 .. 8),
+ *                    target, norm, root.  e[j] = src_row[index + j] - target, j < count.
+ *                      PHYS_EV_SIGNED (count must be 1): out = e[0].
+ *                      PHYS_EV_SUMABS: out = sum_j |e[j]|.
+ *                      PHYS_EV_SUMSQ:  s = sum_j e[j] e[j]; out = root != 0 ? sqrt(s) : s.  (root is ignored by the other norms.)
+ *                      PHYS_EV_MAXABS: s = +0.0, then for every j in order  if (|e[j]| > s) s = |e[j]|  (a NaN element is passed over).
+ *   PHYS_EV_LEVEL    a Schmitt trigger on column src.  on_thr, off_thr (off_thr <= on_thr), sense (+1 or -1).  State word s.
+ *                    w = sense < 0 ? -out[src] : out[src].  Fresh: s = w >= on_thr.  Otherwise: s = s ? (w > off_thr) : (w >= on_thr).
+ *                    out = s (0.0 or 1.0).  A NaN switches it off.
+ *   PHYS_EV_TIMER    the consecutive calls column src has been on (polarity != 0) or off (polarity == 0), times dt.  State word t.
+ *                    Fresh: t = 0.  Then, if on(src) != (polarity == 0): t = t == 0xffffffff ? t : t + 1; otherwise t = 0.
+ *                    out = dt * (double)t: one multiply of an exact conversion.  (A first call on which the condition holds shows dt.)
+ *   PHYS_EV_EDGE     the call on which column src switched.  op: PHYS_EV_RISING, _FALLING or _EITHER.  State word p.
+ *                    c = on(src).  Fresh: p = c, so a first call has no edge.  out = RISING: c && !p; FALLING: !c && p; EITHER: c != p
+ *                    (0.0 or 1.0).  Then p = c.
+ *   PHYS_EV_LATCH    column src's value taken when column trig fires.  lag (0 or 1), keep (0 or 1), offset, scale.  State doubles h, q.
+ *                    Fresh: h = 0, q = 0.  If on(trig): h = offset + scale * (lag ? q : out[src]).  out = (keep or on(trig)) ? h : 0.
+ *                    Then q = out[src].  Air time paid at touchdown is a LATCH with lag = 1 of the off-TIMER, triggered by the
+ *                    rising EDGE: the timer's value on the call before.
+ *   PHYS_EV_ACCUM    a running maximum, minimum or sum of column src.  op: PHYS_EV_MAX, _MIN or _SUM; clear, gate (-1 or a column);
+ *                    init (finite).  State double m.  v = out[src].  If fresh or on(clear): m = init.  Then, if gate < 0 or on(gate):
+ *                    MAX: m = v > m ? v : m;  MIN: m = v < m ? v : m;  SUM: m = m + v.  out = m.  A NaN v is passed over by MAX and
+ *                    MIN; in a SUM it sticks until the next clear.
+ *   PHYS_EV_LOGIC    a combination of columns.  mask: a uint64 over lower columns, not 0; op.  c = the number of on columns of the
+ *                    mask.  out = PHYS_EV_ANY: c > 0;  _ALL: c == popcount(mask);  _NONE: c == 0;  _COUNT: (double)c.
+ * STORES: out[c] goes into the row, cast to nearest even where the rows are PHYS_OBS_F32;  flag[env] = (any on(c) with bit c of
+ *   done_mask set) ? 1 : 0, done_mask a uint64 given to the configure call (0: the word is always 0);  counts[env] += 1 (it wraps, and
+ *   a count that comes round to 0 is fresh).
+ * STATE: per env [2][ncols] doubles (slot 0: a LATCH's h, an ACCUM's m; slot 1: a LATCH's q; 0 elsewhere), [ncols] uint32 words (a
+ *   LEVEL's s, a TIMER's t, an EDGE's p; 0 elsewhere) and the count; the batch owns them.  None is in a state-bank row: as with the action
+ *   and task state, a caller that rewinds or resumes moves them itself (phys_batch_events_state / _set_state).  A fresh env reads none
+ *   of its state.
+ * ORDER IN A POLICY STEP: phys_batch_act; the step launch; the launches that make sources (probe, rays, scan); phys_batch_events;
+ *   phys_batch_reward (a term gated by an event column reads this step's value); phys_batch_end_episodes(force = the range's slice of
+ *   the done words); phys_batch_task; phys_batch_obs.  `reset` is an optional int32 DEVICE array [n], entry i for env env0 + i: the
+ *   range's slice of PHYS_EP_DONE as the PREVIOUS step's phys_batch_end_episodes left it -- the words phys_batch_reward and
+ *   phys_batch_act take -- so the first call that sees a restarted env's state starts its columns afresh.
+ * NaN AND DIVERGED ENVS: values flow through to the env's own row; nothing indexes memory by a value.
+ *   phys_batch_events_configure   cols [ncols] (host memory), the rows' type (PHYS_OBS_F32 / PHYS_OBS_F64) and done_mask.  Refuses, with a
+ *                               message in phys_last_error(): ncols outside 1 .. 64 (0 releases), an unknown kind, norm, op or dtype, a
+ *                               src, trig, clear or gate that is no lower index (clear and gate may be -1), a done_mask or LOGIC mask
+ *                               bit at or above ncols, a LOGIC mask that is 0 or has a bit at or above the column's own index, a
+ *                               constant of the column's kind that is not finite, off_thr > on_thr, a sense other than +1 or -1, a
+ *                               count outside 1 .. 8, SIGNED with count != 1, PHYS_F_DEPTH, an unknown field, a field the batch does
+ *                               not hold, a slice beyond a row, more than 16 sources.  Allocates the table, the rows, the done words,
+ *                               the state and the counts (zeroed); drops the bindings of the rows, the input and the done words; waits
+ *                               for the batch's streams.
+ *   phys_batch_events_bind_rows   the event rows in caller-owned HBM of the configured type, row_stride elements (>= ncols) between two
+ *                               envs' rows.  NULL: the batch's own rows again, zeroed.
+ *   phys_batch_events_bind_input  the caller's per-env array [nenv] rows of dim elements, row_stride elements apart, PHYS_OBS_F32 / _F64.
+ *                               NULL un-binds.
+ *   phys_batch_events_bind_flags  the done words in caller-owned HBM: int32 [nenv], dense.  NULL: the batch's own again, zeroed.
+ *   phys_batch_events_flags_ptr   the device address of the done words now in use (NULL when not configured): env e's word is element e.
+ *   phys_batch_events             ONE launch of cassie_event_kernel over [env0, env0 + n) on `stream` (NULL: the batch's own), in order
+ *                               with the launches there.  No host synchronisation, no allocation, no read on the host.  Writes the
+ *                               rows, the done words, the state and the counts of the range and nothing else.  Refuses: not configured,
+ *                               a range outside the batch, a source field whose row length is no longer what it was at the configure
+ *                               call, a PHYS_EV_INPUT column with nothing bound or with a bound dim its columns reach beyond.
+ *   phys_batch_events_dim         ncols, the rows' type and done_mask; any may be NULL -> 0, -1 when not configured.
+ *   phys_batch_events_download    rows [env0, env0 + n) to dense host memory [n][ncols] of the rows' type; waits for the streams.
+ *   phys_batch_events_download_flags  the done words [nenv] to the host; waits for the streams.
+ *   phys_batch_events_state / _set_state   the state [nenv][2][ncols] (doubles), the words [nenv][ncols] (uint32) and the counts [nenv]
+ *                               (uint32) to / from the host (on the device they lie [2][ncols][nenv] and [ncols][nenv]); both wait
+ *                               for the streams.
+ *   phys_batch_debug_events_launches  diagnostics: the launches phys_batch_events has made. */
+enum { PHYS_EV_MEASURE = 0, PHYS_EV_LEVEL = 1, PHYS_EV_TIMER = 2, PHYS_EV_EDGE = 3, PHYS_EV_LATCH = 4, PHYS_EV_ACCUM = 5, PHYS_EV_LOGIC = 6 };   /* a column's kind */
+enum { PHYS_EV_SIGNED = 0, PHYS_EV_SUMABS = 1, PHYS_EV_SUMSQ = 2, PHYS_EV_MAXABS = 3 };   /* a MEASURE's norm */
+enum { PHYS_EV_RISING = 0, PHYS_EV_FALLING = 1, PHYS_EV_EITHER = 2 };                     /* an EDGE's op */
+enum { PHYS_EV_MAX = 0, PHYS_EV_MIN = 1, PHYS_EV_SUM = 2 };                               /* an ACCUM's op */
+enum { PHYS_EV_ANY = 0, PHYS_EV_ALL = 1, PHYS_EV_NONE = 2, PHYS_EV_COUNT = 3 };           /* a LOGIC's op */
+enum { PHYS_EV_INPUT = -1 };                                                              /* a MEASURE's field, beside PHYS_F_* */
+#define PHYS_EV_MAXCOLS 64
+#define PHYS_EV_MAXCOUNT 8
+typedef struct phys_event_col {
+    int kind, field, index, count, norm, root;        /* MEASURE */
+    int src, trig, clear, gate;                       /* lower columns */
+    int op, sense, polarity, lag, keep, pad;          /* EDGE / ACCUM / LOGIC: op; LEVEL: sense; TIMER: polarity; LATCH: lag, keep */
+    unsigned long long mask;                          /* LOGIC */
+    double target, on_thr, off_thr, dt, offset, scale, init;
+} phys_event_col_t;
+int phys_batch_events_configure(phys_batch_t *b, const phys_event_col_t *cols, int ncols, int dtype, unsigned long long done_mask);   /* ncols 0: release */
+int phys_batch_events_bind_rows(phys_batch_t *b, void *device_ptr, long long row_stride);   /* NULL un-binds */
+int phys_batch_events_bind_input(phys_batch_t *b, const void *device_ptr, int dim, long long row_stride, int dtype);   /* NULL un-binds */
+int phys_batch_events_bind_flags(phys_batch_t *b, void *device_ptr /* int32 [nenv] */);   /* NULL un-binds */
+void *phys_batch_events_flags_ptr(phys_batch_t *b);
+int phys_batch_events(phys_batch_t *b, int env0, int n, const void *reset_ptr /* int32 [n] or NULL */, void *stream);
+int phys_batch_events_dim(const phys_batch_t *b, int *ncols, int *dtype, unsigned long long *done_mask);
+int phys_batch_events_download(phys_batch_t *b, void *host, int env0, int n);
+int phys_batch_events_download_flags(phys_batch_t *b, int *host /*[nenv]*/);
+int phys_batch_events_state(phys_batch_t *b, double *state_host /*[nenv][2][ncols]*/, unsigned *words_host /*[nenv][ncols]*/, unsigned *counts_host /*[nenv]*/);
+int phys_batch_events_set_state(phys_batch_t *b, const double *state_host, const unsigned *words_host, const unsigned *counts_host);
+int phys_batch_debug_events_launches(const phys_batch_t *b, long long *launches);
 
 /* measurement aid: on = every substep of a fused launch evaluates every output (IMU sensors, body quaternions), although
  * only the last substep's values can be read; off (default) = those are formed by the substeps whose values are read */
