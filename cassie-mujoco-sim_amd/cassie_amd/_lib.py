@@ -258,6 +258,18 @@ def _declare(L):
         L.phys_batch_events_state.argtypes = [vp, vp, vp, vp]
         L.phys_batch_events_set_state.argtypes = [vp, vp, vp, vp]
         L.phys_batch_debug_events_launches.argtypes = [vp, c.POINTER(c.c_longlong)]
+    if hasattr(L, "phys_batch_policy"):   # (likewise)
+        L.phys_batch_policy_configure.argtypes = [vp, vp, c.c_int, c.c_int]
+        L.phys_batch_policy_load.argtypes = [vp, c.c_int, c.c_int, vp, c.c_longlong, vp, vp]
+        L.phys_batch_policy_load_host.argtypes = [vp, c.c_int, c.c_int, vp, c.c_longlong, vp]
+        L.phys_batch_policy_bind_input.argtypes = [vp, vp, c.c_int, c.c_longlong, c.c_int]
+        L.phys_batch_policy_bind_norm.argtypes = [vp, vp, vp, c.c_double]
+        L.phys_batch_policy_bind_output.argtypes = [vp, c.c_int, vp, c.c_longlong]
+        L.phys_batch_policy_bind_sample.argtypes = [vp, vp, c.c_longlong, vp, vp, c.c_longlong, vp]
+        L.phys_batch_policy.argtypes = [vp, c.c_int, c.c_int, vp]
+        L.phys_batch_policy_download.argtypes = [vp, c.c_int, vp]
+        L.phys_batch_policy_download_packed.argtypes = [vp, vp, c.POINTER(c.c_longlong)]
+        L.phys_batch_debug_policy_launches.argtypes = [vp, c.POINTER(c.c_longlong)]
     if hasattr(L, "phys_batch_step_sums_enable"):   # (likewise)
         L.phys_batch_step_sums_enable.argtypes = [vp, c.c_int]
     if hasattr(L, "phys_batch_download_progress"):   # (absent from older variant builds selected with CASSIE_LIB)

@@ -306,6 +306,31 @@ def ev_cols(cols):
         table[k] = tuple(t)
     return table
 
+# policy rows: a layer's activations (PHYS_POL_* in cassie_phys.h), the limits and the layout of phys_pol_net_t
+POL_IDENTITY, POL_RELU, POL_ELU, POL_TANH = range(4)
+POL_MAXNETS, POL_MAXLAYERS, POL_MAXDIM, POL_MAXOUT = 2, 4, 512, 64
+POL_NET_DTYPE = np.dtype([("nlayers", np.int32), ("layer", np.int32, (POL_MAXLAYERS, 3))])   # a layer: (in, out, act)
+
+
+def pol_layer(out, act=POL_IDENTITY):
+    """A dense layer of `out` units with an activation POL_IDENTITY, POL_RELU, POL_ELU or POL_TANH; what it reads is the width of the layer
+    before it (the first: in_dim)."""
+    return (int(out), int(act))
+
+
+def pol_nets(nets, in_dim):
+    """A list of networks, each a list of pol_layer(...) (or of (in, out, act) triples, taken as written) -> POL_NET_DTYPE entries."""
+    nets = list(nets)
+    table = np.zeros(max(len(nets), 1), dtype=POL_NET_DTYPE)
+    for a, layers in enumerate(nets[:POL_MAXNETS]):
+        layers, width = list(layers), int(in_dim)
+        table[a]["nlayers"] = len(layers)
+        for l, L in enumerate(layers[:POL_MAXLAYERS]):
+            table[a]["layer"][l] = (width, int(L[0]), int(L[1])) if len(L) == 2 else tuple(int(v) for v in L)
+            width = int(table[a]["layer"][l][1])
+    return table
+
+
 # per-env physical parameters (CM_P_* in cm_model.h): what Batch.randomize takes
 (P_BODY_MASS, P_BODY_IPOS, P_BODY_INERTIA, P_DOF_DAMPING, P_GEOM_FRICTION,
  P_GEOM_POS, P_GEOM_QUAT, P_JNT_STIFFNESS, P_QPOS_SPRING) = range(9)
@@ -1209,6 +1234,90 @@ class Batch:
         """Diagnostics: the launches events() has made so far."""
         a = ctypes.c_longlong(0)
         lib().phys_batch_debug_events_launches(self._h, ctypes.byref(a))
+        return a.value
+
+    # ---- policy rows: an exact MLP actor and critic, the sampled action and its log-probability in one launch (phys_batch_policy) ----
+    def configure_policy(self, nets, in_dim):
+        """The networks of a policy: a list of 1 or 2 networks (the actor, then the critic), each a list of pol_layer(out, act) (none:
+        release); both read the bound input row of in_dim float32.  Allocates the packed weights; drops every binding and every loaded
+        layer."""
+        nets = list(nets)
+        table = pol_nets(nets, in_dim)
+        assert POL_NET_DTYPE.itemsize == 52
+        if lib().phys_batch_policy_configure(self._h, table.ctypes.data if nets else None, len(nets), int(in_dim)) != 0:
+            self._obs_fail("configure_policy")
+        self._pol_out = [int(table[a]["layer"][int(table[a]["nlayers"]) - 1][1]) for a in range(len(nets))]
+
+    def load_policy(self, net, layers, stream=None):
+        """The weights of network `net`: per layer (W, b) as numpy arrays (W float32 [out][in], as torch.nn.Linear.weight) -- the call waits
+        for the batch's streams -- or (w_ptr, w_row_stride, b_ptr) as float32 device pointers -- one small launch per layer on `stream`,
+        no host synchronisation: call it after an optimiser step on the stream the policy call follows on."""
+        for l, L in enumerate(layers):
+            if len(L) == 3:
+                rc = lib().phys_batch_policy_load(self._h, int(net), l, L[0], int(L[1]), L[2], stream)
+            else:
+                w, bias = np.ascontiguousarray(L[0], dtype=np.float32), np.ascontiguousarray(L[1], dtype=np.float32)
+                assert w.ndim == 2 and bias.shape == (w.shape[0],)
+                rc = lib().phys_batch_policy_load_host(self._h, int(net), l, w.ctypes.data, int(w.shape[1]), bias.ctypes.data)
+            if rc != 0:
+                self._obs_fail("load_policy")
+
+    def bind_policy_input(self, device_ptr, dim=0, row_stride=None, dtype=np.float32):
+        """The input rows in device memory: [nenv] rows of `dim` (= in_dim) float32 elements, `row_stride` elements (default: dim) apart --
+        the observation rows.  float64 is refused.  None un-binds."""
+        if lib().phys_batch_policy_bind_input(self._h, device_ptr, int(dim), int(dim if row_stride is None else row_stride), _obs_dtype(dtype)) != 0:
+            self._obs_fail("bind_policy_input")
+
+    def bind_policy_norm(self, mean_ptr, inv_ptr=None, clip=np.inf):
+        """The input's normalisation: float32 device arrays [in_dim] of the mean and of 1 / std, read at every call, and the clip of the
+        result.  None releases."""
+        if lib().phys_batch_policy_bind_norm(self._h, mean_ptr, inv_ptr, float(clip)) != 0:
+            self._obs_fail("bind_policy_norm")
+
+    def bind_policy_output(self, net, device_ptr, row_stride=None):
+        """Network net's output rows in caller-owned HBM: float32 [nenv] rows of its last layer's width, `row_stride` elements apart.
+        None un-binds."""
+        stride = int(row_stride if row_stride is not None else self._pol_out[net]) if device_ptr else 0
+        if lib().phys_batch_policy_bind_output(self._h, int(net), device_ptr, stride) != 0:
+            self._obs_fail("bind_policy_output")
+
+    def bind_policy_sample(self, eps_ptr, log_std_ptr=None, action_ptr=None, logp_ptr=None, eps_stride=None, action_stride=None):
+        """The sampled action: eps float32 [nenv][A] (the caller's standard normal draws), log_std float32 [A] (read at every call), the
+        action tensor float32 [nenv][A] -- what bind_actions points at -- and logp float32 [nenv]; strides default to A, the actor's output
+        width.  None releases."""
+        A = self._pol_out[0] if getattr(self, "_pol_out", None) else 0
+        if lib().phys_batch_policy_bind_sample(self._h, eps_ptr, int(A if eps_stride is None else eps_stride), log_std_ptr, action_ptr,
+                                               int(A if action_stride is None else action_stride), logp_ptr) != 0:
+            self._obs_fail("bind_policy_sample")
+
+    def policy(self, env0=0, n=None, stream=None):
+        """One launch on `stream` (default: the batch's own), between observe and act: the outputs of every network, and the action and
+        its log-probability where a sample is bound, of every env of [env0, env0 + n).  No host synchronisation."""
+        n = self.nenv - env0 if n is None else n
+        if lib().phys_batch_policy(self._h, int(env0), int(n), stream) != 0:
+            self._obs_fail("policy")
+
+    def policy_outputs(self, net):
+        """Network net's bound output rows downloaded: float32 [nenv][width] (waits for the batch's streams)."""
+        out = np.empty((self.nenv, self._pol_out[net]), dtype=np.float32)
+        if lib().phys_batch_policy_download(self._h, int(net), out.ctypes.data) != 0:
+            self._obs_fail("policy_outputs")
+        return out
+
+    def policy_packed(self):
+        """Diagnostics: the packed weights and biases as the kernel reads them (float32; waits for the batch's streams)."""
+        n = ctypes.c_longlong(0)
+        if lib().phys_batch_policy_download_packed(self._h, None, ctypes.byref(n)) != 0:
+            self._obs_fail("policy_packed")
+        out = np.empty(n.value, dtype=np.float32)
+        if lib().phys_batch_policy_download_packed(self._h, out.ctypes.data, ctypes.byref(n)) != 0:
+            self._obs_fail("policy_packed")
+        return out
+
+    def policy_launches(self):
+        """Diagnostics: the launches policy() has made so far."""
+        a = ctypes.c_longlong(0)
+        lib().phys_batch_debug_policy_launches(self._h, ctypes.byref(a))
         return a.value
 
     def set_pd_mode(self, on=True):

@@ -193,6 +193,11 @@ struct phys_batch {
     DevBuf<double> d_event_state;
     DevBuf<unsigned> d_event_words, d_event_counts;
     long long event_launches = 0;   /* launches of cassie_event_kernel (phys_batch_debug_events_launches) */
+    /* policy rows (phys_batch_policy_configure): the record (policy.nnets 0: not configured; the input, the normalisation, the outputs and
+     * the sample are the caller's arrays) and the packed weights and biases of every layer.  No stepping launch reads any of it */
+    ck::PolicyCfg policy = {};
+    DevBuf<float> d_policy_packed;
+    long long policy_launches = 0;  /* launches of cassie_policy_kernel (phys_batch_debug_policy_launches) */
 };
 
 static bool hip_ok(hipError_t e, const char *what) {
@@ -2190,6 +2195,122 @@ int phys_batch_events_set_state(phys_batch_t *b, const double *state_host, const
 int phys_batch_debug_events_launches(const phys_batch_t *b, long long *launches) {
     if (!b) return -1;
     if (launches) *launches = b->event_launches;
+    return 0;
+}
+
+/* ------------------------------------------------ policy rows ---- */
+static_assert(sizeof(ck::PolicyNetDef) == sizeof(phys_pol_net_t) && sizeof(ck::PolicyLayerDef) == sizeof(phys_pol_layer_t) &&
+              offsetof(ck::PolicyNetDef, layer) == offsetof(phys_pol_net_t, layer) && offsetof(ck::PolicyLayerDef, act) == offsetof(phys_pol_layer_t, act),
+              "phys_pol_net_t is the network policy_configure reads");
+static_assert(PHYS_POL_IDENTITY == ck::POL_IDENTITY && PHYS_POL_RELU == ck::POL_RELU && PHYS_POL_ELU == ck::POL_ELU && PHYS_POL_TANH == ck::POL_TANH &&
+              PHYS_POL_MAXNETS == ck::POLICY_MAXNETS && PHYS_POL_MAXLAYERS == ck::POLICY_MAXLAYERS && PHYS_POL_MAXDIM == ck::POLICY_MAXDIM &&
+              PHYS_POL_MAXOUT == ck::POLICY_MAXOUT, "the header's numbers are policy_kernels.h's");
+/* the record of a launch: what was configured and bound, with the pointer to the batch's packed weights */
+static ck::PolicyCfg policy_cfg_of(const phys_batch *b) {
+    ck::PolicyCfg c = b->policy;
+    c.packed = b->d_policy_packed;
+    return c;
+}
+int phys_batch_policy_configure(phys_batch_t *b, const phys_pol_net_t *nets, int nnets, int in_dim) {
+    if (!b) return refuse("phys_batch_policy_configure", ck::POLICY_SIZE_REFUSAL);
+    ck::PolicyCfg cfg;
+    if (const char *why = ck::policy_configure((const ck::PolicyNetDef *)nets, nnets, in_dim, cfg)) return refuse("phys_batch_policy_configure", why);
+    (void)hipSetDevice(b->device);
+    if (!quiesce(b)) return -1;  /* (launches in flight may be reading the weights that go away) */
+    if (nnets == 0) { b->policy = {}; b->d_policy_packed.reset(); return 0; }
+    DevBuf<float> packed;
+    if (!packed.alloc((size_t)cfg.packed_floats, true, "policy weights")) return -1;
+    b->d_policy_packed = std::move(packed);
+    b->policy = cfg;   /* (nothing bound, no layer loaded) */
+    return 0;
+}
+int phys_batch_policy_load(phys_batch_t *b, int net, int layer, const void *w_ptr, long long w_row_stride, const void *b_ptr, void *stream) {
+    if (!b) { phys_set_last_error("phys_batch_policy_load: no batch"); return -1; }
+    const ck::PolicyCfg c = policy_cfg_of(b);
+    if (const char *why = ck::check_policy_load(c, net, layer, w_ptr, w_row_stride, b_ptr)) return refuse("phys_batch_policy_load", why);
+    (void)hipSetDevice(b->device);
+    hipStream_t s = launch_stream(b, stream);
+    hipLaunchKernelGGL(ck::cassie_policy_pack_kernel, dim3((unsigned)ck::policy_pack_grid(c.net[net].layer[layer])), dim3(WV_WAVE), 0, s,
+                       ck::make_policy_pack_io(c, net, layer, (const float *)w_ptr, w_row_stride, (const float *)b_ptr, c.packed + c.net[net].layer[layer].w_off));
+    if (!hip_ok(hipGetLastError(), "cassie_policy_pack_kernel launch")) return -1;
+    b->policy.loaded |= ck::policy_layer_bit(net, layer);
+    return 0;
+}
+int phys_batch_policy_load_host(phys_batch_t *b, int net, int layer, const float *w, long long w_row_stride, const float *bias) {
+    if (!b) { phys_set_last_error("phys_batch_policy_load_host: no batch"); return -1; }
+    const ck::PolicyCfg c = policy_cfg_of(b);
+    if (const char *why = ck::check_policy_load(c, net, layer, w, w_row_stride, bias)) return refuse("phys_batch_policy_load_host", why);
+    (void)hipSetDevice(b->device);
+    const ck::PolicyLayer &L = c.net[net].layer[layer];
+    const size_t count = (size_t)L.out16 * (size_t)L.k4 + (size_t)L.out16;   /* (a layer's biases follow its weights) */
+    std::vector<float> staged(count);
+    ck::PolicyPackIO io = ck::make_policy_pack_io(c, net, layer, w, w_row_stride, bias, staged.data());
+    ck::policy_pack_host(io);
+    if (!quiesce(b)) return -1;  /* (a policy launch in flight may be reading the layer) */
+    if (!hip_ok(hipMemcpy(c.packed + L.w_off, staged.data(), sizeof(float) * count, hipMemcpyHostToDevice), "hipMemcpy(policy weights)")) return -1;
+    b->policy.loaded |= ck::policy_layer_bit(net, layer);
+    return 0;
+}
+int phys_batch_policy_bind_input(phys_batch_t *b, const void *device_ptr, int dim, long long row_stride, int dtype) {
+    if (!b) { phys_set_last_error("phys_batch_policy_bind_input: no batch"); return -1; }
+    if (!device_ptr) { b->policy.x = nullptr; b->policy.sx = 0; return 0; }
+    if (const char *why = ck::check_policy_bind_input(b->policy, dim, row_stride, dtype)) return refuse("phys_batch_policy_bind_input", why);
+    b->policy.x = (const float *)device_ptr; b->policy.sx = row_stride;
+    return 0;
+}
+int phys_batch_policy_bind_norm(phys_batch_t *b, const void *mean_ptr, const void *inv_ptr, double clip) {
+    if (!b) { phys_set_last_error("phys_batch_policy_bind_norm: no batch"); return -1; }
+    if (!mean_ptr && !inv_ptr) { b->policy.mean = b->policy.inv = nullptr; b->policy.clip = 0; return 0; }
+    if (const char *why = ck::check_policy_bind_norm(b->policy, mean_ptr, inv_ptr, clip)) return refuse("phys_batch_policy_bind_norm", why);
+    b->policy.mean = (const float *)mean_ptr; b->policy.inv = (const float *)inv_ptr; b->policy.clip = clip;
+    return 0;
+}
+int phys_batch_policy_bind_output(phys_batch_t *b, int net, void *device_ptr, long long row_stride) {
+    if (!b) { phys_set_last_error("phys_batch_policy_bind_output: no batch"); return -1; }
+    if (const char *why = ck::check_policy_bind_output(b->policy, net, device_ptr ? row_stride : 0x7fffffff)) return refuse("phys_batch_policy_bind_output", why);
+    b->policy.out[net] = (float *)device_ptr; b->policy.sout[net] = device_ptr ? row_stride : 0;
+    return 0;
+}
+int phys_batch_policy_bind_sample(phys_batch_t *b, const void *eps_ptr, long long eps_stride, const void *log_std_ptr, void *action_ptr,
+                                  long long action_stride, void *logp_ptr) {
+    if (!b) { phys_set_last_error("phys_batch_policy_bind_sample: no batch"); return -1; }
+    ck::PolicyCfg &c = b->policy;
+    if (!eps_ptr) { c.eps = nullptr; c.seps = 0; c.log_std = nullptr; c.action = nullptr; c.saction = 0; c.logp = nullptr; return 0; }
+    if (const char *why = ck::check_policy_bind_sample(c, eps_stride, log_std_ptr, action_ptr, action_stride, logp_ptr)) return refuse("phys_batch_policy_bind_sample", why);
+    c.eps = (const float *)eps_ptr; c.seps = eps_stride; c.log_std = (const float *)log_std_ptr;
+    c.action = (float *)action_ptr; c.saction = action_stride; c.logp = (float *)logp_ptr;
+    return 0;
+}
+int phys_batch_policy(phys_batch_t *b, int env0, int n, void *stream) {
+    if (!b) { phys_set_last_error("phys_batch_policy: no batch"); return -1; }
+    const ck::PolicyCfg c = policy_cfg_of(b);
+    if (const char *why = ck::check_policy_call(c, b->nenv, env0, n)) return refuse("phys_batch_policy", why);
+    (void)hipSetDevice(b->device);
+    if (n == 0) return 0;
+    hipStream_t s = launch_stream(b, stream);
+    hipLaunchKernelGGL(ck::cassie_policy_kernel, dim3((unsigned)ck::policy_grid(n, c.nnets)), dim3(WV_WAVE * ck::POLICY_WAVES), ck::policy_lds_bytes(c), s, ck::make_policy_io(c, env0, n));
+    if (!hip_ok(hipGetLastError(), "cassie_policy_kernel launch")) return -1;
+    ++b->policy_launches;
+    return 0;
+}
+int phys_batch_policy_download(phys_batch_t *b, int net, float *host) {
+    if (!b || !host || b->policy.nnets < 1) return refuse("phys_batch_policy_download", ck::POLICY_NOT_CONFIGURED);
+    if (net < 0 || net >= b->policy.nnets || !b->policy.out[net]) return refuse("phys_batch_policy_download", "no output bound to the network (phys_batch_policy_bind_output first)");
+    (void)hipSetDevice(b->device);
+    if (!quiesce(b)) return -1;
+    const size_t row = sizeof(float) * (size_t)b->policy.net[net].layer[b->policy.net[net].nlayers - 1].out;
+    return hip_ok(hipMemcpy2D(host, row, b->policy.out[net], sizeof(float) * (size_t)b->policy.sout[net], row, (size_t)b->nenv, hipMemcpyDeviceToHost), "policy output download") ? 0 : -1;
+}
+int phys_batch_policy_download_packed(phys_batch_t *b, float *host, long long *count) {
+    if (!b || b->policy.nnets < 1 || !b->d_policy_packed) return refuse("phys_batch_policy_download_packed", ck::POLICY_NOT_CONFIGURED);
+    if (count) *count = b->policy.packed_floats;
+    if (!host) return 0;
+    (void)hipSetDevice(b->device);
+    return quiesce(b) && hip_ok(hipMemcpy(host, b->d_policy_packed, sizeof(float) * (size_t)b->policy.packed_floats, hipMemcpyDeviceToHost), "policy weights download") ? 0 : -1;
+}
+int phys_batch_debug_policy_launches(const phys_batch_t *b, long long *launches) {
+    if (!b) return -1;
+    if (launches) *launches = b->policy_launches;
     return 0;
 }
 

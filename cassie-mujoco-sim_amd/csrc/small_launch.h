@@ -1,12 +1,12 @@
 /*
- * small_launch.h -- how the kernels around the step kernel (small_kernels.h, surface_kernels.h, depth_kernel.h, ray_kernel.h, episode_kernels.h, probe_kernels.h, obs_kernels.h, reward_kernels.h, act_kernels.h, task_kernels.h, event_kernels.h) are
+ * small_launch.h -- how the kernels around the step kernel (small_kernels.h, surface_kernels.h, depth_kernel.h, ray_kernel.h, episode_kernels.h, probe_kernels.h, obs_kernels.h, reward_kernels.h, act_kernels.h, task_kernels.h, event_kernels.h, policy_kernels.h) are
  * launched: the records a kernel's arguments are built from, one builder per kernel that returns its filled argument struct for an env
  * range, the grid of every launch, and the checks of what a caller configures, each returning the message of its refusal (null: fine).
  * Pure host code, no HIP runtime calls, in the spirit of step_policy.h: the launcher (phys_batch.hip) keeps the records in the batch,
  * prefixes a message with its entry point's name and launches what a builder returns on the grid given here; the wave emulator's entry
  * points (tests/emu) fill the same records from their arguments and go through the same builders, grids and checks, so a CPU test of
  * one of these kernels also runs the launcher's refusals, grid and choice of kernel (tests/test_small_launch.py pins them one by one).
- * No field of ScanIO, DepthIO, RayIO, EpisodeIO, ResetIO, DeriveIO, SetConstIO, StateIO, ProbeIO, ObsIO, RewardIO, ActIO, TaskIO or EventIO is assigned anywhere else.
+ * No field of ScanIO, DepthIO, RayIO, EpisodeIO, ResetIO, DeriveIO, SetConstIO, StateIO, ProbeIO, ObsIO, RewardIO, ActIO, TaskIO, EventIO, PolicyIO or PolicyPackIO is assigned anywhere else.
  */
 #ifndef CASSIE_SMALL_LAUNCH_H
 #define CASSIE_SMALL_LAUNCH_H
@@ -19,6 +19,7 @@
 #include "episode_kernels.h"
 #include "event_kernels.h"
 #include "obs_kernels.h"
+#include "policy_kernels.h"
 #include "probe_kernels.h"
 #include "ray_kernel.h"
 #include "reward_kernels.h"
@@ -1060,6 +1061,145 @@ inline SetConstIO make_setconst_io(const cm_model_t *model, cm_envparams_t *para
     SetConstIO io = zeroed<SetConstIO>();
     io.model = model; io.params = params; io.env0 = env0; io.nenv = n; io.derive_inertial = mode;
     return io;
+}
+
+/* ---- the policy rows ---- */
+
+/* the policy (phys_batch_policy_configure; nnets 0: not configured): the networks with the offsets of their packed layers, the packed
+ * floats in all, and a bit per (network, layer) that has been loaded (bit POLICY_MAXLAYERS net + layer).  Then what the caller names once
+ * a kernel reads them: the packed floats, the input rows with their stride, the normalisation (mean null: none), the outputs, the sample
+ * (eps null: none) */
+struct PolicyCfg {
+    int nnets, in_dim;
+    int rows0, rows1;       /* the rows of the kernel's two LDS buffers: buffer 0 holds the input and the output of a network's layers 1 and 3, buffer 1 of layers 0 and 2 */
+    unsigned loaded;
+    long long packed_floats;
+    PolicyNet net[POLICY_MAXNETS];
+    float *packed;
+    const float *x; long long sx;
+    const float *mean, *inv; double clip;
+    float *out[POLICY_MAXNETS]; long long sout[POLICY_MAXNETS];
+    const float *eps; long long seps; const float *log_std; float *action; long long saction; float *logp;
+};
+constexpr const char *POLICY_NOT_CONFIGURED = "not configured (phys_batch_policy_configure first)";
+/* (what the launcher also answers a call without a batch) */
+constexpr const char *POLICY_SIZE_REFUSAL = "a policy is 1 or 2 networks (0 releases them) of 1 .. 4 layers";
+/* the policy's configuration: checks the caller's networks and fills c but for what the caller names later.  nnets 0 is accepted and
+ * leaves c empty: the launcher releases what it holds.  The emulator goes through the same */
+inline const char *policy_configure(const PolicyNetDef *nets, int nnets, int in_dim, PolicyCfg &c) {
+    c = {};
+    if (nnets < 0 || nnets > POLICY_MAXNETS || (nnets > 0 && !nets)) return POLICY_SIZE_REFUSAL;
+    if (nnets == 0) return nullptr;
+    if (in_dim < 1 || in_dim > POLICY_MAXDIM) return "in_dim lies in 1 .. 512";
+    long long at = 0;
+    for (int a = 0; a < nnets; ++a) {
+        const PolicyNetDef &d = nets[a];
+        if (d.nlayers < 1 || d.nlayers > POLICY_MAXLAYERS) return POLICY_SIZE_REFUSAL;
+        PolicyNet &N = c.net[a];
+        N.nlayers = d.nlayers;
+        for (int l = 0; l < d.nlayers; ++l) {
+            const PolicyLayerDef &L = d.layer[l];
+            if (L.out < 1 || L.out > POLICY_MAXDIM || L.in < 1 || L.in > POLICY_MAXDIM) return "a layer's width lies in 1 .. 512";
+            if (L.act != POL_IDENTITY && L.act != POL_RELU && L.act != POL_ELU && L.act != POL_TANH)
+                return "a layer's activation is PHYS_POL_IDENTITY, PHYS_POL_RELU, PHYS_POL_ELU or PHYS_POL_TANH";
+            if (l == 0 && L.in != in_dim) return "a network's first layer reads in_dim elements";
+            if (l > 0 && L.in != d.layer[l - 1].out) return "a layer reads as many elements as the layer before it has units";
+            if (l == d.nlayers - 1 && L.out > POLICY_MAXOUT) return "a network's last layer has at most 64 units";
+            PolicyLayer &P = N.layer[l];
+            P.in = L.in; P.out = L.out; P.act = L.act; P.k4 = (L.in + 3) & ~3; P.out16 = (L.out + 15) & ~15;
+            if (l == 0 && P.k4 > c.rows0) c.rows0 = P.k4;
+            int &rows = (l & 1) ? c.rows0 : c.rows1;
+            if (P.out16 > rows) rows = P.out16;
+            P.w_off = at; at += (long long)P.out16 * P.k4;
+            P.b_off = at; at += P.out16;
+        }
+    }
+    c.nnets = nnets; c.in_dim = in_dim; c.packed_floats = at;
+    return nullptr;
+}
+inline unsigned policy_layer_bit(int net, int layer) { return 1u << (POLICY_MAXLAYERS * net + layer); }
+/* what phys_batch_policy_load / _load_host and the binding functions refuse */
+inline const char *check_policy_load(const PolicyCfg &c, int net, int layer, const void *w, long long w_row_stride, const void *b) {
+    if (c.nnets < 1) return POLICY_NOT_CONFIGURED;
+    if (net < 0 || net >= c.nnets || layer < 0 || layer >= c.net[net].nlayers) return "no such network or layer";
+    if (!w || !b) return "a layer needs its weights and its biases";
+    if (w_row_stride < c.net[net].layer[layer].in) return "a weight row stride of at least the layer's in";
+    return nullptr;
+}
+inline const char *check_policy_bind_input(const PolicyCfg &c, int dim, long long row_stride, int dtype) {
+    if (c.nnets < 1) return POLICY_NOT_CONFIGURED;
+    if (dtype == OBS_F64) return "a float64 input is refused: the products with float32 weights would not be exact in a double (bind the float32 row)";
+    if (dtype != OBS_F32) return "the input's dtype is PHYS_OBS_F32";
+    if (dim != c.in_dim) return "the input's rows hold in_dim elements";
+    if (row_stride < dim) return "a row stride of at least the row";
+    return nullptr;
+}
+inline const char *check_policy_bind_norm(const PolicyCfg &c, const void *mean, const void *inv, double clip) {
+    if (c.nnets < 1) return POLICY_NOT_CONFIGURED;
+    if (!mean || !inv) return "a normalisation needs its mean and its inv";
+    if (!(clip >= 0)) return "the clip is >= 0 or +inf";
+    return nullptr;
+}
+inline const char *check_policy_bind_output(const PolicyCfg &c, int net, long long row_stride) {
+    if (c.nnets < 1) return POLICY_NOT_CONFIGURED;
+    if (net < 0 || net >= c.nnets) return "no such network";
+    if (row_stride < c.net[net].layer[c.net[net].nlayers - 1].out) return "a row stride of at least the network's output width";
+    return nullptr;
+}
+inline const char *check_policy_bind_sample(const PolicyCfg &c, long long eps_stride, const void *log_std, const void *action, long long action_stride, const void *logp) {
+    if (c.nnets < 1) return POLICY_NOT_CONFIGURED;
+    if (!log_std || !action || !logp) return "a sample needs eps, log_std, the action tensor and logp";
+    const int A = c.net[0].layer[c.net[0].nlayers - 1].out;
+    if (eps_stride < A || action_stride < A) return "row strides of eps and of the action tensor of at least the actor's output width";
+    return nullptr;
+}
+/* what a policy call refuses */
+inline const char *check_policy_call(const PolicyCfg &c, int nenv, int env0, int n) {
+    if (c.nnets < 1 || !c.packed) return POLICY_NOT_CONFIGURED;
+    for (int a = 0; a < c.nnets; ++a)
+        for (int l = 0; l < c.net[a].nlayers; ++l)
+            if (!(c.loaded & policy_layer_bit(a, l))) return "a layer was never loaded (phys_batch_policy_load first)";
+    if (!c.x) return "no input bound (phys_batch_policy_bind_input first)";
+    if (env0 < 0 || n < 0 || (long long)env0 + n > nenv) return "env range out of bounds";
+    return nullptr;
+}
+/* a workgroup per network of a tile of POLICY_TILE envs up to POLICY_GRID workgroups, which then walk the jobs (policy_kernels.h) */
+inline int policy_grid(int n, int nnets) { const long long t = ((long long)n + POLICY_TILE - 1) / POLICY_TILE * nnets; return t < POLICY_GRID ? (int)t : POLICY_GRID; }
+/* a wave per 64 packed words up to POLICY_PACK_GRID workgroups */
+inline int policy_pack_grid(const PolicyLayer &L) {
+    const long long w = ((long long)L.out16 * L.k4 + L.out16 + WV_WAVE - 1) / WV_WAVE;
+    return w < POLICY_PACK_GRID ? (int)w : POLICY_PACK_GRID;
+}
+/* the dynamic LDS of a policy launch: the two buffers' rows of POLICY_TILE floats (at most 64 KiB) */
+inline unsigned policy_lds_bytes(const PolicyCfg &c) { return (unsigned)(c.rows0 + c.rows1) * POLICY_TILE * (unsigned)sizeof(float); }
+/* cassie_policy_kernel's */
+inline PolicyIO make_policy_io(const PolicyCfg &c, int env0, int n) {
+    PolicyIO io = zeroed<PolicyIO>();
+    io.env0 = env0; io.n = n; io.nnets = c.nnets; io.in_dim = c.in_dim; io.rows0 = c.rows0; io.rows1 = c.rows1;
+    for (int a = 0; a < c.nnets; ++a) { io.net[a] = c.net[a]; io.out[a] = c.out[a]; io.sout[a] = c.sout[a]; }
+    io.packed = c.packed; io.x = c.x; io.sx = c.sx;
+    io.mean = c.mean; io.inv = c.inv; io.clip = c.clip;
+    io.eps = c.eps; io.seps = c.seps; io.log_std = c.log_std; io.action = c.action; io.saction = c.saction; io.logp = c.logp;
+    return io;
+}
+/* cassie_policy_pack_kernel's: layer `layer` of network `net` from w (rows sw elements apart) and b to dst, where the layer's packed
+ * weights begin (the batch's packed floats + w_off, or a staging array of the layer's own); its biases follow them */
+inline PolicyPackIO make_policy_pack_io(const PolicyCfg &c, int net, int layer, const float *w, long long sw, const float *b, float *dst) {
+    PolicyPackIO io = zeroed<PolicyPackIO>();
+    const PolicyLayer &L = c.net[net].layer[layer];
+    io.w = w; io.sw = sw; io.b = b; io.dst_w = dst; io.dst_b = dst + (L.b_off - L.w_off);
+    io.in = L.in; io.out = L.out; io.k4 = L.k4; io.out16 = L.out16;
+    return io;
+}
+/* the pack kernel's words on the host (phys_batch_policy_load_host): the same index arithmetic, word for word */
+inline void policy_pack_host(const PolicyPackIO &io) {
+    const long long per = 16ll * io.k4, total = (long long)(io.out16 >> 4) * per;
+    for (long long p = 0; p < total; ++p) {
+        const long long ub = p / per, r = p - ub * per;
+        const int l = (int)(r & 63), unit = (int)ub * 16 + (l & 15), k = (int)(r >> 6) * 4 + (l >> 4);
+        io.dst_w[p] = unit < io.out && k < io.in ? io.w[(size_t)unit * (size_t)io.sw + (size_t)k] : 0.0f;
+    }
+    for (int unit = 0; unit < io.out16; ++unit) io.dst_b[unit] = unit < io.out ? io.b[unit] : 0.0f;
 }
 
 }  // namespace ck

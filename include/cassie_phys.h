@@ -1179,6 +1179,85 @@ int phys_batch_events_state(phys_batch_t *b, double *state_host /*[nenv][2][ncol
 int phys_batch_events_set_state(phys_batch_t *b, const double *state_host, const unsigned *words_host, const unsigned *counts_host);
 int phys_batch_debug_events_launches(const phys_batch_t *b, long long *launches);
 
+/* POLICY ROWS: the function between the observation row and the action tensor -- a small MLP actor, optionally a critic, and optionally
+ * the sampled action with its log-probability -- in ONE launch per env range on the caller's stream, with every bit of the result
+ * defined.  Weights and activations are float32 and every sum is accumulated in fp64 by fused multiply-add on the matrix core: the product
+ * of two float32 values is exact in a double, so every fma is ONE rounding of acc + w x, and the order of the sum is fixed here, not by
+ * whichever GEMM a BLAS library picks.  The device (cassie_policy_kernel, csrc/policy_kernels.h), the wave emulator and a numpy
+ * restatement (tests/policy_check.py: acc = acc + w * x on doubles) agree bit for bit.  No stepping kernel is handed any of this.
+ *
+ * LIMITS.  A POLICY is 1 or 2 NETWORKS: network 0 is the actor, network 1 if present the critic.  Both read the same input row of in_dim
+ *   float32, 1 <= in_dim <= 512.  A network is 1 .. 4 dense layers; a layer has `out` units, 1 <= out <= 512, a network's last layer at
+ *   most 64, and an activation PHYS_POL_IDENTITY, _RELU, _ELU or _TANH.  Weights are float32 [out][in], row-major with a row stride, as
+ *   torch.nn.Linear.weight; biases float32 [out].
+ * INPUT.  x[k] is the bound row's element k.  Where a normalisation is bound: x[k] = (float) clip((x[k] - mean[k]) * inv[k], -c, c), mean
+ *   and inv float32 [in_dim] in device memory READ AT EVERY CALL (a caller's running statistics act at once); the subtraction and the
+ *   product are individually rounded fp64 operations, the clip is two compares and selects (y < -c ? -c : y > c ? c : y: a NaN passes),
+ *   c >= 0 or +inf, and the conversion rounds to nearest even.
+ * LAYER.  K4 = in rounded up to a multiple of 4.  acc = (double) b[j]; for k = 0 .. K4 - 1 ascending: acc = fma((double) w[j][k],
+ *   (double) x[k], acc), with w and x of the padding k >= in being +0.0 -- so a bias of -0.0 ends as +0.0 when `in` is no multiple of 4
+ *   (the restatement does the same).  z = acc; h[j] = (float) act(z), rounded to nearest even; the next layer's x is h.
+ * ACTIVATIONS, in individually rounded fp64 operations; expn is the reward's (expn(a) ~ exp(-a), above), C3 and C6 the doubles nearest
+ *   1/3 and 1/6:
+ *     IDENTITY  z.
+ *     RELU      z < 0 ? +0.0 : z (a NaN and -0.0 pass).
+ *     TANH      NaN -> NaN; m = |z|; m < 2^-10: v = z - z * ((z * z) * C3); otherwise t = expn(2 m), v = (1 - t) / (1 + t), negated
+ *               where z < 0.
+ *     ELU       (alpha 1) z >= 0 or NaN: z; z > -2^-10: v = z + (z * z) * (0.5 + z * C6); otherwise v = expn(-z) - 1.
+ *   The small branches exist because the large-argument forms lose RELATIVE accuracy near 0 (1 - t and expn - 1 cancel): with them the
+ *   fp64 value is within 2^-34 relative of the exact function (the dropped series terms: z^3 / 24 of ELU at 2^-10 is 2^-34.6 of z), so the
+ *   float32 result is within 1 float32 ulp of the exact value.
+ * OUTPUTS.  A network's last h goes to its bound output: float32 [nenv][out] with a row stride.
+ * SAMPLE (optional, network 0; A its output width, mu its output).  Bound: eps float32 [nenv][A], the caller's standard normal draws;
+ *   log_std float32 [A] in device memory, read at every call; an action tensor float32 [nenv][A] (what phys_batch_act_bind_actions
+ *   points at, so phys_batch_act follows with nothing in between); logp float32 [nenv].  In individually rounded fp64 operations:
+ *   s[j] = expn(-(double) log_std[j]); a[j] = (float)(mu[j] + s[j] * eps[j]); q = sum_j eps[j] * eps[j] and L = sum_j log_std[j], both
+ *   sequential in j from +0.0; logp = (float)((-0.5 * q - L) - A * H), H the double nearest 0.5 ln(2 pi).  mu still goes to the actor's
+ *   output where one is bound.
+ * A NaN flows through an env's own outputs; nothing indexes memory by a value; no env reads another's data; a call over [env0, env0 + n)
+ *   writes what two calls over its halves write.  Rows outside the range are left alone.
+ * ORDER IN A POLICY STEP: end_episodes, task, observe, policy, act, the step launch, events, reward.
+ *
+ *   phys_batch_policy_configure   nets [nnets] (host memory) and in_dim: checks the shapes and allocates the packed weights; drops every
+ *                                 binding and every loaded layer.  nnets 0 releases.  Refuses, with a message in phys_last_error():
+ *                                 more than 2 networks or 4 layers, a width or in_dim outside the limits, an unknown activation, a first
+ *                                 layer whose `in` is not in_dim, a layer whose `in` is not the previous `out`, a last layer wider than 64.
+ *   phys_batch_policy_load        a layer's weights and biases from DEVICE pointers (float32; w rows w_row_stride elements apart): one
+ *                                 small launch on `stream` (NULL: the batch's own) packs them into the layout the kernel reads
+ *                                 (zero-padded to K4 and to 16 units; per block of 16 units and k-step of 4 the 64 words
+ *                                 w[unit l & 15][k0 + (l >> 4)] in lane order).  Called after an optimiser step, on the stream the policy
+ *                                 call follows on.  phys_batch_policy_load_host: the same from host arrays (waits for the streams).
+ *                                 A policy call with a layer that was never loaded is refused.
+ *   phys_batch_policy_bind_input  the input rows: [nenv] rows of dim (= in_dim) float32, row_stride elements apart; dtype PHYS_OBS_F32
+ *                                 (float64 is refused: the products would not be exact).  NULL un-binds.
+ *   phys_batch_policy_bind_norm   mean and inv [in_dim] float32 in device memory and the clip c.  NULL releases.
+ *   phys_batch_policy_bind_output network net's output rows, row_stride elements (>= its width) apart.  NULL un-binds.
+ *   phys_batch_policy_bind_sample eps, log_std, the action tensor and logp (strides >= A).  A NULL eps releases.
+ *   phys_batch_policy             ONE launch of cassie_policy_kernel over [env0, env0 + n) on `stream`; n 0 is accepted.  No host
+ *                                 synchronisation.
+ *   phys_batch_policy_download    network net's bound output rows to dense host memory [nenv][width]; waits for the streams.
+ *   phys_batch_policy_download_packed  the packed floats to the host (count: their number; host NULL: the count alone); waits.
+ *   phys_batch_debug_policy_launches   diagnostics: the launches phys_batch_policy has made. */
+enum { PHYS_POL_IDENTITY = 0, PHYS_POL_RELU = 1, PHYS_POL_ELU = 2, PHYS_POL_TANH = 3 };
+#define PHYS_POL_MAXNETS 2
+#define PHYS_POL_MAXLAYERS 4
+#define PHYS_POL_MAXDIM 512
+#define PHYS_POL_MAXOUT 64
+typedef struct phys_pol_layer { int in, out, act; } phys_pol_layer_t;
+typedef struct phys_pol_net { int nlayers; phys_pol_layer_t layer[PHYS_POL_MAXLAYERS]; } phys_pol_net_t;
+int phys_batch_policy_configure(phys_batch_t *b, const phys_pol_net_t *nets, int nnets, int in_dim);   /* nnets 0: release */
+int phys_batch_policy_load(phys_batch_t *b, int net, int layer, const void *w_ptr, long long w_row_stride, const void *b_ptr, void *stream);
+int phys_batch_policy_load_host(phys_batch_t *b, int net, int layer, const float *w, long long w_row_stride, const float *bias);
+int phys_batch_policy_bind_input(phys_batch_t *b, const void *device_ptr, int dim, long long row_stride, int dtype);   /* NULL un-binds */
+int phys_batch_policy_bind_norm(phys_batch_t *b, const void *mean_ptr, const void *inv_ptr, double clip);   /* NULL releases */
+int phys_batch_policy_bind_output(phys_batch_t *b, int net, void *device_ptr, long long row_stride);   /* NULL un-binds */
+int phys_batch_policy_bind_sample(phys_batch_t *b, const void *eps_ptr, long long eps_stride, const void *log_std_ptr, void *action_ptr,
+                                  long long action_stride, void *logp_ptr);   /* NULL eps releases */
+int phys_batch_policy(phys_batch_t *b, int env0, int n, void *stream);
+int phys_batch_policy_download(phys_batch_t *b, int net, float *host);
+int phys_batch_policy_download_packed(phys_batch_t *b, float *host, long long *count);
+int phys_batch_debug_policy_launches(const phys_batch_t *b, long long *launches);
+
 /* measurement aid: on = every substep of a fused launch evaluates every output (IMU sensors, body quaternions), although
  * only the last substep's values can be read; off (default) = those are formed by the substeps whose values are read */
 int phys_batch_set_all_outputs_every_substep(phys_batch_t *b, int on);
