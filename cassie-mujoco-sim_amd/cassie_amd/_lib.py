@@ -270,6 +270,19 @@ def _declare(L):
         L.phys_batch_policy_download.argtypes = [vp, c.c_int, vp]
         L.phys_batch_policy_download_packed.argtypes = [vp, vp, c.POINTER(c.c_longlong)]
         L.phys_batch_debug_policy_launches.argtypes = [vp, c.POINTER(c.c_longlong)]
+    if hasattr(L, "phys_batch_rollout_record"):   # (likewise)
+        L.phys_batch_rollout_configure.argtypes = [vp, c.c_int, vp, c.c_int, c.c_double, c.c_double, c.c_uint]
+        L.phys_batch_rollout_bind_source.argtypes = [vp, c.c_int, vp, c.c_longlong]
+        L.phys_batch_rollout_bind_storage.argtypes = [vp, c.c_int, vp, c.c_longlong, c.c_longlong]
+        L.phys_batch_rollout_ptr.argtypes = [vp, c.c_int, c.POINTER(c.c_longlong), c.POINTER(c.c_longlong)]
+        L.phys_batch_rollout_ptr.restype = vp
+        L.phys_batch_rollout_record.argtypes = [vp, c.c_int, c.c_int, c.c_int, vp]
+        L.phys_batch_rollout_finish.argtypes = [vp, c.c_int, c.c_int, vp, c.c_longlong, vp]
+        L.phys_batch_rollout_normalise.argtypes = [vp, c.c_double, vp]
+        L.phys_batch_rollout_stats.argtypes = [vp, vp]
+        L.phys_batch_rollout_download.argtypes = [vp, c.c_int, vp]
+        L.phys_batch_rollout_dim.argtypes = [vp, c.POINTER(c.c_int), c.POINTER(c.c_int), vp]
+        L.phys_batch_debug_rollout_launches.argtypes = [vp, c.POINTER(c.c_longlong)]
     if hasattr(L, "phys_batch_step_sums_enable"):   # (likewise)
         L.phys_batch_step_sums_enable.argtypes = [vp, c.c_int]
     if hasattr(L, "phys_batch_download_progress"):   # (absent from older variant builds selected with CASSIE_LIB)

@@ -331,6 +331,25 @@ def pol_nets(nets, in_dim):
     return table
 
 
+# rollout rows: the roles of a source and of the arrays (PHYS_RO_* in cassie_phys.h: numbered from RO_MAXSRC, so that one int names a source by
+# index or by role), the limits and the layout of phys_rollout_src_t
+(RO_DATA, RO_OBS, RO_ACTION, RO_LOGP, RO_MU, RO_VALUE, RO_REWARD, RO_DONE, RO_REASON, RO_ADV, RO_RET, RO_ADVN) = range(16, 28)
+RO_MAXT, RO_MAXSRC, RO_MAXDIM = 1024, 16, 4096
+RO_SRC_DTYPE = np.dtype([("role", np.int32), ("dim", np.int32)])
+RO_NAMES = {"data": RO_DATA, "obs": RO_OBS, "action": RO_ACTION, "logp": RO_LOGP, "mu": RO_MU, "value": RO_VALUE, "reward": RO_REWARD,
+            "done": RO_DONE, "reason": RO_REASON, "adv": RO_ADV, "ret": RO_RET, "advn": RO_ADVN}
+RO_INT_ROLES = (RO_DONE, RO_REASON)      # int32 words; every other role reads as float32
+
+
+def ro_srcs(srcs):
+    """A list of (role, dim) pairs -> RO_SRC_DTYPE entries."""
+    srcs = list(srcs)
+    table = np.zeros(max(len(srcs), 1), dtype=RO_SRC_DTYPE)
+    for k, (role, dim) in enumerate(srcs):
+        table[k] = (RO_NAMES.get(role, role) if isinstance(role, str) else int(role), int(dim))
+    return table
+
+
 # per-env physical parameters (CM_P_* in cm_model.h): what Batch.randomize takes
 (P_BODY_MASS, P_BODY_IPOS, P_BODY_INERTIA, P_DOF_DAMPING, P_GEOM_FRICTION,
  P_GEOM_POS, P_GEOM_QUAT, P_JNT_STIFFNESS, P_QPOS_SPRING) = range(9)
@@ -1319,6 +1338,105 @@ class Batch:
         a = ctypes.c_longlong(0)
         lib().phys_batch_debug_policy_launches(self._h, ctypes.byref(a))
         return a.value
+
+    # ---- rollout rows: the transitions of T policy steps, their advantages and returns, the normalised advantages (phys_batch_rollout_*) ----
+    def configure_rollout(self, T, srcs, gamma=0.99, lam=0.95, timeout_mask=0):
+        """The rollout: T steps of the sources `srcs`, a list of (role, dim) pairs -- role RO_DATA, RO_OBS, ... RO_REASON or its lower-case
+        name, dim in 32-bit words (none: release).  Allocates the stores, ADV and RET, zeroed; drops every binding; waits for the streams."""
+        srcs = list(srcs)
+        table = ro_srcs(srcs)
+        assert RO_SRC_DTYPE.itemsize == 8
+        if lib().phys_batch_rollout_configure(self._h, int(T), table.ctypes.data if srcs else None, len(srcs), float(gamma), float(lam), int(timeout_mask)) != 0:
+            self._obs_fail("configure_rollout")
+        self._ro = (int(T), [(int(r), int(d)) for r, d in table[: len(srcs)]])
+
+    @staticmethod
+    def _ro_id(s):
+        return RO_NAMES[s] if isinstance(s, str) else int(s)
+
+    def bind_rollout_source(self, s, device_ptr, row_stride=None):
+        """Source s (an index, a role or its name) read from caller-owned HBM: [nenv] rows of its dim words, `row_stride` words (default:
+        dim) apart.  None un-binds: a source other than RO_DATA is then resolved at every call from where the batch reads or writes it."""
+        s = self._ro_id(s)
+        stride = 0
+        if device_ptr:
+            stride = int(row_stride) if row_stride is not None else self.rollout_dim(s)
+        if lib().phys_batch_rollout_bind_source(self._h, s, device_ptr, stride) != 0:
+            self._obs_fail("bind_rollout_source")
+
+    def bind_rollout_storage(self, s, device_ptr, step_stride=None, row_stride=None):
+        """A caller's tensor in the place of the store of source s, or of RO_ADV / RO_RET / RO_ADVN: [T][nenv][dim] words, `step_stride`
+        words between two steps and `row_stride` between two envs (default: dense).  None: the batch's own again, zeroed."""
+        s = self._ro_id(s)
+        dim = self.rollout_dim(s)
+        row = int(dim if row_stride is None else row_stride)
+        step = int(self.nenv * row if step_stride is None else step_stride)
+        if lib().phys_batch_rollout_bind_storage(self._h, s, device_ptr, step if device_ptr else 0, row if device_ptr else 0) != 0:
+            self._obs_fail("bind_rollout_storage")
+
+    def rollout_dim(self, s):
+        """The words of a row of source s (an index, a role or its name); 1 for RO_ADV, RO_RET, RO_ADVN."""
+        s = self._ro_id(s)
+        if s in (RO_ADV, RO_RET, RO_ADVN):
+            return 1
+        srcs = self._ro[1]
+        if 0 <= s < RO_MAXSRC:
+            return srcs[s][1]
+        hits = [d for r, d in srcs if r == s]
+        if len(hits) != 1:
+            raise ValueError("rollout: no such source, or a role several sources share")
+        return hits[0]
+
+    def rollout_ptr(self, s):
+        """(device pointer, step stride, row stride) of the store of source s, or of RO_ADV / RO_RET / RO_ADVN; strides in words."""
+        step, row = ctypes.c_longlong(0), ctypes.c_longlong(0)
+        p = lib().phys_batch_rollout_ptr(self._h, self._ro_id(s), ctypes.byref(step), ctypes.byref(row))
+        return p, step.value, row.value
+
+    def rollout_record(self, t, env0=0, n=None, stream=None):
+        """One launch on `stream` (default: the batch's own), behind end_episodes of policy step t: every source's rows of the envs
+        [env0, env0 + n) into slot t of its store.  No host synchronisation."""
+        n = self.nenv - env0 if n is None else n
+        if lib().phys_batch_rollout_record(self._h, int(t), int(env0), int(n), stream) != 0:
+            self._obs_fail("rollout_record")
+
+    def rollout_finish(self, env0=0, n=None, last_value_ptr=None, stride=1, stream=None):
+        """One launch on `stream`, behind the range's T records: ADV and RET of the envs [env0, env0 + n).  last_value_ptr: float32 [nenv]
+        in device memory, `stride` words apart (None: the VALUE source as resolved now, V(o_T) after the next observe and policy)."""
+        n = self.nenv - env0 if n is None else n
+        if lib().phys_batch_rollout_finish(self._h, int(env0), int(n), last_value_ptr, int(stride), stream) != 0:
+            self._obs_fail("rollout_finish")
+
+    def rollout_normalise(self, eps=1e-8, stream=None):
+        """Four short launches on `stream` over the whole batch, behind every range's finish (ordering the streams is the caller's job):
+        ADVN = (ADV - mean) / (std + eps)."""
+        if lib().phys_batch_rollout_normalise(self._h, float(eps), stream) != 0:
+            self._obs_fail("rollout_normalise")
+
+    def rollout_stats(self):
+        """(mean, std, inv) of the last rollout_normalise (waits for the batch's streams)."""
+        out = np.zeros(3, dtype=np.float64)
+        if lib().phys_batch_rollout_stats(self._h, out.ctypes.data) != 0:
+            self._obs_fail("rollout_stats")
+        return tuple(out)
+
+    def rollout(self, s):
+        """The store of source s (an index, a role or its name: "obs", "action", ...), or "adv" / "ret" / "advn", downloaded: [T][nenv][dim]
+        (dim 1: [T][nenv]), int32 for RO_DONE / RO_REASON, uint32 words for RO_DATA, float32 otherwise (waits for the batch's streams)."""
+        s = self._ro_id(s)
+        dim = self.rollout_dim(s)
+        role = self._ro[1][s][0] if 0 <= s < RO_MAXSRC else s
+        out = np.empty((self._ro[0], self.nenv, dim), dtype=np.uint32)
+        if lib().phys_batch_rollout_download(self._h, s, out.ctypes.data) != 0:
+            self._obs_fail("rollout")
+        out = out.view(np.int32 if role in RO_INT_ROLES else np.uint32 if role == RO_DATA else np.float32)
+        return out[:, :, 0] if dim == 1 else out
+
+    def rollout_launches(self):
+        """Diagnostics: the launches rollout_record, rollout_finish and rollout_normalise (four a call) have made so far."""
+        a = (ctypes.c_longlong * 3)()
+        lib().phys_batch_debug_rollout_launches(self._h, a)
+        return tuple(a)
 
     def set_pd_mode(self, on=True):
         lib().phys_batch_set_pd_mode(self._h, 1 if on else 0)

@@ -198,6 +198,15 @@ struct phys_batch {
     ck::PolicyCfg policy = {};
     DevBuf<float> d_policy_packed;
     long long policy_launches = 0;  /* launches of cassie_policy_kernel (phys_batch_debug_policy_launches) */
+    /* rollout rows (phys_batch_rollout_configure): the record (rollout.nsrc 0: not configured; the pointers of its stores are filled in at the
+     * launch, from the buffers; bound sources are the caller's arrays), the store of every source, ADV, RET and ADVN (the batch's own or a
+     * caller's), and the per-env partials with the statistics behind them: q1 [nenv] | q2 [nenv] | {mean, std, inv, the last sum}.  No
+     * stepping launch reads any of it */
+    ck::RolloutCfg rollout = {};
+    DevBuf<unsigned> d_ro_store[ck::ROLLOUT_MAXSRC];
+    DevBuf<unsigned> d_ro_adv, d_ro_ret, d_ro_advn;
+    DevBuf<double> d_ro_q;
+    long long rollout_launches[3] = {0, 0, 0};  /* launches of record, finish and normalise (phys_batch_debug_rollout_launches) */
 };
 
 static bool hip_ok(hipError_t e, const char *what) {
@@ -2311,6 +2320,180 @@ int phys_batch_policy_download_packed(phys_batch_t *b, float *host, long long *c
 int phys_batch_debug_policy_launches(const phys_batch_t *b, long long *launches) {
     if (!b) return -1;
     if (launches) *launches = b->policy_launches;
+    return 0;
+}
+
+/* ------------------------------------------------ rollout rows ---- */
+static_assert(sizeof(ck::RolloutSrcDef) == sizeof(phys_rollout_src_t) && offsetof(ck::RolloutSrcDef, dim) == offsetof(phys_rollout_src_t, dim),
+              "phys_rollout_src_t is the source rollout_configure reads");
+static_assert(PHYS_RO_DATA == ck::RO_DATA && PHYS_RO_OBS == ck::RO_OBS && PHYS_RO_ACTION == ck::RO_ACTION && PHYS_RO_LOGP == ck::RO_LOGP &&
+              PHYS_RO_MU == ck::RO_MU && PHYS_RO_VALUE == ck::RO_VALUE && PHYS_RO_REWARD == ck::RO_REWARD && PHYS_RO_DONE == ck::RO_DONE &&
+              PHYS_RO_REASON == ck::RO_REASON && PHYS_RO_ADV == ck::RO_ADV && PHYS_RO_RET == ck::RO_RET && PHYS_RO_ADVN == ck::RO_ADVN &&
+              PHYS_RO_MAXT == ck::ROLLOUT_MAXT && PHYS_RO_MAXSRC == ck::ROLLOUT_MAXSRC && PHYS_RO_MAXDIM == ck::ROLLOUT_MAXDIM,
+              "the header's numbers are rollout_kernels.h's");
+/* the record of a launch: what was configured and bound, with the pointers into the batch's buffers (or the caller's in their place) */
+static ck::RolloutCfg rollout_cfg_of(const phys_batch *b) {
+    ck::RolloutCfg c = b->rollout;
+    for (int s = 0; s < c.nsrc; ++s) c.store[s].ptr = b->d_ro_store[s].get();
+    c.adv.ptr = b->d_ro_adv.get(); c.ret.ptr = b->d_ro_ret.get(); c.advn.ptr = b->d_ro_advn.get();
+    if (b->d_ro_q) { c.q1 = b->d_ro_q; c.q2 = b->d_ro_q + (size_t)b->nenv; c.stats = b->d_ro_q + 2 * (size_t)b->nenv; }
+    return c;
+}
+/* where the batch reads or writes, at this moment, the things an unbound source is resolved from */
+static ck::RolloutLive rollout_live_of(const phys_batch *b) {
+    ck::RolloutLive L = {};
+    const ck::PolicyCfg &p = b->policy;
+    if (p.nnets >= 1) {
+        const int A = p.net[0].layer[p.net[0].nlayers - 1].out;
+        L.obs = p.x; L.obs_dim = p.in_dim; L.obs_stride = p.sx;
+        L.mu = p.out[0]; L.mu_dim = A; L.mu_stride = p.sout[0];
+        if (p.nnets >= 2) { L.value = p.out[1]; L.value_stride = p.sout[1]; }
+        if (p.eps) { L.action = p.action; L.action_dim = A; L.action_stride = p.saction; L.logp = p.logp; }
+    }
+    if (b->reward.nterms >= 1) { L.rew = b->d_reward.get(); L.rew_stride = b->reward_srew; L.rew_dtype = b->reward.dtype; }
+    if (b->episodes) { L.done = b->d_ep[PHYS_EP_DONE].get(); L.reason = b->d_ep[PHYS_EP_REASON].get(); }
+    return L;
+}
+static void rollout_release(phys_batch *b) {
+    b->rollout = {};
+    for (auto &d : b->d_ro_store) d.reset();
+    b->d_ro_adv.reset(); b->d_ro_ret.reset(); b->d_ro_advn.reset(); b->d_ro_q.reset();
+}
+int phys_batch_rollout_configure(phys_batch_t *b, int T, const phys_rollout_src_t *srcs, int nsrcs, double gamma, double lambda, unsigned timeout_mask) {
+    if (!b) return refuse("phys_batch_rollout_configure", ck::ROLLOUT_SIZE_REFUSAL);
+    ck::RolloutCfg cfg;
+    if (const char *why = ck::rollout_configure((const ck::RolloutSrcDef *)srcs, nsrcs, T, gamma, lambda, timeout_mask, cfg)) return refuse("phys_batch_rollout_configure", why);
+    (void)hipSetDevice(b->device);
+    if (!quiesce(b)) return -1;  /* (launches in flight may be writing the stores that go away) */
+    if (nsrcs == 0) { rollout_release(b); return 0; }
+    const size_t n = (size_t)b->nenv, steps = (size_t)T;
+    DevBuf<unsigned> store[ck::ROLLOUT_MAXSRC], adv, ret;
+    DevBuf<double> q;
+    for (int s = 0; s < nsrcs; ++s) {
+        if (!store[s].alloc(steps * n * (size_t)cfg.dim[s], true, "rollout store")) return -1;
+        cfg.store[s].row = cfg.dim[s]; cfg.store[s].step = (long long)n * cfg.dim[s];
+    }
+    if (!adv.alloc(steps * n, true, "rollout advantages") || !ret.alloc(steps * n, true, "rollout returns") || !q.alloc(2 * n + 4, true, "rollout partials")) return -1;
+    cfg.adv.row = cfg.ret.row = cfg.advn.row = 1; cfg.adv.step = cfg.ret.step = cfg.advn.step = (long long)n;
+    rollout_release(b);
+    for (int s = 0; s < nsrcs; ++s) b->d_ro_store[s] = std::move(store[s]);
+    b->d_ro_adv = std::move(adv); b->d_ro_ret = std::move(ret); b->d_ro_q = std::move(q);
+    b->rollout = cfg;   /* (nothing bound: every store is the batch's own; ADVN comes with the first normalise) */
+    return 0;
+}
+int phys_batch_rollout_bind_source(phys_batch_t *b, int s, const void *device_ptr, long long row_stride) {
+    if (!b) { phys_set_last_error("phys_batch_rollout_bind_source: no batch"); return -1; }
+    if (const char *why = ck::check_rollout_bind_source(b->rollout, s, device_ptr, row_stride)) return refuse("phys_batch_rollout_bind_source", why);
+    const int k = ck::rollout_source_of(b->rollout, s);
+    b->rollout.src[k] = device_ptr; b->rollout.ssrc[k] = device_ptr ? row_stride : 0;
+    return 0;
+}
+/* the buffer behind a store, ADV, RET or ADVN */
+static DevBuf<unsigned> *rollout_buf_of(phys_batch *b, int s) {
+    if (s == PHYS_RO_ADV) return &b->d_ro_adv;
+    if (s == PHYS_RO_RET) return &b->d_ro_ret;
+    if (s == PHYS_RO_ADVN) return &b->d_ro_advn;
+    const int k = ck::rollout_source_of(b->rollout, s);
+    return k < 0 ? nullptr : &b->d_ro_store[k];
+}
+int phys_batch_rollout_bind_storage(phys_batch_t *b, int s, void *device_ptr, long long step_stride, long long row_stride) {
+    if (!b) { phys_set_last_error("phys_batch_rollout_bind_storage: no batch"); return -1; }
+    if (const char *why = ck::check_rollout_bind_storage(b->rollout, b->nenv, s, device_ptr, step_stride, row_stride)) return refuse("phys_batch_rollout_bind_storage", why);
+    (void)hipSetDevice(b->device);
+    int dim;
+    ck::RolloutStore *st = ck::rollout_store_of(b->rollout, s, dim);
+    DevBuf<unsigned> *buf = rollout_buf_of(b, s);
+    /* (as phys_batch_bind: launches already queued keep the pointer they were given; hipFree waits for the device by itself) */
+    if (device_ptr) { buf->borrow((unsigned *)device_ptr); st->step = step_stride; st->row = row_stride; }
+    else if (!buf->owned()) {
+        if (!buf->alloc((size_t)b->rollout.T * (size_t)b->nenv * (size_t)dim, true, "rollout store")) return -1;
+        st->row = dim; st->step = (long long)b->nenv * dim;
+    }
+    return 0;
+}
+void *phys_batch_rollout_ptr(phys_batch_t *b, int s, long long *step_stride, long long *row_stride) {
+    if (!b || b->rollout.nsrc < 1) return nullptr;
+    int dim;
+    const ck::RolloutStore *st = ck::rollout_store_of(b->rollout, s, dim);
+    if (!st) return nullptr;
+    if (step_stride) *step_stride = st->step;
+    if (row_stride) *row_stride = st->row;
+    return rollout_buf_of(b, s)->get();
+}
+int phys_batch_rollout_record(phys_batch_t *b, int t, int env0, int n, void *stream) {
+    if (!b) { phys_set_last_error("phys_batch_rollout_record: no batch"); return -1; }
+    const ck::RolloutCfg c = rollout_cfg_of(b);
+    const ck::RolloutLive L = rollout_live_of(b);
+    if (const char *why = ck::check_rollout_record(c, L, b->nenv, t, env0, n)) return refuse("phys_batch_rollout_record", why);
+    (void)hipSetDevice(b->device);
+    if (n == 0) return 0;
+    hipStream_t s = launch_stream(b, stream);
+    const ck::RolloutRecIO io = ck::make_rollout_rec_io(c, L, t, env0, n);
+    hipLaunchKernelGGL(ck::cassie_rollout_record_kernel, dim3((unsigned)ck::rollout_record_grid(io)), dim3(WV_WAVE), 0, s, io);
+    if (!hip_ok(hipGetLastError(), "cassie_rollout_record_kernel launch")) return -1;
+    ++b->rollout_launches[0];
+    return 0;
+}
+int phys_batch_rollout_finish(phys_batch_t *b, int env0, int n, const void *last_value_ptr, long long stride, void *stream) {
+    if (!b) { phys_set_last_error("phys_batch_rollout_finish: no batch"); return -1; }
+    const ck::RolloutCfg c = rollout_cfg_of(b);
+    const ck::RolloutLive L = rollout_live_of(b);
+    if (const char *why = ck::check_rollout_finish(c, L, b->nenv, env0, n, last_value_ptr, stride)) return refuse("phys_batch_rollout_finish", why);
+    (void)hipSetDevice(b->device);
+    if (n == 0) return 0;
+    hipStream_t s = launch_stream(b, stream);
+    hipLaunchKernelGGL(ck::cassie_rollout_finish_kernel, dim3((unsigned)ck::rollout_env_grid(n)), dim3(WV_WAVE), 0, s, ck::make_rollout_fin_io(c, L, env0, n, last_value_ptr, stride));
+    if (!hip_ok(hipGetLastError(), "cassie_rollout_finish_kernel launch")) return -1;
+    ++b->rollout_launches[1];
+    return 0;
+}
+int phys_batch_rollout_normalise(phys_batch_t *b, double eps, void *stream) {
+    if (!b) { phys_set_last_error("phys_batch_rollout_normalise: no batch"); return -1; }
+    (void)hipSetDevice(b->device);
+    if (b->rollout.nsrc >= 1 && !b->d_ro_advn) {   /* (the first use: the batch's own ADVN, dense) */
+        if (!b->d_ro_advn.alloc((size_t)b->rollout.T * (size_t)b->nenv, true, "rollout normalised advantages")) return -1;
+        b->rollout.advn.row = 1; b->rollout.advn.step = b->nenv;
+    }
+    const ck::RolloutCfg c = rollout_cfg_of(b);
+    if (const char *why = ck::check_rollout_normalise(c, b->nenv, eps)) return refuse("phys_batch_rollout_normalise", why);
+    hipStream_t s = launch_stream(b, stream);
+    const dim3 wave(WV_WAVE), envs((unsigned)ck::rollout_env_grid(b->nenv));
+    hipLaunchKernelGGL(ck::cassie_rollout_reduce_kernel, dim3(1), wave, 0, s, ck::make_rollout_norm_io(c, b->nenv, eps, 0));
+    hipLaunchKernelGGL(ck::cassie_rollout_square_kernel, envs, wave, 0, s, ck::make_rollout_norm_io(c, b->nenv, eps, 0));
+    hipLaunchKernelGGL(ck::cassie_rollout_reduce_kernel, dim3(1), wave, 0, s, ck::make_rollout_norm_io(c, b->nenv, eps, 1));
+    hipLaunchKernelGGL(ck::cassie_rollout_scale_kernel, dim3((unsigned)ck::rollout_scale_grid(b->nenv, c.T)), wave, 0, s, ck::make_rollout_norm_io(c, b->nenv, eps, 1));
+    if (!hip_ok(hipGetLastError(), "rollout normalise launches")) return -1;
+    b->rollout_launches[2] += 4;
+    return 0;
+}
+int phys_batch_rollout_stats(phys_batch_t *b, double *mean_std_inv) {
+    if (!b || !mean_std_inv || b->rollout.nsrc < 1 || !b->d_ro_q) return refuse("phys_batch_rollout_stats", ck::ROLLOUT_NOT_CONFIGURED);
+    (void)hipSetDevice(b->device);
+    return quiesce(b) && hip_ok(hipMemcpy(mean_std_inv, b->d_ro_q + 2 * (size_t)b->nenv, sizeof(double) * 3, hipMemcpyDeviceToHost), "rollout stats download") ? 0 : -1;
+}
+int phys_batch_rollout_download(phys_batch_t *b, int s, void *host) {
+    if (!b || !host || b->rollout.nsrc < 1) return refuse("phys_batch_rollout_download", ck::ROLLOUT_NOT_CONFIGURED);
+    int dim;
+    const ck::RolloutStore *st = ck::rollout_store_of(b->rollout, s, dim);
+    const unsigned *base = st ? rollout_buf_of(b, s)->get() : nullptr;
+    if (!base) return refuse("phys_batch_rollout_download", ck::ROLLOUT_NO_SUCH);
+    (void)hipSetDevice(b->device);
+    if (!quiesce(b)) return -1;
+    const size_t row = sizeof(unsigned) * (size_t)dim, n = (size_t)b->nenv;
+    for (int t = 0; t < b->rollout.T; ++t)
+        if (!hip_ok(hipMemcpy2D((char *)host + (size_t)t * n * row, row, base + (size_t)t * (size_t)st->step, sizeof(unsigned) * (size_t)st->row, row, n, hipMemcpyDeviceToHost), "rollout download")) return -1;
+    return 0;
+}
+int phys_batch_rollout_dim(const phys_batch_t *b, int *T, int *nsrcs, int *dims) {
+    if (!b || b->rollout.nsrc < 1) return refuse("phys_batch_rollout_dim", ck::ROLLOUT_NOT_CONFIGURED);
+    if (T) *T = b->rollout.T;
+    if (nsrcs) *nsrcs = b->rollout.nsrc;
+    if (dims) for (int s = 0; s < b->rollout.nsrc; ++s) dims[s] = b->rollout.dim[s];
+    return 0;
+}
+int phys_batch_debug_rollout_launches(const phys_batch_t *b, long long *launches) {
+    if (!b) return -1;
+    if (launches) for (int k = 0; k < 3; ++k) launches[k] = b->rollout_launches[k];
     return 0;
 }
 

@@ -1,12 +1,12 @@
 /*
- * small_launch.h -- how the kernels around the step kernel (small_kernels.h, surface_kernels.h, depth_kernel.h, ray_kernel.h, episode_kernels.h, probe_kernels.h, obs_kernels.h, reward_kernels.h, act_kernels.h, task_kernels.h, event_kernels.h, policy_kernels.h) are
+ * small_launch.h -- how the kernels around the step kernel (small_kernels.h, surface_kernels.h, depth_kernel.h, ray_kernel.h, episode_kernels.h, probe_kernels.h, obs_kernels.h, reward_kernels.h, act_kernels.h, task_kernels.h, event_kernels.h, policy_kernels.h, rollout_kernels.h) are
  * launched: the records a kernel's arguments are built from, one builder per kernel that returns its filled argument struct for an env
  * range, the grid of every launch, and the checks of what a caller configures, each returning the message of its refusal (null: fine).
  * Pure host code, no HIP runtime calls, in the spirit of step_policy.h: the launcher (phys_batch.hip) keeps the records in the batch,
  * prefixes a message with its entry point's name and launches what a builder returns on the grid given here; the wave emulator's entry
  * points (tests/emu) fill the same records from their arguments and go through the same builders, grids and checks, so a CPU test of
  * one of these kernels also runs the launcher's refusals, grid and choice of kernel (tests/test_small_launch.py pins them one by one).
- * No field of ScanIO, DepthIO, RayIO, EpisodeIO, ResetIO, DeriveIO, SetConstIO, StateIO, ProbeIO, ObsIO, RewardIO, ActIO, TaskIO, EventIO, PolicyIO or PolicyPackIO is assigned anywhere else.
+ * No field of ScanIO, DepthIO, RayIO, EpisodeIO, ResetIO, DeriveIO, SetConstIO, StateIO, ProbeIO, ObsIO, RewardIO, ActIO, TaskIO, EventIO, PolicyIO, PolicyPackIO, RolloutRecIO, RolloutFinIO or RolloutNormIO is assigned anywhere else.
  */
 #ifndef CASSIE_SMALL_LAUNCH_H
 #define CASSIE_SMALL_LAUNCH_H
@@ -23,6 +23,7 @@
 #include "probe_kernels.h"
 #include "ray_kernel.h"
 #include "reward_kernels.h"
+#include "rollout_kernels.h"
 #include "small_kernels.h"
 #include "state_kernels.h"
 #include "task_kernels.h"
@@ -1201,6 +1202,208 @@ inline void policy_pack_host(const PolicyPackIO &io) {
     }
     for (int unit = 0; unit < io.out16; ++unit) io.dst_b[unit] = unit < io.out ? io.b[unit] : 0.0f;
 }
+
+/* ---- the rollout rows ---- */
+
+/* an array of the rollout in device memory: its first word, the words between two steps and between two envs */
+struct RolloutStore { void *ptr; long long step, row; };
+/* the rollout (phys_batch_rollout_configure; nsrc 0: not configured): the steps, the sources with their roles and dims, gamma, lambda and
+ * their product rounded once, the mask of the reasons that count as a time limit; the pointers and row strides the caller bound to
+ * sources (null: resolved at every call).  Then what the caller or the launcher names once a kernel reads them: the store of every
+ * source, ADV, RET and ADVN (null until normalise is first used, or bound), the per-env partials and the statistics */
+struct RolloutCfg {
+    int T, nsrc; unsigned tmask;
+    double gamma, lambda, gl;
+    int role[ROLLOUT_MAXSRC], dim[ROLLOUT_MAXSRC];
+    const void *src[ROLLOUT_MAXSRC]; long long ssrc[ROLLOUT_MAXSRC];
+    RolloutStore store[ROLLOUT_MAXSRC], adv, ret, advn;
+    double *q1, *q2, *stats;
+};
+/* where the batch reads or writes the things a source without a pointer of its own is resolved from, at this moment: the policy's bound
+ * input (null: none) with its width and row stride, network 0's bound output, network 1's, the sample's action tensor and log-probabilities
+ * with the actor's width, the rewards with their type (0: not configured), the episodes' done and reason words (null: not enabled) */
+struct RolloutLive {
+    const void *obs; int obs_dim; long long obs_stride;
+    const void *mu; int mu_dim; long long mu_stride;
+    const void *value; long long value_stride;
+    const void *action; int action_dim; long long action_stride; const void *logp;
+    const void *rew; long long rew_stride; int rew_dtype;
+    const void *done, *reason;
+};
+constexpr const char *ROLLOUT_NOT_CONFIGURED = "not configured (phys_batch_rollout_configure first)";
+/* (what the launcher also answers a call without a batch) */
+constexpr const char *ROLLOUT_SIZE_REFUSAL = "a rollout is 1 .. 1024 steps of 1 .. 16 sources (0 releases them)";
+inline bool rollout_is_single_role(int role) { return role >= RO_OBS && role <= RO_REASON; }
+/* the rollout's configuration: checks the caller's sources and fills c but for what is bound or named later.  nsrc 0 is accepted and leaves
+ * c empty: the launcher releases what it holds.  The emulator goes through the same */
+inline const char *rollout_configure(const RolloutSrcDef *srcs, int nsrc, int T, double gamma, double lambda, unsigned tmask, RolloutCfg &c) {
+    c = {};
+    if (nsrc < 0 || nsrc > ROLLOUT_MAXSRC || (nsrc > 0 && !srcs)) return ROLLOUT_SIZE_REFUSAL;
+    if (nsrc == 0) return nullptr;
+    if (T < 1 || T > ROLLOUT_MAXT) return ROLLOUT_SIZE_REFUSAL;
+    if (!(gamma >= 0.0 && gamma <= 1.0)) return "gamma is finite and lies in [0, 1]";
+    if (!(lambda >= 0.0 && lambda <= 1.0)) return "lambda is finite and lies in [0, 1]";
+    bool reason = false;
+    for (int s = 0; s < nsrc; ++s) {
+        const int role = srcs[s].role, dim = srcs[s].dim;
+        if (role != RO_DATA && !rollout_is_single_role(role)) return "a source's role is PHYS_RO_DATA, _OBS, _ACTION, _LOGP, _MU, _VALUE, _REWARD, _DONE or _REASON";
+        if (dim < 1 || dim > ROLLOUT_MAXDIM) return "a source's dim lies in 1 .. 4096 words";
+        if ((role == RO_VALUE || role == RO_REWARD || role == RO_DONE || role == RO_REASON || role == RO_LOGP) && dim != 1)
+            return "VALUE, REWARD, DONE, REASON and LOGP have dim 1";
+        if (role != RO_DATA)
+            for (int k = 0; k < s; ++k) if (srcs[k].role == role) return "a role other than PHYS_RO_DATA names at most one source";
+        reason = reason || role == RO_REASON;
+        c.role[s] = role; c.dim[s] = dim;
+    }
+    if (tmask != 0u && !reason) return "a timeout_mask needs a REASON source";
+    c.T = T; c.nsrc = nsrc; c.tmask = tmask; c.gamma = gamma; c.lambda = lambda; c.gl = gamma * lambda;
+    return nullptr;
+}
+/* the source an int names: an index 0 .. nsrc - 1, or the role of exactly one source (-1: none, or a role several DATA sources share) */
+inline int rollout_source_of(const RolloutCfg &c, int s_or_role) {
+    if (s_or_role >= 0 && s_or_role < ROLLOUT_MAXSRC) return s_or_role < c.nsrc ? s_or_role : -1;
+    int found = -1;
+    for (int s = 0; s < c.nsrc; ++s) if (c.role[s] == s_or_role) { if (found >= 0) return -1; found = s; }
+    return found;
+}
+/* the array an int names: a source's store, or ADV / RET / ADVN (null: none) -- with the words of its rows */
+inline RolloutStore *rollout_store_of(RolloutCfg &c, int s_or_role, int &dim) {
+    dim = 1;
+    if (s_or_role == RO_ADV) return &c.adv;
+    if (s_or_role == RO_RET) return &c.ret;
+    if (s_or_role == RO_ADVN) return &c.advn;
+    const int s = rollout_source_of(c, s_or_role);
+    if (s < 0) return nullptr;
+    dim = c.dim[s];
+    return &c.store[s];
+}
+constexpr const char *ROLLOUT_NO_SUCH = "no such source: an index below the configured count, the role of exactly one source, or PHYS_RO_ADV, _RET, _ADVN";
+inline const char *check_rollout_bind_source(const RolloutCfg &c, int s_or_role, const void *ptr, long long row_stride) {
+    if (c.nsrc < 1) return ROLLOUT_NOT_CONFIGURED;
+    const int s = rollout_source_of(c, s_or_role);
+    if (s < 0) return ROLLOUT_NO_SUCH;
+    if (ptr && row_stride < c.dim[s]) return "a row stride of at least the source's dim";
+    return nullptr;
+}
+/* a caller's tensor in the place of a store: steps and rows may be padded, never overlap */
+inline const char *check_rollout_bind_storage(RolloutCfg &c, int nenv, int s_or_role, const void *ptr, long long step_stride, long long row_stride) {
+    if (c.nsrc < 1) return ROLLOUT_NOT_CONFIGURED;
+    int dim;
+    if (!rollout_store_of(c, s_or_role, dim)) return ROLLOUT_NO_SUCH;
+    if (!ptr) return nullptr;
+    if (row_stride < dim) return "a row stride of at least the source's dim";
+    if (step_stride < (long long)(nenv - 1) * row_stride + dim) return "a step stride of at least a step's rows";
+    return nullptr;
+}
+/* where source s is read at this call: the caller's pointer, or what the batch reads or writes of its role now.  DONE and REASON are
+ * int32 words, everything else resolved is float32 */
+inline const char *rollout_resolve(const RolloutCfg &c, const RolloutLive &L, int s, const void *&ptr, long long &stride) {
+    if (c.src[s]) { ptr = c.src[s]; stride = c.ssrc[s]; return nullptr; }
+    int dim = 1;
+    switch (c.role[s]) {
+    case RO_DATA: return "a PHYS_RO_DATA source has no pointer (phys_batch_rollout_bind_source first)";
+    case RO_OBS: ptr = L.obs; stride = L.obs_stride; dim = L.obs_dim; if (!ptr) return "OBS: the policy has no input bound to resolve it from"; break;
+    case RO_MU: ptr = L.mu; stride = L.mu_stride; dim = L.mu_dim; if (!ptr) return "MU: network 0 has no output bound to resolve it from"; break;
+    case RO_VALUE: ptr = L.value; stride = L.value_stride; if (!ptr) return "VALUE: network 1 has no output bound to resolve it from"; break;
+    case RO_ACTION: ptr = L.action; stride = L.action_stride; dim = L.action_dim; if (!ptr) return "ACTION: the policy has no sample bound to resolve it from"; break;
+    case RO_LOGP: ptr = L.logp; stride = 1; if (!ptr) return "LOGP: the policy has no sample bound to resolve it from"; break;
+    case RO_REWARD:
+        if (!L.rew) return "REWARD: the rewards are not configured";
+        if (L.rew_dtype != OBS_F32) return "REWARD: the rewards must be configured PHYS_OBS_F32 (a source is 32-bit words)";
+        ptr = L.rew; stride = L.rew_stride; break;
+    case RO_DONE: ptr = L.done; stride = 1; if (!ptr) return "DONE: episodes are not enabled (phys_batch_episodes_enable, or bind the source)"; break;
+    case RO_REASON: ptr = L.reason; stride = 1; if (!ptr) return "REASON: episodes are not enabled (phys_batch_episodes_enable, or bind the source)"; break;
+    default: return ROLLOUT_NO_SUCH;
+    }
+    if (dim != c.dim[s]) return "a resolved source's dim no longer fits the configured dim";
+    if (stride < c.dim[s]) return "a resolved source's row stride no longer fits the configured dim";
+    return nullptr;
+}
+/* what a record call refuses */
+inline const char *check_rollout_record(const RolloutCfg &c, const RolloutLive &L, int nenv, int t, int env0, int n) {
+    if (c.nsrc < 1) return ROLLOUT_NOT_CONFIGURED;
+    if (t < 0 || t >= c.T) return "the slot t lies in 0 .. T - 1";
+    if (env0 < 0 || n < 0 || (long long)env0 + n > nenv) return "env range out of bounds";
+    for (int s = 0; s < c.nsrc; ++s) {
+        const void *p; long long st;
+        if (const char *why = rollout_resolve(c, L, s, p, st)) return why;
+        if (!c.store[s].ptr) return "a source has no store";
+    }
+    return nullptr;
+}
+inline bool rollout_aligned16(const void *p) { return ((unsigned long long)(__UINTPTR_TYPE__)p & 15ull) == 0ull; }
+/* cassie_rollout_record_kernel's (after check_rollout_record): per source the rows of env0 on both sides, and whether a lane moves 16 bytes */
+inline RolloutRecIO make_rollout_rec_io(const RolloutCfg &c, const RolloutLive &L, int t, int env0, int n) {
+    RolloutRecIO io = zeroed<RolloutRecIO>();
+    io.n = n; io.nsrc = c.nsrc;
+    long long job = 0;
+    for (int s = 0; s < c.nsrc; ++s) {
+        const void *p = nullptr; long long st = 0;
+        (void)rollout_resolve(c, L, s, p, st);
+        RolloutRecSrc &S = io.s[s];
+        S.src = (const unsigned *)p + (size_t)env0 * (size_t)st; S.ssrc = st;
+        S.dst = (unsigned *)c.store[s].ptr + (size_t)t * (size_t)c.store[s].step + (size_t)env0 * (size_t)c.store[s].row; S.sdst = c.store[s].row;
+        S.dim = c.dim[s];
+        S.vec = rollout_aligned16(S.src) && rollout_aligned16(S.dst) && (S.dim & 3) == 0 && (S.ssrc & 3) == 0 && (S.sdst & 3) == 0;
+        S.job0 = job;
+        job += ((long long)n * S.dim + ROLLOUT_JOB - 1) / ROLLOUT_JOB;
+    }
+    io.njobs = job;
+    return io;
+}
+/* a workgroup per job up to ROLLOUT_GRID, which then walk the jobs */
+inline int rollout_record_grid(const RolloutRecIO &io) { return io.njobs < ROLLOUT_GRID ? (int)io.njobs : ROLLOUT_GRID; }
+/* the source of a role (-1: none) */
+inline int rollout_role(const RolloutCfg &c, int role) { for (int s = 0; s < c.nsrc; ++s) if (c.role[s] == role) return s; return -1; }
+/* what a finish call refuses.  last null: the VALUE source as resolved now */
+inline const char *check_rollout_finish(const RolloutCfg &c, const RolloutLive &L, int nenv, int env0, int n, const void *last, long long stride) {
+    if (c.nsrc < 1) return ROLLOUT_NOT_CONFIGURED;
+    const int sv = rollout_role(c, RO_VALUE), sr = rollout_role(c, RO_REWARD);
+    if (sv < 0 || sr < 0) return "finish needs a VALUE and a REWARD source";
+    if (env0 < 0 || n < 0 || (long long)env0 + n > nenv) return "env range out of bounds";
+    if (!c.adv.ptr || !c.ret.ptr || !c.q1) return "ADV or RET has no store";
+    if (last) return stride < 1 ? "a stride of the last values of at least 1" : nullptr;
+    const void *p; long long st;
+    return rollout_resolve(c, L, sv, p, st);
+}
+/* cassie_rollout_finish_kernel's (after check_rollout_finish) */
+inline RolloutFinIO make_rollout_fin_io(const RolloutCfg &c, const RolloutLive &L, int env0, int n, const void *last, long long stride) {
+    RolloutFinIO io = zeroed<RolloutFinIO>();
+    const int sv = rollout_role(c, RO_VALUE), sr = rollout_role(c, RO_REWARD), sd = rollout_role(c, RO_DONE), sq = rollout_role(c, RO_REASON);
+    io.env0 = env0; io.n = n; io.T = c.T; io.tmask = sd >= 0 && sq >= 0 ? c.tmask : 0u; io.gamma = c.gamma; io.gl = c.gl;
+    io.val = (const float *)c.store[sv].ptr; io.val_step = c.store[sv].step; io.val_row = c.store[sv].row;
+    io.rew = (const float *)c.store[sr].ptr; io.rew_step = c.store[sr].step; io.rew_row = c.store[sr].row;
+    if (sd >= 0) { io.done = (const int *)c.store[sd].ptr; io.done_step = c.store[sd].step; io.done_row = c.store[sd].row; }
+    if (sq >= 0) { io.reason = (const int *)c.store[sq].ptr; io.reason_step = c.store[sq].step; io.reason_row = c.store[sq].row; }
+    if (!last) (void)rollout_resolve(c, L, sv, last, stride);
+    io.last = (const float *)last; io.last_row = stride;
+    io.adv = (float *)c.adv.ptr; io.adv_step = c.adv.step; io.adv_row = c.adv.row;
+    io.ret = (float *)c.ret.ptr; io.ret_step = c.ret.step; io.ret_row = c.ret.row;
+    io.q1 = c.q1;
+    return io;
+}
+/* lane = env: a workgroup per 64 envs up to ROLLOUT_FIN_GRID */
+inline int rollout_env_grid(int n) { const int w = (n + WV_WAVE - 1) / WV_WAVE; return w < ROLLOUT_FIN_GRID ? w : ROLLOUT_FIN_GRID; }
+/* what a normalise call refuses (ADVN: the launcher allocates it before this check, or the caller bound it) */
+inline const char *check_rollout_normalise(const RolloutCfg &c, int nenv, double eps) {
+    if (c.nsrc < 1) return ROLLOUT_NOT_CONFIGURED;
+    if ((long long)c.T * nenv < 2) return "normalise needs T * nenv >= 2";
+    if (!(eps >= 0.0 && eps < INFINITY)) return "eps is finite and >= 0";
+    if (!c.adv.ptr || !c.advn.ptr || !c.q1 || !c.q2 || !c.stats) return "ADV or ADVN has no store";
+    return nullptr;
+}
+/* the three normalise kernels' (stage: the reduce kernel's) */
+inline RolloutNormIO make_rollout_norm_io(const RolloutCfg &c, int nenv, double eps, int stage) {
+    RolloutNormIO io = zeroed<RolloutNormIO>();
+    const long long M = (long long)c.T * nenv;
+    io.nenv = nenv; io.T = c.T; io.stage = stage; io.count = (double)M; io.count1 = (double)(M - 1); io.eps = eps;
+    io.adv = (const float *)c.adv.ptr; io.adv_step = c.adv.step; io.adv_row = c.adv.row;
+    io.advn = (float *)c.advn.ptr; io.advn_step = c.advn.step; io.advn_row = c.advn.row;
+    io.q1 = c.q1; io.q2 = c.q2; io.stats = c.stats;
+    return io;
+}
+/* a workgroup per (step, block of 64 envs) up to ROLLOUT_SCALE_GRID */
+inline int rollout_scale_grid(int nenv, int T) { const long long j = ((long long)nenv + WV_WAVE - 1) / WV_WAVE * T; return j < ROLLOUT_SCALE_GRID ? (int)j : ROLLOUT_SCALE_GRID; }
 
 }  // namespace ck
 #endif

@@ -1258,6 +1258,97 @@ int phys_batch_policy_download(phys_batch_t *b, int net, float *host);
 int phys_batch_policy_download_packed(phys_batch_t *b, float *host, long long *count);
 int phys_batch_debug_policy_launches(const phys_batch_t *b, long long *launches);
 
+/* ROLLOUT ROWS: what lies between the policy step and the optimiser -- the T transitions of a rollout stored by ONE launch per env range
+ * per policy step, their advantages and returns (GAE) by ONE launch per range, and the advantages normalised over the whole batch -- with
+ * every bit of the result defined.  The device (csrc/rollout_kernels.h), the wave emulator and a numpy restatement
+ * (tests/rollout_check.py) agree bit for bit; a recorded run can be replayed, or compared across ranks, up to the tensors the optimiser
+ * reads.  No stepping kernel is handed any of this.
+ *
+ * LIMITS.  1 <= T <= 1024 steps (PHYS_RO_MAXT); 1 .. 16 SOURCES (PHYS_RO_MAXSRC); a source is {role, dim} with 1 <= dim <= 4096
+ *   (PHYS_RO_MAXDIM) 32-BIT WORDS a row: float32 and int32 are both copied as words, the copy is bit-exact and type-blind (float64 is out
+ *   of scope).  Where a function takes `s`, it is a source's index 0 .. nsrcs - 1, or the role of exactly one source, or -- for storage
+ *   and downloads -- PHYS_RO_ADV, _RET, _ADVN (the roles are numbered from 16 on, so that one int does for both).
+ * ROLES.  PHYS_RO_DATA: any rows of the caller's; its pointer is mandatory (phys_batch_rollout_bind_source) and several sources may have
+ *   the role.  PHYS_RO_OBS, _ACTION, _LOGP, _MU, _VALUE, _REWARD, _DONE, _REASON: at most one source each; VALUE, REWARD, DONE, REASON and
+ *   LOGP have dim 1.  A source of these roles that is unbound (or bound to NULL) is RESOLVED AT EVERY CALL from where the batch reads or
+ *   writes that thing at that moment, the reward's convention:
+ *     OBS            the policy's bound input (phys_batch_policy_bind_input)
+ *     MU             network 0's bound output
+ *     VALUE          network 1's bound output, column 0
+ *     ACTION, LOGP   the sample binding (phys_batch_policy_bind_sample)
+ *     REWARD         the rewards, the batch's own or bound; they must be configured PHYS_OBS_F32, refused at the call otherwise
+ *     DONE, REASON   PHYS_EP_DONE / PHYS_EP_REASON, the batch's own or bound (int32)
+ *   A resolved width or row stride that no longer fits the configured dim refuses the call, with a message in phys_last_error().
+ * STORAGE.  Per source [T][nenv][dim] words, TIME-MAJOR: a range's slot is one contiguous block, and the GAE reads consecutive envs.  The
+ *   batch's own, zeroed at configure (phys_batch_rollout_ptr), or a caller's tensor in its place (phys_batch_rollout_bind_storage: the
+ *   words between two steps and between two rows, both may be padded; NULL goes back to the batch's own, zeroed), so that the update
+ *   reads a torch view with no copy.  ADV and RET, float32 [T][nenv], are own or bound the same way; ADVN, a third array of that shape, is
+ *   allocated on the first phys_batch_rollout_normalise, or bound.  None of it is in a state-bank row: as with the reward's returns, a
+ *   caller that rewinds an env decides itself what becomes of the steps it had recorded.
+ * RECORD.  phys_batch_rollout_record(b, t, env0, n, stream) is ONE launch: for every source s, every env of the range and every j < dim,
+ *   store[s][t][env][j] = src_s[env * row_stride + j].  Nothing else is written: rows outside the range, slots other than t and the
+ *   padding between rows are left alone.  t is the caller's (0 <= t < T): there is no device counter, and two ranges on two streams stay
+ *   independent.  n 0 is accepted.  The call never synchronises the host.  Where a source's pointer, its slot, its dim and both row
+ *   strides are multiples of 4 words a lane moves 16 bytes, otherwise a word; the host decides per source and call.
+ * ORDER IN A POLICY STEP, as a cycle: end_episodes, ROLLOUT_RECORD, task, observe, policy, act, the step launch, events, reward.  Behind
+ *   end_episodes of step t the bound tensors still hold o_t, a_t, logp_t, mu_t, v_t and r_t -- observe and policy have not run again --
+ *   and PHYS_EP_DONE / _REASON are that step's verdict.
+ * FINISH.  phys_batch_rollout_finish(b, env0, n, last_value_ptr, stride, stream) is ONE launch, a lane per env, behind the range's T
+ *   records.  last_value float32 [nenv] rows `stride` words apart; NULL: the VALUE source as resolved now, which is V(o_T) after the
+ *   caller's next observe and policy (it runs them anyway).  VALUE and REWARD sources are required; without a DONE source every d is
+ *   false.  Every step is ONE individually rounded fp64 operation, no fma, no reassociation; gl = gamma * lambda is rounded once on the host:
+ *     nv = (double) last_value[env];  a = +0.0
+ *     for t = T - 1 .. 0:
+ *         v = (double) V[t][env];  r = (double) R[t][env];  d = DONE[t][env] != 0
+ *         if timeout_mask and d and (REASON[t][env] & timeout_mask) != 0 and (REASON[t][env] & ~timeout_mask) == 0:
+ *             r = r + gamma * v        (an episode cut by the time limit alone bootstraps from the step's own value)
+ *         nvs = d ? +0.0 : nv;  as = d ? +0.0 : a        (SELECTS, not products: 0 * NaN would carry an ended episode's NaN backwards)
+ *         delta = (r + gamma * nvs) - v
+ *         a = delta + gl * as
+ *         ADV[t][env] = (float) a;  RET[t][env] = (float)(a + v);  nv = v
+ *     q1[env] = sum over t ascending from +0.0 of (double) ADV[t][env]        (the env's partial of the mean)
+ *   A NaN stays in its env; a call over a range writes what two calls over its halves write.
+ * NORMALISE.  phys_batch_rollout_normalise(b, eps, stream) is FOUR short launches on `stream` over the WHOLE batch, behind every range's
+ *   finish: ORDERING THE STREAMS IS THE CALLER'S JOB (the ranges' streams wait for nothing here).  No kernel spins on another workgroup
+ *   or uses a grid-wide barrier: the stream orders the four.  Refuses M = T * nenv < 2 and an eps that is negative or not finite.
+ *   reduce(x[nenv]): the envs padded with +0.0 to a multiple of 64; every block of 64 consecutive envs summed by the wave's tree
+ *   (wv::wave_sum, pinned by tests/test_wave_primitives.py); the block sums added sequentially in block order from +0.0.
+ *     mean = reduce(q1) / M
+ *     q2[env] = sum over t ascending from +0.0 of ((double) ADV[t][env] - mean)^2
+ *     std = sqrt(reduce(q2) / (M - 1));  inv = 1 / (std + eps)
+ *     ADVN[t][env] = (float)(((double) ADV[t][env] - mean) * inv)
+ *   The result does not depend on how finish was cut into ranges.  phys_batch_rollout_stats downloads {mean, std, inv}.
+ *
+ *   phys_batch_rollout_configure     srcs [nsrcs] (host memory), T, gamma, lambda, timeout_mask: allocates and zeroes the stores, ADV and
+ *                                    RET; drops every binding.  Waits for the streams.  nsrcs 0 releases.  Refuses: T or a dim outside
+ *                                    the limits, an unknown or duplicate role, a dim other than 1 where the role fixes it, a gamma or
+ *                                    lambda that is not finite or outside [0, 1], a non-zero timeout_mask without a REASON source.
+ *   phys_batch_rollout_bind_source   a source's rows in device memory, row_stride words (>= dim) apart.  NULL un-binds.
+ *   phys_batch_rollout_bind_storage  a caller's tensor in the place of a store, of ADV, RET or ADVN: step_stride and row_stride in words.
+ *   phys_batch_rollout_ptr           where a store, ADV, RET or ADVN lies now (NULL: none), with its strides.
+ *   phys_batch_rollout_record / _finish / _normalise   above.
+ *   phys_batch_rollout_stats         {mean, std, inv} of the last normalise to the host; waits for the streams.
+ *   phys_batch_rollout_download      a store, ADV, RET or ADVN to dense host memory [T][nenv][dim] words; waits for the streams.
+ *   phys_batch_rollout_dim           T, the count of sources and (dims non-NULL) their dims.
+ *   phys_batch_debug_rollout_launches  diagnostics: the launches of record, of finish and of normalise (4 a call) so far. */
+enum { PHYS_RO_DATA = 16, PHYS_RO_OBS = 17, PHYS_RO_ACTION = 18, PHYS_RO_LOGP = 19, PHYS_RO_MU = 20, PHYS_RO_VALUE = 21, PHYS_RO_REWARD = 22,
+       PHYS_RO_DONE = 23, PHYS_RO_REASON = 24, PHYS_RO_ADV = 25, PHYS_RO_RET = 26, PHYS_RO_ADVN = 27 };
+#define PHYS_RO_MAXT 1024
+#define PHYS_RO_MAXSRC 16
+#define PHYS_RO_MAXDIM 4096
+typedef struct phys_rollout_src { int role, dim; } phys_rollout_src_t;
+int phys_batch_rollout_configure(phys_batch_t *b, int T, const phys_rollout_src_t *srcs, int nsrcs, double gamma, double lambda, unsigned timeout_mask);   /* nsrcs 0: release */
+int phys_batch_rollout_bind_source(phys_batch_t *b, int s, const void *device_ptr, long long row_stride);   /* NULL un-binds */
+int phys_batch_rollout_bind_storage(phys_batch_t *b, int s, void *device_ptr, long long step_stride, long long row_stride);   /* NULL: the batch's own */
+void *phys_batch_rollout_ptr(phys_batch_t *b, int s, long long *step_stride, long long *row_stride);
+int phys_batch_rollout_record(phys_batch_t *b, int t, int env0, int n, void *stream);
+int phys_batch_rollout_finish(phys_batch_t *b, int env0, int n, const void *last_value_ptr, long long stride, void *stream);
+int phys_batch_rollout_normalise(phys_batch_t *b, double eps, void *stream);
+int phys_batch_rollout_stats(phys_batch_t *b, double *mean_std_inv /*[3]*/);
+int phys_batch_rollout_download(phys_batch_t *b, int s, void *host);
+int phys_batch_rollout_dim(const phys_batch_t *b, int *T, int *nsrcs, int *dims /*[nsrcs] or NULL*/);
+int phys_batch_debug_rollout_launches(const phys_batch_t *b, long long *launches /*[3]: record, finish, normalise*/);
+
 /* measurement aid: on = every substep of a fused launch evaluates every output (IMU sensors, body quaternions), although
  * only the last substep's values can be read; off (default) = those are formed by the substeps whose values are read */
 int phys_batch_set_all_outputs_every_substep(phys_batch_t *b, int on);
