@@ -350,6 +350,12 @@ def ro_srcs(srcs):
     return table
 
 
+# gradient rows: what Batch.grad_download names (PHYS_GRAD_* in cassie_phys.h), the chunk's limits, the count of statistics and their names
+(GRAD_DW, GRAD_DB, GRAD_DLS, GRAD_ACT, GRAD_DELTA, GRAD_PARTIAL, GRAD_PACKT) = range(7)
+GRAD_MINCHUNK, GRAD_MAXCHUNK, GRAD_NSTATS = 16, 4096, 8
+GRAD_STATS = ("policy_loss", "value_loss", "kl", "clipped", "entropy", "void", "m", "spare")
+
+
 # per-env physical parameters (CM_P_* in cm_model.h): what Batch.randomize takes
 (P_BODY_MASS, P_BODY_IPOS, P_BODY_INERTIA, P_DOF_DAMPING, P_GEOM_FRICTION,
  P_GEOM_POS, P_GEOM_QUAT, P_JNT_STIFFNESS, P_QPOS_SPRING) = range(9)
@@ -1436,6 +1442,68 @@ class Batch:
         """Diagnostics: the launches rollout_record, rollout_finish and rollout_normalise (four a call) have made so far."""
         a = (ctypes.c_longlong * 3)()
         lib().phys_batch_debug_rollout_launches(self._h, a)
+        return tuple(a)
+
+    # ---- gradient rows: the PPO loss of a minibatch of the rollout and its exact gradient (phys_batch_grad_*) ----
+    def configure_grad(self, max_m, chunk=512, clip_eps=0.2, c_v=0.5, c_ent=0.0):
+        """The gradient of minibatches of up to max_m samples of the rollout (0: release): the clipped surrogate with clip_eps, c_v times
+        the value loss, c_ent times the entropy.  `chunk`, a multiple of 16 in 16 .. 4096, is the run of positions a weight sum's partial
+        covers: part of the definition.  Needs configure_policy and configure_rollout; waits for the batch's streams."""
+        if lib().phys_batch_grad_configure(self._h, int(max_m), int(chunk), float(clip_eps), float(c_v), float(c_ent)) != 0:
+            self._obs_fail("configure_grad")
+
+    def bind_grad(self, net, layer, dw_ptr, dw_row_stride=None, db_ptr=None):
+        """A caller's float32 device tensors for a layer's gradients: dW [out][in], `dw_row_stride` elements (default: in) apart, as
+        torch.nn.Linear.weight.grad, and db [out].  None: the batch's own again."""
+        stride = 0
+        if dw_ptr:
+            stride = int(dw_row_stride) if dw_row_stride is not None else int(self.grad_count(GRAD_DW, net, layer) // max(self.grad_count(GRAD_DB, net, layer), 1))
+        if lib().phys_batch_grad_bind(self._h, int(net), int(layer), dw_ptr, stride, db_ptr) != 0:
+            self._obs_fail("bind_grad")
+
+    def bind_grad_log_std(self, device_ptr):
+        """A caller's float32 device tensor [A] for log_std's gradient.  None: the batch's own again."""
+        if lib().phys_batch_grad_bind_log_std(self._h, device_ptr) != 0:
+            self._obs_fail("bind_grad_log_std")
+
+    def grad(self, idx_ptr, m, stream=None):
+        """The launches of one minibatch on `stream` (default: the batch's own): idx_ptr int32 [m] in device memory, sample indices
+        t * nenv + env into the rollout.  The gradients land in the bound tensors (or the batch's own).  No host synchronisation."""
+        if lib().phys_batch_grad(self._h, idx_ptr, int(m), stream) != 0:
+            self._obs_fail("grad")
+
+    def grad_stats(self):
+        """The eight statistics of the last grad call, by name (GRAD_STATS), and as an array under "all" (waits for the batch's streams)."""
+        out = np.zeros(GRAD_NSTATS, dtype=np.float64)
+        if lib().phys_batch_grad_stats(self._h, out.ctypes.data) != 0:
+            self._obs_fail("grad_stats")
+        d = dict(zip(GRAD_STATS, out))
+        d["all"] = out
+        return d
+
+    def grad_count(self, what, net=0, layer=0):
+        """The elements grad_download(what, net, layer) returns (-1: no such thing)."""
+        return int(lib().phys_batch_grad_count(self._h, int(what), int(net), int(layer)))
+
+    def grad_download(self, what, net=0, layer=0):
+        """GRAD_DW / _DB / _DLS: a gradient (bound or own); GRAD_ACT: the kept activations h_layer of the last call's m positions; GRAD_DELTA:
+        its deltas; GRAD_PARTIAL: the float64 partials; GRAD_PACKT: the transposed packing.  A flat array (waits for the batch's streams)."""
+        n = self.grad_count(what, net, layer)
+        if n < 0:
+            raise ValueError("grad_download: no such network, layer or kind")
+        out = np.zeros(n, dtype=np.float64 if what == GRAD_PARTIAL else np.float32)
+        if n and lib().phys_batch_grad_download(self._h, int(what), int(net), int(layer), out.ctypes.data) != 0:
+            self._obs_fail("grad_download")
+        return out
+
+    def grad_launch_mask(self, mask=31):
+        """Measurement aid: bit k set = grad() makes launch k (forward, backward, partials, reduce, statistics); 31: all, the default."""
+        lib().phys_batch_debug_grad_mask(self._h, int(mask))
+
+    def grad_launches(self):
+        """Diagnostics: the launches so far of forward, backward, partials, reduce, statistics and the transposed packing."""
+        a = (ctypes.c_longlong * 6)()
+        lib().phys_batch_debug_grad_launches(self._h, a)
         return tuple(a)
 
     def set_pd_mode(self, on=True):

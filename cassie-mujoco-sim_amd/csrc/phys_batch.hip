@@ -207,6 +207,15 @@ struct phys_batch {
     DevBuf<unsigned> d_ro_adv, d_ro_ret, d_ro_advn;
     DevBuf<double> d_ro_q;
     long long rollout_launches[3] = {0, 0, 0};  /* launches of record, finish and normalise (phys_batch_debug_rollout_launches) */
+    /* gradient rows (phys_batch_grad_configure): the record (grad.max_m 0: not configured; bound gradient tensors are the caller's), the kept
+     * activations, the deltas, the fp64 partials of the weight sums, the transposed packing of the weights, the per-position doubles of the
+     * head with the eight statistics behind them, and the batch's own gradient floats.  No stepping launch reads any of it */
+    ck::GradCfg grad = {};
+    DevBuf<float> d_grad_act, d_grad_delta, d_grad_packt, d_grad_own;
+    DevBuf<double> d_grad_part, d_grad_pos;
+    int grad_last_m = 0;            /* the m of the last phys_batch_grad (what the downloads of activations and deltas hold) */
+    unsigned grad_mask = 31u;       /* measurement aid (phys_batch_debug_grad_mask): which of the five launches a call makes */
+    long long grad_launches[6] = {0, 0, 0, 0, 0, 0};  /* forward, backward, partials, reduce, statistics, transposed packings */
 };
 
 static bool hip_ok(hipError_t e, const char *what) {
@@ -2208,6 +2217,8 @@ int phys_batch_debug_events_launches(const phys_batch_t *b, long long *launches)
 }
 
 /* ------------------------------------------------ policy rows ---- */
+static void grad_release(phys_batch *b);
+static bool grad_pack_layer(phys_batch *b, int net, int layer, hipStream_t s);
 static_assert(sizeof(ck::PolicyNetDef) == sizeof(phys_pol_net_t) && sizeof(ck::PolicyLayerDef) == sizeof(phys_pol_layer_t) &&
               offsetof(ck::PolicyNetDef, layer) == offsetof(phys_pol_net_t, layer) && offsetof(ck::PolicyLayerDef, act) == offsetof(phys_pol_layer_t, act),
               "phys_pol_net_t is the network policy_configure reads");
@@ -2226,6 +2237,7 @@ int phys_batch_policy_configure(phys_batch_t *b, const phys_pol_net_t *nets, int
     if (const char *why = ck::policy_configure((const ck::PolicyNetDef *)nets, nnets, in_dim, cfg)) return refuse("phys_batch_policy_configure", why);
     (void)hipSetDevice(b->device);
     if (!quiesce(b)) return -1;  /* (launches in flight may be reading the weights that go away) */
+    grad_release(b);             /* (the gradient rows are laid out for the policy that goes away) */
     if (nnets == 0) { b->policy = {}; b->d_policy_packed.reset(); return 0; }
     DevBuf<float> packed;
     if (!packed.alloc((size_t)cfg.packed_floats, true, "policy weights")) return -1;
@@ -2243,6 +2255,7 @@ int phys_batch_policy_load(phys_batch_t *b, int net, int layer, const void *w_pt
                        ck::make_policy_pack_io(c, net, layer, (const float *)w_ptr, w_row_stride, (const float *)b_ptr, c.packed + c.net[net].layer[layer].w_off));
     if (!hip_ok(hipGetLastError(), "cassie_policy_pack_kernel launch")) return -1;
     b->policy.loaded |= ck::policy_layer_bit(net, layer);
+    if (b->grad.max_m > 0 && !grad_pack_layer(b, net, layer, s)) return -1;   /* (gradient rows configured: the transposed packing too) */
     return 0;
 }
 int phys_batch_policy_load_host(phys_batch_t *b, int net, int layer, const float *w, long long w_row_stride, const float *bias) {
@@ -2258,6 +2271,7 @@ int phys_batch_policy_load_host(phys_batch_t *b, int net, int layer, const float
     if (!quiesce(b)) return -1;  /* (a policy launch in flight may be reading the layer) */
     if (!hip_ok(hipMemcpy(c.packed + L.w_off, staged.data(), sizeof(float) * count, hipMemcpyHostToDevice), "hipMemcpy(policy weights)")) return -1;
     b->policy.loaded |= ck::policy_layer_bit(net, layer);
+    if (b->grad.max_m > 0 && !(grad_pack_layer(b, net, layer, launch_stream(b, nullptr)) && quiesce(b))) return -1;
     return 0;
 }
 int phys_batch_policy_bind_input(phys_batch_t *b, const void *device_ptr, int dim, long long row_stride, int dtype) {
@@ -2365,6 +2379,7 @@ int phys_batch_rollout_configure(phys_batch_t *b, int T, const phys_rollout_src_
     if (const char *why = ck::rollout_configure((const ck::RolloutSrcDef *)srcs, nsrcs, T, gamma, lambda, timeout_mask, cfg)) return refuse("phys_batch_rollout_configure", why);
     (void)hipSetDevice(b->device);
     if (!quiesce(b)) return -1;  /* (launches in flight may be writing the stores that go away) */
+    grad_release(b);             /* (the gradient rows gather from the stores that go away) */
     if (nsrcs == 0) { rollout_release(b); return 0; }
     const size_t n = (size_t)b->nenv, steps = (size_t)T;
     DevBuf<unsigned> store[ck::ROLLOUT_MAXSRC], adv, ret;
@@ -2494,6 +2509,158 @@ int phys_batch_rollout_dim(const phys_batch_t *b, int *T, int *nsrcs, int *dims)
 int phys_batch_debug_rollout_launches(const phys_batch_t *b, long long *launches) {
     if (!b) return -1;
     if (launches) for (int k = 0; k < 3; ++k) launches[k] = b->rollout_launches[k];
+    return 0;
+}
+
+/* ------------------------------------------------ gradient rows ---- */
+static_assert(PHYS_GRAD_DW == ck::GRAD_DW && PHYS_GRAD_DB == ck::GRAD_DB && PHYS_GRAD_DLS == ck::GRAD_DLS && PHYS_GRAD_ACT == ck::GRAD_ACT &&
+              PHYS_GRAD_DELTA == ck::GRAD_DELTA && PHYS_GRAD_PARTIAL == ck::GRAD_PARTIAL && PHYS_GRAD_PACKT == ck::GRAD_PACKT &&
+              PHYS_GRAD_MINCHUNK == ck::GRAD_MINCHUNK && PHYS_GRAD_MAXCHUNK == ck::GRAD_MAXCHUNK && PHYS_GRAD_NSTATS == ck::GRAD_NSTATS,
+              "the header's numbers are grad_kernels.h's");
+/* the record of a launch: what was configured and bound, with the pointers into the batch's buffers */
+static ck::GradCfg grad_cfg_of(const phys_batch *b) {
+    ck::GradCfg c = b->grad;
+    c.act = b->d_grad_act; c.delta = b->d_grad_delta; c.packt = b->d_grad_packt; c.own = b->d_grad_own;
+    c.part = b->d_grad_part; c.pos = b->d_grad_pos;
+    c.stats = b->d_grad_pos ? b->d_grad_pos + (size_t)c.pos_doubles : nullptr;
+    return c;
+}
+static void grad_release(phys_batch *b) {
+    b->grad = {};
+    b->grad_last_m = 0;
+    b->d_grad_act.reset(); b->d_grad_delta.reset(); b->d_grad_packt.reset(); b->d_grad_own.reset(); b->d_grad_part.reset(); b->d_grad_pos.reset();
+}
+/* the transposed packing of a loaded layer from the policy's packed weights, behind whatever wrote them on s */
+static bool grad_pack_layer(phys_batch *b, int net, int layer, hipStream_t s) {
+    const ck::GradPackIO io = ck::make_grad_pack_io(grad_cfg_of(b), policy_cfg_of(b), net, layer);
+    hipLaunchKernelGGL(ck::cassie_grad_pack_kernel, dim3((unsigned)ck::grad_pack_grid(io)), dim3(WV_WAVE), 0, s, io);
+    if (!hip_ok(hipGetLastError(), "cassie_grad_pack_kernel launch")) return false;
+    ++b->grad_launches[5];
+    return true;
+}
+int phys_batch_grad_configure(phys_batch_t *b, int max_m, int chunk, double clip_eps, double c_v, double c_ent) {
+    if (!b) return refuse("phys_batch_grad_configure", ck::GRAD_NEEDS);
+    ck::GradCfg cfg;
+    const long long total = b->rollout.nsrc >= 1 ? (long long)b->rollout.T * b->nenv : 0;
+    if (const char *why = ck::grad_configure(b->policy, total, max_m, chunk, clip_eps, c_v, c_ent, cfg)) return refuse("phys_batch_grad_configure", why);
+    (void)hipSetDevice(b->device);
+    if (!quiesce(b)) return -1;  /* (launches in flight may be using the stores that go away) */
+    if (max_m == 0) { grad_release(b); return 0; }
+    DevBuf<float> act, delta, packt, own;
+    DevBuf<double> part, pos;
+    if (!act.alloc((size_t)cfg.act_floats, true, "gradient activations") || !delta.alloc((size_t)cfg.delta_floats, true, "gradient deltas") ||
+        !packt.alloc((size_t)cfg.packt_floats, true, "transposed weights") || !own.alloc((size_t)cfg.own_floats, true, "gradients") ||
+        !part.alloc((size_t)cfg.part_doubles, true, "gradient partials") || !pos.alloc((size_t)cfg.pos_doubles + ck::GRAD_NSTATS, true, "gradient head values")) return -1;
+    grad_release(b);
+    b->d_grad_act = std::move(act); b->d_grad_delta = std::move(delta); b->d_grad_packt = std::move(packt); b->d_grad_own = std::move(own);
+    b->d_grad_part = std::move(part); b->d_grad_pos = std::move(pos);
+    b->grad = cfg;   /* (nothing bound: every gradient is the batch's own) */
+    /* the layers loaded before now: their transposed packing from the packed weights */
+    hipStream_t s = launch_stream(b, nullptr);
+    for (int a = 0; a < b->policy.nnets; ++a)
+        for (int l = 0; l < b->policy.net[a].nlayers; ++l)
+            if ((b->policy.loaded & ck::policy_layer_bit(a, l)) && !grad_pack_layer(b, a, l, s)) return -1;
+    return quiesce(b) ? 0 : -1;
+}
+int phys_batch_grad_bind(phys_batch_t *b, int net, int layer, void *dw_ptr, long long dw_row_stride, void *db_ptr) {
+    if (!b) { phys_set_last_error("phys_batch_grad_bind: no batch"); return -1; }
+    if (const char *why = ck::check_grad_bind(b->grad, b->policy, net, layer, dw_ptr, dw_row_stride, db_ptr)) return refuse("phys_batch_grad_bind", why);
+    const int s = ck::grad_slot(b->grad, net, layer);
+    b->grad.dw[s] = (float *)dw_ptr; b->grad.sdw[s] = dw_ptr ? dw_row_stride : 0; b->grad.db[s] = (float *)db_ptr;
+    return 0;
+}
+int phys_batch_grad_bind_log_std(phys_batch_t *b, void *ptr) {
+    if (!b) { phys_set_last_error("phys_batch_grad_bind_log_std: no batch"); return -1; }
+    if (b->grad.max_m < 1) return refuse("phys_batch_grad_bind_log_std", ck::GRAD_NOT_CONFIGURED);
+    b->grad.dls = (float *)ptr;
+    return 0;
+}
+int phys_batch_grad(phys_batch_t *b, const void *idx_ptr, int m, void *stream) {
+    if (!b) { phys_set_last_error("phys_batch_grad: no batch"); return -1; }
+    const ck::GradCfg c = grad_cfg_of(b);
+    const ck::PolicyCfg p = policy_cfg_of(b);
+    if (c.max_m < 1) return refuse("phys_batch_grad", ck::GRAD_NOT_CONFIGURED);
+    ck::GradSources S;
+    if (const char *why = ck::grad_sources(rollout_cfg_of(b), p, b->nenv, S)) return refuse("phys_batch_grad", why);
+    if (const char *why = ck::check_grad_call(c, p, idx_ptr, m)) return refuse("phys_batch_grad", why);
+    (void)hipSetDevice(b->device);
+    hipStream_t s = launch_stream(b, stream);
+    const ck::GradIO io = ck::make_grad_io(c, p, S, b->nenv, (const int *)idx_ptr, m);
+    const dim3 wave(WV_WAVE), group(WV_WAVE * ck::POLICY_WAVES), tiles((unsigned)ck::grad_tile_grid(io));
+    const unsigned lds = ck::grad_lds_bytes(p);
+    const unsigned mask = b->grad_mask;
+    if (mask & 1u) { hipLaunchKernelGGL(ck::cassie_grad_forward_kernel, tiles, group, lds, s, io); ++b->grad_launches[0]; }
+    if ((mask & 2u) && ck::grad_has_backward(p)) { hipLaunchKernelGGL(ck::cassie_grad_backward_kernel, tiles, group, lds, s, io); ++b->grad_launches[1]; }
+    if (mask & 4u) { hipLaunchKernelGGL(ck::cassie_grad_partial_kernel, dim3((unsigned)ck::grad_partial_grid(io)), wave, 0, s, io); ++b->grad_launches[2]; }
+    if (mask & 8u) { hipLaunchKernelGGL(ck::cassie_grad_reduce_kernel, dim3((unsigned)ck::grad_reduce_grid(io)), wave, 0, s, io); ++b->grad_launches[3]; }
+    if (mask & 16u) { hipLaunchKernelGGL(ck::cassie_grad_stats_kernel, dim3((unsigned)ck::grad_stats_grid(io)), wave, 0, s, io); ++b->grad_launches[4]; }
+    if (!hip_ok(hipGetLastError(), "gradient launches")) return -1;
+    b->grad_last_m = m;
+    return 0;
+}
+int phys_batch_grad_stats(phys_batch_t *b, double *stats) {
+    if (!b || !stats || b->grad.max_m < 1 || !b->d_grad_pos) return refuse("phys_batch_grad_stats", ck::GRAD_NOT_CONFIGURED);
+    (void)hipSetDevice(b->device);
+    return quiesce(b) && hip_ok(hipMemcpy(stats, b->d_grad_pos + (size_t)b->grad.pos_doubles, sizeof(double) * ck::GRAD_NSTATS, hipMemcpyDeviceToHost), "gradient stats download") ? 0 : -1;
+}
+long long phys_batch_grad_count(const phys_batch_t *b, int what, int net, int layer) {
+    if (!b || b->grad.max_m < 1) return -1;
+    const ck::GradCfg &c = b->grad;
+    if (what == ck::GRAD_DLS) return c.A;
+    if (net < 0 || net >= b->policy.nnets) return -1;
+    const ck::PolicyNet &N = b->policy.net[net];
+    const long long m = b->grad_last_m;
+    if (what == ck::GRAD_ACT) return layer >= 0 && layer <= N.nlayers ? m * (layer == 0 ? b->policy.in_dim : N.layer[layer - 1].out) : -1;
+    if (layer < 0 || layer >= N.nlayers) return -1;
+    const ck::PolicyLayer &L = N.layer[layer];
+    switch (what) {
+    case ck::GRAD_DW: return (long long)L.out * L.in;
+    case ck::GRAD_DB: return L.out;
+    case ck::GRAD_DELTA: return m * L.out;
+    case ck::GRAD_PARTIAL: return (m + c.chunk - 1) / c.chunk * L.out * (L.in + 1);
+    case ck::GRAD_PACKT: return (long long)c.g[net].hw[layer] * ((L.out + 3) & ~3);
+    default: return -1;
+    }
+}
+int phys_batch_grad_download(phys_batch_t *b, int what, int net, int layer, void *host) {
+    if (!b || !host || b->grad.max_m < 1) return refuse("phys_batch_grad_download", ck::GRAD_NOT_CONFIGURED);
+    if (phys_batch_grad_count(b, what, net, layer) < 0) return refuse("phys_batch_grad_download", "no such network, layer or kind (PHYS_GRAD_*)");
+    (void)hipSetDevice(b->device);
+    if (!quiesce(b)) return -1;
+    const ck::GradCfg c = grad_cfg_of(b);
+    const size_t m = (size_t)b->grad_last_m, f = sizeof(float);
+    if (what == ck::GRAD_DLS) return hip_ok(hipMemcpy(host, c.dls ? c.dls : c.own + c.own_ls, f * (size_t)c.A, hipMemcpyDeviceToHost), "gradient download") ? 0 : -1;
+    const ck::GradNet &G = c.g[net];
+    if (what == ck::GRAD_ACT) {
+        const size_t w = (size_t)(layer == 0 ? b->policy.in_dim : b->policy.net[net].layer[layer - 1].out);
+        if (m == 0) return 0;
+        return hip_ok(hipMemcpy2D(host, f * w, c.act + G.h_off[layer], f * (size_t)G.hw[layer], f * w, m, hipMemcpyDeviceToHost), "gradient download") ? 0 : -1;
+    }
+    const ck::PolicyLayer &L = b->policy.net[net].layer[layer];
+    const int s = ck::grad_slot(c, net, layer);
+    const size_t out = (size_t)L.out, in = (size_t)L.in;
+    switch (what) {
+    case ck::GRAD_DW:
+        return hip_ok(hipMemcpy2D(host, f * in, c.dw[s] ? c.dw[s] : c.own + c.own_w[s], f * (size_t)(c.dw[s] ? c.sdw[s] : L.in), f * in, out, hipMemcpyDeviceToHost), "gradient download") ? 0 : -1;
+    case ck::GRAD_DB: return hip_ok(hipMemcpy(host, c.db[s] ? c.db[s] : c.own + c.own_b[s], f * out, hipMemcpyDeviceToHost), "gradient download") ? 0 : -1;
+    case ck::GRAD_DELTA:
+        if (m == 0) return 0;
+        return hip_ok(hipMemcpy2D(host, f * out, c.delta + G.d_off[layer], f * (size_t)L.out16, f * out, m, hipMemcpyDeviceToHost), "gradient download") ? 0 : -1;
+    case ck::GRAD_PARTIAL:
+        if (m == 0) return 0;
+        return hip_ok(hipMemcpy(host, c.part + G.p_off[layer], sizeof(double) * (size_t)phys_batch_grad_count(b, what, net, layer), hipMemcpyDeviceToHost), "gradient download") ? 0 : -1;
+    default:
+        return hip_ok(hipMemcpy(host, c.packt + G.t_off[layer], f * (size_t)phys_batch_grad_count(b, what, net, layer), hipMemcpyDeviceToHost), "gradient download") ? 0 : -1;
+    }
+}
+int phys_batch_debug_grad_mask(phys_batch_t *b, unsigned mask) {
+    if (!b) return -1;
+    b->grad_mask = mask & 31u;
+    return 0;
+}
+int phys_batch_debug_grad_launches(const phys_batch_t *b, long long *launches) {
+    if (!b) return -1;
+    if (launches) for (int k = 0; k < 6; ++k) launches[k] = b->grad_launches[k];
     return 0;
 }
 

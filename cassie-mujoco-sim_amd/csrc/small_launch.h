@@ -1,12 +1,12 @@
 /*
- * small_launch.h -- how the kernels around the step kernel (small_kernels.h, surface_kernels.h, depth_kernel.h, ray_kernel.h, episode_kernels.h, probe_kernels.h, obs_kernels.h, reward_kernels.h, act_kernels.h, task_kernels.h, event_kernels.h, policy_kernels.h, rollout_kernels.h) are
+ * small_launch.h -- how the kernels around the step kernel (small_kernels.h, surface_kernels.h, depth_kernel.h, ray_kernel.h, episode_kernels.h, probe_kernels.h, obs_kernels.h, reward_kernels.h, act_kernels.h, task_kernels.h, event_kernels.h, policy_kernels.h, rollout_kernels.h, grad_kernels.h) are
  * launched: the records a kernel's arguments are built from, one builder per kernel that returns its filled argument struct for an env
  * range, the grid of every launch, and the checks of what a caller configures, each returning the message of its refusal (null: fine).
  * Pure host code, no HIP runtime calls, in the spirit of step_policy.h: the launcher (phys_batch.hip) keeps the records in the batch,
  * prefixes a message with its entry point's name and launches what a builder returns on the grid given here; the wave emulator's entry
  * points (tests/emu) fill the same records from their arguments and go through the same builders, grids and checks, so a CPU test of
  * one of these kernels also runs the launcher's refusals, grid and choice of kernel (tests/test_small_launch.py pins them one by one).
- * No field of ScanIO, DepthIO, RayIO, EpisodeIO, ResetIO, DeriveIO, SetConstIO, StateIO, ProbeIO, ObsIO, RewardIO, ActIO, TaskIO, EventIO, PolicyIO, PolicyPackIO, RolloutRecIO, RolloutFinIO or RolloutNormIO is assigned anywhere else.
+ * No field of ScanIO, DepthIO, RayIO, EpisodeIO, ResetIO, DeriveIO, SetConstIO, StateIO, ProbeIO, ObsIO, RewardIO, ActIO, TaskIO, EventIO, PolicyIO, PolicyPackIO, RolloutRecIO, RolloutFinIO, RolloutNormIO, GradIO or GradPackIO is assigned anywhere else.
  */
 #ifndef CASSIE_SMALL_LAUNCH_H
 #define CASSIE_SMALL_LAUNCH_H
@@ -18,6 +18,7 @@
 #include "depth_kernel.h"
 #include "episode_kernels.h"
 #include "event_kernels.h"
+#include "grad_kernels.h"
 #include "obs_kernels.h"
 #include "policy_kernels.h"
 #include "probe_kernels.h"
@@ -1404,6 +1405,157 @@ inline RolloutNormIO make_rollout_norm_io(const RolloutCfg &c, int nenv, double 
 }
 /* a workgroup per (step, block of 64 envs) up to ROLLOUT_SCALE_GRID */
 inline int rollout_scale_grid(int nenv, int T) { const long long j = ((long long)nenv + WV_WAVE - 1) / WV_WAVE * T; return j < ROLLOUT_SCALE_GRID ? (int)j : ROLLOUT_SCALE_GRID; }
+
+/* ---- the gradient rows ---- */
+
+/* the gradient (phys_batch_grad_configure; max_m 0: not configured): the largest minibatch, the chunk (part of the definition: it fixes the
+ * order of the weight sums), max_m rounded up to the chunk and the chunks that makes; eps with 1 - eps and 1 + eps rounded once, the two
+ * coefficients; where every network's rows begin in the stores and how large the stores are; the (network, layer) slots in launch order
+ * with the first float of their dW and db among the batch's own gradient floats (dls follows the last).  The caller's gradient tensors
+ * (null: the batch's own).  Then what the launcher names once a kernel reads them */
+struct GradCfg {
+    int max_m, chunk, mcap, maxchunks, nslots, A;
+    double eps, lo, hi, c_v, c_ent;
+    GradNet g[POLICY_MAXNETS];
+    long long act_floats, delta_floats, part_doubles, packt_floats, pos_doubles, own_floats, own_ls;
+    int slot_net[GRAD_MAXSLOTS], slot_layer[GRAD_MAXSLOTS];
+    long long own_w[GRAD_MAXSLOTS], own_b[GRAD_MAXSLOTS];
+    float *dw[GRAD_MAXSLOTS]; long long sdw[GRAD_MAXSLOTS]; float *db[GRAD_MAXSLOTS]; float *dls;
+    float *act, *delta, *packt, *own; double *part, *pos, *stats;
+};
+/* the rollout's arrays a minibatch is gathered from, and the samples the rollout holds */
+struct GradSources { GradSrc obs, action, logp, advn, ret; int total; };
+constexpr const char *GRAD_NOT_CONFIGURED = "not configured (phys_batch_grad_configure first)";
+constexpr const char *GRAD_NEEDS = "the gradient needs a configured policy and rollout (phys_batch_policy_configure, phys_batch_rollout_configure first)";
+inline int grad_slot(const GradCfg &c, int net, int layer) {
+    for (int s = 0; s < c.nslots; ++s) if (c.slot_net[s] == net && c.slot_layer[s] == layer) return s;
+    return -1;
+}
+/* the gradient's configuration: checks the caller's numbers against the policy and fills c but for what is bound or named later.  max_m 0
+ * is accepted and leaves c empty: the launcher releases what it holds.  total: the rollout's T nenv.  The emulator goes through the same */
+inline const char *grad_configure(const PolicyCfg &p, long long total, int max_m, int chunk, double eps, double c_v, double c_ent, GradCfg &c) {
+    c = {};
+    if (max_m == 0) return nullptr;
+    if (p.nnets < 1 || total < 1) return GRAD_NEEDS;
+    if (total > 0x7fffffffll) return "the rollout's T nenv must fit an int32 index";
+    if (max_m < 0 || max_m > total) return "max_m lies in 1 .. T nenv (0 releases)";
+    if (chunk < GRAD_MINCHUNK || chunk > GRAD_MAXCHUNK || (chunk & 15) != 0) return "chunk is a multiple of 16 in 16 .. 4096";
+    if (!(eps >= 0.0 && eps < INFINITY)) return "clip_eps is finite and >= 0";
+    if (!(c_v >= 0.0 && c_v < INFINITY)) return "c_v is finite and >= 0";
+    if (!(c_ent >= 0.0 && c_ent < INFINITY)) return "c_ent is finite and >= 0";
+    if (p.nnets > 1 && p.net[1].layer[p.net[1].nlayers - 1].out != 1) return "the critic's last layer has one unit";
+    c.max_m = max_m; c.chunk = chunk; c.mcap = (int)(((long long)max_m + chunk - 1) / chunk * chunk); c.maxchunks = c.mcap / chunk;
+    c.eps = eps; c.lo = 1.0 - eps; c.hi = 1.0 + eps; c.c_v = c_v; c.c_ent = c_ent;
+    c.A = p.net[0].layer[p.net[0].nlayers - 1].out;
+    const long long mcap = c.mcap;
+    long long act = 0, delta = 0, part = 0, packt = 0, own = 0;
+    const int in16 = (p.in_dim + 15) & ~15;
+    for (int a = 0; a < p.nnets; ++a) {
+        GradNet &G = c.g[a];
+        const PolicyNet &N = p.net[a];
+        G.hw[0] = in16;
+        if (a == 0) { G.h_off[0] = act; act += mcap * in16; } else G.h_off[0] = c.g[0].h_off[0];
+        for (int l = 0; l < N.nlayers; ++l) {
+            const PolicyLayer &L = N.layer[l];
+            G.hw[l + 1] = L.out16; G.h_off[l + 1] = act; act += mcap * L.out16;
+            G.d_off[l] = delta; delta += mcap * L.out16;
+            G.p_off[l] = part; part += (long long)c.maxchunks * L.out * (L.in + 1);
+            G.t_off[l] = packt; packt += (long long)G.hw[l] * ((L.out + 3) & ~3);
+            const int s = c.nslots++;
+            c.slot_net[s] = a; c.slot_layer[s] = l;
+            c.own_w[s] = own; own += (long long)L.out * L.in;
+            c.own_b[s] = own; own += L.out;
+        }
+    }
+    c.own_ls = own; own += c.A;
+    c.act_floats = act; c.delta_floats = delta; c.part_doubles = part; c.packt_floats = packt; c.own_floats = own;
+    c.pos_doubles = (long long)(c.A + GRAD_POS_ROWS) * mcap;
+    return nullptr;
+}
+/* what phys_batch_grad_bind refuses (ptr null: the batch's own again) */
+inline const char *check_grad_bind(const GradCfg &c, const PolicyCfg &p, int net, int layer, const void *dw, long long dw_row_stride, const void *db) {
+    if (c.max_m < 1) return GRAD_NOT_CONFIGURED;
+    if (net < 0 || net >= p.nnets || layer < 0 || layer >= p.net[net].nlayers) return "no such network or layer";
+    if (!dw != !db) return "a layer's dW and db are bound together (both null: the batch's own)";
+    if (dw && dw_row_stride < p.net[net].layer[layer].in) return "a dW row stride of at least the layer's in";
+    return nullptr;
+}
+/* the rollout's arrays the gradient gathers from (null message: all there).  VALUE and RET only with a critic */
+inline const char *grad_sources(const RolloutCfg &r, const PolicyCfg &p, int nenv, GradSources &S) {
+    S = {};
+    if (r.nsrc < 1 || p.nnets < 1) return GRAD_NEEDS;
+    const int so = rollout_role(r, RO_OBS), sa = rollout_role(r, RO_ACTION), sl = rollout_role(r, RO_LOGP), sv = rollout_role(r, RO_VALUE);
+    if (so < 0 || sa < 0 || sl < 0) return "the rollout needs sources of role OBS, ACTION and LOGP";
+    if (p.nnets > 1 && sv < 0) return "with a critic the rollout needs a source of role VALUE";
+    if (r.dim[so] != p.in_dim) return "the rollout's OBS rows hold in_dim elements";
+    if (r.dim[sa] != p.net[0].layer[p.net[0].nlayers - 1].out) return "the rollout's ACTION rows hold as many elements as the actor has outputs";
+    if (!r.store[so].ptr || !r.store[sa].ptr || !r.store[sl].ptr) return "a source has no store";
+    if (!r.advn.ptr) return "no ADVN (phys_batch_rollout_normalise first, or bind its storage)";
+    if (p.nnets > 1 && !r.ret.ptr) return "no RET (phys_batch_rollout_finish first)";
+    auto src = [](const RolloutStore &st) { GradSrc g; g.ptr = (const float *)st.ptr; g.step = st.step; g.row = st.row; return g; };
+    S.obs = src(r.store[so]); S.action = src(r.store[sa]); S.logp = src(r.store[sl]); S.advn = src(r.advn);
+    if (p.nnets > 1) S.ret = src(r.ret);
+    S.total = (int)((long long)r.T * nenv);
+    return nullptr;
+}
+/* what a grad call refuses (after grad_sources) */
+inline const char *check_grad_call(const GradCfg &c, const PolicyCfg &p, const void *idx, int m) {
+    if (c.max_m < 1 || !c.act || !c.delta || !c.part || !c.packt || !c.pos || !c.stats || !c.own) return GRAD_NOT_CONFIGURED;
+    if (p.nnets < 1 || !p.packed) return POLICY_NOT_CONFIGURED;
+    for (int a = 0; a < p.nnets; ++a)
+        for (int l = 0; l < p.net[a].nlayers; ++l)
+            if (!(p.loaded & policy_layer_bit(a, l))) return "a layer was never loaded (phys_batch_policy_load first)";
+    if (!p.log_std) return "no log_std (phys_batch_policy_bind_sample first)";
+    if (!idx) return "no idx";
+    if (m < 1 || m > c.max_m) return "m lies in 1 .. max_m";
+    return nullptr;
+}
+/* the five kernels' (after check_grad_call) */
+inline GradIO make_grad_io(const GradCfg &c, const PolicyCfg &p, const GradSources &S, int nenv, const int *idx, int m) {
+    GradIO io = zeroed<GradIO>();
+    io.m = m; io.chunk = c.chunk; io.mcap = (int)(((long long)m + c.chunk - 1) / c.chunk * c.chunk); io.nchunks = io.mcap / c.chunk;
+    io.nnets = p.nnets; io.in_dim = p.in_dim; io.rows0 = p.rows0; io.rows1 = p.rows1;
+    io.nenv = nenv; io.total = S.total; io.A = c.A; io.nslots = c.nslots;
+    for (int a = 0; a < p.nnets; ++a) { io.net[a] = p.net[a]; io.g[a] = c.g[a]; }
+    io.packed = p.packed; io.packt = c.packt; io.idx = idx;
+    io.obs = S.obs; io.action = S.action; io.logp = S.logp; io.advn = S.advn; io.ret = S.ret;
+    io.mean = p.mean; io.inv = p.inv; io.clip = p.clip; io.log_std = p.log_std;
+    io.act = c.act; io.delta = c.delta; io.part = c.part; io.pos = c.pos; io.stats = c.stats;
+    io.lo = c.lo; io.hi = c.hi; io.eps = c.eps; io.c_v = c.c_v; io.c_ent = c.c_ent; io.inv_m = 1.0 / (double)m;
+    long long job = 0, par = 0;
+    for (int s = 0; s < c.nslots; ++s) {
+        const PolicyLayer &L = p.net[c.slot_net[s]].layer[c.slot_layer[s]];
+        io.slot_net[s] = c.slot_net[s]; io.slot_layer[s] = c.slot_layer[s];
+        io.dw[s] = c.dw[s] ? c.dw[s] : c.own + c.own_w[s]; io.sdw[s] = c.dw[s] ? c.sdw[s] : L.in; io.db[s] = c.db[s] ? c.db[s] : c.own + c.own_b[s];
+        io.job0[s] = job; io.par0[s] = par;
+        job += (long long)io.nchunks * (L.out16 >> 4) * ((((L.in + 16) >> 4) + 3) >> 2);
+        par += (long long)L.out * (L.in + 1);
+    }
+    io.job0[c.nslots] = job; io.par0[c.nslots] = par;
+    io.dls = c.dls ? c.dls : c.own + c.own_ls;
+    return io;
+}
+/* note: the chunks of a call are those of ITS m; the stores are laid out for max_m (GradNet's offsets use the configured mcap, a call's
+ * rows are its first io.mcap) */
+inline int grad_tile_grid(const GradIO &io) { const long long t = (long long)(io.mcap / POLICY_TILE) * io.nnets; return t < GRAD_GRID ? (int)t : GRAD_GRID; }
+inline int grad_partial_grid(const GradIO &io) { const long long j = io.job0[io.nslots]; return j < GRAD_PART_GRID ? (int)j : GRAD_PART_GRID; }
+inline int grad_reduce_grid(const GradIO &io) { const long long w = (io.par0[io.nslots] + WV_WAVE - 1) / WV_WAVE; return w < GRAD_RED_GRID ? (int)w : GRAD_RED_GRID; }
+inline int grad_stats_grid(const GradIO &io) { return io.A + GRAD_POS_ROWS; }
+inline bool grad_has_backward(const PolicyCfg &p) { for (int a = 0; a < p.nnets; ++a) if (p.net[a].nlayers > 1) return true; return false; }
+/* the dynamic LDS of launches 1 and 2: the policy's two buffers and a word per position of the tile */
+inline unsigned grad_lds_bytes(const PolicyCfg &p) { return policy_lds_bytes(p) + POLICY_TILE * (unsigned)sizeof(int); }
+/* cassie_grad_pack_kernel's: the transposed packing of layer `layer` of network `net` from the policy's packed weights */
+inline GradPackIO make_grad_pack_io(const GradCfg &c, const PolicyCfg &p, int net, int layer) {
+    GradPackIO io = zeroed<GradPackIO>();
+    const PolicyLayer &L = p.net[net].layer[layer];
+    io.src = p.packed + L.w_off; io.dst = c.packt + c.g[net].t_off[layer];
+    io.in = L.in; io.out = L.out; io.k4 = L.k4; io.in16 = c.g[net].hw[layer]; io.u4 = (L.out + 3) & ~3;
+    return io;
+}
+inline int grad_pack_grid(const GradPackIO &io) {
+    const long long w = ((long long)io.in16 * io.u4 + WV_WAVE - 1) / WV_WAVE;
+    return w < GRAD_PACK_GRID ? (int)w : GRAD_PACK_GRID;
+}
 
 }  // namespace ck
 #endif

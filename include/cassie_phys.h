@@ -1349,6 +1349,87 @@ int phys_batch_rollout_download(phys_batch_t *b, int s, void *host);
 int phys_batch_rollout_dim(const phys_batch_t *b, int *T, int *nsrcs, int *dims /*[nsrcs] or NULL*/);
 int phys_batch_debug_rollout_launches(const phys_batch_t *b, long long *launches /*[3]: record, finish, normalise*/);
 
+/* GRADIENT ROWS: for a minibatch of the rollout's samples, the PPO clipped-surrogate loss, the value loss and the entropy term, and their
+ * gradient with respect to every weight, every bias and log_std of the policy, by FIVE launches on the caller's stream with every bit
+ * defined.  The forward pass the gradient is taken through IS the one the policy acts with (POLICY ROWS); the gradients land in float32
+ * tensors an optimiser takes as param.grad with no copy; the optimiser step itself stays the caller's (phys_batch_policy_load follows it).
+ * The device (csrc/grad_kernels.h), the wave emulator and a numpy restatement (tests/grad_check.py) agree bit for bit.  No stepping kernel
+ * is handed any of this.
+ *
+ * All arithmetic is individually rounded fp64 operations unless stated as an fma chain; every fma chain multiplies two float32 values, so
+ * its products are exact and every step is ONE rounding of acc + a b.  expn is the reward's (expn(a) ~ exp(-a)), H the double nearest
+ * 0.5 ln(2 pi).
+ *
+ * MINIBATCH.  idx int32 [M] in device memory, 1 <= M <= max_m <= T nenv; a value is s = t nenv + env, an index into the rollout's stores;
+ *   position p of the minibatch is sample idx[p].  Rows are gathered through the strides of the stores of the sources of role OBS,
+ *   ACTION and LOGP (and VALUE must exist with a critic), of ADVN and -- with a critic -- of RET; a call is refused when one is missing.
+ *   A position whose idx lies outside [0, T nenv) is VOID, and so are the positions from M up to the next multiple of the chunk.  A void
+ *   position loads +0.0 rows; every kept activation, every delta row and every head value of a void position is +0.0 BY A SELECT AT THE
+ *   STORE, never a product with zero (a weight of +inf makes NaN of a void position's own sums, which go nowhere).  Void positions inside
+ *   [0, M) are counted in the statistics, and 1 / M is the divisor whatever their number.
+ * FORWARD.  POLICY ROWS' INPUT (the normalisation as bound at the call) and LAYER on the gathered observation row: h_0 is the normalised
+ *   input, h_l layer l's float32 output, bit for bit what phys_batch_policy writes for that row with the same weights.  Every h_l,
+ *   l = 0 .. L, is KEPT in a device store for the backward passes.
+ * HEAD, ACTOR (A its output width, mu = h_L, a the stored action, ls = log_std as bound by phys_batch_policy_bind_sample and read at the
+ *   call; all float32 read as doubles):
+ *     is_j = expn(ls_j);  d_j = (a_j - mu_j) * is_j;  q = sum_j d_j * d_j and L = sum_j ls_j, sequential in j from +0.0
+ *     logp = (-0.5 * q - L) - A * H;  lr = logp - logp_old;  ratio = expn(-lr);  adv = ADVN[s]
+ *     s1 = ratio * adv;  rc = ratio < lo ? lo : ratio > hi ? hi : ratio  (lo = 1 - eps and hi = 1 + eps rounded once on the host)
+ *     s2 = rc * adv;  active = !(s2 < s1);  g = active ? -s1 : +0.0
+ *     gmu_j = (float)(g * (d_j * is_j));  gls_j = g * (d_j * d_j - 1), a double kept per position
+ *   per-position statistics, doubles: policy loss -(active ? s1 : s2); kl = (ratio - 1) - lr; clipped = |ratio - 1| > eps ? 1 : 0.
+ * HEAD, CRITIC (network 1, whose last layer has ONE unit; v = h_L[0]): dv = v - RET[s]; gv = (float)(c_v * dv); per-position value loss
+ *   (0.5 * dv) * dv.  A clipped value loss is out of scope.
+ * BACKWARD, per network, from the last layer down; g_L is gmu (actor) or gv (critic).  delta_l[u] = (float) D(act_l, g_l[u], h_l[u]):
+ *     IDENTITY g;  RELU h > 0 ? g : +0.0;  TANH g * (1 - h * h);  ELU h > 0 ? g : g * (h + 1)
+ *   For l > 1, g_{l-1}[k] is the fma chain from +0.0 over u ascending to out_l rounded up to 4 (+0.0 in the padding):
+ *   acc = fma((double) delta_l[u], (double) W_l[u][k], acc); g stays a double until D has been applied.  The input's gradient is not formed.
+ * WEIGHT GRADIENTS.  The positions are cut into CHUNKS of `chunk` consecutive positions, a multiple of 16 in 16 .. 4096 set at
+ *   configuration: it is part of the definition, for it fixes the order.  P[c][u][k] is the fma chain from +0.0 over p ascending within
+ *   chunk c: acc = fma((double) delta_l[p][u], (double) h_{l-1}[p][k], acc); the bias' partial is the same chain with h = 1 (column
+ *   k = in).  dW_l[u][k] = (float)((sum_c P[c][u][k]) * invM), the sum over c sequential and ascending from +0.0, invM = 1 / M rounded
+ *   once on the host; db_l alike.
+ * LOG_STD AND STATISTICS.  reduce(x[M]) is the rollout's: padded with +0.0 to a multiple of 64, every block of 64 consecutive positions
+ *   summed by wv::wave_sum's tree, the block sums added in block order from +0.0.  dls_j = (float)(reduce(gls_j) * invM - c_ent).  The
+ *   statistics are eight doubles: reduce(policy loss) * invM, the same of the value loss (+0.0 without a critic), of kl, of clipped, the
+ *   entropy L + A * (0.5 + H), the count of void positions in [0, M), M, a spare +0.0.
+ * A NaN of one sample stays in that sample's activations and deltas; it reaches the sums that sample enters -- every weight gradient its
+ *   chunk's partial enters, and the statistics -- and no other sample's rows.
+ *
+ *   phys_batch_grad_configure   needs a configured policy and rollout (reconfiguring either releases the gradient rows).  Allocates the
+ *                               stores for max_m positions and max_m / chunk partials, and makes the TRANSPOSED PACKING of every layer
+ *                               already loaded: per block of 16 k and u-step of 4 the 64 words W[4 ustep + (l >> 4)][16 block + (l & 15)]
+ *                               in lane order, zero-padded.  While gradient rows are configured phys_batch_policy_load (and _load_host)
+ *                               make it too, on the same stream.  max_m 0 releases.  Refuses a chunk outside the limits, coefficients
+ *                               that are not finite or negative, a critic whose last layer is wider than 1.
+ *   phys_batch_grad_bind        a caller's float32 tensors for a layer's dW ([out][in], dw_row_stride elements apart, as
+ *                               torch.nn.Linear.weight.grad) and db; both NULL: the batch's own again.  phys_batch_grad_bind_log_std: the same
+ *                               for log_std's gradient [A].
+ *   phys_batch_grad             the launches (forward + head, backward deltas -- where a network has more than one layer --, weight
+ *                               partials, reduce, statistics) on `stream`; no host synchronisation.  Refused when a layer was never
+ *                               loaded, when m > max_m, when a needed source or the sample's log_std is missing.
+ *   phys_batch_grad_stats       the eight doubles to the host; waits for the streams.
+ *   phys_batch_grad_download    what = PHYS_GRAD_DW [out][in], _DB [out], _DLS [A] (bound or own), _ACT: the kept activations h_layer
+ *                               [m][width], layer 0 .. L; _DELTA [m][out]; _PARTIAL: the fp64 partials [chunks of the last call][out][in + 1];
+ *                               _PACKT: the transposed packing.  Dense host memory; m is the last call's.  phys_batch_grad_count: the
+ *                               elements such a download writes (-1: no such thing).
+ *   phys_batch_debug_grad_launches  diagnostics: the launches so far of the five kernels and of the transposed packing.
+ *   phys_batch_debug_grad_mask  measurement aid: bit k set = a call makes launch k (default 31, all five); the stores keep what the last
+ *                               full call left, so one launch alone can be timed (tools/grad_rate.py). */
+enum { PHYS_GRAD_DW = 0, PHYS_GRAD_DB = 1, PHYS_GRAD_DLS = 2, PHYS_GRAD_ACT = 3, PHYS_GRAD_DELTA = 4, PHYS_GRAD_PARTIAL = 5, PHYS_GRAD_PACKT = 6 };
+#define PHYS_GRAD_MINCHUNK 16
+#define PHYS_GRAD_MAXCHUNK 4096
+#define PHYS_GRAD_NSTATS 8
+int phys_batch_grad_configure(phys_batch_t *b, int max_m, int chunk, double clip_eps, double c_v, double c_ent);   /* max_m 0: release */
+int phys_batch_grad_bind(phys_batch_t *b, int net, int layer, void *dw_ptr, long long dw_row_stride, void *db_ptr);   /* NULL: the batch's own */
+int phys_batch_grad_bind_log_std(phys_batch_t *b, void *ptr);   /* NULL: the batch's own */
+int phys_batch_grad(phys_batch_t *b, const void *idx_ptr, int m, void *stream);
+int phys_batch_grad_stats(phys_batch_t *b, double *stats /*[8]*/);
+long long phys_batch_grad_count(const phys_batch_t *b, int what, int net, int layer);
+int phys_batch_grad_download(phys_batch_t *b, int what, int net, int layer, void *host);
+int phys_batch_debug_grad_launches(const phys_batch_t *b, long long *launches /*[6]*/);
+int phys_batch_debug_grad_mask(phys_batch_t *b, unsigned mask);
+
 /* measurement aid: on = every substep of a fused launch evaluates every output (IMU sensors, body quaternions), although
  * only the last substep's values can be read; off (default) = those are formed by the substeps whose values are read */
 int phys_batch_set_all_outputs_every_substep(phys_batch_t *b, int on);
