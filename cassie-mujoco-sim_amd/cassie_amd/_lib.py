@@ -294,6 +294,18 @@ def _declare(L):
         L.phys_batch_grad_download.argtypes = [vp, c.c_int, c.c_int, c.c_int, vp]
         L.phys_batch_debug_grad_launches.argtypes = [vp, c.POINTER(c.c_longlong)]
         L.phys_batch_debug_grad_mask.argtypes = [vp, c.c_uint]
+    if hasattr(L, "phys_batch_opt_step"):   # (likewise)
+        L.phys_batch_opt_configure.argtypes = [vp, c.c_double, c.c_double, c.c_double, c.c_double]
+        L.phys_batch_opt_bind_param.argtypes = [vp, c.c_int, c.c_int, vp, c.c_longlong, vp]
+        L.phys_batch_opt_bind_log_std.argtypes = [vp, vp]
+        L.phys_batch_opt_step.argtypes = [vp, c.c_double, vp]
+        L.phys_batch_opt_stats.argtypes = [vp, vp]
+        L.phys_batch_opt_count.argtypes = [vp, c.c_int, c.c_int, c.c_int]
+        L.phys_batch_opt_count.restype = c.c_longlong
+        L.phys_batch_opt_download.argtypes = [vp, c.c_int, c.c_int, c.c_int, vp]
+        L.phys_batch_opt_upload.argtypes = [vp, c.c_int, c.c_int, c.c_int, vp]
+        L.phys_batch_debug_opt_launches.argtypes = [vp, c.POINTER(c.c_longlong)]
+        L.phys_batch_debug_opt_mask.argtypes = [vp, c.c_uint]
     if hasattr(L, "phys_batch_step_sums_enable"):   # (likewise)
         L.phys_batch_step_sums_enable.argtypes = [vp, c.c_int]
     if hasattr(L, "phys_batch_download_progress"):   # (absent from older variant builds selected with CASSIE_LIB)

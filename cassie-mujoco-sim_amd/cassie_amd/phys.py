@@ -355,6 +355,11 @@ def ro_srcs(srcs):
 GRAD_MINCHUNK, GRAD_MAXCHUNK, GRAD_NSTATS = 16, 4096, 8
 GRAD_STATS = ("policy_loss", "value_loss", "kl", "clipped", "entropy", "void", "m", "spare")
 
+# optimiser rows: what Batch.opt_download / opt_upload name (PHYS_OPT_* in cassie_phys.h), the NORM's segment, the statistics and their names
+(OPT_M_W, OPT_M_B, OPT_V_W, OPT_V_B, OPT_M_LS, OPT_V_LS, OPT_SCALARS, OPT_PARTIALS) = range(8)
+OPT_SEG, OPT_NSTATS = 256, 8
+OPT_STATS = ("norm", "scale", "skip", "t", "skipped", "lr", "p1", "p2")
+
 
 # per-env physical parameters (CM_P_* in cm_model.h): what Batch.randomize takes
 (P_BODY_MASS, P_BODY_IPOS, P_BODY_INERTIA, P_DOF_DAMPING, P_GEOM_FRICTION,
@@ -1504,6 +1509,75 @@ class Batch:
         """Diagnostics: the launches so far of forward, backward, partials, reduce, statistics and the transposed packing."""
         a = (ctypes.c_longlong * 6)()
         lib().phys_batch_debug_grad_launches(self._h, a)
+        return tuple(a)
+
+    # ---- optimiser rows: the global-norm clip, an Adam step and the packed weights rewritten in place (phys_batch_opt_*) ----
+    def configure_opt(self, beta1=0.9, beta2=0.999, eps=1e-8, max_norm=float("inf"), release=False):
+        """Adam with a clip of the global gradient norm at max_norm (+inf: none) on every weight, bias and log_std the gradient rows
+        differentiate (release: drop it).  Needs configure_grad; the moments start at +0.0, t at 0; waits for the batch's streams."""
+        args = (0.0, 0.0, 0.0, 0.0) if release else (float(beta1), float(beta2), float(eps), float(max_norm))
+        if lib().phys_batch_opt_configure(self._h, *args) != 0:
+            self._obs_fail("configure_opt")
+
+    def bind_opt_param(self, net, layer, w_ptr, w_row_stride, b_ptr):
+        """The master tensors of a layer, float32 in device memory and writable: W [out][in], `w_row_stride` elements apart, as
+        torch.nn.Linear.weight, and b [out].  They must hold what load_policy was last given."""
+        if lib().phys_batch_opt_bind_param(self._h, int(net), int(layer), w_ptr, int(w_row_stride), b_ptr) != 0:
+            self._obs_fail("bind_opt_param")
+
+    def bind_opt_log_std(self, device_ptr):
+        """The master log_std [A]: the very tensor bind_policy_sample names."""
+        if lib().phys_batch_opt_bind_log_std(self._h, device_ptr) != 0:
+            self._obs_fail("bind_opt_log_std")
+
+    def opt_step(self, lr, stream=None):
+        """Three launches on `stream` (default: the batch's own) behind grad(): the norm and the clip coefficient, the Adam step, and every
+        new parameter into its master tensor, the policy's packed weights and the transposed packing -- policy() and the next grad()
+        follow with no load_policy.  A norm that is not finite skips the call on the device.  No host synchronisation."""
+        if lib().phys_batch_opt_step(self._h, float(lr), stream) != 0:
+            self._obs_fail("opt_step")
+
+    def opt_stats(self):
+        """The eight statistics of the last opt_step, by name (OPT_STATS), and as an array under "all" (waits for the batch's streams)."""
+        out = np.zeros(OPT_NSTATS, dtype=np.float64)
+        if lib().phys_batch_opt_stats(self._h, out.ctypes.data) != 0:
+            self._obs_fail("opt_stats")
+        d = dict(zip(OPT_STATS, out))
+        d["all"] = out
+        return d
+
+    def opt_count(self, what, net=0, layer=0):
+        """The elements opt_download(what, net, layer) returns (-1: no such thing)."""
+        return int(lib().phys_batch_opt_count(self._h, int(what), int(net), int(layer)))
+
+    def opt_download(self, what, net=0, layer=0):
+        """OPT_M_W / _V_W [out][in], OPT_M_B / _V_B [out] of a layer, OPT_M_LS / _V_LS [A]: the moments, float32; OPT_SCALARS: (t, p1, p2,
+        skipped); OPT_PARTIALS: the norm's partials of the last call; float64.  A flat array (waits for the batch's streams)."""
+        n = self.opt_count(what, net, layer)
+        if n < 0:
+            raise ValueError("opt_download: no such network, layer or kind")
+        out = np.zeros(n, dtype=np.float64 if what in (OPT_SCALARS, OPT_PARTIALS) else np.float32)
+        if n and lib().phys_batch_opt_download(self._h, int(what), int(net), int(layer), out.ctypes.data) != 0:
+            self._obs_fail("opt_download")
+        return out
+
+    def opt_upload(self, what, values, net=0, layer=0):
+        """What opt_download(what, net, layer) gave, back into the batch: a checkpoint restored bit for bit."""
+        n = self.opt_count(what, net, layer)
+        a = np.ascontiguousarray(values, dtype=np.float64 if what == OPT_SCALARS else np.float32).reshape(-1)
+        if n < 0 or what == OPT_PARTIALS or a.size != n:
+            raise ValueError("opt_upload: no such network, layer or kind, or not its count of elements")
+        if n and lib().phys_batch_opt_upload(self._h, int(what), int(net), int(layer), a.ctypes.data) != 0:
+            self._obs_fail("opt_upload")
+
+    def opt_launch_mask(self, mask=7):
+        """Measurement aid: bit k set = opt_step() makes launch k (squares, scalars, step); 7: all, the default."""
+        lib().phys_batch_debug_opt_mask(self._h, int(mask))
+
+    def opt_launches(self):
+        """Diagnostics: the launches so far of the norm's squares, the scalars and the step."""
+        a = (ctypes.c_longlong * 3)()
+        lib().phys_batch_debug_opt_launches(self._h, a)
         return tuple(a)
 
     def set_pd_mode(self, on=True):

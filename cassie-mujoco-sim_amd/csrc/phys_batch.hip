@@ -216,6 +216,13 @@ struct phys_batch {
     int grad_last_m = 0;            /* the m of the last phys_batch_grad (what the downloads of activations and deltas hold) */
     unsigned grad_mask = 31u;       /* measurement aid (phys_batch_debug_grad_mask): which of the five launches a call makes */
     long long grad_launches[6] = {0, 0, 0, 0, 0, 0};  /* forward, backward, partials, reduce, statistics, transposed packings */
+    /* optimiser rows (phys_batch_opt_configure): the record (opt.on 0: not configured; the master tensors are the caller's), the moments
+     * (m [Q], then v [Q]), the NORM's partials with the doubles behind them.  No stepping launch reads any of it */
+    ck::OptCfg opt = {};
+    DevBuf<float> d_opt_mom;
+    DevBuf<double> d_opt_part;
+    unsigned opt_mask = 7u;                           /* measurement aid (phys_batch_debug_opt_mask): which of the three launches a call makes */
+    long long opt_launches[3] = {0, 0, 0};            /* squares, scalars, step */
 };
 
 static bool hip_ok(hipError_t e, const char *what) {
@@ -2525,7 +2532,12 @@ static ck::GradCfg grad_cfg_of(const phys_batch *b) {
     c.stats = b->d_grad_pos ? b->d_grad_pos + (size_t)c.pos_doubles : nullptr;
     return c;
 }
+static void opt_release(phys_batch *b) {
+    b->opt = {};
+    b->d_opt_mom.reset(); b->d_opt_part.reset();
+}
 static void grad_release(phys_batch *b) {
+    opt_release(b);              /* (the optimiser rows are laid out for the gradient rows that go away) */
     b->grad = {};
     b->grad_last_m = 0;
     b->d_grad_act.reset(); b->d_grad_delta.reset(); b->d_grad_packt.reset(); b->d_grad_own.reset(); b->d_grad_part.reset(); b->d_grad_pos.reset();
@@ -2661,6 +2673,105 @@ int phys_batch_debug_grad_mask(phys_batch_t *b, unsigned mask) {
 int phys_batch_debug_grad_launches(const phys_batch_t *b, long long *launches) {
     if (!b) return -1;
     if (launches) for (int k = 0; k < 6; ++k) launches[k] = b->grad_launches[k];
+    return 0;
+}
+
+/* ------------------------------------------------ optimiser rows ---- */
+static_assert(PHYS_OPT_M_W == ck::OPT_M_W && PHYS_OPT_M_B == ck::OPT_M_B && PHYS_OPT_V_W == ck::OPT_V_W && PHYS_OPT_V_B == ck::OPT_V_B &&
+              PHYS_OPT_M_LS == ck::OPT_M_LS && PHYS_OPT_V_LS == ck::OPT_V_LS && PHYS_OPT_SCALARS == ck::OPT_SCALARS &&
+              PHYS_OPT_PARTIALS == ck::OPT_PARTIALS && PHYS_OPT_SEG == ck::OPT_SEG && PHYS_OPT_NSTATS == ck::OPT_NSTATS,
+              "the header's numbers are opt_kernels.h's");
+/* the record of a launch: what was configured and bound, with the pointers into the batch's buffers */
+static ck::OptCfg opt_cfg_of(const phys_batch *b) {
+    ck::OptCfg c = b->opt;
+    c.mom = b->d_opt_mom; c.part = b->d_opt_part;
+    c.sc = b->d_opt_part ? b->d_opt_part + (size_t)c.nseg : nullptr;
+    return c;
+}
+int phys_batch_opt_configure(phys_batch_t *b, double beta1, double beta2, double eps, double max_norm) {
+    if (!b) return refuse("phys_batch_opt_configure", ck::OPT_NEEDS);
+    ck::OptCfg cfg;
+    if (const char *why = ck::opt_configure(b->grad, b->policy, beta1, beta2, eps, max_norm, cfg)) return refuse("phys_batch_opt_configure", why);
+    (void)hipSetDevice(b->device);
+    if (!quiesce(b)) return -1;  /* (launches in flight may be using the moments that go away) */
+    if (!cfg.on) { opt_release(b); return 0; }
+    DevBuf<float> mom;
+    DevBuf<double> part;
+    if (!mom.alloc(2 * (size_t)cfg.Q, true, "optimiser moments") || !part.alloc((size_t)cfg.nseg + ck::OPT_SC_COUNT, true, "optimiser partials")) return -1;
+    double sc[ck::OPT_SC_COUNT];
+    ck::opt_initial_scalars(sc);
+    if (!hip_ok(hipMemcpy(part.get() + (size_t)cfg.nseg, sc, sizeof sc, hipMemcpyHostToDevice), "optimiser scalars upload")) return -1;
+    opt_release(b);
+    b->d_opt_mom = std::move(mom); b->d_opt_part = std::move(part);
+    b->opt = cfg;   /* (nothing bound) */
+    return 0;
+}
+int phys_batch_opt_bind_param(phys_batch_t *b, int net, int layer, void *w_ptr, long long w_row_stride, void *b_ptr) {
+    if (!b) { phys_set_last_error("phys_batch_opt_bind_param: no batch"); return -1; }
+    if (const char *why = ck::check_opt_bind_param(b->opt, b->policy, net, layer, w_ptr, w_row_stride, b_ptr)) return refuse("phys_batch_opt_bind_param", why);
+    const int s = ck::grad_slot(b->grad, net, layer);
+    b->opt.w[s] = (float *)w_ptr; b->opt.sw[s] = w_row_stride; b->opt.b[s] = (float *)b_ptr;
+    return 0;
+}
+int phys_batch_opt_bind_log_std(phys_batch_t *b, void *ptr) {
+    if (!b) { phys_set_last_error("phys_batch_opt_bind_log_std: no batch"); return -1; }
+    if (const char *why = ck::check_opt_bind_log_std(b->opt, b->policy, ptr)) return refuse("phys_batch_opt_bind_log_std", why);
+    b->opt.ls = (float *)ptr;
+    return 0;
+}
+int phys_batch_opt_step(phys_batch_t *b, double lr, void *stream) {
+    if (!b) { phys_set_last_error("phys_batch_opt_step: no batch"); return -1; }
+    const ck::OptCfg c = opt_cfg_of(b);
+    const ck::GradCfg g = grad_cfg_of(b);
+    const ck::PolicyCfg p = policy_cfg_of(b);
+    if (const char *why = ck::check_opt_step(c, g, p, lr, b->grad_last_m > 0)) return refuse("phys_batch_opt_step", why);
+    (void)hipSetDevice(b->device);
+    hipStream_t s = launch_stream(b, stream);
+    const ck::OptIO io = ck::make_opt_io(c, g, p, lr);
+    const dim3 wave(WV_WAVE);
+    const unsigned mask = b->opt_mask;
+    if (mask & 1u) { hipLaunchKernelGGL(ck::cassie_opt_sq_kernel, dim3((unsigned)ck::opt_sq_grid(io)), wave, 0, s, io); ++b->opt_launches[0]; }
+    if (mask & 2u) { hipLaunchKernelGGL(ck::cassie_opt_scalars_kernel, dim3(1), wave, 0, s, io); ++b->opt_launches[1]; }
+    if (mask & 4u) { hipLaunchKernelGGL(ck::cassie_opt_step_kernel, dim3((unsigned)ck::opt_step_grid(io)), wave, 0, s, io); ++b->opt_launches[2]; }
+    return hip_ok(hipGetLastError(), "optimiser launches") ? 0 : -1;
+}
+int phys_batch_opt_stats(phys_batch_t *b, double *stats) {
+    if (!b || !stats || !b->opt.on || !b->d_opt_part) return refuse("phys_batch_opt_stats", ck::OPT_NOT_CONFIGURED);
+    (void)hipSetDevice(b->device);
+    return quiesce(b) && hip_ok(hipMemcpy(stats, b->d_opt_part + (size_t)b->opt.nseg, sizeof(double) * ck::OPT_NSTATS, hipMemcpyDeviceToHost), "optimiser stats download") ? 0 : -1;
+}
+long long phys_batch_opt_count(const phys_batch_t *b, int what, int net, int layer) {
+    if (!b) return -1;
+    ck::OptRegion R;
+    return ck::opt_region(b->opt, b->grad, b->policy, what, net, layer, R) ? R.rows * R.width : -1;
+}
+/* a download (up false) or an upload of a region: dense host rows against the region's pitch */
+static int opt_transfer(phys_batch_t *b, const char *fn, int what, int net, int layer, void *host, bool up) {
+    if (!b || !host || !b->opt.on) return refuse(fn, ck::OPT_NOT_CONFIGURED);
+    ck::OptRegion R;
+    if (!ck::opt_region(opt_cfg_of(b), b->grad, b->policy, what, net, layer, R) || !R.ptr || (up && what == ck::OPT_PARTIALS))
+        return refuse(fn, "no such network, layer or kind (PHYS_OPT_*)");
+    (void)hipSetDevice(b->device);
+    if (!quiesce(b)) return -1;
+    const size_t e = R.doubles ? sizeof(double) : sizeof(float);
+    const hipError_t rc = up ? hipMemcpy2D(R.ptr, e * (size_t)R.pitch, host, e * (size_t)R.width, e * (size_t)R.width, (size_t)R.rows, hipMemcpyHostToDevice)
+                             : hipMemcpy2D(host, e * (size_t)R.width, R.ptr, e * (size_t)R.pitch, e * (size_t)R.width, (size_t)R.rows, hipMemcpyDeviceToHost);
+    return hip_ok(rc, up ? "optimiser upload" : "optimiser download") ? 0 : -1;
+}
+int phys_batch_opt_download(phys_batch_t *b, int what, int net, int layer, void *host) {
+    return opt_transfer(b, "phys_batch_opt_download", what, net, layer, host, false);
+}
+int phys_batch_opt_upload(phys_batch_t *b, int what, int net, int layer, const void *host) {
+    return opt_transfer(b, "phys_batch_opt_upload", what, net, layer, (void *)host, true);
+}
+int phys_batch_debug_opt_mask(phys_batch_t *b, unsigned mask) {
+    if (!b) return -1;
+    b->opt_mask = mask & 7u;
+    return 0;
+}
+int phys_batch_debug_opt_launches(const phys_batch_t *b, long long *launches) {
+    if (!b) return -1;
+    if (launches) for (int k = 0; k < 3; ++k) launches[k] = b->opt_launches[k];
     return 0;
 }
 

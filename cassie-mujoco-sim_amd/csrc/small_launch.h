@@ -1,12 +1,12 @@
 /*
- * small_launch.h -- how the kernels around the step kernel (small_kernels.h, surface_kernels.h, depth_kernel.h, ray_kernel.h, episode_kernels.h, probe_kernels.h, obs_kernels.h, reward_kernels.h, act_kernels.h, task_kernels.h, event_kernels.h, policy_kernels.h, rollout_kernels.h, grad_kernels.h) are
+ * small_launch.h -- how the kernels around the step kernel (small_kernels.h, surface_kernels.h, depth_kernel.h, ray_kernel.h, episode_kernels.h, probe_kernels.h, obs_kernels.h, reward_kernels.h, act_kernels.h, task_kernels.h, event_kernels.h, policy_kernels.h, rollout_kernels.h, grad_kernels.h, opt_kernels.h) are
  * launched: the records a kernel's arguments are built from, one builder per kernel that returns its filled argument struct for an env
  * range, the grid of every launch, and the checks of what a caller configures, each returning the message of its refusal (null: fine).
  * Pure host code, no HIP runtime calls, in the spirit of step_policy.h: the launcher (phys_batch.hip) keeps the records in the batch,
  * prefixes a message with its entry point's name and launches what a builder returns on the grid given here; the wave emulator's entry
  * points (tests/emu) fill the same records from their arguments and go through the same builders, grids and checks, so a CPU test of
  * one of these kernels also runs the launcher's refusals, grid and choice of kernel (tests/test_small_launch.py pins them one by one).
- * No field of ScanIO, DepthIO, RayIO, EpisodeIO, ResetIO, DeriveIO, SetConstIO, StateIO, ProbeIO, ObsIO, RewardIO, ActIO, TaskIO, EventIO, PolicyIO, PolicyPackIO, RolloutRecIO, RolloutFinIO, RolloutNormIO, GradIO or GradPackIO is assigned anywhere else.
+ * No field of ScanIO, DepthIO, RayIO, EpisodeIO, ResetIO, DeriveIO, SetConstIO, StateIO, ProbeIO, ObsIO, RewardIO, ActIO, TaskIO, EventIO, PolicyIO, PolicyPackIO, RolloutRecIO, RolloutFinIO, RolloutNormIO, GradIO, GradPackIO or OptIO is assigned anywhere else.
  */
 #ifndef CASSIE_SMALL_LAUNCH_H
 #define CASSIE_SMALL_LAUNCH_H
@@ -19,6 +19,7 @@
 #include "episode_kernels.h"
 #include "event_kernels.h"
 #include "grad_kernels.h"
+#include "opt_kernels.h"
 #include "obs_kernels.h"
 #include "policy_kernels.h"
 #include "probe_kernels.h"
@@ -1555,6 +1556,121 @@ inline GradPackIO make_grad_pack_io(const GradCfg &c, const PolicyCfg &p, int ne
 inline int grad_pack_grid(const GradPackIO &io) {
     const long long w = ((long long)io.in16 * io.u4 + WV_WAVE - 1) / WV_WAVE;
     return w < GRAD_PACK_GRID ? (int)w : GRAD_PACK_GRID;
+}
+
+/* ---- the optimiser rows ---- */
+
+/* the optimiser (phys_batch_opt_configure; on 0: not configured): the betas with 1 - beta rounded once, eps, max_norm (+inf: no clipping);
+ * the parameters of the flat order and the segments of the NORM; the master tensors the caller bound (null: not yet).  Then what the
+ * launcher names once a kernel reads them: the moments (m [Q], then v [Q]), the segments' partials and the doubles */
+struct OptCfg {
+    int on, nseg;
+    double beta1, beta2, omb1, omb2, eps, max_norm;
+    long long Q;
+    float *w[GRAD_MAXSLOTS]; long long sw[GRAD_MAXSLOTS]; float *b[GRAD_MAXSLOTS]; float *ls;
+    float *mom; double *part, *sc;
+};
+constexpr const char *OPT_NOT_CONFIGURED = "not configured (phys_batch_opt_configure first)";
+constexpr const char *OPT_NEEDS = "the optimiser needs configured gradient rows (phys_batch_grad_configure first)";
+/* the release form of phys_batch_opt_configure: eps 0 and max_norm 0 */
+inline bool opt_is_release(double eps, double max_norm) { return eps == 0.0 && max_norm == 0.0; }
+/* the first parameter of slot s in the flat order (s = nslots: log_std's first) */
+inline long long opt_par0(const GradCfg &g, const PolicyCfg &p, int s) {
+    long long par = 0;
+    for (int k = 0; k < s; ++k) { const PolicyLayer &L = p.net[g.slot_net[k]].layer[g.slot_layer[k]]; par += (long long)L.out * (L.in + 1); }
+    return par;
+}
+/* the optimiser's configuration: checks the caller's numbers and fills c but for what is bound or named later.  The release form is
+ * accepted and leaves c empty: the launcher releases what it holds.  The emulator goes through the same */
+inline const char *opt_configure(const GradCfg &g, const PolicyCfg &p, double beta1, double beta2, double eps, double max_norm, OptCfg &c) {
+    c = {};
+    if (opt_is_release(eps, max_norm)) return nullptr;
+    if (g.max_m < 1 || p.nnets < 1) return OPT_NEEDS;
+    if (!(beta1 >= 0.0 && beta1 < 1.0)) return "beta1 lies in [0, 1)";
+    if (!(beta2 >= 0.0 && beta2 < 1.0)) return "beta2 lies in [0, 1)";
+    if (!(eps > 0.0 && eps < INFINITY)) return "eps is finite and > 0";
+    if (!(max_norm > 0.0)) return "max_norm is > 0 (+inf: no clipping)";
+    c.on = 1; c.beta1 = beta1; c.beta2 = beta2; c.omb1 = 1.0 - beta1; c.omb2 = 1.0 - beta2; c.eps = eps; c.max_norm = max_norm;
+    c.Q = opt_par0(g, p, g.nslots) + g.A;
+    c.nseg = (int)((c.Q + OPT_SEG - 1) / OPT_SEG);
+    return nullptr;
+}
+/* what phys_batch_opt_bind_param refuses */
+inline const char *check_opt_bind_param(const OptCfg &c, const PolicyCfg &p, int net, int layer, const void *w, long long w_row_stride, const void *b) {
+    if (!c.on) return OPT_NOT_CONFIGURED;
+    if (net < 0 || net >= p.nnets || layer < 0 || layer >= p.net[net].nlayers) return "no such network or layer";
+    if (!w || !b) return "a layer's master W and b are both needed";
+    if (w_row_stride < p.net[net].layer[layer].in) return "a W row stride of at least the layer's in";
+    return nullptr;
+}
+constexpr const char *OPT_LS_MISMATCH = "the log_std pointer must be the one phys_batch_policy_bind_sample names";
+inline const char *check_opt_bind_log_std(const OptCfg &c, const PolicyCfg &p, const void *ptr) {
+    if (!c.on) return OPT_NOT_CONFIGURED;
+    if (!ptr || ptr != (const void *)p.log_std) return OPT_LS_MISMATCH;
+    return nullptr;
+}
+/* what a step call refuses.  grad_called: whether a phys_batch_grad call has been made since the gradient rows were configured */
+inline const char *check_opt_step(const OptCfg &c, const GradCfg &g, const PolicyCfg &p, double lr, bool grad_called) {
+    if (!c.on || !c.mom || !c.part || !c.sc) return OPT_NOT_CONFIGURED;
+    if (g.max_m < 1 || !g.packt || !g.own || p.nnets < 1 || !p.packed) return OPT_NEEDS;
+    for (int s = 0; s < g.nslots; ++s) if (!c.w[s] || !c.b[s]) return "a master tensor is not bound (phys_batch_opt_bind_param for every layer first)";
+    if (!c.ls) return "the master log_std is not bound (phys_batch_opt_bind_log_std first)";
+    if (c.ls != p.log_std) return OPT_LS_MISMATCH;
+    for (int s = 0; s < g.nslots; ++s)
+        if (!(p.loaded & policy_layer_bit(g.slot_net[s], g.slot_layer[s]))) return "a layer was never loaded (phys_batch_policy_load first: the packings' padding comes from it)";
+    if (!(lr >= 0.0 && lr < INFINITY)) return "lr is finite and >= 0";
+    if (!grad_called) return "no gradient yet (phys_batch_grad first)";
+    return nullptr;
+}
+/* the three kernels' (after check_opt_step) */
+inline OptIO make_opt_io(const OptCfg &c, const GradCfg &g, const PolicyCfg &p, double lr) {
+    OptIO io = zeroed<OptIO>();
+    io.nslots = g.nslots; io.A = g.A; io.nseg = c.nseg; io.Q = c.Q;
+    long long job = 0, par = 0;
+    for (int s = 0; s < g.nslots; ++s) {
+        const int net = g.slot_net[s], layer = g.slot_layer[s];
+        const PolicyLayer &L = p.net[net].layer[layer];
+        OptSlot &S = io.s[s];
+        S.gw = g.dw[s] ? g.dw[s] : g.own + g.own_w[s]; S.sgw = g.dw[s] ? g.sdw[s] : L.in; S.gb = g.db[s] ? g.db[s] : g.own + g.own_b[s];
+        S.w = c.w[s]; S.sw = c.sw[s]; S.b = c.b[s];
+        S.pw = p.packed + L.w_off; S.pb = p.packed + L.b_off; S.pt = g.packt + g.g[net].t_off[layer];
+        S.in = L.in; S.out = L.out; S.k4 = L.k4; S.u4 = (L.out + 3) & ~3;
+        S.par0 = par; S.job0 = job;
+        par += (long long)L.out * (L.in + 1);
+        job += (long long)(L.out16 >> 4) * ((L.in + 16) >> 4);
+    }
+    io.tiles = job; io.njobs = job + (g.A + WV_WAVE - 1) / WV_WAVE;
+    io.gls = g.dls ? g.dls : g.own + g.own_ls; io.ls = c.ls;
+    io.m = c.mom; io.v = c.mom + c.Q; io.part = c.part; io.sc = c.sc;
+    io.beta1 = c.beta1; io.beta2 = c.beta2; io.omb1 = c.omb1; io.omb2 = c.omb2; io.eps = c.eps; io.max_norm = c.max_norm; io.lr = lr;
+    return io;
+}
+inline int opt_sq_grid(const OptIO &io) { return io.nseg < OPT_SQ_GRID ? io.nseg : OPT_SQ_GRID; }
+inline int opt_step_grid(const OptIO &io) { return io.njobs < OPT_STEP_GRID ? (int)io.njobs : OPT_STEP_GRID; }
+/* the doubles at configuration: t = 0, p1 = p2 = 1, nothing skipped, everything else +0.0 */
+inline void opt_initial_scalars(double *sc) {
+    for (int k = 0; k < OPT_SC_COUNT; ++k) sc[k] = 0.0;
+    sc[OPT_SC_P1] = sc[OPT_SC_P2] = 1.0; sc[6] = sc[7] = 1.0;
+}
+/* where a thing phys_batch_opt_download / _upload names lies: rows of `width` elements, `pitch` elements apart (floats, or doubles for
+ * OPT_SCALARS and OPT_PARTIALS); false: no such thing */
+struct OptRegion { void *ptr; long long rows, width, pitch; int doubles; };
+inline bool opt_region(const OptCfg &c, const GradCfg &g, const PolicyCfg &p, int what, int net, int layer, OptRegion &R) {
+    R = {};
+    if (!c.on) return false;
+    if (what == OPT_SCALARS) { R.ptr = c.sc ? c.sc + OPT_SC_T : nullptr; R.rows = 1; R.width = R.pitch = 4; R.doubles = 1; return true; }
+    if (what == OPT_PARTIALS) { R.ptr = c.part; R.rows = 1; R.width = R.pitch = c.nseg; R.doubles = 1; return true; }
+    if (what == OPT_M_LS || what == OPT_V_LS) {
+        R.ptr = c.mom ? c.mom + (what == OPT_V_LS ? c.Q : 0) + (c.Q - g.A) : nullptr; R.rows = 1; R.width = R.pitch = g.A; return true;
+    }
+    if (what < OPT_M_W || what > OPT_V_B) return false;
+    const int s = net >= 0 && net < p.nnets && layer >= 0 && layer < p.net[net].nlayers ? grad_slot(g, net, layer) : -1;
+    if (s < 0) return false;
+    const PolicyLayer &L = p.net[net].layer[layer];
+    const bool second = what == OPT_V_W || what == OPT_V_B, bias = what == OPT_M_B || what == OPT_V_B;
+    R.ptr = c.mom ? c.mom + (second ? c.Q : 0) + opt_par0(g, p, s) + (bias ? L.in : 0) : nullptr;
+    R.rows = L.out; R.width = bias ? 1 : L.in; R.pitch = L.in + 1;
+    return true;
 }
 
 }  // namespace ck

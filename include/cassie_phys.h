@@ -1352,7 +1352,8 @@ int phys_batch_debug_rollout_launches(const phys_batch_t *b, long long *launches
 /* GRADIENT ROWS: for a minibatch of the rollout's samples, the PPO clipped-surrogate loss, the value loss and the entropy term, and their
  * gradient with respect to every weight, every bias and log_std of the policy, by FIVE launches on the caller's stream with every bit
  * defined.  The forward pass the gradient is taken through IS the one the policy acts with (POLICY ROWS); the gradients land in float32
- * tensors an optimiser takes as param.grad with no copy; the optimiser step itself stays the caller's (phys_batch_policy_load follows it).
+ * tensors an optimiser takes as param.grad with no copy; the optimiser step is the caller's (phys_batch_policy_load follows it) or
+ * OPTIMISER ROWS' below (nothing follows it).
  * The device (csrc/grad_kernels.h), the wave emulator and a numpy restatement (tests/grad_check.py) agree bit for bit.  No stepping kernel
  * is handed any of this.
  *
@@ -1429,6 +1430,76 @@ long long phys_batch_grad_count(const phys_batch_t *b, int what, int net, int la
 int phys_batch_grad_download(phys_batch_t *b, int what, int net, int layer, void *host);
 int phys_batch_debug_grad_launches(const phys_batch_t *b, long long *launches /*[6]*/);
 int phys_batch_debug_grad_mask(phys_batch_t *b, unsigned mask);
+
+/* OPTIMISER ROWS: from the gradients GRADIENT ROWS left, the global gradient norm with its clip coefficient, an Adam step on every weight,
+ * every bias and log_std, and each new float32 parameter written to the caller's master tensor, to the policy's packed weights and to the
+ * transposed packing, by THREE launches on the caller's stream with every bit defined: phys_batch_policy and the next phys_batch_grad
+ * follow on the same stream with no phys_batch_policy_load.  No float atomics, no grid-wide barrier, no kernel waits for another
+ * workgroup, no host synchronisation.  The device (csrc/opt_kernels.h), the wave emulator and a numpy restatement (tests/opt_check.py)
+ * agree bit for bit.  No stepping kernel is handed any of this.
+ *
+ * All arithmetic is individually rounded fp64 operations (add, mul, sub, div, sqrt) unless stated as an fma chain; float32 values are
+ * read as doubles; conversions to float32 round to nearest even.
+ *
+ * PARAMETERS, flat order.  The slots (network, layer) in the gradient rows' slot order; within a slot r = u (in + 1) + k with the bias at
+ *   column k = in; the A elements of log_std behind the last slot; Q the total count.  Gradients are read from where the gradient rows
+ *   write them: the caller's bound tensors, or the batch's own.
+ * NORM.  [0, Q) is cut into segments of 256 consecutive parameters (part of the definition).  In segment s lane l runs the fma chain
+ *   from +0.0 over i = 0 .. 3 ascending, acc = fma(g, g, acc) with g the gradient of parameter 256 s + 64 i + l (+0.0 past Q); g is
+ *   float32, so the product is exact.  The segment's partial is wave_sum(acc).  S = reduce(partials), the rollout's reduce: blocks of 64
+ *   by wv::wave_sum's tree, block sums in block order from +0.0.  norm = sqrt(S); finite = norm < +inf (false for a NaN);
+ *   raw = max_norm / (norm + 1e-6); scale = raw < 1 ? raw : 1 (max_norm = +inf gives scale = 1).
+ * SCALARS, device state the batch owns, doubles: t (steps taken), p1 and p2 (the running products of beta1 and beta2, from 1.0),
+ *   skipped (a count).  If !finite the call is SKIPPED: skipped += 1, and t, p1, p2 and every word of every parameter, moment and packing
+ *   stay as they are.  Otherwise t += 1; p1 = p1 * beta1; p2 = p2 * beta2; bc1 = 1 - p1; sbc2 = sqrt(1 - p2); step = lr / bc1.  There
+ *   is no pow: the host never needs to know how many calls were skipped.
+ * STEP, per parameter; m and v are the batch's own float32 moments, +0.0 at configuration; omb1 = 1 - beta1 and omb2 = 1 - beta2 are
+ *   rounded once on the host; the update uses m' and v' AS STORED, after rounding to float32:
+ *     gs = g * scale
+ *     m' = (float)(beta1 * m + omb1 * gs)
+ *     v' = (float)(beta2 * v + omb2 * (gs * gs))
+ *     den = sqrt(v') / sbc2 + eps
+ *     w' = (float)(w - (step * m') / den)
+ *   w is read from the caller's master tensor ([out][in] with a row stride and a bias [out], torch.nn.Linear's); w' goes to the master
+ *   tensor, to word (u >> 4) * 16 * k4 + (k >> 2) * 64 + (k & 3) * 16 + (u & 15) of the layer's packed weights (b_off + u for a bias) and
+ *   to the word of the transposed packing phys_batch_grad_configure describes for (u, k).  The packings' zero padding is never touched.
+ *   log_std' goes to the bound log_std tensor alone.
+ * STATISTICS, eight doubles: norm, scale, this call's skip (0 or 1), t, skipped, lr, p1, p2.
+ * Out of scope: weight decay, per-group learning rates, a KL-adaptive lr on the device, amsgrad, an all-reduce across ranks.
+ *
+ *   phys_batch_opt_configure    needs configured gradient rows (reconfiguring the policy, the rollout or the gradient rows releases the
+ *                               optimiser rows).  Allocates the moments, the partials and the scalars; moments +0.0, t = 0, p1 = p2 = 1.
+ *                               Refuses a beta outside [0, 1), an eps that is not finite or <= 0, a max_norm <= 0 or NaN (+inf: no
+ *                               clipping).  eps 0 with max_norm 0 releases.
+ *   phys_batch_opt_bind_param   the master tensors of a layer, writable: W [out][in], w_row_stride elements apart, and b [out].
+ *   phys_batch_opt_bind_log_std the master log_std [A]: it must be the pointer phys_batch_policy_bind_sample names (checked here and at
+ *                               the step).
+ *   phys_batch_opt_step         the three launches on `stream`.  Refused when a master tensor is not bound, when a layer was never loaded
+ *                               (the padding of the packings comes from the first load), when lr is not finite or negative, when no
+ *                               phys_batch_grad call has been made.  The master tensors must hold what was last loaded: after the caller
+ *                               changes them itself (a checkpoint) phys_batch_policy_load is called as before.
+ *   phys_batch_opt_stats        the eight doubles to the host; waits for the streams.
+ *   phys_batch_opt_download, _upload   what = PHYS_OPT_M_W [out][in], _M_B [out], _V_W, _V_B of a layer, _M_LS, _V_LS [A], _SCALARS
+ *                               (t, p1, p2, skipped: four doubles), and -- download only -- _PARTIALS (the NORM's partials of the last
+ *                               call, doubles).  Dense host memory.  An upload of everything a download gave restores a checkpoint bit
+ *                               for bit.  phys_batch_opt_count: the elements (-1: no such thing).
+ *   phys_batch_debug_opt_launches  diagnostics: the launches so far of the three kernels.
+ *   phys_batch_debug_opt_mask   measurement aid: bit k set = a call makes launch k (default 7, all three); the partials and the doubles keep
+ *                               what the last full call left, so one launch alone can be timed (tools/opt_rate.py). */
+enum { PHYS_OPT_M_W = 0, PHYS_OPT_M_B = 1, PHYS_OPT_V_W = 2, PHYS_OPT_V_B = 3, PHYS_OPT_M_LS = 4, PHYS_OPT_V_LS = 5, PHYS_OPT_SCALARS = 6,
+       PHYS_OPT_PARTIALS = 7 };
+#define PHYS_OPT_SEG 256
+#define PHYS_OPT_NSTATS 8
+int phys_batch_opt_configure(phys_batch_t *b, double beta1, double beta2, double eps, double max_norm);   /* eps 0, max_norm 0: release */
+int phys_batch_opt_bind_param(phys_batch_t *b, int net, int layer, void *w_ptr, long long w_row_stride, void *b_ptr);
+int phys_batch_opt_bind_log_std(phys_batch_t *b, void *ptr);
+int phys_batch_opt_step(phys_batch_t *b, double lr, void *stream);
+int phys_batch_opt_stats(phys_batch_t *b, double *stats /*[8]*/);
+long long phys_batch_opt_count(const phys_batch_t *b, int what, int net, int layer);
+int phys_batch_opt_download(phys_batch_t *b, int what, int net, int layer, void *host);
+int phys_batch_opt_upload(phys_batch_t *b, int what, int net, int layer, const void *host);
+int phys_batch_debug_opt_launches(const phys_batch_t *b, long long *launches /*[3]*/);
+int phys_batch_debug_opt_mask(phys_batch_t *b, unsigned mask);
 
 /* measurement aid: on = every substep of a fused launch evaluates every output (IMU sensors, body quaternions), although
  * only the last substep's values can be read; off (default) = those are formed by the substeps whose values are read */
