@@ -306,6 +306,19 @@ def _declare(L):
         L.phys_batch_opt_upload.argtypes = [vp, c.c_int, c.c_int, c.c_int, vp]
         L.phys_batch_debug_opt_launches.argtypes = [vp, c.POINTER(c.c_longlong)]
         L.phys_batch_debug_opt_mask.argtypes = [vp, c.c_uint]
+    if hasattr(L, "phys_batch_norm_update"):   # (likewise)
+        L.phys_batch_norm_configure.argtypes = [vp, c.c_int, c.c_int, c.c_longlong, c.c_double]
+        L.phys_batch_norm_bind_source.argtypes = [vp, vp, c.c_int, c.c_int, c.c_longlong, c.c_longlong]
+        L.phys_batch_norm_bind_output.argtypes = [vp, vp, vp]
+        L.phys_batch_norm_update.argtypes = [vp, vp]
+        L.phys_batch_norm_write.argtypes = [vp, vp]
+        L.phys_batch_norm_stats.argtypes = [vp, vp]
+        L.phys_batch_norm_count.argtypes = [vp, c.c_int]
+        L.phys_batch_norm_count.restype = c.c_longlong
+        L.phys_batch_norm_download.argtypes = [vp, c.c_int, vp]
+        L.phys_batch_norm_upload.argtypes = [vp, c.c_int, vp]
+        L.phys_batch_debug_norm_launches.argtypes = [vp, c.POINTER(c.c_longlong)]
+        L.phys_batch_debug_norm_mask.argtypes = [vp, c.c_uint]
     if hasattr(L, "phys_batch_step_sums_enable"):   # (likewise)
         L.phys_batch_step_sums_enable.argtypes = [vp, c.c_int]
     if hasattr(L, "phys_batch_download_progress"):   # (absent from older variant builds selected with CASSIE_LIB)

@@ -360,6 +360,11 @@ GRAD_STATS = ("policy_loss", "value_loss", "kl", "clipped", "entropy", "void", "
 OPT_SEG, OPT_NSTATS = 256, 8
 OPT_STATS = ("norm", "scale", "skip", "t", "skipped", "lr", "p1", "p2")
 
+# normaliser rows: what Batch.norm_download / norm_upload name (PHYS_NORM_* in cassie_phys.h), the limits, the statistics and their names
+(NORM_N, NORM_MEAN, NORM_M2, NORM_SKIPPED, NORM_EXCLUDED, NORM_MB, NORM_COUNTS, NORM_PARTIALS) = range(8)
+NORM_MINBLOCK, NORM_MAXBLOCK, NORM_MAXROWS, NORM_NSTATS = 16, 4096, 1 << 30, 8
+NORM_STATS = ("rows", "blocks", "updated", "skipped", "excluded", "calls", "n_max", "spare")
+
 
 # per-env physical parameters (CM_P_* in cm_model.h): what Batch.randomize takes
 (P_BODY_MASS, P_BODY_IPOS, P_BODY_INERTIA, P_DOF_DAMPING, P_GEOM_FRICTION,
@@ -1578,6 +1583,90 @@ class Batch:
         """Diagnostics: the launches so far of the norm's squares, the scalars and the step."""
         a = (ctypes.c_longlong * 3)()
         lib().phys_batch_debug_opt_launches(self._h, a)
+        return tuple(a)
+
+    # ---- normaliser rows: the running mean and variance of the observation columns, written where the policy reads them (phys_batch_norm_*) ----
+    def configure_norm(self, dim, block=256, max_rows=None, eps=1e-8, release=False):
+        """Running statistics of `dim` float32 columns, summed in blocks of `block` samples (part of the definition), at most `max_rows`
+        samples a call (default: the configured rollout's T steps of every env; one step without a rollout).  n, mean and m2 start at +0.0 (release: drop them).  Stays configured when the
+        policy, the rollout, the gradient rows or the optimiser rows are reconfigured; waits for the batch's streams."""
+        if max_rows is None:
+            max_rows = (self._ro[0] if getattr(self, "_ro", None) and self._ro[1] else 1) * self.nenv
+        args = (0, 0, 0, 0.0) if release else (int(dim), int(block), int(max_rows), float(eps))
+        if lib().phys_batch_norm_configure(self._h, *args) != 0:
+            self._obs_fail("configure_norm")
+
+    def bind_norm_source(self, device_ptr, steps=1, rows=None, step_stride=0, row_stride=None):
+        """A float32 tensor of the caller's as the source: sample step * rows + row at device_ptr + step * step_stride + row * row_stride
+        words (None: the store of the rollout's OBS source again).  One policy step's live observation is steps = 1, rows = nenv."""
+        if device_ptr is None:
+            rc = lib().phys_batch_norm_bind_source(self._h, None, 0, 0, 0, 0)
+        else:
+            row = int(max(self.norm_count(NORM_N), 0) if row_stride is None else row_stride)      # (default: dense rows)
+            rows = int(self.nenv if rows is None else rows)
+            rc = lib().phys_batch_norm_bind_source(self._h, device_ptr, int(steps), rows, int(step_stride) if step_stride else rows * row, row)
+        if rc != 0:
+            self._obs_fail("bind_norm_source")
+
+    def bind_norm_output(self, mean_ptr, inv_ptr):
+        """Two float32 [dim] tensors of the caller's as the outputs (both None: the tensors bind_policy_norm names, resolved at every call)."""
+        if lib().phys_batch_norm_bind_output(self._h, mean_ptr, inv_ptr) != 0:
+            self._obs_fail("bind_norm_output")
+
+    def norm_update(self, stream=None):
+        """Four launches on `stream` (default: the batch's own): the source's finite values merged into the state, and every updated
+        column's mean and inv written as float32 where the policy reads them -- policy() and grad() behind it on the stream act with the
+        new words.  No host synchronisation."""
+        if lib().phys_batch_norm_update(self._h, stream) != 0:
+            self._obs_fail("norm_update")
+
+    def norm_write(self, stream=None):
+        """One launch: mean and inv of every column with n > 0 from the state, no update (what follows norm_upload of a checkpoint)."""
+        if lib().phys_batch_norm_write(self._h, stream) != 0:
+            self._obs_fail("norm_write")
+
+    def norm_stats(self):
+        """The eight statistics of the last norm_update, by name (NORM_STATS), and as an array under "all" (waits for the batch's streams)."""
+        out = np.zeros(NORM_NSTATS, dtype=np.float64)
+        if lib().phys_batch_norm_stats(self._h, out.ctypes.data) != 0:
+            self._obs_fail("norm_stats")
+        d = dict(zip(NORM_STATS, out))
+        d["all"] = out
+        return d
+
+    def norm_count(self, what):
+        """The doubles norm_download(what) returns (-1: no such thing)."""
+        return int(lib().phys_batch_norm_count(self._h, int(what)))
+
+    def norm_download(self, what):
+        """NORM_N, _MEAN, _M2, _SKIPPED, _EXCLUDED, _MB, _COUNTS: float64 [dim]; NORM_PARTIALS: a1 then a2 of the last call,
+        [2][blocks][dim] (waits for the batch's streams)."""
+        n = self.norm_count(what)
+        if n < 0:
+            raise ValueError("norm_download: no such kind")
+        out = np.zeros(n, dtype=np.float64)
+        if n and lib().phys_batch_norm_download(self._h, int(what), out.ctypes.data) != 0:
+            self._obs_fail("norm_download")
+        D = self.norm_count(NORM_N)
+        return out.reshape(2, n // (2 * D), D) if what == NORM_PARTIALS else out
+
+    def norm_upload(self, what, values):
+        """What norm_download(what) gave for NORM_N, _MEAN, _M2, _SKIPPED or _EXCLUDED, back into the batch; norm_write() then restores the
+        two output vectors bit for bit."""
+        a = np.ascontiguousarray(values, dtype=np.float64).reshape(-1)
+        if what not in (NORM_N, NORM_MEAN, NORM_M2, NORM_SKIPPED, NORM_EXCLUDED) or a.size != self.norm_count(what):
+            raise ValueError("norm_upload: no such kind, or not its count of elements")
+        if lib().phys_batch_norm_upload(self._h, int(what), a.ctypes.data) != 0:
+            self._obs_fail("norm_upload")
+
+    def norm_launch_mask(self, mask=15):
+        """Measurement aid: bit k set = norm_update() makes launch k (sum, mean, sq, merge); 15: all, the default."""
+        lib().phys_batch_debug_norm_mask(self._h, int(mask))
+
+    def norm_launches(self):
+        """Diagnostics: the launches so far of sum, mean, sq, merge and write."""
+        a = (ctypes.c_longlong * 5)()
+        lib().phys_batch_debug_norm_launches(self._h, a)
         return tuple(a)
 
     def set_pd_mode(self, on=True):

@@ -223,6 +223,14 @@ struct phys_batch {
     DevBuf<double> d_opt_part;
     unsigned opt_mask = 7u;                           /* measurement aid (phys_batch_debug_opt_mask): which of the three launches a call makes */
     long long opt_launches[3] = {0, 0, 0};            /* squares, scalars, step */
+    /* normaliser rows (phys_batch_norm_configure): the record (norm.on 0: not configured; it holds no pointer of the policy's or the
+     * rollout's: both are resolved at the call), the state [NORM_STATE_ROWS][D], the partials and the blocks' counts.  No stepping launch
+     * reads any of it */
+    ck::NormCfg norm = {};
+    DevBuf<double> d_norm_state, d_norm_part;
+    DevBuf<int> d_norm_cnt;
+    unsigned norm_mask = 15u;                         /* measurement aid (phys_batch_debug_norm_mask): which of the four launches an update makes */
+    long long norm_launches[5] = {0, 0, 0, 0, 0};     /* sum, mean, sq, merge, write */
 };
 
 static bool hip_ok(hipError_t e, const char *what) {
@@ -2772,6 +2780,124 @@ int phys_batch_debug_opt_mask(phys_batch_t *b, unsigned mask) {
 int phys_batch_debug_opt_launches(const phys_batch_t *b, long long *launches) {
     if (!b) return -1;
     if (launches) for (int k = 0; k < 3; ++k) launches[k] = b->opt_launches[k];
+    return 0;
+}
+
+/* ------------------------------------------------ normaliser rows ---- */
+static_assert(PHYS_NORM_N == ck::NORM_N && PHYS_NORM_MEAN == ck::NORM_MEAN && PHYS_NORM_M2 == ck::NORM_M2 && PHYS_NORM_SKIPPED == ck::NORM_SKIPPED &&
+              PHYS_NORM_EXCLUDED == ck::NORM_EXCLUDED && PHYS_NORM_MB == ck::NORM_MB && PHYS_NORM_COUNTS == ck::NORM_COUNTS &&
+              PHYS_NORM_PARTIALS == ck::NORM_PARTIALS && PHYS_NORM_MINBLOCK == ck::NORM_MINBLOCK && PHYS_NORM_MAXBLOCK == ck::NORM_MAXBLOCK &&
+              PHYS_NORM_MAXROWS == ck::NORM_MAXROWS && PHYS_NORM_NSTATS == ck::NORM_NSTATS && PHYS_POL_MAXDIM == ck::NORM_MAXDIM,
+              "the header's numbers are norm_kernels.h's");
+/* the record of a launch: what was configured and bound, with the pointers into the batch's buffers */
+static ck::NormCfg norm_cfg_of(const phys_batch *b) {
+    ck::NormCfg c = b->norm;
+    c.state = b->d_norm_state; c.part = b->d_norm_part; c.cnt = b->d_norm_cnt;
+    return c;
+}
+static void norm_release(phys_batch *b) {
+    b->norm = {};
+    b->d_norm_state.reset(); b->d_norm_part.reset(); b->d_norm_cnt.reset();
+}
+int phys_batch_norm_configure(phys_batch_t *b, int dim, int block, long long max_rows, double eps) {
+    if (!b) { phys_set_last_error("phys_batch_norm_configure: no batch"); return -1; }
+    ck::NormCfg cfg;
+    if (const char *why = ck::norm_configure(dim, block, max_rows, eps, cfg)) return refuse("phys_batch_norm_configure", why);
+    (void)hipSetDevice(b->device);
+    if (!quiesce(b)) return -1;  /* (launches in flight may be using the state that goes away) */
+    if (!cfg.on) { norm_release(b); return 0; }
+    DevBuf<double> state, part;
+    DevBuf<int> cnt;
+    const size_t words = (size_t)cfg.max_blocks * (size_t)cfg.D;
+    if (!state.alloc((size_t)ck::NORM_STATE_ROWS * (size_t)cfg.D, true, "normaliser state") || !part.alloc(2 * words, true, "normaliser partials") ||
+        !cnt.alloc(words, true, "normaliser counts")) return -1;
+    norm_release(b);
+    b->d_norm_state = std::move(state); b->d_norm_part = std::move(part); b->d_norm_cnt = std::move(cnt);
+    b->norm = cfg;   /* (nothing bound: n, mean and m2 +0.0) */
+    return 0;
+}
+int phys_batch_norm_bind_source(phys_batch_t *b, const void *ptr, int steps, int rows, long long step_stride, long long row_stride) {
+    if (!b) { phys_set_last_error("phys_batch_norm_bind_source: no batch"); return -1; }
+    if (const char *why = ck::check_norm_bind_source(b->norm, ptr, steps, rows, step_stride, row_stride)) return refuse("phys_batch_norm_bind_source", why);
+    ck::NormCfg &c = b->norm;
+    c.src = (const float *)ptr;
+    c.steps = ptr ? steps : 0; c.rows = ptr ? rows : 0; c.step_stride = ptr ? step_stride : 0; c.row_stride = ptr ? row_stride : 0;
+    return 0;
+}
+int phys_batch_norm_bind_output(phys_batch_t *b, void *mean_ptr, void *inv_ptr) {
+    if (!b) { phys_set_last_error("phys_batch_norm_bind_output: no batch"); return -1; }
+    if (const char *why = ck::check_norm_bind_output(b->norm, mean_ptr, inv_ptr)) return refuse("phys_batch_norm_bind_output", why);
+    b->norm.out_mean = (float *)mean_ptr; b->norm.out_inv = (float *)inv_ptr;
+    return 0;
+}
+int phys_batch_norm_update(phys_batch_t *b, void *stream) {
+    if (!b) { phys_set_last_error("phys_batch_norm_update: no batch"); return -1; }
+    const ck::NormCfg c = norm_cfg_of(b);
+    ck::NormSource S;
+    ck::NormOutput O;
+    if (const char *why = ck::check_norm_update(c, rollout_cfg_of(b), b->policy, b->nenv, S, O)) return refuse("phys_batch_norm_update", why);
+    (void)hipSetDevice(b->device);
+    hipStream_t s = launch_stream(b, stream);
+    const ck::NormIO io = ck::make_norm_io(c, S, O);
+    const dim3 wave(WV_WAVE), pass((unsigned)ck::norm_pass_grid(io)), cols((unsigned)ck::norm_column_grid(io));
+    const unsigned mask = b->norm_mask;
+    if (mask & 1u) { hipLaunchKernelGGL(ck::cassie_norm_sum_kernel, pass, wave, 0, s, io); ++b->norm_launches[0]; }
+    if (mask & 2u) { hipLaunchKernelGGL(ck::cassie_norm_mean_kernel, cols, wave, 0, s, io); ++b->norm_launches[1]; }
+    if (mask & 4u) { hipLaunchKernelGGL(ck::cassie_norm_sq_kernel, pass, wave, 0, s, io); ++b->norm_launches[2]; }
+    if (mask & 8u) { hipLaunchKernelGGL(ck::cassie_norm_merge_kernel, cols, wave, 0, s, io); ++b->norm_launches[3]; }
+    b->norm.last_R = io.R; b->norm.last_blocks = io.blocks; ++b->norm.calls;
+    return hip_ok(hipGetLastError(), "normaliser launches") ? 0 : -1;
+}
+int phys_batch_norm_write(phys_batch_t *b, void *stream) {
+    if (!b) { phys_set_last_error("phys_batch_norm_write: no batch"); return -1; }
+    const ck::NormCfg c = norm_cfg_of(b);
+    ck::NormOutput O;
+    if (const char *why = ck::check_norm_write(c, b->policy, O)) return refuse("phys_batch_norm_write", why);
+    (void)hipSetDevice(b->device);
+    hipStream_t s = launch_stream(b, stream);
+    const ck::NormIO io = ck::make_norm_io(c, ck::NormSource{}, O);
+    hipLaunchKernelGGL(ck::cassie_norm_write_kernel, dim3((unsigned)ck::norm_column_grid(io)), dim3(WV_WAVE), 0, s, io);
+    ++b->norm_launches[4];
+    return hip_ok(hipGetLastError(), "cassie_norm_write_kernel launch") ? 0 : -1;
+}
+int phys_batch_norm_stats(phys_batch_t *b, double *stats) {
+    if (!b || !stats || !b->norm.on || !b->d_norm_state) return refuse("phys_batch_norm_stats", ck::NORM_NOT_CONFIGURED);
+    (void)hipSetDevice(b->device);
+    const size_t D = (size_t)b->norm.D;
+    std::vector<double> n(D), counts(D);
+    if (!quiesce(b) || !hip_ok(hipMemcpy(n.data(), b->d_norm_state + ck::NORM_N * D, sizeof(double) * D, hipMemcpyDeviceToHost), "normaliser stats download") ||
+        !hip_ok(hipMemcpy(counts.data(), b->d_norm_state + ck::NORM_COUNTS * D, sizeof(double) * D, hipMemcpyDeviceToHost), "normaliser stats download")) return -1;
+    ck::norm_stats_host(b->norm, n.data(), counts.data(), stats);
+    return 0;
+}
+long long phys_batch_norm_count(const phys_batch_t *b, int what) {
+    if (!b) return -1;
+    ck::NormRegion R;
+    return ck::norm_region(b->norm, what, false, R) ? R.rows * R.width : -1;
+}
+/* a download (up false) or an upload of a region: dense host doubles against the region's pitch */
+static int norm_transfer(phys_batch_t *b, const char *fn, int what, void *host, bool up) {
+    if (!b || !host || !b->norm.on) return refuse(fn, ck::NORM_NOT_CONFIGURED);
+    ck::NormRegion R;
+    if (!ck::norm_region(norm_cfg_of(b), what, up, R) || !R.ptr) return refuse(fn, "no such kind (PHYS_NORM_*; an upload takes N, MEAN, M2, SKIPPED and EXCLUDED)");
+    (void)hipSetDevice(b->device);
+    if (!quiesce(b)) return -1;
+    if (R.width == 0) return 0;
+    const size_t e = sizeof(double);
+    const hipError_t rc = up ? hipMemcpy2D(R.ptr, e * (size_t)R.pitch, host, e * (size_t)R.width, e * (size_t)R.width, (size_t)R.rows, hipMemcpyHostToDevice)
+                             : hipMemcpy2D(host, e * (size_t)R.width, R.ptr, e * (size_t)R.pitch, e * (size_t)R.width, (size_t)R.rows, hipMemcpyDeviceToHost);
+    return hip_ok(rc, up ? "normaliser upload" : "normaliser download") ? 0 : -1;
+}
+int phys_batch_norm_download(phys_batch_t *b, int what, void *host) { return norm_transfer(b, "phys_batch_norm_download", what, host, false); }
+int phys_batch_norm_upload(phys_batch_t *b, int what, const void *host) { return norm_transfer(b, "phys_batch_norm_upload", what, (void *)host, true); }
+int phys_batch_debug_norm_mask(phys_batch_t *b, unsigned mask) {
+    if (!b) return -1;
+    b->norm_mask = mask & 15u;
+    return 0;
+}
+int phys_batch_debug_norm_launches(const phys_batch_t *b, long long *launches) {
+    if (!b) return -1;
+    if (launches) for (int k = 0; k < 5; ++k) launches[k] = b->norm_launches[k];
     return 0;
 }
 

@@ -1,12 +1,12 @@
 /*
- * small_launch.h -- how the kernels around the step kernel (small_kernels.h, surface_kernels.h, depth_kernel.h, ray_kernel.h, episode_kernels.h, probe_kernels.h, obs_kernels.h, reward_kernels.h, act_kernels.h, task_kernels.h, event_kernels.h, policy_kernels.h, rollout_kernels.h, grad_kernels.h, opt_kernels.h) are
+ * small_launch.h -- how the kernels around the step kernel (small_kernels.h, surface_kernels.h, depth_kernel.h, ray_kernel.h, episode_kernels.h, probe_kernels.h, obs_kernels.h, reward_kernels.h, act_kernels.h, task_kernels.h, event_kernels.h, policy_kernels.h, rollout_kernels.h, grad_kernels.h, opt_kernels.h, norm_kernels.h) are
  * launched: the records a kernel's arguments are built from, one builder per kernel that returns its filled argument struct for an env
  * range, the grid of every launch, and the checks of what a caller configures, each returning the message of its refusal (null: fine).
  * Pure host code, no HIP runtime calls, in the spirit of step_policy.h: the launcher (phys_batch.hip) keeps the records in the batch,
  * prefixes a message with its entry point's name and launches what a builder returns on the grid given here; the wave emulator's entry
  * points (tests/emu) fill the same records from their arguments and go through the same builders, grids and checks, so a CPU test of
  * one of these kernels also runs the launcher's refusals, grid and choice of kernel (tests/test_small_launch.py pins them one by one).
- * No field of ScanIO, DepthIO, RayIO, EpisodeIO, ResetIO, DeriveIO, SetConstIO, StateIO, ProbeIO, ObsIO, RewardIO, ActIO, TaskIO, EventIO, PolicyIO, PolicyPackIO, RolloutRecIO, RolloutFinIO, RolloutNormIO, GradIO, GradPackIO or OptIO is assigned anywhere else.
+ * No field of ScanIO, DepthIO, RayIO, EpisodeIO, ResetIO, DeriveIO, SetConstIO, StateIO, ProbeIO, ObsIO, RewardIO, ActIO, TaskIO, EventIO, PolicyIO, PolicyPackIO, RolloutRecIO, RolloutFinIO, RolloutNormIO, GradIO, GradPackIO, OptIO or NormIO is assigned anywhere else.
  */
 #ifndef CASSIE_SMALL_LAUNCH_H
 #define CASSIE_SMALL_LAUNCH_H
@@ -20,6 +20,7 @@
 #include "event_kernels.h"
 #include "grad_kernels.h"
 #include "opt_kernels.h"
+#include "norm_kernels.h"
 #include "obs_kernels.h"
 #include "policy_kernels.h"
 #include "probe_kernels.h"
@@ -1671,6 +1672,127 @@ inline bool opt_region(const OptCfg &c, const GradCfg &g, const PolicyCfg &p, in
     R.ptr = c.mom ? c.mom + (second ? c.Q : 0) + opt_par0(g, p, s) + (bias ? L.in : 0) : nullptr;
     R.rows = L.out; R.width = bias ? 1 : L.in; R.pitch = L.in + 1;
     return true;
+}
+
+/* ---- the normaliser rows ---- */
+
+/* the normaliser (phys_batch_norm_configure; on 0: not configured): the columns, the samples of a block, the most samples of a call with
+ * the blocks they make, eps; the source the caller bound (src null: the rollout's OBS store, resolved at every call) and the outputs
+ * (null: the policy's bound normalisation, resolved at every call).  Then what the launcher names once a kernel reads them: the state
+ * [NORM_STATE_ROWS][D], the partials (a1 [max_blocks][D], then a2) and the blocks' counts -- and what the last call left for the
+ * statistics and the downloads: its samples, its blocks, the calls so far */
+struct NormCfg {
+    int on, D, block;
+    long long max_rows, max_blocks;
+    double eps;
+    const float *src; int steps, rows; long long step_stride, row_stride;
+    float *out_mean, *out_inv;
+    double *state, *part; int *cnt;
+    long long last_R, last_blocks, calls;
+};
+/* a source and the outputs as resolved at a call */
+struct NormSource { const float *ptr; int steps, rows; long long step_stride, row_stride; };
+struct NormOutput { float *mean, *inv; };
+constexpr const char *NORM_NOT_CONFIGURED = "not configured (phys_batch_norm_configure first)";
+constexpr const char *NORM_STRIDE_REFUSAL = "strides of at least dim words";
+/* the normaliser's configuration: checks the caller's numbers and fills c but for what is bound or named later.  dim 0 is accepted and
+ * leaves c empty: the launcher releases what it holds.  The emulator goes through the same */
+inline const char *norm_configure(int dim, int block, long long max_rows, double eps, NormCfg &c) {
+    c = {};
+    if (dim == 0) return nullptr;
+    if (dim < 1 || dim > NORM_MAXDIM) return "dim lies in 1 .. 512 (0 releases)";
+    if (block < NORM_MINBLOCK || block > NORM_MAXBLOCK || (block & 15) != 0) return "block is a multiple of 16 in 16 .. 4096";
+    if (max_rows < 1 || max_rows > NORM_MAXROWS) return "max_rows lies in 1 .. 2^30";
+    if (!(eps > 0.0 && eps < INFINITY)) return "eps is finite and > 0";
+    c.on = 1; c.D = dim; c.block = block; c.max_rows = max_rows; c.max_blocks = (max_rows + block - 1) / block; c.eps = eps;
+    return nullptr;
+}
+/* what phys_batch_norm_bind_source refuses (ptr null: back to the rollout's OBS store) */
+inline const char *check_norm_bind_source(const NormCfg &c, const void *ptr, int steps, int rows, long long step_stride, long long row_stride) {
+    if (!c.on) return NORM_NOT_CONFIGURED;
+    if (!ptr) return nullptr;
+    if (steps < 1 || rows < 1) return "a source has at least one step of at least one row";
+    if (row_stride < c.D || (steps > 1 && step_stride < c.D)) return NORM_STRIDE_REFUSAL;
+    return nullptr;
+}
+/* what phys_batch_norm_bind_output refuses (both null: back to the policy's bound normalisation) */
+inline const char *check_norm_bind_output(const NormCfg &c, const void *mean, const void *inv) {
+    if (!c.on) return NORM_NOT_CONFIGURED;
+    if ((mean == nullptr) != (inv == nullptr)) return "the outputs are a mean and an inv, both or neither";
+    return nullptr;
+}
+/* the source of a call: the caller's, or the store of the rollout's OBS source as it is now, by the reward's convention */
+inline const char *norm_resolve_source(const NormCfg &c, const RolloutCfg &r, int nenv, NormSource &S) {
+    S = {};
+    if (c.src) { S.ptr = c.src; S.steps = c.steps; S.rows = c.rows; S.step_stride = c.step_stride; S.row_stride = c.row_stride; return nullptr; }
+    if (r.nsrc < 1) return "no source: no rollout is configured (phys_batch_rollout_configure, or phys_batch_norm_bind_source)";
+    const int so = rollout_role(r, RO_OBS);
+    if (so < 0 || !r.store[so].ptr) return "no source: the rollout has no OBS source (or phys_batch_norm_bind_source)";
+    if (r.dim[so] != c.D) return "the rollout's OBS source does not have dim words";
+    S.ptr = (const float *)r.store[so].ptr; S.steps = r.T; S.rows = nenv; S.step_stride = r.store[so].step; S.row_stride = r.store[so].row;
+    if (S.row_stride < c.D || (S.steps > 1 && S.step_stride < c.D)) return NORM_STRIDE_REFUSAL;
+    return nullptr;
+}
+/* the outputs of a call: the caller's, or the tensors phys_batch_policy_bind_norm names now */
+inline const char *norm_resolve_output(const NormCfg &c, const PolicyCfg &p, NormOutput &O) {
+    O = {};
+    if (c.out_mean) { O.mean = c.out_mean; O.inv = c.out_inv; return nullptr; }
+    if (p.nnets < 1 || !p.mean || !p.inv) return "no output: the policy has no normalisation bound (phys_batch_policy_bind_norm, or phys_batch_norm_bind_output)";
+    if (p.in_dim != c.D) return "the policy's in_dim is not dim";
+    O.mean = (float *)p.mean; O.inv = (float *)p.inv;
+    return nullptr;
+}
+/* what an update refuses (S and O filled where it accepts) */
+inline const char *check_norm_update(const NormCfg &c, const RolloutCfg &r, const PolicyCfg &p, int nenv, NormSource &S, NormOutput &O) {
+    if (!c.on || !c.state || !c.part || !c.cnt) return NORM_NOT_CONFIGURED;
+    if (const char *why = norm_resolve_source(c, r, nenv, S)) return why;
+    if ((long long)S.steps * S.rows > c.max_rows) return "more samples than max_rows";
+    return norm_resolve_output(c, p, O);
+}
+/* what a write refuses */
+inline const char *check_norm_write(const NormCfg &c, const PolicyCfg &p, NormOutput &O) {
+    if (!c.on || !c.state) return NORM_NOT_CONFIGURED;
+    return norm_resolve_output(c, p, O);
+}
+/* the five kernels' (after the check; a write reads no source: S empty) */
+inline NormIO make_norm_io(const NormCfg &c, const NormSource &S, const NormOutput &O) {
+    NormIO io = zeroed<NormIO>();
+    io.D = c.D; io.block = c.block; io.eps = c.eps;
+    io.state = c.state; io.a1 = c.part; io.a2 = c.part ? c.part + (size_t)c.max_blocks * (size_t)c.D : nullptr; io.cnt = c.cnt;
+    io.mean = O.mean; io.inv = O.inv;
+    io.src = S.ptr; io.rows = S.rows > 0 ? S.rows : 1; io.step_stride = S.step_stride; io.row_stride = S.row_stride;
+    io.wrap = S.step_stride - (long long)(io.rows - 1) * S.row_stride;
+    io.R = (long long)S.steps * S.rows; io.Rd = (double)io.R;
+    io.blocks = (io.R + c.block - 1) / c.block;
+    io.vec = rollout_aligned16(S.ptr) && (c.D & 3) == 0 && (S.step_stride & 3) == 0 && (S.row_stride & 3) == 0;
+    io.groups = io.vec ? (c.D / 4 + WV_WAVE - 1) / WV_WAVE : (c.D + WV_WAVE - 1) / WV_WAVE;
+    io.njobs = io.blocks * io.groups;
+    return io;
+}
+/* a workgroup per job up to NORM_GRID, which then walk the jobs (launches 1 and 3); a wave per 64 columns (launches 2 and 4, the write) */
+inline int norm_pass_grid(const NormIO &io) { return io.njobs < NORM_GRID ? (int)io.njobs : NORM_GRID; }
+inline int norm_column_grid(const NormIO &io) { return (io.D + WV_WAVE - 1) / WV_WAVE; }
+/* where a thing phys_batch_norm_download / _upload names lies: `rows` runs of `width` doubles, `pitch` doubles apart; false: no such
+ * thing.  Uploads take the state's first five alone */
+struct NormRegion { double *ptr; long long rows, width, pitch; };
+inline bool norm_region(const NormCfg &c, int what, bool upload, NormRegion &R) {
+    R = {};
+    if (!c.on) return false;
+    if (what >= NORM_N && what < (upload ? NORM_MB : NORM_PARTIALS)) {
+        R.ptr = c.state ? c.state + (size_t)what * (size_t)c.D : nullptr; R.rows = 1; R.width = R.pitch = c.D; return true;
+    }
+    if (what == NORM_PARTIALS && !upload) { R.ptr = c.part; R.rows = 2; R.width = c.last_blocks * c.D; R.pitch = c.max_blocks * c.D; return true; }
+    return false;
+}
+/* the eight statistics from the per-column arrays of the state (n, the last call's counts) and what the host knows of the last call */
+inline void norm_stats_host(const NormCfg &c, const double *n, const double *counts, double *stats) {
+    double updated = 0, skipped = 0, excluded = 0, nmax = 0;
+    for (int j = 0; j < c.D; ++j) {
+        if (c.calls > 0) { if (counts[j] > 0) { updated += 1; excluded += (double)c.last_R - counts[j]; } else skipped += 1; }
+        if (n[j] > nmax) nmax = n[j];
+    }
+    stats[0] = (double)c.last_R; stats[1] = (double)c.last_blocks; stats[2] = updated; stats[3] = skipped; stats[4] = excluded;
+    stats[5] = (double)c.calls; stats[6] = nmax; stats[7] = 0.0;
 }
 
 }  // namespace ck

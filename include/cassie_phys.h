@@ -1191,7 +1191,7 @@ int phys_batch_debug_events_launches(const phys_batch_t *b, long long *launches)
  *   most 64, and an activation PHYS_POL_IDENTITY, _RELU, _ELU or _TANH.  Weights are float32 [out][in], row-major with a row stride, as
  *   torch.nn.Linear.weight; biases float32 [out].
  * INPUT.  x[k] is the bound row's element k.  Where a normalisation is bound: x[k] = (float) clip((x[k] - mean[k]) * inv[k], -c, c), mean
- *   and inv float32 [in_dim] in device memory READ AT EVERY CALL (a caller's running statistics act at once); the subtraction and the
+ *   and inv float32 [in_dim] in device memory READ AT EVERY CALL (a caller's running statistics, or NORMALISER ROWS' below, act at once); the subtraction and the
  *   product are individually rounded fp64 operations, the clip is two compares and selects (y < -c ? -c : y > c ? c : y: a NaN passes),
  *   c >= 0 or +inf, and the conversion rounds to nearest even.
  * LAYER.  K4 = in rounded up to a multiple of 4.  acc = (double) b[j]; for k = 0 .. K4 - 1 ascending: acc = fma((double) w[j][k],
@@ -1368,7 +1368,7 @@ int phys_batch_debug_rollout_launches(const phys_batch_t *b, long long *launches
  *   position loads +0.0 rows; every kept activation, every delta row and every head value of a void position is +0.0 BY A SELECT AT THE
  *   STORE, never a product with zero (a weight of +inf makes NaN of a void position's own sums, which go nowhere).  Void positions inside
  *   [0, M) are counted in the statistics, and 1 / M is the divisor whatever their number.
- * FORWARD.  POLICY ROWS' INPUT (the normalisation as bound at the call) and LAYER on the gathered observation row: h_0 is the normalised
+ * FORWARD.  POLICY ROWS' INPUT (the normalisation as bound at the call: NORMALISER ROWS say where an update goes) and LAYER on the gathered observation row: h_0 is the normalised
  *   input, h_l layer l's float32 output, bit for bit what phys_batch_policy writes for that row with the same weights.  Every h_l,
  *   l = 0 .. L, is KEPT in a device store for the backward passes.
  * HEAD, ACTOR (A its output width, mu = h_L, a the stored action, ls = log_std as bound by phys_batch_policy_bind_sample and read at the
@@ -1500,6 +1500,92 @@ int phys_batch_opt_download(phys_batch_t *b, int what, int net, int layer, void 
 int phys_batch_opt_upload(phys_batch_t *b, int what, int net, int layer, const void *host);
 int phys_batch_debug_opt_launches(const phys_batch_t *b, long long *launches /*[3]*/);
 int phys_batch_debug_opt_mask(phys_batch_t *b, unsigned mask);
+
+/* NORMALISER ROWS: the running per-column mean and variance of float32 rows -- the observations -- and from them the `mean` and `inv` that
+ * INPUT of POLICY ROWS applies, by FOUR launches on the caller's stream with every bit defined.  The policy READS the two tensors
+ * phys_batch_policy_bind_norm names and THIS CALL WRITES them (or two tensors of the caller's, phys_batch_norm_bind_output): the policy
+ * and the gradient rows read them at every call, so an update acts on the next launch behind it on the stream.  No float atomics, no
+ * grid-wide barrier, no kernel waits for another workgroup, no host synchronisation in update or write.  The device
+ * (csrc/norm_kernels.h), the wave emulator and a numpy restatement (tests/norm_check.py) agree bit for bit.  No stepping kernel is
+ * handed any of this.
+ *
+ * All arithmetic is individually rounded fp64 operations (add, sub, mul, div, sqrt), no fma; float32 values are read as doubles;
+ * conversions to float32 round to nearest even.
+ *
+ * SOURCE.  Rows of D float32 words, 1 <= D <= PHYS_POL_MAXDIM, laid out as steps x rows: sample s = step * rows + row lies at
+ *   ptr + step * step_stride + row * row_stride (strides in words, row_stride >= D).  Unbound, the source is resolved at every call from
+ *   the rollout, by the reward's convention: the store of the source of role PHYS_RO_OBS, the batch's own or bound, steps = T,
+ *   rows = nenv, with its strides; refused when there is no rollout, no OBS source, or its dim is not D.  Bound
+ *   (phys_batch_norm_bind_source), it is any tensor of the caller's: one policy step's live observation (steps = 1, rows = nenv) is a
+ *   valid source and needs no rollout.  R = steps * rows, 1 <= R <= max_rows.
+ * BLOCKS.  [0, R) is cut into blocks of `block` consecutive samples; `block` is set at configuration, a multiple of 16 in 16 .. 4096, and
+ *   PART OF THE DEFINITION, as the gradient rows' chunk is.  The last block may be short; a block may straddle a step.
+ * FINITE.  fin(x) = |x| < +inf, false for a NaN.  A value that is not finite is left out by a select: never added, never multiplied by
+ *   zero.  A diverged env does not poison a column and does not stop the others from updating it.
+ * PASS 1, per block c and column j: a1[c][j], from +0.0 over the block's samples ascending, acc = fin ? acc + x : acc; n1[c][j], the
+ *   count of the finite values, an integer.
+ * MEAN, per column: S1 the sum of a1[c][j] over c ascending from +0.0; Mj the integer sum of n1, converted exactly;
+ *   mb = Mj > 0 ? S1 / Mj : +0.0.
+ * PASS 2, per block and column: a2[c][j], from +0.0 ascending, d = x - mb, acc = fin ? acc + d * d : acc.
+ * MERGE, per column; the state is three doubles the batch owns, n, mean and m2, +0.0 at configuration.  S2 the sum of a2 over c
+ *   ascending.  If Mj == 0 the column is SKIPPED: its state and its two output words stay as they are, skipped[j] += 1.  Otherwise
+ *     nn = n + Mj;  delta = mb - mean;  w = Mj / nn
+ *     mean' = mean + delta * w
+ *     m2'   = (m2 + S2) + (delta * delta) * (n * w)
+ *     var = m2' / nn;  inv = 1 / sqrt(var + eps)
+ *   (float) mean' and (float) inv go to the outputs, excluded[j] += (R - Mj).  The first update of a column gives mean' = mb and
+ *   m2' = S2 exactly (w = 1, n * w = 0).
+ * OUTPUTS.  mean and inv, float32 [D] in device memory.  Unbound, they are resolved at every call from phys_batch_policy_bind_norm's
+ *   pointers; refused when no normalisation is bound or in_dim != D.  Bound (phys_batch_norm_bind_output), any two tensors.
+ * WRITE.  One launch writes (float) mean and (float) inv of every column with n > 0 from the state, with no update: what follows an
+ *   upload of a checkpoint.
+ * The result depends on nothing but the source's words, `block`, eps and the state: not on the grid, not on whether a lane moves 16
+ * bytes or a word, not on how phys_batch_rollout_record was cut into ranges.  As with phys_batch_rollout_normalise, ordering the ranges'
+ * streams in front of the call is the caller's job.
+ * WHERE THE UPDATE GOES.  The gradient rows read the normalisation AS BOUND AT THE CALL.  An update between the rollout and the first
+ * phys_batch_grad makes the first minibatch's ratio differ from 1 (the stored log-probabilities were made with the old words); an update
+ * behind the iteration's last phys_batch_opt_step does not.  Both are legitimate; the choice is the caller's.
+ * Out of scope: a count cap or forgetting factor; a return or value normaliser; merging states across ranks (a download, a host merge and
+ * an upload is possible and bit-exact); per-column masks.
+ *
+ *   phys_batch_norm_configure   dim columns, block, the most samples of a call, eps (finite, > 0); allocates the state, the partials and
+ *                               the counts; n = mean = m2 = +0.0.  dim 0 releases.  Waits for the batch's streams.  The normaliser rows
+ *                               STAY configured when the policy, the rollout, the gradient rows or the optimiser rows are reconfigured:
+ *                               they resolve at the call and hold no pointer of theirs.
+ *   phys_batch_norm_bind_source a tensor of the caller's as the source (ptr NULL: the rollout's OBS store again).  Refuses a stride
+ *                               smaller than dim.
+ *   phys_batch_norm_bind_output two tensors of the caller's as the outputs (both NULL: the policy's bound normalisation again).  Refuses
+ *                               one pointer without the other.
+ *   phys_batch_norm_update      the four launches on `stream`: sum, mean, sq, merge.  Refuses an unresolved source or output and
+ *                               R > max_rows.
+ *   phys_batch_norm_write       the one launch on `stream`.
+ *   phys_batch_norm_stats       eight doubles, summarised on the host from the per-column arrays; waits for the streams: R of the last
+ *                               call, its blocks, the columns it updated, the columns it skipped, the values it excluded (R - Mj over the
+ *                               columns it updated), the calls so far, the largest n[j], a spare +0.0.
+ *   phys_batch_norm_download, _upload   what = PHYS_NORM_N, _MEAN, _M2, _SKIPPED, _EXCLUDED: doubles [D]; download only: _MB, _COUNTS
+ *                               (Mj as doubles) [D] and _PARTIALS (a1 then a2, [blocks of the last call][D] each).  Dense host memory.
+ *                               An upload of everything a download gave, followed by phys_batch_norm_write, restores a checkpoint bit for
+ *                               bit.  phys_batch_norm_count: the doubles (-1: no such thing).
+ *   phys_batch_debug_norm_launches  diagnostics: the launches so far of sum, mean, sq, merge and write.
+ *   phys_batch_debug_norm_mask  measurement aid: bit k set = an update makes launch k (default 15, all four); the partials and the state
+ *                               keep what the last full call left, so one launch alone can be timed (tools/norm_rate.py). */
+enum { PHYS_NORM_N = 0, PHYS_NORM_MEAN = 1, PHYS_NORM_M2 = 2, PHYS_NORM_SKIPPED = 3, PHYS_NORM_EXCLUDED = 4, PHYS_NORM_MB = 5,
+       PHYS_NORM_COUNTS = 6, PHYS_NORM_PARTIALS = 7 };
+#define PHYS_NORM_MINBLOCK 16
+#define PHYS_NORM_MAXBLOCK 4096
+#define PHYS_NORM_MAXROWS (1ll << 30)
+#define PHYS_NORM_NSTATS 8
+int phys_batch_norm_configure(phys_batch_t *b, int dim, int block, long long max_rows, double eps);   /* dim 0: release */
+int phys_batch_norm_bind_source(phys_batch_t *b, const void *ptr, int steps, int rows, long long step_stride, long long row_stride);   /* NULL: the rollout's OBS store */
+int phys_batch_norm_bind_output(phys_batch_t *b, void *mean_ptr, void *inv_ptr);   /* both NULL: the policy's bound normalisation */
+int phys_batch_norm_update(phys_batch_t *b, void *stream);     /* four launches */
+int phys_batch_norm_write(phys_batch_t *b, void *stream);      /* one launch */
+int phys_batch_norm_stats(phys_batch_t *b, double *stats /*[8]*/);
+long long phys_batch_norm_count(const phys_batch_t *b, int what);
+int phys_batch_norm_download(phys_batch_t *b, int what, void *host);
+int phys_batch_norm_upload(phys_batch_t *b, int what, const void *host);
+int phys_batch_debug_norm_launches(const phys_batch_t *b, long long *launches /*[5]*/);
+int phys_batch_debug_norm_mask(phys_batch_t *b, unsigned mask);   /* default 15 */
 
 /* measurement aid: on = every substep of a fused launch evaluates every output (IMU sensors, body quaternions), although
  * only the last substep's values can be read; off (default) = those are formed by the substeps whose values are read */
