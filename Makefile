@@ -68,7 +68,7 @@ AGILITY_LINK := $(AGILITY_ABSENT)
 AGILITY_DEPS := $(AGILITY_ABSENT)
 endif
 
-.PHONY: all product oracle emu wave_check models clean apps grad_resources opt_resources norm_resources FORCE
+.PHONY: all product oracle emu wave_check models clean apps grad_resources opt_resources norm_resources draw_resources FORCE
 all: product oracle emu apps
 apps: $(PKG)/bin/cassiesim
 product: $(PRODUCT)
@@ -116,7 +116,7 @@ oracle/libcassie_oracle.so: oracle/cassie_oracle.c oracle/cassie_oracle.h $(CSRC
 	gcc -O2 -std=gnu11 -fPIC -shared -fopenmp -I$(CSRC) -Ioracle oracle/cassie_oracle.c -o $@ -lm
 
 # the wave emulator: the scheduler (emu_runtime), the step kernel (emu_step: the one unit that instantiates it, and most of the build
-# time; emu_lean: its lean and profiled fast forms; emu_sums: the forms of launches that accumulate the step sums), the small kernels and probes (emu_kernels), the depth image (emu_depth, emu_depth_scene), the placed restarts (emu_placement), the range sensors (emu_rays), the bank of full states (emu_states), the probes (emu_probes), the observation rows (emu_obs), the reward rows (emu_rewards), the action rows (emu_actions), the task rows (emu_task), the event rows (emu_events), the policy rows (emu_policy), the rollout rows (emu_rollout), the gradient rows (emu_grad), the optimiser rows (emu_opt) and the normaliser rows (emu_norm), compiled in parallel.  Baseline x86-64, no
+# time; emu_lean: its lean and profiled fast forms; emu_sums: the forms of launches that accumulate the step sums), the small kernels and probes (emu_kernels), the depth image (emu_depth, emu_depth_scene), the placed restarts (emu_placement), the range sensors (emu_rays), the bank of full states (emu_states), the probes (emu_probes), the observation rows (emu_obs), the reward rows (emu_rewards), the action rows (emu_actions), the task rows (emu_task), the event rows (emu_events), the policy rows (emu_policy), the rollout rows (emu_rollout), the gradient rows (emu_grad), the optimiser rows (emu_opt), the normaliser rows (emu_norm) and the draw rows (emu_draw), compiled in parallel.  Baseline x86-64, no
 # -march, no FMA contraction: the emulator's bit-exactness rests on these flags
 # (the emulator's sources live in the test tree too: an older tests/, whose emulator is one chain of .cpp files that include each other
 # from emu_terrain.cpp down, builds as it did -- one translation unit)
@@ -130,7 +130,8 @@ ifeq ($(wildcard tests/emu/emu_terrain.cpp),)
 EMU_OBJS := $(OBJD)/emu/emu_runtime.o $(OBJD)/emu/emu_step.o $(OBJD)/emu/emu_kernels.o $(OBJD)/emu/emu_depth.o $(OBJD)/emu/emu_depth_scene.o \
             $(OBJD)/emu/emu_placement.o $(OBJD)/emu/emu_rays.o $(OBJD)/emu/emu_lean.o $(OBJD)/emu/emu_sums.o $(OBJD)/emu/emu_states.o \
             $(OBJD)/emu/emu_probes.o $(OBJD)/emu/emu_obs.o $(OBJD)/emu/emu_rewards.o $(OBJD)/emu/emu_actions.o $(OBJD)/emu/emu_task.o \
-            $(OBJD)/emu/emu_events.o $(OBJD)/emu/emu_policy.o $(OBJD)/emu/emu_rollout.o $(OBJD)/emu/emu_grad.o $(OBJD)/emu/emu_opt.o $(OBJD)/emu/emu_norm.o
+            $(OBJD)/emu/emu_events.o $(OBJD)/emu/emu_policy.o $(OBJD)/emu/emu_rollout.o $(OBJD)/emu/emu_grad.o $(OBJD)/emu/emu_opt.o $(OBJD)/emu/emu_norm.o \
+            $(OBJD)/emu/emu_draw.o
 $(OBJD)/emu/%.o: tests/emu/%.cpp $(EMU_DEPS)
 	@mkdir -p $(OBJD)/emu
 	g++ $(EMU_FLAGS) -c $< -o $@
@@ -157,6 +158,10 @@ opt_resources:
 # the same of the normaliser rows' kernels (csrc/norm_kernels.h)
 norm_resources:
 	SMALL=norm bash tools/kernel_resources.sh
+
+# the same of the draw rows' kernels (csrc/draw_kernels.h)
+draw_resources:
+	SMALL=draw bash tools/kernel_resources.sh
 
 models: product
 	python3 tools/make_models.py $(REF)/model models tests/golden

@@ -319,6 +319,20 @@ def _declare(L):
         L.phys_batch_norm_upload.argtypes = [vp, c.c_int, vp]
         L.phys_batch_debug_norm_launches.argtypes = [vp, c.POINTER(c.c_longlong)]
         L.phys_batch_debug_norm_mask.argtypes = [vp, c.c_uint]
+    if hasattr(L, "phys_batch_draw"):   # (likewise)
+        L.phys_batch_draw_configure.argtypes = [vp, c.c_int, c.c_longlong, c.c_ulonglong, c.c_uint]
+        L.phys_batch_draw_bind.argtypes = [vp, vp, c.c_longlong]
+        L.phys_batch_draw_bind_perm.argtypes = [vp, vp]
+        L.phys_batch_draw.argtypes = [vp, c.c_int, c.c_int, vp]
+        L.phys_batch_draw_perm.argtypes = [vp, c.c_uint, vp]
+        L.phys_batch_draw_perm_ptr.argtypes = [vp]
+        L.phys_batch_draw_perm_ptr.restype = vp
+        L.phys_batch_draw_dim.argtypes = [vp, c.POINTER(c.c_int), c.POINTER(c.c_longlong)]
+        L.phys_batch_draw_rows.argtypes = [vp, vp]
+        L.phys_batch_draw_perm_rows.argtypes = [vp, vp]
+        L.phys_batch_draw_download.argtypes = [vp, vp]
+        L.phys_batch_draw_upload.argtypes = [vp, vp]
+        L.phys_batch_debug_draw_launches.argtypes = [vp, c.POINTER(c.c_longlong)]
     if hasattr(L, "phys_batch_step_sums_enable"):   # (likewise)
         L.phys_batch_step_sums_enable.argtypes = [vp, c.c_int]
     if hasattr(L, "phys_batch_download_progress"):   # (absent from older variant builds selected with CASSIE_LIB)

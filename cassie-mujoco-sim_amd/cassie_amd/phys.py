@@ -365,6 +365,9 @@ OPT_STATS = ("norm", "scale", "skip", "t", "skipped", "lr", "p1", "p2")
 NORM_MINBLOCK, NORM_MAXBLOCK, NORM_MAXROWS, NORM_NSTATS = 16, 4096, 1 << 30, 8
 NORM_STATS = ("rows", "blocks", "updated", "skipped", "excluded", "calls", "n_max", "spare")
 
+# draw rows: the limits (PHYS_DRAW_* in cassie_phys.h)
+DRAW_MAXA, DRAW_MAXPERM = 64, 1 << 30
+
 
 # per-env physical parameters (CM_P_* in cm_model.h): what Batch.randomize takes
 (P_BODY_MASS, P_BODY_IPOS, P_BODY_INERTIA, P_DOF_DAMPING, P_GEOM_FRICTION,
@@ -1667,6 +1670,94 @@ class Batch:
         """Diagnostics: the launches so far of sum, mean, sq, merge and write."""
         a = (ctypes.c_longlong * 5)()
         lib().phys_batch_debug_norm_launches(self._h, a)
+        return tuple(a)
+
+    # ---- draw rows: the policy's standard normal eps and the minibatch shuffle from one seed, every bit defined (phys_batch_draw_*) ----
+    def configure_draws(self, A=None, perm_n=None, seed=0, env_base=0, release=False):
+        """Standard normal float32 rows of `A` columns (default: the configured actor's output width; 0: none) and a shuffle of `perm_n`
+        indices (default: the configured rollout's T steps of every env; 0: none), both keyed by `seed`; env_base: what is added to the
+        env index in the counter (a rank that holds envs [k n, (k + 1) n) of a larger run passes k n).  The envs' call counts start at 0
+        (release: drop them).  Stays configured when the policy, the rollout, the gradient, the optimiser or the normaliser rows are
+        reconfigured; waits for the batch's streams."""
+        if A is None:
+            A = self._pol_out[0] if getattr(self, "_pol_out", None) else 0
+        if perm_n is None:
+            perm_n = self._ro[0] * self.nenv if getattr(self, "_ro", None) and self._ro[1] else 0
+        args = (0, 0, 0, 0) if release else (int(A), int(perm_n), int(seed) & 0xFFFFFFFFFFFFFFFF, int(env_base) & 0xFFFFFFFF)
+        if lib().phys_batch_draw_configure(self._h, *args) != 0:
+            self._obs_fail("configure_draws")
+
+    def draw_dim(self):
+        """(A, perm_n) as configured."""
+        a, n = ctypes.c_int(0), ctypes.c_longlong(0)
+        if lib().phys_batch_draw_dim(self._h, ctypes.byref(a), ctypes.byref(n)) != 0:
+            self._obs_fail("draw_dim")
+        return a.value, n.value
+
+    def bind_draws(self, device_ptr, row_stride=None):
+        """A float32 tensor of the caller's as the destination: [nenv] rows of A words, `row_stride` words (default: A) apart (None: the
+        eps tensor bind_policy_sample names again, resolved at every call)."""
+        stride = int(self.draw_dim()[0] if row_stride is None else row_stride) if device_ptr else 0
+        if lib().phys_batch_draw_bind(self._h, device_ptr, stride) != 0:
+            self._obs_fail("bind_draws")
+
+    def bind_draw_perm(self, device_ptr):
+        """An int32 tensor of the caller's of perm_n words as the shuffle's destination (None: the batch's own buffer again)."""
+        if lib().phys_batch_draw_bind_perm(self._h, device_ptr) != 0:
+            self._obs_fail("bind_draw_perm")
+
+    def draw(self, env0=0, n=None, stream=None):
+        """One launch on `stream` (default: the batch's own), in front of policy(): the standard normal row of every env of
+        [env0, env0 + n), a function of (seed, env_base + env, column, the env's call count) alone; the count moves on.  No host
+        synchronisation."""
+        n = self.nenv - env0 if n is None else n
+        if lib().phys_batch_draw(self._h, int(env0), int(n), stream) != 0:
+            self._obs_fail("draw")
+
+    def draw_perm(self, epoch, stream=None):
+        """One launch on `stream`: the permutation of [0, perm_n) keyed by (seed, epoch), int32, where draw_perm_ptr() points; minibatch k
+        of M samples is grad(draw_perm_ptr() + 4 * k * M, M).  No host synchronisation."""
+        if lib().phys_batch_draw_perm(self._h, int(epoch) & 0xFFFFFFFF, stream) != 0:
+            self._obs_fail("draw_perm")
+
+    def draw_perm_ptr(self):
+        """The device address of the permutation: the bound tensor's, or the batch's own buffer's."""
+        p = lib().phys_batch_draw_perm_ptr(self._h)
+        if not p:
+            raise RuntimeError("draw_perm_ptr failed: no shuffle is configured (configure_draws with perm_n first)")
+        return int(p)
+
+    def draws(self):
+        """The destination's rows downloaded: float32 [nenv][A] (waits for the batch's streams)."""
+        out = np.empty((self.nenv, self.draw_dim()[0]), dtype=np.float32)
+        if lib().phys_batch_draw_rows(self._h, out.ctypes.data) != 0:
+            self._obs_fail("draws")
+        return out
+
+    def draw_perm_values(self):
+        """The permutation downloaded: int32 [perm_n] (waits for the batch's streams)."""
+        out = np.empty(self.draw_dim()[1], dtype=np.int32)
+        if lib().phys_batch_draw_perm_rows(self._h, out.ctypes.data) != 0:
+            self._obs_fail("draw_perm_values")
+        return out
+
+    def draw_state(self):
+        """counts uint32 [nenv]: the draws every env has seen, the third word of the counter.  With the seed and the caller's epoch
+        counter, a checkpoint of the run's randomness."""
+        counts = np.empty(self.nenv, dtype=np.uint32)
+        if lib().phys_batch_draw_download(self._h, counts.ctypes.data) != 0:
+            self._obs_fail("draw_state")
+        return counts
+
+    def set_draw_state(self, counts):
+        k = np.ascontiguousarray(counts, dtype=np.uint32).reshape(self.nenv)
+        if lib().phys_batch_draw_upload(self._h, k.ctypes.data) != 0:
+            self._obs_fail("set_draw_state")
+
+    def draw_launches(self):
+        """Diagnostics: the launches so far of draw() and of draw_perm()."""
+        a = (ctypes.c_longlong * 2)()
+        lib().phys_batch_debug_draw_launches(self._h, a)
         return tuple(a)
 
     def set_pd_mode(self, on=True):

@@ -231,6 +231,12 @@ struct phys_batch {
     DevBuf<int> d_norm_cnt;
     unsigned norm_mask = 15u;                         /* measurement aid (phys_batch_debug_norm_mask): which of the four launches an update makes */
     long long norm_launches[5] = {0, 0, 0, 0, 0};     /* sum, mean, sq, merge, write */
+    /* draw rows (phys_batch_draw_configure): the record (draw.on 0: not configured; it holds no pointer of the policy's: the eps of the
+     * sample binding is resolved at the call), the envs' call counts and the batch's own permutation.  No stepping launch reads any of it */
+    ck::DrawCfg draw = {};
+    DevBuf<unsigned> d_draw_counts;
+    DevBuf<int> d_draw_perm;
+    long long draw_launches[2] = {0, 0};              /* normal rows, shuffle */
 };
 
 static bool hip_ok(hipError_t e, const char *what) {
@@ -2898,6 +2904,112 @@ int phys_batch_debug_norm_mask(phys_batch_t *b, unsigned mask) {
 int phys_batch_debug_norm_launches(const phys_batch_t *b, long long *launches) {
     if (!b) return -1;
     if (launches) for (int k = 0; k < 5; ++k) launches[k] = b->norm_launches[k];
+    return 0;
+}
+
+/* ------------------------------------------------ draw rows ---- */
+static_assert(PHYS_DRAW_MAXA == ck::DRAW_MAXA && PHYS_DRAW_MAXPERM == ck::DRAW_MAXPERM, "the header's numbers are draw_kernels.h's");
+/* the record of a launch: what was configured and bound, with the pointers into the batch's buffers */
+static ck::DrawCfg draw_cfg_of(const phys_batch *b) {
+    ck::DrawCfg c = b->draw;
+    c.counts = b->d_draw_counts; c.perm = b->d_draw_perm;
+    return c;
+}
+static void draw_release(phys_batch *b) {
+    b->draw = {};
+    b->d_draw_counts.reset(); b->d_draw_perm.reset();
+}
+int phys_batch_draw_configure(phys_batch_t *b, int A, long long perm_n, unsigned long long seed, unsigned env_base) {
+    if (!b) { phys_set_last_error("phys_batch_draw_configure: no batch"); return -1; }
+    ck::DrawCfg cfg;
+    if (const char *why = ck::draw_configure(A, perm_n, seed, env_base, cfg)) return refuse("phys_batch_draw_configure", why);
+    (void)hipSetDevice(b->device);
+    if (!quiesce(b)) return -1;  /* (launches in flight may be using the buffers that go away) */
+    if (!cfg.on) { draw_release(b); return 0; }
+    DevBuf<unsigned> counts;
+    DevBuf<int> perm;
+    if (!counts.alloc((size_t)b->nenv, true, "draw call counts") || (cfg.perm_n > 0 && !perm.alloc((size_t)cfg.perm_n, true, "draw permutation"))) return -1;
+    draw_release(b);
+    b->d_draw_counts = std::move(counts); b->d_draw_perm = std::move(perm);
+    b->draw = cfg;   /* (nothing bound: the counts 0) */
+    return 0;
+}
+int phys_batch_draw_bind(phys_batch_t *b, void *ptr, long long row_stride) {
+    if (!b) { phys_set_last_error("phys_batch_draw_bind: no batch"); return -1; }
+    if (const char *why = ck::check_draw_bind(b->draw, ptr, row_stride)) return refuse("phys_batch_draw_bind", why);
+    b->draw.dst = (float *)ptr; b->draw.sdst = ptr ? row_stride : 0;
+    return 0;
+}
+int phys_batch_draw_bind_perm(phys_batch_t *b, void *ptr) {
+    if (!b) { phys_set_last_error("phys_batch_draw_bind_perm: no batch"); return -1; }
+    if (const char *why = ck::check_draw_bind_perm(b->draw, ptr)) return refuse("phys_batch_draw_bind_perm", why);
+    b->draw.perm_dst = (int *)ptr;
+    return 0;
+}
+int phys_batch_draw(phys_batch_t *b, int env0, int n, void *stream) {
+    if (!b) { phys_set_last_error("phys_batch_draw: no batch"); return -1; }
+    const ck::DrawCfg c = draw_cfg_of(b);
+    ck::DrawDst D;
+    if (const char *why = ck::check_draw(c, b->policy, b->nenv, env0, n, D)) return refuse("phys_batch_draw", why);
+    if (n == 0) return 0;
+    (void)hipSetDevice(b->device);
+    hipStream_t s = launch_stream(b, stream);
+    const ck::DrawIO io = ck::make_draw_io(c, D, env0, n);
+    hipLaunchKernelGGL(ck::cassie_draw_kernel, dim3((unsigned)ck::draw_grid(io)), dim3(WV_WAVE), 0, s, io);
+    ++b->draw_launches[0];
+    return hip_ok(hipGetLastError(), "cassie_draw_kernel launch") ? 0 : -1;
+}
+int phys_batch_draw_perm(phys_batch_t *b, unsigned epoch, void *stream) {
+    if (!b) { phys_set_last_error("phys_batch_draw_perm: no batch"); return -1; }
+    const ck::DrawCfg c = draw_cfg_of(b);
+    if (const char *why = ck::check_draw_perm(c)) return refuse("phys_batch_draw_perm", why);
+    (void)hipSetDevice(b->device);
+    hipStream_t s = launch_stream(b, stream);
+    const ck::DrawPermIO io = ck::make_draw_perm_io(c, epoch);
+    hipLaunchKernelGGL(ck::cassie_draw_perm_kernel, dim3((unsigned)ck::draw_perm_grid(io)), dim3(WV_WAVE), 0, s, io);
+    ++b->draw_launches[1];
+    return hip_ok(hipGetLastError(), "cassie_draw_perm_kernel launch") ? 0 : -1;
+}
+void *phys_batch_draw_perm_ptr(const phys_batch_t *b) {
+    if (!b || !b->draw.on || b->draw.perm_n < 1) return nullptr;
+    return b->draw.perm_dst ? (void *)b->draw.perm_dst : (void *)b->d_draw_perm.get();
+}
+int phys_batch_draw_dim(const phys_batch_t *b, int *A, long long *perm_n) {
+    if (!b || !b->draw.on) return refuse("phys_batch_draw_dim", ck::DRAW_NOT_CONFIGURED);
+    if (A) *A = b->draw.A;
+    if (perm_n) *perm_n = b->draw.perm_n;
+    return 0;
+}
+int phys_batch_draw_rows(phys_batch_t *b, float *host) {
+    if (!b || !host) return refuse("phys_batch_draw_rows", ck::DRAW_NOT_CONFIGURED);
+    ck::DrawDst D;
+    if (const char *why = ck::check_draw(draw_cfg_of(b), b->policy, b->nenv, 0, b->nenv, D)) return refuse("phys_batch_draw_rows", why);
+    (void)hipSetDevice(b->device);
+    if (!quiesce(b)) return -1;
+    const size_t e = sizeof(float), A = (size_t)b->draw.A;
+    return hip_ok(hipMemcpy2D(host, e * A, D.ptr, e * (size_t)D.stride, e * A, (size_t)b->nenv, hipMemcpyDeviceToHost), "draw rows download") ? 0 : -1;
+}
+int phys_batch_draw_perm_rows(phys_batch_t *b, int *host) {
+    if (!b || !host) return refuse("phys_batch_draw_perm_rows", ck::DRAW_NOT_CONFIGURED);
+    const ck::DrawCfg c = draw_cfg_of(b);
+    if (const char *why = ck::check_draw_perm(c)) return refuse("phys_batch_draw_perm_rows", why);
+    (void)hipSetDevice(b->device);
+    if (!quiesce(b)) return -1;
+    return hip_ok(hipMemcpy(host, c.perm_dst ? c.perm_dst : c.perm, sizeof(int) * (size_t)c.perm_n, hipMemcpyDeviceToHost), "draw permutation download") ? 0 : -1;
+}
+int phys_batch_draw_download(phys_batch_t *b, unsigned *counts_host) {
+    if (!b || !counts_host || !b->draw.on || !b->d_draw_counts) return refuse("phys_batch_draw_download", ck::DRAW_NOT_CONFIGURED);
+    (void)hipSetDevice(b->device);
+    return quiesce(b) && hip_ok(hipMemcpy(counts_host, b->d_draw_counts, sizeof(unsigned) * (size_t)b->nenv, hipMemcpyDeviceToHost), "draw call counts download") ? 0 : -1;
+}
+int phys_batch_draw_upload(phys_batch_t *b, const unsigned *counts_host) {
+    if (!b || !counts_host || !b->draw.on || !b->d_draw_counts) return refuse("phys_batch_draw_upload", ck::DRAW_NOT_CONFIGURED);
+    (void)hipSetDevice(b->device);
+    return quiesce(b) && hip_ok(hipMemcpy(b->d_draw_counts, counts_host, sizeof(unsigned) * (size_t)b->nenv, hipMemcpyHostToDevice), "draw call counts upload") ? 0 : -1;
+}
+int phys_batch_debug_draw_launches(const phys_batch_t *b, long long *launches) {
+    if (!b) return -1;
+    if (launches) { launches[0] = b->draw_launches[0]; launches[1] = b->draw_launches[1]; }
     return 0;
 }
 

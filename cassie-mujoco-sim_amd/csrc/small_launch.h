@@ -1,12 +1,12 @@
 /*
- * small_launch.h -- how the kernels around the step kernel (small_kernels.h, surface_kernels.h, depth_kernel.h, ray_kernel.h, episode_kernels.h, probe_kernels.h, obs_kernels.h, reward_kernels.h, act_kernels.h, task_kernels.h, event_kernels.h, policy_kernels.h, rollout_kernels.h, grad_kernels.h, opt_kernels.h, norm_kernels.h) are
+ * small_launch.h -- how the kernels around the step kernel (small_kernels.h, surface_kernels.h, depth_kernel.h, ray_kernel.h, episode_kernels.h, probe_kernels.h, obs_kernels.h, reward_kernels.h, act_kernels.h, task_kernels.h, event_kernels.h, policy_kernels.h, rollout_kernels.h, grad_kernels.h, opt_kernels.h, norm_kernels.h, draw_kernels.h) are
  * launched: the records a kernel's arguments are built from, one builder per kernel that returns its filled argument struct for an env
  * range, the grid of every launch, and the checks of what a caller configures, each returning the message of its refusal (null: fine).
  * Pure host code, no HIP runtime calls, in the spirit of step_policy.h: the launcher (phys_batch.hip) keeps the records in the batch,
  * prefixes a message with its entry point's name and launches what a builder returns on the grid given here; the wave emulator's entry
  * points (tests/emu) fill the same records from their arguments and go through the same builders, grids and checks, so a CPU test of
  * one of these kernels also runs the launcher's refusals, grid and choice of kernel (tests/test_small_launch.py pins them one by one).
- * No field of ScanIO, DepthIO, RayIO, EpisodeIO, ResetIO, DeriveIO, SetConstIO, StateIO, ProbeIO, ObsIO, RewardIO, ActIO, TaskIO, EventIO, PolicyIO, PolicyPackIO, RolloutRecIO, RolloutFinIO, RolloutNormIO, GradIO, GradPackIO, OptIO or NormIO is assigned anywhere else.
+ * No field of ScanIO, DepthIO, RayIO, EpisodeIO, ResetIO, DeriveIO, SetConstIO, StateIO, ProbeIO, ObsIO, RewardIO, ActIO, TaskIO, EventIO, PolicyIO, PolicyPackIO, RolloutRecIO, RolloutFinIO, RolloutNormIO, GradIO, GradPackIO, OptIO, NormIO, DrawIO or DrawPermIO is assigned anywhere else.
  */
 #ifndef CASSIE_SMALL_LAUNCH_H
 #define CASSIE_SMALL_LAUNCH_H
@@ -16,6 +16,7 @@
 
 #include "act_kernels.h"
 #include "depth_kernel.h"
+#include "draw_kernels.h"
 #include "episode_kernels.h"
 #include "event_kernels.h"
 #include "grad_kernels.h"
@@ -1794,6 +1795,98 @@ inline void norm_stats_host(const NormCfg &c, const double *n, const double *cou
     stats[0] = (double)c.last_R; stats[1] = (double)c.last_blocks; stats[2] = updated; stats[3] = skipped; stats[4] = excluded;
     stats[5] = (double)c.calls; stats[6] = nmax; stats[7] = 0.0;
 }
+
+/* ---- the draw rows ---- */
+
+/* the draws (phys_batch_draw_configure; on 0: not configured): the columns of a normal row (0: none), the shuffle's n (0: none), the
+ * counter's offset and the key; the destinations the caller bound (dst null: the eps the policy's sample binding names, resolved at every
+ * call; perm_dst null: the batch's own buffer).  Then what the launcher names once a kernel reads them: the envs' call counts and the
+ * batch's permutation */
+struct DrawCfg {
+    int on, A;
+    long long perm_n;
+    unsigned env_base, key0, key1, pad;
+    float *dst; long long sdst;
+    int *perm_dst;
+    unsigned *counts; int *perm;
+};
+/* the destination of a call of the normal rows as resolved */
+struct DrawDst { float *ptr; long long stride; };
+constexpr const char *DRAW_NOT_CONFIGURED = "not configured (phys_batch_draw_configure first)";
+/* the draws' configuration: checks the caller's numbers and fills c but for what is bound or named later.  A 0 with perm_n 0 is accepted
+ * and leaves c empty: the launcher releases what it holds.  The emulator goes through the same */
+inline const char *draw_configure(int A, long long perm_n, unsigned long long seed, unsigned env_base, DrawCfg &c) {
+    c = {};
+    if (A == 0 && perm_n == 0) return nullptr;
+    if (A < 0 || A > DRAW_MAXA) return "A lies in 1 .. 64 (0: no normal rows; 0 with perm_n 0 releases)";
+    if (perm_n < 0 || perm_n > DRAW_MAXPERM) return "perm_n lies in 1 .. 2^30 (0: no shuffle)";
+    c.on = 1; c.A = A; c.perm_n = perm_n; c.env_base = env_base; c.key0 = (unsigned)(seed & 0xffffffffull); c.key1 = (unsigned)(seed >> 32);
+    return nullptr;
+}
+/* what phys_batch_draw_bind refuses (ptr null: back to the policy's eps) */
+inline const char *check_draw_bind(const DrawCfg &c, const void *ptr, long long row_stride) {
+    if (!c.on) return DRAW_NOT_CONFIGURED;
+    if (c.A < 1) return "no normal rows are configured (A is 0)";
+    if (ptr && row_stride < c.A) return "a row stride of at least A";
+    return nullptr;
+}
+/* what phys_batch_draw_bind_perm refuses (ptr null: back to the batch's own buffer) */
+inline const char *check_draw_bind_perm(const DrawCfg &c, const void *) {
+    if (!c.on) return DRAW_NOT_CONFIGURED;
+    if (c.perm_n < 1) return "no shuffle is configured (perm_n is 0)";
+    return nullptr;
+}
+/* what a call of the normal rows refuses (D filled where it accepts): the destination is the caller's, or the eps tensor and stride that
+ * phys_batch_policy_bind_sample names now */
+inline const char *check_draw(const DrawCfg &c, const PolicyCfg &p, int nenv, int env0, int n, DrawDst &D) {
+    D = {};
+    if (!c.on || !c.counts) return DRAW_NOT_CONFIGURED;
+    if (c.A < 1) return "no normal rows are configured (A is 0)";
+    if (env0 < 0 || n < 0 || (long long)env0 + n > nenv) return "env range out of bounds";
+    if (c.dst) { D.ptr = c.dst; D.stride = c.sdst; return nullptr; }
+    if (p.nnets < 1 || !p.eps) return "no destination: nothing is bound and the policy has no sample bound (phys_batch_policy_bind_sample, or phys_batch_draw_bind)";
+    if (p.net[0].layer[p.net[0].nlayers - 1].out != c.A) return "the actor's output width is not A";
+    D.ptr = (float *)p.eps; D.stride = p.seps;
+    return nullptr;
+}
+/* what a shuffle refuses */
+inline const char *check_draw_perm(const DrawCfg &c) {
+    if (!c.on) return DRAW_NOT_CONFIGURED;
+    if (c.perm_n < 1) return "no shuffle is configured (perm_n is 0)";
+    if (!c.perm_dst && !c.perm) return "no destination: nothing is bound and the batch holds no permutation";
+    return nullptr;
+}
+/* cassie_draw_kernel's (after the check) */
+inline DrawIO make_draw_io(const DrawCfg &c, const DrawDst &D, int env0, int n) {
+    DrawIO io = zeroed<DrawIO>();
+    io.env0 = env0; io.n = n; io.A = c.A;
+    const int blocks = (c.A + 3) / 4;
+    io.lanes = 1;
+    while (io.lanes < blocks) io.lanes *= 2;
+    io.per_wave = WV_WAVE / io.lanes;
+    io.vec = rollout_aligned16(D.ptr) && (D.stride & 3) == 0;
+    io.env_base = c.env_base; io.key0 = c.key0; io.key1 = c.key1;
+    io.rows = D.ptr; io.srow = D.stride; io.counts = c.counts;
+    return io;
+}
+/* the bits of a half of the shuffle's word: b = 2 h the smallest even number of bits with 2^b >= max(n, 4) */
+inline unsigned draw_perm_half(long long n) {
+    unsigned h = 1;
+    while ((1ll << (2 * h)) < n) ++h;
+    return h;
+}
+/* cassie_draw_perm_kernel's (after the check) */
+inline DrawPermIO make_draw_perm_io(const DrawCfg &c, unsigned epoch) {
+    DrawPermIO io = zeroed<DrawPermIO>();
+    io.n = (unsigned)c.perm_n; io.h = draw_perm_half(c.perm_n); io.mask = (1u << io.h) - 1u;
+    io.walk_max = (1ll << (2 * io.h)) - c.perm_n + 1;
+    io.epoch = epoch; io.key0 = c.key0; io.key1 = c.key1;
+    io.perm = c.perm_dst ? c.perm_dst : c.perm;
+    return io;
+}
+/* a wave per 64 / lanes envs up to DRAW_GRID workgroups, a wave per 64 indices up to DRAW_PERM_GRID, which then walk */
+inline int draw_grid(const DrawIO &io) { const int w = (io.n + io.per_wave - 1) / io.per_wave; return w < 1 ? 1 : (w < DRAW_GRID ? w : DRAW_GRID); }
+inline int draw_perm_grid(const DrawPermIO &io) { const long long w = ((long long)io.n + WV_WAVE - 1) / WV_WAVE; return w < DRAW_PERM_GRID ? (int)w : DRAW_PERM_GRID; }
 
 }  // namespace ck
 #endif

@@ -1587,6 +1587,83 @@ int phys_batch_norm_upload(phys_batch_t *b, int what, const void *host);
 int phys_batch_debug_norm_launches(const phys_batch_t *b, long long *launches /*[5]*/);
 int phys_batch_debug_norm_mask(phys_batch_t *b, unsigned mask);   /* default 15 */
 
+/* DRAW ROWS: the two random inputs of an iteration -- the standard normal rows SAMPLE of POLICY ROWS reads as eps, and the permutation an
+ * epoch's minibatches are cut from (the idx of GRADIENT ROWS) -- as functions of ONE seed and counters of the batch's own, with every bit
+ * defined.  One launch per env range on the caller's stream fills the normal rows; one launch writes a permutation.  The device
+ * (csrc/draw_kernels.h), the wave emulator and a numpy restatement (tests/draw_check.py) agree bit for bit.  The result for an env
+ * depends on (seed, env_base + env, column, the env's call count) alone: not on the range, the grid, the stream or the order of calls for
+ * other envs.  No stepping kernel is handed any of this; the observation, action and task rows' own noise stays uniform and untouched.
+ *
+ * All arithmetic is individually rounded fp64 operations (add, sub, mul, div, sqrt), no fma, no library call; the conversion to float32
+ * rounds to nearest even.  philox(c0, c1, c2, c3) is Philox4x32-10 (OBSERVATION ROWS) with the key (seed & 0xffffffff, seed >> 32).
+ *
+ * LOGN.  logn(x) ~ ln x for a finite double x > 0 (csrc/logn.h):
+ *   1. selects, before anything else: a NaN gives that NaN; x < 0 (and -inf) gives NaN; +0.0 and -0.0 give -inf; +inf gives +inf.
+ *   2. x = m 2^e, by integer operations on the bits (a subnormal x is first multiplied by 2^54, exact, and e lowered by 54): m in [1, 2)
+ *      has x's mantissa; if m >= 1.4142135623730951 (the double nearest sqrt 2), m = m / 2 (exact) and e = e + 1.  So m lies in
+ *      [sqrt 1/2, sqrt 2).
+ *   3. f = m - 1, exact.  s = f / (2 + f).  z = s s.
+ *   4. P = 1/23; P = 1/k + z P for k = 21, 19, ..., 3: the doubles nearest 1/k, one multiply and one add a step.
+ *   5. t = s + (s z) P;  r = 2 t.
+ *   6. logn = e ln2_hi + (e ln2_lo + r), with ln2_hi = 6.93147180369123816490e-01 and ln2_lo = 1.90821492927058770002e-10 (REWARD ROWS'
+ *      expn's constants; e ln2_hi is exact).
+ *   logn(1) = +0.0.  On the points the draws can produce the relative error is measured by tests/test_draw.py (DESIGN 4.3 has the figure).
+ *
+ * NORMAL ROWS.  phys_batch_draw(b, env0, n, stream) fills float32 rows [nenv][A], 1 <= A <= PHYS_DRAW_MAXA.  counts[env], a uint32 per
+ *   env, starts at 0, is incremented behind the env's draw and wraps.  For env i and column j:
+ *     w = philox(env_base + i, j >> 2, counts[i], 4)          (word 3: 0 .. 3 are the observation's, the action's and the task's two)
+ *     a = w[j & 2];  b = w[(j & 2) + 1]
+ *     u = (a + 0.5) 2^-32, exact, in (0, 1);   theta = b 2^-32, exact, in [0, 1)
+ *     rad = sqrt(-2 logn(u));   (sn, cs) = sincos2pi(theta) of TASK ROWS
+ *     z = rad * ((j & 1) ? sn : cs);   the row takes (float) z, one rounding.
+ *   |z| <= sqrt(66 ln 2) ~ 6.76; no rejection, no loop.  Envs outside the range and words past column A are not touched.
+ *   DESTINATION.  Unbound, the rows go to the eps tensor with the stride that phys_batch_policy_bind_sample names, resolved at every call
+ *   (refused when no sample is bound or the actor's output width is not A); phys_batch_draw_bind names another tensor.
+ *
+ * SHUFFLE.  phys_batch_draw_perm(b, epoch, stream) writes int32 perm[0 .. n), a bijection of [0, n) keyed by (seed, epoch),
+ *   1 <= n <= PHYS_DRAW_MAXPERM.  b is the smallest even number of bits with 2^b >= max(n, 4); h = b / 2; mask = 2^h - 1.  For index i:
+ *     x = i
+ *     repeat:  (L, R) = (x >> h, x & mask);  for r = 0 .. 5: (L, R) = (R, L ^ (philox(R, r, epoch, 5)[0] & mask));  x = L << h | R
+ *     while x >= n                                                                                       (cycle walking)
+ *     perm[i] = x
+ *   The six rounds are a bijection of [0, 2^b), so the values >= n a walk from i < n meets are distinct: a walk ends within
+ *   2^b - n + 1 <= max(3 n, 4) applications.  The destination is the batch's own buffer (phys_batch_draw_perm_ptr) or a bound int32 tensor;
+ *   phys_batch_grad(b, perm + k M, M, ...) reads minibatch k from it.
+ *
+ * A checkpoint of a run's randomness is the seed, the counts (phys_batch_draw_download) and the caller's epoch counter.
+ * Out of scope: uniform or truncated draws as a kind; Gaussian noise inside the observation, action and task kernels; more than one draw
+ * configuration per batch; A > 64; a sort-based shuffle.
+ *
+ *   phys_batch_draw_configure   A columns (0: no normal rows), the shuffle's n (0: no shuffle), the seed, env_base (what a rank that
+ *                               holds envs [k nenv, (k + 1) nenv) of a larger run passes: k nenv).  Allocates the counts, zeroed, and the
+ *                               batch's permutation.  A 0 with perm_n 0 releases.  Waits for the batch's streams.  The draw rows STAY
+ *                               configured when the policy, the rollout, the gradient, the optimiser or the normaliser rows are
+ *                               reconfigured: they resolve at the call and hold no pointer of theirs.
+ *   phys_batch_draw_bind        a float32 tensor of the caller's, rows row_stride >= A words apart, as the destination (NULL: the policy's
+ *                               eps again).
+ *   phys_batch_draw_bind_perm   an int32 tensor of the caller's of n words as the shuffle's destination (NULL: the batch's own again).
+ *   phys_batch_draw             the one launch on `stream`.  Refuses: not configured, A 0, a range beyond nenv, no destination.
+ *   phys_batch_draw_perm        the one launch on `stream`.  Refuses: not configured, no shuffle configured.
+ *   phys_batch_draw_perm_ptr    where the permutation is written, in device memory (NULL: none).
+ *   phys_batch_draw_dim         A and n.
+ *   phys_batch_draw_rows, _perm_rows   the destination's rows [nenv][A], dense, and the permutation [n] to the host; wait for the streams.
+ *   phys_batch_draw_download, _upload  the counts, uint32 [nenv]; wait for the streams.
+ *   phys_batch_debug_draw_launches     diagnostics: the launches so far of the normal rows and of the shuffle. */
+#define PHYS_DRAW_MAXA 64
+#define PHYS_DRAW_MAXPERM (1ll << 30)
+int phys_batch_draw_configure(phys_batch_t *b, int A, long long perm_n, unsigned long long seed, unsigned env_base);   /* A 0, perm_n 0: release */
+int phys_batch_draw_bind(phys_batch_t *b, void *ptr, long long row_stride);   /* NULL: the policy's eps */
+int phys_batch_draw_bind_perm(phys_batch_t *b, void *ptr);                    /* NULL: the batch's own buffer */
+int phys_batch_draw(phys_batch_t *b, int env0, int n, void *stream);          /* one launch */
+int phys_batch_draw_perm(phys_batch_t *b, unsigned epoch, void *stream);      /* one launch */
+void *phys_batch_draw_perm_ptr(const phys_batch_t *b);
+int phys_batch_draw_dim(const phys_batch_t *b, int *A, long long *perm_n);
+int phys_batch_draw_rows(phys_batch_t *b, float *host);
+int phys_batch_draw_perm_rows(phys_batch_t *b, int *host);
+int phys_batch_draw_download(phys_batch_t *b, unsigned *counts_host);
+int phys_batch_draw_upload(phys_batch_t *b, const unsigned *counts_host);
+int phys_batch_debug_draw_launches(const phys_batch_t *b, long long *launches /*[2]*/);
+
 /* measurement aid: on = every substep of a fused launch evaluates every output (IMU sensors, body quaternions), although
  * only the last substep's values can be read; off (default) = those are formed by the substeps whose values are read */
 int phys_batch_set_all_outputs_every_substep(phys_batch_t *b, int on);
